@@ -97,6 +97,24 @@ def emit(obj):
         os.write(_REAL_STDOUT, line)
 
 
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array, as float64 (counts are
+    exact in float64 up to 2**53).  An array over its share of DUMP_LIMIT_BYTES is replaced by a fixed sample: the elements
+    at sorted indices drawn with a seeded generator, written beside it as DIR/<name>_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1).astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def kernel_source_sha16(files=("gtx_kernels.hip", "gtx_kernels.h", "gtx_capi.hip")):
     """identity of the kernel sources a committed PMC profile belongs to (the GPU box has no .git to ask)"""
     import hashlib
@@ -399,6 +417,8 @@ def bench_scans(args, eng, reads, n, rank, world, device, rehearse, total_reads,
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"windows": out.cpu().numpy().view(np.uint64)})
     k_ms = float(np.mean([eng.profile_last(b)[0] for b in range(eng.profiled_calls())])) if eng.profiled_calls() else float("nan")
     if DIST_ON:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else device)
@@ -481,6 +501,8 @@ def bench_perm(args, rank, world, local, device, rehearse):
         counts = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"exceed_counts": acc.cpu().numpy() if DIST_ON else counts})
     if DIST_ON:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -652,6 +674,8 @@ def bench_count_group(args, rank, world, local, device, rehearse, force_dist):
         grp.profile(locals_[0], False)
         hits_final = hits_pp[(step_no[0] - 1) & 1]
         member_reads = [int(x) for x in grp.member_reads()]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"counts": hits_final.cpu().numpy().view(np.uint64)})
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else device)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
@@ -729,7 +753,12 @@ def main():
     ap.add_argument("--two-streams", action="store_true",
                     help="count, N=1: after the timed region also time the same steps alternating two contexts on two HIP streams "
                          "(extra 'two_streams' object; off by default so that a kernel trace of the default command sees only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the count / window / exceed-count vector) "
+                         "as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.scaling is None:
         args.scaling = "strong" if args.workload == "count" else "weak"
@@ -851,6 +880,9 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                                     # before the parity passes below reuse `hits`
+        last = hits_pp[(step_no[0] - 1) & 1] if pipelined and not rehearse else hits
+        dump_outputs(args.dump_outputs, {"counts": last.cpu().numpy().view(np.uint64)})
     k_ms = [eng.profile_last(b)[0] for b in range(eng.profiled_calls())]
     eng.profile(False)
     if world > 1:
