@@ -9,6 +9,8 @@
 #include <unistd.h>
 #include <algorithm>
 #include <functional>
+#include <map>
+#include <set>
 #include <shared_mutex>
 #include <sys/mman.h>
 #include <stdint.h>
@@ -1773,4 +1775,220 @@ StringLIntMap *ReadBounds(char *genome_reg_file, bool verbose)
     }
   }
   return bounds;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// genomic_overlaps overlap / intersect: the device join under the reference's per-query loop
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// what GenomicRegionBED::Print (genomic_intervals.cpp:2188-2220) needs of a query, kept until its batch is joined
+struct PairQuery {
+  std::string chrom, label, rgb;
+  char strand;
+  long int n_tokens, score, thick_start, thick_end;
+  std::vector<long int> iv;                                        // start, stop of every interval
+};
+
+// columns 5, 7, 8, 9 of the raw line as GenomicRegionBED::Read takes them (:2157-2182: blank- or tab-separated, atol)
+void ParseTail(const std::string &raw, PairQuery &q)
+{
+  const char sep = raw.find('\t') == std::string::npos ? ' ' : '\t';
+  std::vector<std::string> tok;
+  size_t k = 0;
+  while (k < raw.size() && tok.size() < 9) {
+    while (k < raw.size() && raw[k] == ' ') k++;
+    size_t e = raw.find(sep, k);
+    if (e == std::string::npos) e = raw.size();
+    tok.push_back(raw.substr(k, e - k));
+    k = e + 1;
+  }
+  q.score = tok.size() > 4 ? atol(tok[4].c_str()) : 0;
+  q.thick_start = tok.size() > 7 ? atol(tok[6].c_str()) : 0;
+  q.thick_end = tok.size() > 7 ? atol(tok[7].c_str()) : 0;
+  q.rgb = tok.size() > 8 ? tok[8] : std::string();
+}
+
+void AppendNum(std::string &out, long int v) { char b[24]; int n = snprintf(b, sizeof b, "%ld", v); out.append(b, (size_t)n); }
+
+// GenomicRegionBED::Print of a region with these intervals and this label
+void PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> &iv, const std::string &label, long int score,
+              long int thick_start, long int thick_end)
+{
+  out += q.chrom; out += '\t'; AppendNum(out, iv[0] - 1); out += '\t'; AppendNum(out, iv.back());
+  const long int nt = q.n_tokens;
+  if (nt >= 4) {
+    out += '\t'; out += label;
+    if (nt >= 5) {
+      out += '\t'; AppendNum(out, score);
+      if (nt >= 6) {
+        out += '\t'; out += q.strand;
+        if (nt >= 8) {
+          out += '\t'; AppendNum(out, thick_start); out += '\t'; AppendNum(out, thick_end);
+          if (nt >= 9) {
+            out += '\t'; out += q.rgb;
+            if (nt == 12) {
+              const size_t n = iv.size() / 2;
+              out += '\t'; AppendNum(out, (long int)n); out += '\t';
+              for (size_t j = 0; j < n; j++) { AppendNum(out, iv[2 * j + 1] - iv[2 * j] + 1); if (j + 1 < n) out += ','; }
+              out += "\t0";
+              for (size_t j = 1; j < n; j++) { out += ','; AppendNum(out, iv[2 * j] - iv[0]); }
+            }
+          }
+        }
+      }
+    }
+  }
+  out += '\n';
+}
+}  // namespace
+
+void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits)
+{
+  GenomicRegionSet *IS = ov->IndexSet, *QS = ov->QuerySet;
+  const bool sorted = dynamic_cast<SortedGenomicRegionSetOverlaps *>(ov) != NULL;
+  if (!IS->load_in_memory) { fprintf(stderr, "Error: [GtxPrintPairs] the index set must be loaded in memory!\n"); exit(1); }
+  if (QS->format == "GTX") { fprintf(stderr, "Error: overlap / intersect print the query lines: a packed region file has no labels, give the BED text!\n"); exit(1); }
+  const long int M = IS->n_regions;
+
+  // ---- index side: classes (chromosome rank in strcmp order, x2 + strand unless -i), envelopes, intervals, order keys ----
+  std::map<std::string, int> cid;
+  for (long int k = 0; k < M; k++) cid[IS->R[k]->I.front()->CHROMOSOME] = 0;
+  { int n = 0; for (auto &c : cid) c.second = n++; }
+  const int ns = ignore_strand ? 1 : 2, n_classes = std::max<int>(1, (int)cid.size() * ns);
+  auto class_of = [&](const GenomicInterval *i) -> int {
+    std::map<std::string, int>::const_iterator it = cid.find(i->CHROMOSOME);
+    return it == cid.end() ? -1 : it->second * ns + (ignore_strand ? 0 : (i->STRAND == '-'));
+  };
+  auto fits = [](long int v) { return v < INT_MAX - 1 && v > INT_MIN + 1; };
+  // under the merge an index region out of order or with overlapping blocks is the reference's error when the merge pulls it
+  // (LoadIndexBuffer): the regions from there on can pair with no query before that error, so they are placeholders here
+  long int v = M;
+  if (sorted) {
+    const bool by_strand = static_cast<SortedGenomicRegionSetOverlaps *>(ov)->sorted_by_strand;
+    for (long int k = 0; k < M && v == M; k++)
+      if (!IS->R[k]->IsCompatibleSortedAndNonoverlapping() || (k > 0 && IS->R[k]->IsBefore(IS->R[k - 1], by_strand))) v = k;
+  }
+  std::vector<int32_t> tri((size_t)3 * std::max<long int>(M, 1)), blocks; std::vector<int64_t> first((size_t)M + 1, 0);
+  std::set<std::string> valid_chrom;                                  // chromosomes the bin index has (a valid region on them)
+  bool multi = false;
+  for (long int k = 0; k < M; k++) {
+    GenomicRegion *r = IS->R[k];
+    const long int s = r->I.front()->START, e = r->I.back()->STOP;
+    if (k >= v) { tri[3 * k] = -1; tri[3 * k + 1] = 1; tri[3 * k + 2] = 0; blocks.push_back(1); blocks.push_back(0); first[k + 1] = (int64_t)blocks.size() / 2; continue; }
+    if (!fits(s) || !fits(e)) r->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
+    tri[3 * k] = class_of(r->I.front()); tri[3 * k + 1] = (int32_t)s; tri[3 * k + 2] = (int32_t)e;
+    if (r->I.size() > 1) multi = true;
+    for (GenomicInterval *i : r->I) { blocks.push_back((int32_t)i->START); blocks.push_back((int32_t)i->STOP); }
+    first[k + 1] = (int64_t)blocks.size() / 2;
+    if (!(s > e || e <= 0)) valid_chrom.insert(r->I.front()->CHROMOSOME);
+  }
+  std::vector<int64_t> key;
+  if (!sorted) {                                                      // the bin index's order: (level, bin, -ordinal) (:5619-5674, :5729-5764)
+    std::vector<int> bits;
+    std::string bb = bin_bits ? bin_bits : "";
+    if (bb.empty()) bits = {17, 20, 23, 26, 60};
+    else {
+      size_t p = 0;
+      for (;;) { size_t q = bb.find(',', p); bits.push_back(atoi(bb.substr(p, q == std::string::npos ? q : q - p).c_str())); if (q == std::string::npos) break; p = q + 1; }
+      bits.push_back(60);
+    }
+    struct LB { long int level, bin, k; };
+    std::vector<LB> lb((size_t)M);
+    for (long int k = 0; k < M; k++) {
+      long int s = IS->R[k]->I.front()->START; const long int e = IS->R[k]->I.back()->STOP;
+      if (s <= 0) s = 1;
+      lb[k] = {(long int)bits.size(), 0, k};
+      for (size_t l = 0; l < bits.size(); l++) if ((s >> bits[l]) == (e >> bits[l])) { lb[k] = {(long int)l, s >> bits[l], k}; break; }
+    }
+    std::sort(lb.begin(), lb.end(), [](const LB &a, const LB &b) { return a.level != b.level ? a.level < b.level : (a.bin != b.bin ? a.bin < b.bin : a.k > b.k); });
+    key.resize((size_t)std::max<long int>(M, 1));
+    for (long int j = 0; j < M; j++) key[lb[j].k] = j;
+  }
+  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
+  auto chk = [&](int rc) { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(ctx)); exit(1); } };
+  chk(gtx_set_refs_ex(ctx, tri.data(), M, n_classes, sorted ? GTX_REFS_KEEP_ZERO_LENGTH : 0));
+  chk(gtx_set_ref_blocks(ctx, multi && !match_gaps ? first.data() : NULL, blocks.data()));
+  chk(gtx_set_ref_order(ctx, sorted ? NULL : key.data()));
+  const uint32_t flags = (sorted ? GTX_ZERO_LENGTH_OK : 0) | (match_gaps ? GTX_JOIN_GAPS : 0);
+
+  // ---- query side: batches of the queries the loop hands out, joined and printed in order ----
+  const size_t kBatch = 1 << 20;
+  std::vector<PairQuery> batch; batch.reserve(4096);
+  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst(1, 0), off; std::vector<int32_t> pairs;
+  bool qmulti = false;
+  std::string out;
+  auto flush = [&]() {
+    const int64_t n = (int64_t)batch.size();
+    if (n == 0) return;
+    off.assign((size_t)n + 1, 0);
+    if (pairs.empty()) pairs.resize(1 << 16);
+    gtx_count_info info;
+    chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
+    if (off[n] > (int64_t)pairs.size()) {
+      pairs.resize((size_t)off[n]);
+      chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
+    }
+    std::vector<long int> civ;
+    for (int64_t i = 0; i < n; i++) {
+      const PairQuery &q = batch[i];
+      for (int64_t p = off[i]; p < off[i + 1]; p++) {
+        GenomicRegion *r = IS->R[pairs[p]];
+        const std::string label = merge_labels ? q.label + ":" + r->LABEL : q.label;
+        if (!intersect) PrintBed(out, q, q.iv, label, q.score, q.thick_start, q.thick_end);
+        else {                                                              // Constrain (:2543-2561), match_gaps = false
+          const long int rs = r->I.front()->START, re = r->I.back()->STOP;
+          civ.clear();
+          for (size_t j = 0; j < q.iv.size(); j += 2) {
+            const long int a = std::max(q.iv[j], rs), b = std::min(q.iv[j + 1], re);
+            if (a <= b) { civ.push_back(a); civ.push_back(b); }
+          }
+          if (civ.empty()) continue;
+          PrintBed(out, q, civ, label, q.n_tokens >= 5 ? q.score : 0, q.n_tokens >= 7 ? std::max(q.thick_start, rs - 1) : rs - 1,
+                   q.n_tokens >= 8 ? std::min(q.thick_end, re) : re);
+        }
+        if (out.size() > (1u << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+      }
+    }
+    fwrite(out.data(), 1, out.size(), stdout); out.clear();
+    batch.clear(); qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qmulti = false;
+  };
+
+  LoadError err;
+  tls_load_error = &err;
+  try {
+    bool index_checked = sorted;
+    for (GenomicRegion *q = ov->GetQuery(); ov->Done() == false; q = ov->NextQuery()) {
+      if (!index_checked) {                                               // the bin index is built at the first query's match (:5603-5616)
+        for (long int k = 0; k < M; k++)
+          if (!IS->R[k]->IsCompatibleSortedAndNonoverlapping()) IS->R[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
+        index_checked = true;
+      }
+      GenomicInterval *f = q->I.front();
+      const long int s = f->START, e = q->I.back()->STOP;
+      if (sorted) { for (GenomicRegion *r = ov->GetMatch(); r; r = ov->NextMatch()) {} }   // the merge's buffer as the reference's walk leaves it
+      else if (valid_chrom.count(f->CHROMOSOME)) {                       // :5740-5741, on chromosomes the index knows
+        if (e <= 0) q->PrintError("stop position must be positive!");
+        if (s > e) q->PrintError("start position cannot be greater than stop position!");
+      }
+      if (!fits(s) || !fits(e)) q->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
+      PairQuery pq;
+      pq.chrom = f->CHROMOSOME; pq.strand = f->STRAND; pq.label = q->LABEL;
+      pq.n_tokens = static_cast<GenomicRegionBED *>(q)->n_tokens;
+      ParseTail(QS->CurrentLine(), pq);
+      for (GenomicInterval *i : q->I) { pq.iv.push_back(i->START); pq.iv.push_back(i->STOP); qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
+      if (q->I.size() > 1) qmulti = true;
+      qfirst.push_back((int64_t)qblk.size() / 2);
+      qtri.push_back(class_of(f)); qtri.push_back((int32_t)s); qtri.push_back((int32_t)e);
+      batch.push_back(std::move(pq));
+      if (batch.size() >= kBatch) flush();
+    }
+  } catch (const LoadAbort &) {}
+  tls_load_error = NULL;
+  flush();                                                                // the pairs before an error are printed, then the error
+  fflush(stdout);
+  if (err.set) {
+    fprintf(stderr, "\n");
+    if (err.with_prefix) fprintf(stderr, "Error: Line %ld: %s\n", err.line, err.msg.c_str()); else fprintf(stderr, "%s\n", err.msg.c_str());
+    exit(1);
+  }
 }

@@ -11,10 +11,12 @@
 // reductions here; without a GPU they fail with an error message and exit(1), like every other
 // error of the reference (genomic_intervals.cpp:1001-1006).
 //
-// Scope: BED3..BED6 single-interval regions.  REG/SAM/GFF/SEQ input, BED12
-// blocks, the ~45 Run*/Print* text transforms of GenomicRegionSet, GenomicRegionSetIndex beyond the
-// "does anything overlap" query of the scanners' reference filter, and the per-pair enumeration
-// (GetMatch/NextMatch) are outside the path.
+// Scope: BED3..BED12 regions (BED12 blocks as multi-interval regions), the
+// reductions of count / rpkm / coverage / density and the scanners, and the per-pair iteration
+// (GetQuery / GetOverlap / NextOverlap) on the host.  REG/SAM/GFF/SEQ input, the ~45 Run*/Print*
+// text transforms of GenomicRegionSet and GenomicRegionSetIndex beyond the "does anything overlap"
+// query of the scanners' reference filter are outside the path; the device-side pair join is the
+// C ABI's gtx_join (include/gtx.h).
 #ifndef GTX_GENOMIC_INTERVALS_H
 #define GTX_GENOMIC_INTERVALS_H
 
@@ -128,6 +130,7 @@ class GenomicRegionSet
   FILE *file_ptr;                                                  // the FILE* constructor's stream (NULL otherwise)
   unsigned long int buffer_size;
   bool verbose, load_in_memory, from_stdin, hide_header;
+  const std::string &CurrentLine() const { return cur_raw; }      // MI355X path: the unparsed line of the current region of a streamed text set
   long int StreamBytesLeft();                     // size of a streamed regular text file, -1 otherwise (MI355X build: the device-side tokenizer's test)
   long int n_regions;
   std::string format;                                              // "BED", "EMPTY" or "GTX" (a packed region file, gtx_bed.h)
@@ -319,6 +322,15 @@ class UnsortedGenomicRegionSetScanner : public GenomicRegionSetScanner
   virtual long int Next(GenomicRegionSet *Ref);
   virtual long int Next(GenomicRegionSetIndex *index);
 };
+
+// genomic_overlaps overlap / intersect (gtools/genomic_overlaps.cpp:676-741) in bulk: the reference's loop
+//   for (q = GetQuery(); Done() == false; q = NextQuery()) for each overlap (GetOverlap / NextOverlap) print
+// with the query stream, its errors and Done() (the merge's early stop) taken from the overlaps object itself, and the pairs of
+// every batch of queries from the device join (gtx_join) in the reference's iteration order.  Each pair prints the query as
+// GenomicRegionBED::Print does -- with `intersect` clipped to the index region's envelope (Constrain) -- and, with merge_labels,
+// the label "query:index".  bin_bits: the -B of the bin index (its order); ignored under the sorted merge.  The query set is a
+// streamed BED text set; the index set is loaded in memory.
+void GtxPrintPairs(GenomicRegionSetOverlaps *overlaps, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits);
 
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)

@@ -1,9 +1,10 @@
-// genomic_overlaps -- MI355X edition of the `count`, `rpkm`, `coverage` and `density` operations of
-// GenomicTools' genomic_overlaps (reference driver: gtools/genomic_overlaps.cpp:73-261 options,
-// :298-305, :408-431 count, :438-459 coverage, :466-490 density, :746-775 rpkm).  Same command line,
-// same output, same errors; the reductions are GenomicRegionSetOverlaps::CountIndexOverlaps /
-// CalcIndexCoverage of this package, i.e. HIP kernels through libgtx.so.  The other seven operations
-// of the reference tool emit per-pair text and are outside this path.
+// genomic_overlaps -- MI355X edition of the `count`, `rpkm`, `coverage`, `density`, `overlap` and
+// `intersect` operations of GenomicTools' genomic_overlaps (reference driver: gtools/genomic_overlaps.cpp:
+// 73-261 options, :298-305, :408-431 count, :438-459 coverage, :466-490 density, :676-701 intersect,
+// :706-741 overlap, :746-775 rpkm).  Same command line, same output, same errors; the reductions are
+// GenomicRegionSetOverlaps::CountIndexOverlaps / CalcIndexCoverage of this package and the pairs of
+// overlap / intersect come from the device join (GtxPrintPairs), i.e. HIP kernels through libgtx.so.
+// annotate, bin, dist, offset and subset are outside this path.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,14 +24,17 @@ int main(int argc, char *argv[])
                     "  count      Counts the number of overlapping test regions per reference region.\n"
                     "  coverage   Calculates the depth coverage (total number of overlapping nucleotides) per reference region.\n"
                     "  density    Computes the density (coverage divided by the size of the reference region) per reference region.\n"
+                    "  intersect  Prints the test regions clipped to each overlapping reference region.\n"
+                    "  overlap    Prints the test regions once per overlapping reference region.\n"
                     "  rpkm       Computing reference region RPKM values.\n\n", PROGRAM);
     return 1;
   }
   std::string op = argv[1];
   if (op[0] == '-') op = op.substr(1);                        // compatibility with the old "-count" spelling
-  static const char *others[] = {"annotate", "bin", "dist", "intersect", "offset", "overlap", "subset"};
+  static const char *others[] = {"annotate", "bin", "dist", "offset", "subset"};
   for (const char *o : others) if (op == o) { fprintf(stderr, "Operation '%s' is outside the MI355X counting path of this build (count, coverage, density, rpkm)!\n", o); return 1; }
-  if (op != "count" && op != "rpkm" && op != "coverage" && op != "density") { fprintf(stderr, "Unknown operation '%s'!\n", op.c_str()); return 1; }
+  if (op != "count" && op != "rpkm" && op != "coverage" && op != "density" && op != "overlap" && op != "intersect") { fprintf(stderr, "Unknown operation '%s'!\n", op.c_str()); return 1; }
+  const bool per_pair = op == "overlap" || op == "intersect";
 
   bool HELP, HELP2, VERBOSE, IS_SORTED, SORTED_BY_STRAND, IGNORE_STRAND, MATCH_GAPS;
   const char *BIN_BITS; long MAX_LABEL_VALUE; unsigned long MIN_COUNT = 0; double MIN_RPKM, MIN_DENSITY = 0.0;
@@ -38,17 +42,20 @@ int main(int argc, char *argv[])
   opts.Flag("--help", &HELP, "help");
   opts.Flag("-h", &HELP2, "help");
   opts.Flag("-v", &VERBOSE, "verbose mode");
-  opts.Str("-B", &BIN_BITS, "17,20,23,26", "number of shift-bits for each bin level (accepted, unused: no bin index on the device)");
+  opts.Str("-B", &BIN_BITS, "17,20,23,26", "number of shift-bits for each bin level (count / coverage: accepted, unused; overlap / intersect: the order of the pairs)");
   opts.Flag("-S", &IS_SORTED, "test and reference regions are sorted by chromosome and start position");
   opts.Flag("-s", &SORTED_BY_STRAND, "test and reference regions are also sorted by strand (-S must be set)");
   opts.Flag("-i", &IGNORE_STRAND, "ignore strand while finding overlaps");
-  opts.Flag("-gaps", &MATCH_GAPS, "matching gaps between intervals are considered overlaps");
-  opts.Long("--max-label-value", &MAX_LABEL_VALUE, 1, "maximum region label value to be used");
+  bool MERGE_LABELS = false;
+  MATCH_GAPS = false; MAX_LABEL_VALUE = 1;
+  if (op != "intersect") opts.Flag("-gaps", &MATCH_GAPS, "matching gaps between intervals are considered overlaps");
+  if (per_pair) opts.Flag("-label", &MERGE_LABELS, "print test and reference labels as test:reference");
+  if (!per_pair) opts.Long("--max-label-value", &MAX_LABEL_VALUE, 1, "maximum region label value to be used");
   if (op == "count") opts.ULong("-min", &MIN_COUNT, 0, "minimum count");
   else if (op == "coverage") opts.ULong("-min", &MIN_COUNT, 0, "minimum coverage");
   else if (op == "density") opts.Double("-min", &MIN_DENSITY, 0.0, "minimum density");
-  else opts.Double("-min", &MIN_RPKM, 0.0, "minimum RPKM");
-  long NGPU; opts.Long("--ngpu", &NGPU, 0, "MI355X: number of GPUs the reduction is spread over, by chromosome, RCCL reduce of the result (default: GTX_NGPU or 1)");
+  else if (op == "rpkm") opts.Double("-min", &MIN_RPKM, 0.0, "minimum RPKM");
+  long NGPU = 0; if (!per_pair) opts.Long("--ngpu", &NGPU, 0, "MI355X: number of GPUs the reduction is spread over, by chromosome, RCCL reduce of the result (default: GTX_NGPU or 1)");
   int next_arg = opts.Parse(argc, argv, 2);
   if (NGPU > 0) GtxSetDevices((int)NGPU);
   if (HELP || HELP2 || argc - next_arg < 1) { opts.Usage(PROGRAM, op.c_str(), "[OPTIONS] REFERENCE-REGION-FILE <TEST-REGION-FILE>"); return 1; }
@@ -61,6 +68,18 @@ int main(int argc, char *argv[])
 
   char *REF_REG_FILE = argv[next_arg];
   char *TEST_REG_FILE = next_arg + 1 == argc ? NULL : argv[next_arg + 1];
+  if (per_pair) {                                             // :676-741: the test set is streamed with its header echoed
+    GenomicRegionSet RefRegSet(REF_REG_FILE, BUFFER_SIZE, VERBOSE, true, true);
+    GenomicRegionSet TestRegSet(TEST_REG_FILE, BUFFER_SIZE, VERBOSE, false, false);
+    GenomicRegionSetOverlaps *overlaps;
+    if (IS_SORTED) overlaps = new SortedGenomicRegionSetOverlaps(&TestRegSet, &RefRegSet, SORTED_BY_STRAND);
+    else overlaps = new UnsortedGenomicRegionSetOverlaps(&TestRegSet, &RefRegSet, BIN_BITS);
+    GtxPrintPairs(overlaps, op == "intersect", MATCH_GAPS, IGNORE_STRAND, MERGE_LABELS, BIN_BITS);
+    GtxMark("output written");
+    GtxFinish(0);
+    delete overlaps;
+    return 0;
+  }
   GenomicRegionSet RefRegSet(REF_REG_FILE, BUFFER_SIZE, VERBOSE, true, true);
   GenomicRegionSet TestRegSet(TEST_REG_FILE, BUFFER_SIZE, VERBOSE, false, true);
 

@@ -16,6 +16,7 @@
 #include "gtx.h"
 #include "gtx_kernels.h"
 #include "gtx_pairs.h"
+#include "gtx_join.h"
 #include "gtx_text.h"
 #include "gtx_internal.h"
 
@@ -84,6 +85,15 @@ struct gtx_ctx {
   int2 *d_blkOf = nullptr, *d_blkIv = nullptr; bool refBlocks = false;
   u64 *d_pairAcc = nullptr; bool pairUsed = false;
   int4 *d_pairQ = nullptr; size_t capPairQ = 0, capPairIv = 0; int2 *d_pairQBlk = nullptr, *d_pairQIv = nullptr;
+  // the overlap join (gtx_join.hip) over the envelope index pairAll: the regions' order keys (host copy too), whether the index
+  // is already in key order (-1: not yet looked at), offsets / scan / pair buffers of the host-buffer entry, its queries
+  long long *d_joinKey = nullptr; std::vector<long long> h_joinKey; int joinMono = -1;
+  long long *d_joinOff = nullptr, *d_joinPart = nullptr, *d_joinCut = nullptr; size_t capJoinOff = 0, capJoinPart = 0;
+  int *d_joinPairs = nullptr, *d_joinScratch = nullptr; size_t capJoinPairs = 0, capJoinScratch = 0;
+  unsigned *d_joinBig = nullptr; size_t capJoinBig = 0;
+  int *d_joinReads = nullptr; size_t capJoinReads = 0; int2 *d_joinQBlk = nullptr, *d_joinQIv = nullptr; size_t capJoinQBlk = 0, capJoinQIv = 0;
+  gtx::JoinInfo *d_joinInfo = nullptr;
+  int64_t joinBuffer = 1ll << 26;       // pairs per device chunk of gtx_join (gtx_set_join_buffer)
 
   gtx::DevInfo *d_info = nullptr;       // 2 blocks: the finalize of one call resets the block of the next
   int infoCur = 0;
@@ -269,6 +279,8 @@ void gtx_destroy(gtx_ctx *c)
   dfree(c->d_sortedT); dfree(c->d_segT); dfree(c->d_topT); dfree(c->d_posTE); dfree(c->d_posTS); dfree(c->d_classBaseT);
   dfree(c->d_refS); dfree(c->d_refE); dfree(c->d_refC); dfree(c->d_specialRefs); dfree(c->d_specialIdx); dfree(c->d_specialOut); dfree(c->d_side); dfree(c->d_sideCount);
   dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv); dfree(c->d_pairAcc); dfree(c->d_pairQ); dfree(c->d_pairQBlk); dfree(c->d_pairQIv);
+  dfree(c->d_joinKey); dfree(c->d_joinOff); dfree(c->d_joinPart); dfree(c->d_joinCut); dfree(c->d_joinPairs); dfree(c->d_joinScratch); dfree(c->d_joinBig);
+  dfree(c->d_joinReads); dfree(c->d_joinQBlk); dfree(c->d_joinQIv); dfree(c->d_joinInfo);
   if (c->h_info) (void)hipHostFree(c->h_info);
   for (auto &slot : c->evRing) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
   delete c;
@@ -497,6 +509,7 @@ int gtx_set_refs_ex(gtx_ctx *c, const int32_t *tri, int64_t m, int32_t nClasses,
   }
   dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv); dfree(c->d_pairAcc);
   c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->pairUsed = false;
+  dfree(c->d_joinKey); c->h_joinKey.clear(); c->joinMono = -1;
   c->nRefs = m; c->nValid = nv; c->nClasses = nClasses; c->histLen = histLen;
   c->h_seg = seg;
   c->shareOn = false; dfree(c->d_shareTiles); dfree(c->d_shareRegions); dfree(c->d_shareOwned); c->nShareTiles = 0; c->nShareRegions = 0; c->shareOffset = 0;
@@ -1031,7 +1044,7 @@ int gtx_set_ref_blocks(gtx_ctx *c, const int64_t *first, const int32_t *blocks)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv);
-  c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false;
+  c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->joinMono = -1;
   if (!first) return GTX_OK;                                   // back to single-interval regions
   const int64_t m = c->nRefs;
   if (first[0] != 0) return fail(c, GTX_E_ARG, "gtx_set_ref_blocks: first[0] must be 0");
@@ -1097,6 +1110,226 @@ int gtx_count_add_regions(gtx_ctx *c, const int32_t *env, const int32_t *weights
 }
 
 int gtxi_pairs_on(gtx_ctx *c) { return c && (c->refBlocks || c->pairUsed) ? 1 : 0; }
+
+// ---------------------------------------------------------------------------------------------
+// the overlap join (gtx_join.hip)
+// ---------------------------------------------------------------------------------------------
+} // extern "C"
+
+template <class T> static int grow(gtx_ctx *c, T *&p, size_t &cap, size_t n)
+{
+  if (n <= cap && p) return GTX_OK;
+  dfree(p); cap = 0;
+  HIPCHK(c, hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)));
+  cap = std::max<size_t>(n, 1);
+  return GTX_OK;
+}
+
+// the envelope index over all regions, and whether a query's pairs come out of the walk already in key order: the emit pass
+// writes them by ascending index position, so that holds when (key, ordinal) ascends along the index inside every class --
+// ordinal keys on a position-sorted set (the sorted merge's) are the common case
+static int join_prepare(gtx_ctx *c)
+{
+  if (!c->pairAll.built) { c->joinMono = -1; int rc = build_pair_index(c, &c->pairAll, [](int64_t) { return true; }); if (rc) return rc; }
+  if (c->joinMono >= 0) return GTX_OK;
+  const int n = c->pairAll.n, nc = c->nClasses;
+  std::vector<int32_t> seg(nc + 1), id(std::max(n, 1));
+  HIPCHK(c, hipMemcpy(seg.data(), c->pairAll.ix.seg, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost));
+  if (n) HIPCHK(c, hipMemcpy(id.data(), c->pairAll.ix.id, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  const bool keyed = !c->h_joinKey.empty();
+  bool mono = true;
+  for (int cl = 0; cl < nc && mono; cl++)
+    for (int i = seg[cl] + 1; i < seg[cl + 1] && mono; i++) {
+      const int32_t a = id[i - 1], b = id[i];
+      const long long ka = keyed ? c->h_joinKey[a] : a, kb = keyed ? c->h_joinKey[b] : b;
+      mono = ka < kb || (ka == kb && a < b);
+    }
+  c->joinMono = mono ? 1 : 0;
+  return GTX_OK;
+}
+
+static int join_mode(gtx_ctx *c, uint32_t flags)
+{
+  return ((flags & GTX_ZERO_LENGTH_OK) ? gtx::JOIN_ZERO_OK : 0) | (c->mergeRefs ? gtx::JOIN_MERGE : 0) |
+         ((flags & GTX_CHECK_SORTED) ? gtx::JOIN_CHECK : 0) | ((flags & GTX_JOIN_GAPS) ? gtx::JOIN_GAPS : 0);
+}
+
+// count + scan of the n queries into d_off (n + 1 offsets from 0), *total = d_off[n]; info of the count pass in *hi
+static int join_count(gtx_ctx *c, const gtx::JoinQueries &q, int mode, long long *d_off, int64_t *total, gtx::JoinInfo *hi)
+{
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = join_prepare(c); if (rc) return rc;
+  if (!c->d_joinInfo) { HIPCHK(c, hipMalloc(&c->d_joinInfo, sizeof(gtx::JoinInfo))); }
+  if (!c->d_joinCut) { HIPCHK(c, hipMalloc(&c->d_joinCut, sizeof(long long) * 2)); }
+  rc = grow(c, c->d_joinPart, c->capJoinPart, (size_t)gtx::join_scan_partials(q.n + 1)); if (rc) return rc;
+  const gtx::JoinInfo init = {0, 0, INT64_MAX, INT64_MAX, 0};
+  HIPCHK(c, hipMemcpyAsync(c->d_joinInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  const gtx::RegionBlocks rb{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
+  HIPCHK(c, gtx::launch_join_count(q, c->pairAll.ix, rb, mode, d_off, c->d_joinInfo, c->stream));
+  HIPCHK(c, hipMemsetAsync(d_off + q.n, 0, sizeof(long long), c->stream));
+  HIPCHK(c, gtx::launch_join_scan(d_off, q.n + 1, c->d_joinPart, c->stream));
+  long long t = 0;
+  HIPCHK(c, hipMemcpyAsync(&t, d_off + q.n, sizeof t, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hi, c->d_joinInfo, sizeof *hi, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *total = t;
+  return GTX_OK;
+}
+
+// the pairs of queries [q0, q1) into d_pairs (their offsets relative to d_off[q0]), sorted by key; scratch: a buffer as long
+static int join_emit(gtx_ctx *c, const gtx::JoinQueries &q, int mode, const long long *d_off, int64_t q0, int64_t q1, int *d_pairs, int *d_scratch)
+{
+  const gtx::RegionBlocks rb{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
+  HIPCHK(c, gtx::launch_join_emit(q, q0, q1, c->pairAll.ix, rb, mode, d_off, d_pairs, c->d_joinInfo, c->stream));
+  if (!c->joinMono) {
+    int rc = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(q1 - q0 + 1)); if (rc) return rc;
+    HIPCHK(c, gtx::launch_join_sort(d_off, q0, q1, c->d_joinKey, d_pairs, d_scratch, c->d_joinBig, c->stream));
+  }
+  long long mismatch = 0;
+  HIPCHK(c, hipMemcpyAsync(&mismatch, &c->d_joinInfo->mismatch, sizeof mismatch, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (mismatch) return fail(c, GTX_E_HIP, "gtx_join: the emit pass found another number of pairs than the count pass");
+  return GTX_OK;
+}
+
+// the longest run of queries from q0 whose pairs fit `cap`
+static int join_cut(gtx_ctx *c, const long long *d_off, int64_t q0, int64_t n, int64_t cap, int64_t *q1)
+{
+  HIPCHK(c, gtx::launch_join_cut(d_off, q0, n, cap, c->d_joinCut, c->stream));
+  long long v = 0;
+  HIPCHK(c, hipMemcpyAsync(&v, c->d_joinCut, sizeof v, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *q1 = v;
+  return GTX_OK;
+}
+
+static void join_info_merge(gtx_count_info *info, const gtx::JoinInfo &h, int64_t base)
+{
+  info->n_no_class += h.noClass;
+  info->n_degenerate += h.degenerate;
+  if (h.firstDegenerate != INT64_MAX && info->first_degenerate < 0) info->first_degenerate = h.firstDegenerate + base;
+  if (h.firstUnsorted != INT64_MAX && info->first_unsorted < 0) info->first_unsorted = h.firstUnsorted + base;
+}
+
+extern "C" {
+
+int gtx_set_ref_order(gtx_ctx *c, const int64_t *key)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_set_ref_order: gtx_set_refs has not been called");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_joinKey); c->h_joinKey.clear(); c->joinMono = -1;
+  if (!key || c->nRefs == 0) return GTX_OK;
+  c->h_joinKey.assign(key, key + c->nRefs);
+  HIPCHK(c, hipMalloc(&c->d_joinKey, sizeof(long long) * (size_t)c->nRefs));
+  HIPCHK(c, hipMemcpy(c->d_joinKey, key, sizeof(long long) * (size_t)c->nRefs, hipMemcpyHostToDevice));
+  return GTX_OK;
+}
+
+int gtx_set_join_buffer(gtx_ctx *c, int64_t max_pairs)
+{
+  if (!c) return GTX_E_ARG;
+  if (max_pairs < 1) return fail(c, GTX_E_ARG, "gtx_set_join_buffer: at least one pair");
+  c->joinBuffer = max_pairs;
+  return GTX_OK;
+}
+
+int gtx_join_device(gtx_ctx *c, const void *d_reads, int64_t n, uint32_t flags, void *d_offsets, void *d_pairs, int64_t cap,
+                    int64_t *n_pairs_out, int64_t *n_done_out, gtx_count_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_join_device: gtx_set_refs has not been called");
+  if (n < 0 || (n > 0 && !d_reads) || !d_offsets || cap < 0 || (cap > 0 && !d_pairs)) return fail(c, GTX_E_ARG, "gtx_join_device: bad argument");
+  const int mode = join_mode(c, flags);
+  const gtx::JoinQueries q{(const int *)d_reads, nullptr, nullptr, n};
+  long long *off = (long long *)d_offsets;
+  int64_t total = 0; gtx::JoinInfo hi;
+  int rc = join_count(c, q, mode, off, &total, &hi); if (rc) return rc;
+  int64_t q1 = n;
+  if (total > cap) { rc = join_cut(c, off, 0, n, cap, &q1); if (rc) return rc; }
+  if (q1 > 0) {
+    int64_t len = 0;
+    if (q1 < n) HIPCHK(c, hipMemcpy(&len, off + q1, sizeof len, hipMemcpyDeviceToHost)); else len = total;
+    if (!c->joinMono) { rc = grow(c, c->d_joinScratch, c->capJoinScratch, (size_t)len); if (rc) return rc; }
+    rc = join_emit(c, q, mode, off, 0, q1, (int *)d_pairs, c->d_joinScratch); if (rc) return rc;
+  }
+  if (n_pairs_out) *n_pairs_out = total;
+  if (n_done_out) *n_done_out = q1;
+  if (info) { memset(info, 0, sizeof *info); info->first_unsorted = -1; info->first_degenerate = -1; join_info_merge(info, hi, 0); }
+  return GTX_OK;
+}
+
+int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t n, uint32_t flags,
+             int64_t *offsets_out, int32_t *pairs_out, int64_t cap, gtx_count_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_join: gtx_set_refs has not been called");
+  if (n < 0 || (n > 0 && !reads) || !offsets_out || cap < 0 || (cap > 0 && !pairs_out) || (first && (first[0] != 0 || (first[n] > 0 && !blocks))))
+    return fail(c, GTX_E_ARG, "gtx_join: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int mode = join_mode(c, flags);
+  gtx_count_info acc; memset(&acc, 0, sizeof acc); acc.first_unsorted = -1; acc.first_degenerate = -1;
+  int64_t base = 0;                                            // pairs before the batch
+  offsets_out[0] = 0;
+  const int64_t per = std::max<int64_t>(1, c->batchReads);
+  for (int64_t b0 = 0; b0 < n; b0 += per) {
+    const int64_t b1 = std::min(n, b0 + per), m = b1 - b0;
+    int rc = grow(c, c->d_joinReads, c->capJoinReads, (size_t)(3 * m)); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+    gtx::JoinQueries q{c->d_joinReads, nullptr, nullptr, m};
+    std::vector<int2> qb, iv;
+    if (first && !(mode & gtx::JOIN_GAPS)) {
+      qb.resize((size_t)m);
+      const int64_t i0 = first[b0];
+      if (first[b1] - i0 >= INT32_MAX) return fail(c, GTX_E_ARG, "gtx_join: too many intervals in one batch");
+      for (int64_t i = b0; i < b1; i++) {
+        const int64_t cnt = first[i + 1] - first[i];
+        if (cnt < 1) return fail(c, GTX_E_ARG, "gtx_join: every query has at least one interval");
+        const int32_t *b = blocks + 2 * first[i];
+        if (b[0] != reads[3 * i + 1] || b[2 * cnt - 1] != reads[3 * i + 2]) return fail(c, GTX_E_ARG, "gtx_join: a query's triple must be its envelope");
+        if (!blocks_monotone(b, cnt)) return fail(c, GTX_E_RANGE, "gtx_join: the intervals of a query must be sorted (starts and stops non-decreasing)");
+        qb[i - b0] = make_int2((int)(first[i] - i0), (int)cnt);
+      }
+      iv.resize((size_t)std::max<int64_t>(first[b1] - i0, 1));
+      for (int64_t j = i0; j < first[b1]; j++) iv[j - i0] = make_int2(blocks[2 * j], blocks[2 * j + 1]);
+      rc = grow(c, c->d_joinQBlk, c->capJoinQBlk, qb.size()); if (rc) return rc;
+      rc = grow(c, c->d_joinQIv, c->capJoinQIv, iv.size()); if (rc) return rc;
+      HIPCHK(c, hipMemcpyAsync(c->d_joinQBlk, qb.data(), sizeof(int2) * qb.size(), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->d_joinQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice, c->stream));
+      q.blk = c->d_joinQBlk; q.iv = c->d_joinQIv;
+    }
+    rc = grow(c, c->d_joinOff, c->capJoinOff, (size_t)(m + 1)); if (rc) return rc;
+    int64_t total = 0; gtx::JoinInfo hi;
+    rc = join_count(c, q, mode, c->d_joinOff, &total, &hi); if (rc) return rc;      // (synchronises: qb / iv may go)
+    if ((flags & GTX_CHECK_SORTED) && b0 > 0 && acc.first_unsorted < 0) {           // the seam between two batches comes before the batch's own
+      const int32_t *p = reads + 3 * (b0 - 1), *r = reads + 3 * b0;
+      if (r[0] < p[0] || (r[0] == p[0] && r[1] < p[1])) acc.first_unsorted = b0;
+    }
+    join_info_merge(&acc, hi, b0);
+    HIPCHK(c, hipMemcpy(offsets_out + b0, c->d_joinOff, sizeof(int64_t) * (m + 1), hipMemcpyDeviceToHost));
+    for (int64_t i = b0; i <= b1; i++) offsets_out[i] += base;
+    // pairs chunk by chunk: the longest run of queries that fits the device buffer, or one query alone in a buffer of its size
+    const int64_t chunk = std::min<int64_t>(c->joinBuffer, std::max<int64_t>(total, 1));
+    for (int64_t q0 = 0; q0 < m && offsets_out[b0 + q0] < cap;) {
+      int64_t q1 = m;
+      if (offsets_out[b1] - offsets_out[b0 + q0] > chunk) { rc = join_cut(c, c->d_joinOff, q0, m, chunk, &q1); if (rc) return rc; }
+      if (q1 == q0) q1 = q0 + 1;
+      const int64_t p0 = offsets_out[b0 + q0], len = offsets_out[b0 + q1] - p0;
+      if (len > 0) {
+        rc = grow(c, c->d_joinPairs, c->capJoinPairs, (size_t)len); if (rc) return rc;
+        if (!c->joinMono) { rc = grow(c, c->d_joinScratch, c->capJoinScratch, (size_t)len); if (rc) return rc; }
+        rc = join_emit(c, q, mode, c->d_joinOff, q0, q1, c->d_joinPairs, c->d_joinScratch); if (rc) return rc;
+        const int64_t keep = std::min(len, cap - p0);
+        HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
+      }
+      q0 = q1;
+    }
+    base = offsets_out[b1];
+  }
+  if (info) *info = acc;
+  return GTX_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // coverage

@@ -17,6 +17,7 @@ CHECK_SORTED = 2
 ZERO_LENGTH_OK = 4
 GAPS_FORMULA = 8
 READS_UNSORTED = 16
+JOIN_GAPS = 32
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
 
@@ -133,6 +134,12 @@ ABI = {
     "gtx_count_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_coverage_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_text_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gtx_set_ref_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_set_join_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "gtx_join": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "gtx_join_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "gtx_profile_last": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_profile_count": (ctypes.c_int, [ctypes.c_void_p]),
@@ -282,6 +289,48 @@ class Engine:
     def count_device(self, d_reads, n_reads, d_hits, d_weights=None, flags=READS_SORTED):
         """reads/weights/hits are raw device addresses (e.g. torch tensor .data_ptr()); asynchronous."""
         self._chk(self.lib.gtx_count_device(self.ctx, _ptr(d_reads), _ptr(d_weights), int(n_reads), int(flags), _ptr(d_hits)))
+
+    def set_ref_order(self, key=None):
+        """gtx_set_ref_order: pairs of a query come out in ascending (key[k], k); None: ordinal order."""
+        if key is None:
+            self._chk(self.lib.gtx_set_ref_order(self.ctx, None))
+            return
+        key = np.ascontiguousarray(key, dtype=np.int64)
+        if len(key) != self.n_refs:
+            raise GtxError("set_ref_order: one key per reference region")
+        self._chk(self.lib.gtx_set_ref_order(self.ctx, _ptr(key)))
+
+    def set_join_buffer(self, max_pairs):
+        self._chk(self.lib.gtx_set_join_buffer(self.ctx, int(max_pairs)))
+
+    def join(self, reads, flags=0, first=None, blocks=None, capacity=None):
+        """gtx_join: (offsets [n+1] int64, pairs int32, info); query i's reference ordinals are pairs[offsets[i]:offsets[i+1]].
+        first / blocks: the intervals of multi-interval queries (as set_ref_blocks).  capacity: room for pairs (None: all of them,
+        found by a first call with no room)."""
+        reads = _triples(reads)
+        n = reads.shape[0]
+        if first is not None:
+            first = np.ascontiguousarray(first, dtype=np.int64)
+            blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 2)
+            if len(first) != n + 1 or first[-1] != len(blocks):
+                raise GtxError("join: first must have n + 1 entries and end at len(blocks)")
+        off = np.zeros(n + 1, dtype=np.int64)
+        info = CountInfo()
+        if capacity is None:
+            self._chk(self.lib.gtx_join(self.ctx, _ptr(reads), _ptr(first), _ptr(blocks), n, int(flags), _ptr(off), None, 0, ctypes.byref(info)))
+            capacity = int(off[-1])
+        pairs = np.zeros(max(int(capacity), 1), dtype=np.int32)
+        self._chk(self.lib.gtx_join(self.ctx, _ptr(reads), _ptr(first), _ptr(blocks), n, int(flags), _ptr(off), _ptr(pairs), int(capacity),
+                                    ctypes.byref(info)))
+        return off, pairs[:min(int(capacity), int(off[-1]))], info.as_dict()
+
+    def join_device(self, d_reads, n_reads, d_offsets, d_pairs, capacity, flags=0):
+        """gtx_join_device on raw device addresses: (total pairs, queries done, info)."""
+        tot, done = ctypes.c_int64(0), ctypes.c_int64(0)
+        info = CountInfo()
+        self._chk(self.lib.gtx_join_device(self.ctx, _ptr(d_reads), int(n_reads), int(flags), _ptr(d_offsets), _ptr(d_pairs), int(capacity),
+                                           ctypes.byref(tot), ctypes.byref(done), ctypes.byref(info)))
+        return tot.value, done.value, info.as_dict()
 
     def coverage(self, reads, weights=None, flags=READS_SORTED):
         reads = _triples(reads)

@@ -192,6 +192,45 @@ int gtx_set_ref_blocks(gtx_ctx *ctx, const int64_t *first /* n_refs + 1, or NULL
 int gtx_count_add_regions(gtx_ctx *ctx, const int32_t *env_triples, const int32_t *weights /* may be NULL */,
                           const int64_t *first /* n + 1 */, const int32_t *blocks, int64_t n);
 
+/* ---- genomic_overlaps overlap / intersect: the overlap join ----------------------------------- */
+
+/* The per-pair operations of the reference (genomic_overlaps overlap :706-741, intersect :676-701) walk
+ * GetOverlap / NextOverlap for every query and print one line per (query, reference region) pair.  The join
+ * computes all pairs of a batch of queries at once, as a CSR array: offsets[i] .. offsets[i+1] are the
+ * positions of query i's pairs, each pair the ordinal (position in the set given to gtx_set_refs[_ex]) of a
+ * reference region the query overlaps.  Which pairs: those count would count with the same flags -- the
+ * merge's two comparisons on the envelopes (genomic_intervals.cpp:1225-1236) under the rules of the reference
+ * set (gtx_set_refs_ex) and of GTX_ZERO_LENGTH_OK, then, without GTX_JOIN_GAPS, some pair of intervals
+ * (:1167-1172) over the intervals of gtx_set_ref_blocks and those of multi-interval queries.
+ *
+ * Within a query the pairs follow a per-region order key: ascending (key[k], k).  gtx_set_ref_order sets the
+ * keys (n_refs int64; NULL = the ordinal itself, the default and the order of the sorted merge, :5844-5930).
+ * The bin index of UnsortedGenomicRegionSetOverlaps hands regions out level by level from the finest, bins
+ * ascending within a level, last inserted first within a bin (:5655-5674, :5729-5764); a region's level and
+ * bin depend on the region alone, so that order is the key (level, bin, -ordinal), e.g. its rank.
+ * gtx_set_refs clears the keys.
+ *
+ * gtx_join: queries from host memory (triples; multi-interval queries as in gtx_count_add_regions: first /
+ * blocks, NULL when every query has one interval), offsets_out (n_reads + 1) always complete, pairs_out
+ * receives the first min(offsets_out[n_reads], pair_capacity) pairs.  Internally the queries travel in
+ * batches and the pairs in chunks of at most gtx_set_join_buffer pairs (default 2^26): a chunk is the
+ * longest run of queries that fits, a query with more pairs than that is emitted alone into a buffer of
+ * its own size.  info as for gtx_count (indices are query positions; n_unplaced stays 0).
+ *
+ * gtx_join_device: queries (single-interval triples), offsets (int64[n_reads + 1]) and pairs (int32[pair_capacity])
+ * in this device's HBM.  The offsets of all n_reads queries are written; the pairs of the longest run of
+ * queries from the first whose pairs fit pair_capacity: *n_done_out of them (0 when the first query alone has
+ * more), *n_pairs_out = offsets[n_reads].  Returns with the work complete. */
+#define GTX_JOIN_GAPS       32u  /* gtx_join*: -gaps -- the envelopes alone decide (match_gaps = true)            */
+int gtx_set_ref_order(gtx_ctx *ctx, const int64_t *key /* n_refs, or NULL = ordinal */);
+int gtx_set_join_buffer(gtx_ctx *ctx, int64_t max_pairs);
+int gtx_join(gtx_ctx *ctx, const int32_t *read_triples, const int64_t *first /* n + 1, or NULL */, const int32_t *blocks,
+             int64_t n_reads, uint32_t flags, int64_t *offsets_out /* n_reads + 1 */, int32_t *pairs_out,
+             int64_t pair_capacity, gtx_count_info *info /* may be NULL */);
+int gtx_join_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_reads, uint32_t flags, void *d_offsets,
+                    void *d_pairs, int64_t pair_capacity, int64_t *n_pairs_out, int64_t *n_done_out,
+                    gtx_count_info *info /* may be NULL */);
+
 /* ---- genomic_overlaps coverage / density ------------------------------------------------- */
 
 /* Replaces GenomicRegionSetOverlaps::CalcIndexCoverage (genomic_intervals.cpp:5269-5285, decl
