@@ -1840,50 +1840,66 @@ void PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> 
   }
   out += '\n';
 }
-}  // namespace
 
-void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits)
-{
-  GenomicRegionSet *IS = ov->IndexSet, *QS = ov->QuerySet;
-  const bool sorted = dynamic_cast<SortedGenomicRegionSetOverlaps *>(ov) != NULL;
-  if (!IS->load_in_memory) { fprintf(stderr, "Error: [GtxPrintPairs] the index set must be loaded in memory!\n"); exit(1); }
-  if (QS->format == "GTX") { fprintf(stderr, "Error: overlap / intersect print the query lines: a packed region file has no labels, give the BED text!\n"); exit(1); }
-  const long int M = IS->n_regions;
+bool FitsPacked(long int v) { return v < INT_MAX - 1 && v > INT_MIN + 1; }
 
-  // ---- index side: classes (chromosome rank in strcmp order, x2 + strand unless -i), envelopes, intervals, order keys ----
+// the index side of the join: classes (chromosome rank in strcmp order, x2 + strand unless -i), envelopes, intervals, order keys
+struct JoinIndex {
+  GenomicRegionSet *IS;
+  bool sorted, ignore_strand;
+  long int M;
   std::map<std::string, int> cid;
-  for (long int k = 0; k < M; k++) cid[IS->R[k]->I.front()->CHROMOSOME] = 0;
-  { int n = 0; for (auto &c : cid) c.second = n++; }
-  const int ns = ignore_strand ? 1 : 2, n_classes = std::max<int>(1, (int)cid.size() * ns);
-  auto class_of = [&](const GenomicInterval *i) -> int {
+  int n_classes;
+  std::vector<int32_t> tri, blocks; std::vector<int64_t> first;
+  bool multi = false;                                                   // some region has more than one interval
+  std::set<std::string> valid_chrom;                                    // chromosomes the bin index has (a valid region on them)
+  gtx_ctx *ctx = NULL;
+  int ClassOf(const GenomicInterval *i) const
+  {
     std::map<std::string, int>::const_iterator it = cid.find(i->CHROMOSOME);
-    return it == cid.end() ? -1 : it->second * ns + (ignore_strand ? 0 : (i->STRAND == '-'));
-  };
-  auto fits = [](long int v) { return v < INT_MAX - 1 && v > INT_MIN + 1; };
+    return it == cid.end() ? -1 : it->second * (ignore_strand ? 1 : 2) + (ignore_strand ? 0 : (i->STRAND == '-'));
+  }
+  void Chk(int rc) const { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(ctx)); exit(1); } }
+};
+
+// the index set of the overlaps object on the device (gtx_set_refs_ex, gtx_set_ref_order; the caller sets the blocks).  With
+// single_if_invalid a region that is not compatible, sorted and non-overlapping is given its envelope alone: no pair of it can be
+// printed (the bin index raises its error at the first query, the merge treats it as below), and its intervals may not be what
+// gtx_set_ref_blocks accepts.
+void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char *bin_bits, bool single_if_invalid, JoinIndex &ix)
+{
+  GenomicRegionSet *IS = ov->IndexSet;
+  const long int M = IS->n_regions;
+  ix.IS = IS; ix.M = M; ix.ignore_strand = ignore_strand;
+  ix.sorted = dynamic_cast<SortedGenomicRegionSetOverlaps *>(ov) != NULL;
+  for (long int k = 0; k < M; k++) ix.cid[IS->R[k]->I.front()->CHROMOSOME] = 0;
+  { int n = 0; for (auto &c : ix.cid) c.second = n++; }
+  ix.n_classes = std::max<int>(1, (int)ix.cid.size() * (ignore_strand ? 1 : 2));
   // under the merge an index region out of order or with overlapping blocks is the reference's error when the merge pulls it
   // (LoadIndexBuffer): the regions from there on can pair with no query before that error, so they are placeholders here
   long int v = M;
-  if (sorted) {
+  if (ix.sorted) {
     const bool by_strand = static_cast<SortedGenomicRegionSetOverlaps *>(ov)->sorted_by_strand;
     for (long int k = 0; k < M && v == M; k++)
       if (!IS->R[k]->IsCompatibleSortedAndNonoverlapping() || (k > 0 && IS->R[k]->IsBefore(IS->R[k - 1], by_strand))) v = k;
   }
-  std::vector<int32_t> tri((size_t)3 * std::max<long int>(M, 1)), blocks; std::vector<int64_t> first((size_t)M + 1, 0);
-  std::set<std::string> valid_chrom;                                  // chromosomes the bin index has (a valid region on them)
-  bool multi = false;
+  ix.tri.assign((size_t)3 * std::max<long int>(M, 1), 0); ix.first.assign((size_t)M + 1, 0);
   for (long int k = 0; k < M; k++) {
     GenomicRegion *r = IS->R[k];
     const long int s = r->I.front()->START, e = r->I.back()->STOP;
-    if (k >= v) { tri[3 * k] = -1; tri[3 * k + 1] = 1; tri[3 * k + 2] = 0; blocks.push_back(1); blocks.push_back(0); first[k + 1] = (int64_t)blocks.size() / 2; continue; }
-    if (!fits(s) || !fits(e)) r->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
-    tri[3 * k] = class_of(r->I.front()); tri[3 * k + 1] = (int32_t)s; tri[3 * k + 2] = (int32_t)e;
-    if (r->I.size() > 1) multi = true;
-    for (GenomicInterval *i : r->I) { blocks.push_back((int32_t)i->START); blocks.push_back((int32_t)i->STOP); }
-    first[k + 1] = (int64_t)blocks.size() / 2;
-    if (!(s > e || e <= 0)) valid_chrom.insert(r->I.front()->CHROMOSOME);
+    if (k >= v) { ix.tri[3 * k] = -1; ix.tri[3 * k + 1] = 1; ix.tri[3 * k + 2] = 0; ix.blocks.push_back(1); ix.blocks.push_back(0); ix.first[k + 1] = (int64_t)ix.blocks.size() / 2; continue; }
+    if (!FitsPacked(s) || !FitsPacked(e)) r->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
+    ix.tri[3 * k] = ix.ClassOf(r->I.front()); ix.tri[3 * k + 1] = (int32_t)s; ix.tri[3 * k + 2] = (int32_t)e;
+    if (single_if_invalid && r->I.size() > 1 && !r->IsCompatibleSortedAndNonoverlapping()) { ix.blocks.push_back((int32_t)s); ix.blocks.push_back((int32_t)e); }
+    else {
+      if (r->I.size() > 1) ix.multi = true;
+      for (GenomicInterval *i : r->I) { ix.blocks.push_back((int32_t)i->START); ix.blocks.push_back((int32_t)i->STOP); }
+    }
+    ix.first[k + 1] = (int64_t)ix.blocks.size() / 2;
+    if (!(s > e || e <= 0)) ix.valid_chrom.insert(r->I.front()->CHROMOSOME);
   }
   std::vector<int64_t> key;
-  if (!sorted) {                                                      // the bin index's order: (level, bin, -ordinal) (:5619-5674, :5729-5764)
+  if (!ix.sorted) {                                                   // the bin index's order: (level, bin, -ordinal) (:5619-5674, :5729-5764)
     std::vector<int> bits;
     std::string bb = bin_bits ? bin_bits : "";
     if (bb.empty()) bits = {17, 20, 23, 26, 60};
@@ -1904,12 +1920,59 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
     key.resize((size_t)std::max<long int>(M, 1));
     for (long int j = 0; j < M; j++) key[lb[j].k] = j;
   }
-  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
-  auto chk = [&](int rc) { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(ctx)); exit(1); } };
-  chk(gtx_set_refs_ex(ctx, tri.data(), M, n_classes, sorted ? GTX_REFS_KEEP_ZERO_LENGTH : 0));
-  chk(gtx_set_ref_blocks(ctx, multi && !match_gaps ? first.data() : NULL, blocks.data()));
-  chk(gtx_set_ref_order(ctx, sorted ? NULL : key.data()));
-  const uint32_t flags = (sorted ? GTX_ZERO_LENGTH_OK : 0) | (match_gaps ? GTX_JOIN_GAPS : 0);
+  ix.ctx = gtx_group_ctx(Devices(), 0);
+  ix.Chk(gtx_set_refs_ex(ix.ctx, ix.tri.data(), M, ix.n_classes, ix.sorted ? GTX_REFS_KEEP_ZERO_LENGTH : 0));
+  ix.Chk(gtx_set_ref_order(ix.ctx, ix.sorted ? NULL : key.data()));
+}
+
+// the reference's query loop on the overlaps object: errors, the merge's buffer and Done() (its early stop) come from the class
+// layer; add(q) takes every query in order.  Returns with err set when the loop stopped at an error.
+void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &err, const std::function<void(GenomicRegion *)> &add)
+{
+  tls_load_error = &err;
+  try {
+    bool index_checked = ix.sorted;
+    for (GenomicRegion *q = ov->GetQuery(); ov->Done() == false; q = ov->NextQuery()) {
+      if (!index_checked) {                                               // the bin index is built at the first query's match (:5603-5616)
+        for (long int k = 0; k < ix.M; k++)
+          if (!ix.IS->R[k]->IsCompatibleSortedAndNonoverlapping()) ix.IS->R[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
+        index_checked = true;
+      }
+      GenomicInterval *f = q->I.front();
+      const long int s = f->START, e = q->I.back()->STOP;
+      if (ix.sorted) { for (GenomicRegion *r = ov->GetMatch(); r; r = ov->NextMatch()) {} }   // the merge's buffer as the reference's walk leaves it
+      else if (ix.valid_chrom.count(f->CHROMOSOME)) {                    // :5740-5741, on chromosomes the index knows
+        if (e <= 0) q->PrintError("stop position must be positive!");
+        if (s > e) q->PrintError("start position cannot be greater than stop position!");
+      }
+      if (!FitsPacked(s) || !FitsPacked(e)) q->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
+      add(q);
+    }
+  } catch (const LoadAbort &) {}
+  tls_load_error = NULL;
+}
+
+// the error the loop stopped at, as the reference prints it (after the output before it)
+void ExitOnLoadError(const LoadError &err)
+{
+  fflush(stdout);
+  if (!err.set) return;
+  fprintf(stderr, "\n");
+  if (err.with_prefix) fprintf(stderr, "Error: Line %ld: %s\n", err.line, err.msg.c_str()); else fprintf(stderr, "%s\n", err.msg.c_str());
+  exit(1);
+}
+}  // namespace
+
+void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits)
+{
+  GenomicRegionSet *IS = ov->IndexSet, *QS = ov->QuerySet;
+  if (!IS->load_in_memory) { fprintf(stderr, "Error: [GtxPrintPairs] the index set must be loaded in memory!\n"); exit(1); }
+  if (QS->format == "GTX") { fprintf(stderr, "Error: overlap / intersect print the query lines: a packed region file has no labels, give the BED text!\n"); exit(1); }
+  JoinIndex ix;
+  BuildJoinIndex(ov, ignore_strand, bin_bits, false, ix);
+  gtx_ctx *ctx = ix.ctx;
+  ix.Chk(gtx_set_ref_blocks(ctx, ix.multi && !match_gaps ? ix.first.data() : NULL, ix.blocks.data()));
+  const uint32_t flags = (ix.sorted ? GTX_ZERO_LENGTH_OK : 0) | (match_gaps ? GTX_JOIN_GAPS : 0);
 
   // ---- query side: batches of the queries the loop hands out, joined and printed in order ----
   const size_t kBatch = 1 << 20;
@@ -1923,10 +1986,10 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
     off.assign((size_t)n + 1, 0);
     if (pairs.empty()) pairs.resize(1 << 16);
     gtx_count_info info;
-    chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
+    ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
     if (off[n] > (int64_t)pairs.size()) {
       pairs.resize((size_t)off[n]);
-      chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
+      ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
     }
     std::vector<long int> civ;
     for (int64_t i = 0; i < n; i++) {
@@ -1954,41 +2017,136 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
   };
 
   LoadError err;
-  tls_load_error = &err;
-  try {
-    bool index_checked = sorted;
-    for (GenomicRegion *q = ov->GetQuery(); ov->Done() == false; q = ov->NextQuery()) {
-      if (!index_checked) {                                               // the bin index is built at the first query's match (:5603-5616)
-        for (long int k = 0; k < M; k++)
-          if (!IS->R[k]->IsCompatibleSortedAndNonoverlapping()) IS->R[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
-        index_checked = true;
-      }
-      GenomicInterval *f = q->I.front();
-      const long int s = f->START, e = q->I.back()->STOP;
-      if (sorted) { for (GenomicRegion *r = ov->GetMatch(); r; r = ov->NextMatch()) {} }   // the merge's buffer as the reference's walk leaves it
-      else if (valid_chrom.count(f->CHROMOSOME)) {                       // :5740-5741, on chromosomes the index knows
-        if (e <= 0) q->PrintError("stop position must be positive!");
-        if (s > e) q->PrintError("start position cannot be greater than stop position!");
-      }
-      if (!fits(s) || !fits(e)) q->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
-      PairQuery pq;
-      pq.chrom = f->CHROMOSOME; pq.strand = f->STRAND; pq.label = q->LABEL;
-      pq.n_tokens = static_cast<GenomicRegionBED *>(q)->n_tokens;
-      ParseTail(QS->CurrentLine(), pq);
-      for (GenomicInterval *i : q->I) { pq.iv.push_back(i->START); pq.iv.push_back(i->STOP); qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
-      if (q->I.size() > 1) qmulti = true;
-      qfirst.push_back((int64_t)qblk.size() / 2);
-      qtri.push_back(class_of(f)); qtri.push_back((int32_t)s); qtri.push_back((int32_t)e);
-      batch.push_back(std::move(pq));
-      if (batch.size() >= kBatch) flush();
-    }
-  } catch (const LoadAbort &) {}
-  tls_load_error = NULL;
+  RunQueryLoop(ov, ix, err, [&](GenomicRegion *q) {
+    GenomicInterval *f = q->I.front();
+    PairQuery pq;
+    pq.chrom = f->CHROMOSOME; pq.strand = f->STRAND; pq.label = q->LABEL;
+    pq.n_tokens = static_cast<GenomicRegionBED *>(q)->n_tokens;
+    ParseTail(QS->CurrentLine(), pq);
+    for (GenomicInterval *i : q->I) { pq.iv.push_back(i->START); pq.iv.push_back(i->STOP); qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
+    if (q->I.size() > 1) qmulti = true;
+    qfirst.push_back((int64_t)qblk.size() / 2);
+    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
+    batch.push_back(std::move(pq));
+    if (batch.size() >= kBatch) flush();
+  });
   flush();                                                                // the pairs before an error are printed, then the error
-  fflush(stdout);
-  if (err.set) {
-    fprintf(stderr, "\n");
-    if (err.with_prefix) fprintf(stderr, "Error: Line %ld: %s\n", err.line, err.msg.c_str()); else fprintf(stderr, "%s\n", err.msg.c_str());
-    exit(1);
+  ExitOnLoadError(err);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// genomic_overlaps offset: the device join and its pair offsets under the reference's per-query loop
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// printf("%ld %ld") / ("%f %f") / -c of one entry (gtools/genomic_overlaps.cpp:566-575): float division by a size_t size
+void AppendOffsets(std::string &out, long int a, long int b, size_t size, bool fraction, bool center)
+{
+  char buf[160];
+  int n;
+  if (center) n = fraction ? snprintf(buf, sizeof buf, "%f", ((float)a / size + (float)b / size) / 2) : snprintf(buf, sizeof buf, "%ld", (a + b) / 2);
+  else n = fraction ? snprintf(buf, sizeof buf, "%f %f", (float)a / size, (float)b / size) : snprintf(buf, sizeof buf, "%ld %ld", a, b);
+  out.append(buf, (size_t)std::min<int>(n, (int)sizeof buf - 1));
+}
+
+// what a line needs of a query, kept until its batch is joined
+struct OffsetQuery { std::string label; long int n_line; size_t n_intervals; long int start, stop; };
+}  // namespace
+
+void GtxPrintOffsets(GenomicRegionSetOverlaps *ov, const char *op, bool skip_ref_gaps, bool fraction, bool center, bool print_labels,
+                     bool match_gaps, bool ignore_strand, const char *bin_bits)
+{
+  GenomicRegionSet *IS = ov->IndexSet;
+  if (!IS->load_in_memory) { fprintf(stderr, "Error: [GtxPrintOffsets] the index set must be loaded in memory!\n"); exit(1); }
+  JoinIndex ix;
+  BuildJoinIndex(ov, ignore_strand, bin_bits, true, ix);
+  gtx_ctx *ctx = ix.ctx;
+  const bool sorted = ix.sorted;
+  // the reference point's front / back intervals and strand: the index regions' unless -S, where the merge's queries are the
+  // reference file (its branch :545-583) and the index regions' envelopes are offset
+  ix.Chk(gtx_set_ref_blocks(ctx, ix.multi ? ix.first.data() : NULL, ix.blocks.data()));
+  {
+    std::vector<int8_t> strand((size_t)std::max<long int>(ix.M, 1), '+');
+    for (long int k = 0; k < ix.M; k++) strand[k] = IS->R[k]->I.front()->STRAND == '-' ? '-' : '+';
+    ix.Chk(gtx_set_ref_strands(ctx, strand.data()));
   }
+  const std::string ops = op;
+  const int32_t code = ops == "1" ? GTX_OFFSET_1 : ops == "2" ? GTX_OFFSET_2 : ops == "5p" ? GTX_OFFSET_5P : ops == "3p" ? GTX_OFFSET_3P : 0;
+  const uint32_t flags = (sorted ? GTX_ZERO_LENGTH_OK | GTX_OFFSET_FROM_QUERY : 0) | (match_gaps ? GTX_JOIN_GAPS : 0) |
+                         (skip_ref_gaps ? GTX_OFFSET_SKIP_REF_GAPS : 0);
+  // GetSize of the reference region: the envelope (:1047-1055), with --skip-ref-gaps the sum of its intervals (GetSize() of an
+  // interval: 0 when inverted, :488-491)
+  auto ref_size = [&](GenomicRegion *r) -> size_t {
+    if (!skip_ref_gaps) return r->I.back()->STOP - r->I.front()->START + 1;
+    size_t z = 0;
+    for (GenomicInterval *i : r->I) z += i->START > i->STOP ? 0 : i->STOP - i->START + 1;
+    return z;
+  };
+  std::vector<size_t> isize((size_t)std::max<long int>(ix.M, 1));
+  for (long int k = 0; k < ix.M; k++) isize[k] = ref_size(IS->R[k]);
+
+  const size_t kBatch = 1 << 20;
+  std::vector<OffsetQuery> batch; batch.reserve(4096);
+  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst(1, 0), off, eoff, ent; std::vector<int32_t> pairs; std::vector<int8_t> qstrand;
+  bool qmulti = false;
+  std::string out;
+  auto die = [&](const char *msg) { fwrite(out.data(), 1, out.size(), stdout); fflush(stdout); fprintf(stderr, "%s", msg); exit(1); };
+  auto die_line = [&](long int n_line, const char *msg) {
+    fwrite(out.data(), 1, out.size(), stdout); fflush(stdout); fprintf(stderr, "\nError: Line %ld: %s\n", n_line, msg); exit(1);
+  };
+  auto flush = [&]() {
+    const int64_t n = (int64_t)batch.size();
+    if (n == 0) return;
+    off.assign((size_t)n + 1, 0);
+    if (pairs.empty()) { pairs.resize(1 << 16); eoff.resize(pairs.size() + 1); ent.resize(2 * pairs.size()); }
+    int64_t inverted = -1;
+    auto join = [&]() {
+      ix.Chk(gtx_join_offsets(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), sorted ? qstrand.data() : NULL, n, flags,
+                              code ? code : GTX_OFFSET_1, off.data(), pairs.data(), (int64_t)pairs.size(), eoff.data(), ent.data(),
+                              (int64_t)ent.size() / 2, &inverted, NULL));
+    };
+    join();
+    const int64_t np = off[n];
+    if (np > (int64_t)pairs.size()) { pairs.resize((size_t)np); eoff.resize((size_t)np + 1); if (!skip_ref_gaps) ent.resize(2 * (size_t)np); join(); }
+    if (eoff[np] > (int64_t)ent.size() / 2) { ent.resize(2 * (size_t)eoff[np]); join(); }
+    for (int64_t i = 0; i < n; i++) {
+      const OffsetQuery &q = batch[i];
+      for (int64_t p = off[i]; p < off[i + 1]; p++) {
+        GenomicRegion *r = IS->R[pairs[p]];
+        if (skip_ref_gaps) {                                                // :634-670: a line only for a pair with entries
+          if (eoff[p + 1] == eoff[p]) continue;
+          if (!code) die("Error: unknown offset reference point operation!\n");
+          out += r->LABEL; out += '\t';
+          if (print_labels) { out += q.label; out += ' '; }
+          for (int64_t e = eoff[p]; e < eoff[p + 1]; e++) AppendOffsets(out, ent[2 * e], ent[2 * e + 1], isize[pairs[p]], fraction, center);
+        } else {
+          // :556-576 (-S: the query is the reference region, r the test region) and :604-624
+          if (sorted ? r->I.size() > 1 : q.n_intervals > 1) die_line(sorted ? r->n_line : q.n_line, "multi-interval test regions are not allowed for this operation!");
+          out += sorted ? q.label.c_str() : r->LABEL; out += '\t';
+          if (print_labels) { out += sorted ? r->LABEL : q.label.c_str(); out += ' '; }
+          if (!code) die("Error: unknown offset reference point operation!\n");
+          if (p == inverted) die("Error: start offset is greater than stop offset (this must be a bug)!\n");
+          const size_t size = sorted ? (size_t)(q.stop - q.start + 1) : isize[pairs[p]];
+          AppendOffsets(out, ent[2 * eoff[p]], ent[2 * eoff[p] + 1], size, fraction, center);
+        }
+        out += '\n';
+        if (out.size() > (1u << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+      }
+    }
+    fwrite(out.data(), 1, out.size(), stdout); out.clear();
+    batch.clear(); qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qstrand.clear(); qmulti = false;
+  };
+
+  LoadError err;
+  RunQueryLoop(ov, ix, err, [&](GenomicRegion *q) {
+    GenomicInterval *f = q->I.front();
+    batch.push_back(OffsetQuery{q->LABEL, q->n_line, q->I.size(), f->START, q->I.back()->STOP});
+    for (GenomicInterval *i : q->I) { qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
+    if (q->I.size() > 1) qmulti = true;
+    qfirst.push_back((int64_t)qblk.size() / 2);
+    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
+    qstrand.push_back(f->STRAND == '-' ? '-' : '+');
+    if (batch.size() >= kBatch) flush();
+  });
+  flush();
+  ExitOnLoadError(err);
 }

@@ -332,6 +332,16 @@ class UnsortedGenomicRegionSetScanner : public GenomicRegionSetScanner
 // streamed BED text set; the index set is loaded in memory.
 void GtxPrintPairs(GenomicRegionSetOverlaps *overlaps, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits);
 
+// genomic_overlaps offset (gtools/genomic_overlaps.cpp:545-670) in bulk, on the overlaps object the driver built: without -S the
+// index set is the reference file and every (reference region, test region) pair prints the test envelope's offsets from the
+// reference region (:595-632), with skip_ref_gaps those of every test interval inside a reference interval, less the gaps
+// (:634-670); under -S the merge's queries are the reference file and the index set the test file (:545-583).  The query loop,
+// its errors and the merge's early stop are GtxPrintPairs'; the offsets come from the device (gtx_join_offsets).  Per-pair errors
+// of the reference (a multi-interval test region, an unknown op, start offset > stop offset) end the output where it would.
+// The index set is loaded in memory.
+void GtxPrintOffsets(GenomicRegionSetOverlaps *overlaps, const char *op, bool skip_ref_gaps, bool fraction, bool center, bool print_labels,
+                     bool match_gaps, bool ignore_strand, const char *bin_bits);
+
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)
 void GtxFinish(int code);                                        // flush and leave without the teardown (see genomic_intervals.cpp)

@@ -1,10 +1,10 @@
-// genomic_overlaps -- MI355X edition of the `count`, `rpkm`, `coverage`, `density`, `overlap` and
-// `intersect` operations of GenomicTools' genomic_overlaps (reference driver: gtools/genomic_overlaps.cpp:
-// 73-261 options, :298-305, :408-431 count, :438-459 coverage, :466-490 density, :676-701 intersect,
-// :706-741 overlap, :746-775 rpkm).  Same command line, same output, same errors; the reductions are
-// GenomicRegionSetOverlaps::CountIndexOverlaps / CalcIndexCoverage of this package and the pairs of
-// overlap / intersect come from the device join (GtxPrintPairs), i.e. HIP kernels through libgtx.so.
-// annotate, bin, dist, offset and subset are outside this path.
+// genomic_overlaps -- MI355X edition of the `count`, `rpkm`, `coverage`, `density`, `offset`, `overlap`
+// and `intersect` operations of GenomicTools' genomic_overlaps (reference driver: gtools/genomic_overlaps.cpp:
+// 73-261 options, :298-305, :408-431 count, :438-459 coverage, :466-490 density, :545-670 offset,
+// :676-701 intersect, :706-741 overlap, :746-775 rpkm).  Same command line, same output, same errors; the
+// reductions are GenomicRegionSetOverlaps::CountIndexOverlaps / CalcIndexCoverage of this package, the pairs
+// of overlap / intersect come from the device join (GtxPrintPairs) and those of offset with their offsets
+// (GtxPrintOffsets), i.e. HIP kernels through libgtx.so.  annotate, bin, dist and subset are outside this path.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,15 +25,16 @@ int main(int argc, char *argv[])
                     "  coverage   Calculates the depth coverage (total number of overlapping nucleotides) per reference region.\n"
                     "  density    Computes the density (coverage divided by the size of the reference region) per reference region.\n"
                     "  intersect  Prints the test regions clipped to each overlapping reference region.\n"
+                    "  offset     Computes the distances of test regions from their overlapping reference regions.\n"
                     "  overlap    Prints the test regions once per overlapping reference region.\n"
                     "  rpkm       Computing reference region RPKM values.\n\n", PROGRAM);
     return 1;
   }
   std::string op = argv[1];
   if (op[0] == '-') op = op.substr(1);                        // compatibility with the old "-count" spelling
-  static const char *others[] = {"annotate", "bin", "dist", "offset", "subset"};
+  static const char *others[] = {"annotate", "bin", "dist", "subset"};
   for (const char *o : others) if (op == o) { fprintf(stderr, "Operation '%s' is outside the MI355X counting path of this build (count, coverage, density, rpkm)!\n", o); return 1; }
-  if (op != "count" && op != "rpkm" && op != "coverage" && op != "density" && op != "overlap" && op != "intersect") { fprintf(stderr, "Unknown operation '%s'!\n", op.c_str()); return 1; }
+  if (op != "count" && op != "rpkm" && op != "coverage" && op != "density" && op != "overlap" && op != "intersect" && op != "offset") { fprintf(stderr, "Unknown operation '%s'!\n", op.c_str()); return 1; }
   const bool per_pair = op == "overlap" || op == "intersect";
 
   bool HELP, HELP2, VERBOSE, IS_SORTED, SORTED_BY_STRAND, IGNORE_STRAND, MATCH_GAPS;
@@ -42,7 +43,7 @@ int main(int argc, char *argv[])
   opts.Flag("--help", &HELP, "help");
   opts.Flag("-h", &HELP2, "help");
   opts.Flag("-v", &VERBOSE, "verbose mode");
-  opts.Str("-B", &BIN_BITS, "17,20,23,26", "number of shift-bits for each bin level (count / coverage: accepted, unused; overlap / intersect: the order of the pairs)");
+  opts.Str("-B", &BIN_BITS, "17,20,23,26", "number of shift-bits for each bin level (count / coverage: accepted, unused; overlap / intersect / offset: the order of the pairs)");
   opts.Flag("-S", &IS_SORTED, "test and reference regions are sorted by chromosome and start position");
   opts.Flag("-s", &SORTED_BY_STRAND, "test and reference regions are also sorted by strand (-S must be set)");
   opts.Flag("-i", &IGNORE_STRAND, "ignore strand while finding overlaps");
@@ -50,12 +51,20 @@ int main(int argc, char *argv[])
   MATCH_GAPS = false; MAX_LABEL_VALUE = 1;
   if (op != "intersect") opts.Flag("-gaps", &MATCH_GAPS, "matching gaps between intervals are considered overlaps");
   if (per_pair) opts.Flag("-label", &MERGE_LABELS, "print test and reference labels as test:reference");
-  if (!per_pair) opts.Long("--max-label-value", &MAX_LABEL_VALUE, 1, "maximum region label value to be used");
+  bool SKIP_REF_GAPS = false, FRACTION = false, CENTER = false; const char *OFFSET_OP = "5p";
+  if (op == "offset") {                                       // :229-236
+    opts.Flag("--skip-ref-gaps", &SKIP_REF_GAPS, "ignore gaps in reference regions when computing offsets");
+    opts.Flag("-label", &MERGE_LABELS, "print test region labels");
+    opts.Str("-op", &OFFSET_OP, "5p", "reference point (1=start, 2=stop, 5p=5'-end, 3p=3'-end)");
+    opts.Flag("-a", &FRACTION, "print distances as a fraction of total size");
+    opts.Flag("-c", &CENTER, "print center of interval only");
+  }
+  if (!per_pair && op != "offset") opts.Long("--max-label-value", &MAX_LABEL_VALUE, 1, "maximum region label value to be used");
   if (op == "count") opts.ULong("-min", &MIN_COUNT, 0, "minimum count");
   else if (op == "coverage") opts.ULong("-min", &MIN_COUNT, 0, "minimum coverage");
   else if (op == "density") opts.Double("-min", &MIN_DENSITY, 0.0, "minimum density");
   else if (op == "rpkm") opts.Double("-min", &MIN_RPKM, 0.0, "minimum RPKM");
-  long NGPU = 0; if (!per_pair) opts.Long("--ngpu", &NGPU, 0, "MI355X: number of GPUs the reduction is spread over, by chromosome, RCCL reduce of the result (default: GTX_NGPU or 1)");
+  long NGPU = 0; if (!per_pair && op != "offset") opts.Long("--ngpu", &NGPU, 0, "MI355X: number of GPUs the reduction is spread over, by chromosome, RCCL reduce of the result (default: GTX_NGPU or 1)");
   int next_arg = opts.Parse(argc, argv, 2);
   if (NGPU > 0) GtxSetDevices((int)NGPU);
   if (HELP || HELP2 || argc - next_arg < 1) { opts.Usage(PROGRAM, op.c_str(), "[OPTIONS] REFERENCE-REGION-FILE <TEST-REGION-FILE>"); return 1; }
@@ -68,6 +77,24 @@ int main(int argc, char *argv[])
 
   char *REF_REG_FILE = argv[next_arg];
   char *TEST_REG_FILE = next_arg + 1 == argc ? NULL : argv[next_arg + 1];
+  if (op == "offset") {                                       // :545-670: both sets without their headers
+    if (IS_SORTED && SKIP_REF_GAPS) {
+      fprintf(stderr, "Error: option --subtract-gaps is not implemented for the -S option. Simply drop the -S and re-run!\n");
+      return 1;
+    }
+    // without -S the reference set is the index (:600-604); under -S the merge's queries are the reference file (:551-555), and
+    // the test set, its index, is loaded in memory here
+    GenomicRegionSet RefRegSet(REF_REG_FILE, BUFFER_SIZE, VERBOSE, !IS_SORTED, true);
+    GenomicRegionSet TestRegSet(TEST_REG_FILE, BUFFER_SIZE, VERBOSE, IS_SORTED, true);
+    GenomicRegionSetOverlaps *overlaps;
+    if (IS_SORTED) overlaps = new SortedGenomicRegionSetOverlaps(&RefRegSet, &TestRegSet, SORTED_BY_STRAND);
+    else overlaps = new UnsortedGenomicRegionSetOverlaps(&TestRegSet, &RefRegSet, BIN_BITS);
+    GtxPrintOffsets(overlaps, OFFSET_OP, SKIP_REF_GAPS, FRACTION, CENTER, MERGE_LABELS, MATCH_GAPS, IGNORE_STRAND, BIN_BITS);
+    GtxMark("output written");
+    GtxFinish(0);
+    delete overlaps;
+    return 0;
+  }
   if (per_pair) {                                             // :676-741: the test set is streamed with its header echoed
     GenomicRegionSet RefRegSet(REF_REG_FILE, BUFFER_SIZE, VERBOSE, true, true);
     GenomicRegionSet TestRegSet(TEST_REG_FILE, BUFFER_SIZE, VERBOSE, false, false);

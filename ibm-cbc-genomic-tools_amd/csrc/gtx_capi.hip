@@ -10,6 +10,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -17,6 +18,7 @@
 #include "gtx_kernels.h"
 #include "gtx_pairs.h"
 #include "gtx_join.h"
+#include "gtx_offset.h"
 #include "gtx_text.h"
 #include "gtx_internal.h"
 
@@ -94,6 +96,10 @@ struct gtx_ctx {
   int *d_joinReads = nullptr; size_t capJoinReads = 0; int2 *d_joinQBlk = nullptr, *d_joinQIv = nullptr; size_t capJoinQBlk = 0, capJoinQIv = 0;
   gtx::JoinInfo *d_joinInfo = nullptr;
   int64_t joinBuffer = 1ll << 26;       // pairs per device chunk of gtx_join (gtx_set_join_buffer)
+  // pair offsets (gtx_offset.hip): per-ordinal front / back interval, strands (gtx_set_ref_strands), the host entry's buffers
+  int4 *d_offRef = nullptr; int8_t *d_refStrand = nullptr; long long *d_offInv = nullptr;
+  long long *d_offOut = nullptr, *d_offCnt = nullptr, *d_offPart = nullptr; size_t capOffOut = 0, capOffCnt = 0, capOffPart = 0;
+  int8_t *d_offQStrand = nullptr; size_t capOffQStrand = 0;
 
   gtx::DevInfo *d_info = nullptr;       // 2 blocks: the finalize of one call resets the block of the next
   int infoCur = 0;
@@ -281,6 +287,7 @@ void gtx_destroy(gtx_ctx *c)
   dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv); dfree(c->d_pairAcc); dfree(c->d_pairQ); dfree(c->d_pairQBlk); dfree(c->d_pairQIv);
   dfree(c->d_joinKey); dfree(c->d_joinOff); dfree(c->d_joinPart); dfree(c->d_joinCut); dfree(c->d_joinPairs); dfree(c->d_joinScratch); dfree(c->d_joinBig);
   dfree(c->d_joinReads); dfree(c->d_joinQBlk); dfree(c->d_joinQIv); dfree(c->d_joinInfo);
+  dfree(c->d_offRef); dfree(c->d_refStrand); dfree(c->d_offInv); dfree(c->d_offOut); dfree(c->d_offCnt); dfree(c->d_offPart); dfree(c->d_offQStrand);
   if (c->h_info) (void)hipHostFree(c->h_info);
   for (auto &slot : c->evRing) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
   delete c;
@@ -510,6 +517,7 @@ int gtx_set_refs_ex(gtx_ctx *c, const int32_t *tri, int64_t m, int32_t nClasses,
   dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv); dfree(c->d_pairAcc);
   c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->pairUsed = false;
   dfree(c->d_joinKey); c->h_joinKey.clear(); c->joinMono = -1;
+  dfree(c->d_offRef); dfree(c->d_refStrand);
   c->nRefs = m; c->nValid = nv; c->nClasses = nClasses; c->histLen = histLen;
   c->h_seg = seg;
   c->shareOn = false; dfree(c->d_shareTiles); dfree(c->d_shareRegions); dfree(c->d_shareOwned); c->nShareTiles = 0; c->nShareRegions = 0; c->shareOffset = 0;
@@ -1044,7 +1052,7 @@ int gtx_set_ref_blocks(gtx_ctx *c, const int64_t *first, const int32_t *blocks)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv);
-  c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->joinMono = -1;
+  c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->joinMono = -1; dfree(c->d_offRef);
   if (!first) return GTX_OK;                                   // back to single-interval regions
   const int64_t m = c->nRefs;
   if (first[0] != 0) return fail(c, GTX_E_ARG, "gtx_set_ref_blocks: first[0] must be 0");
@@ -1260,13 +1268,21 @@ int gtx_join_device(gtx_ctx *c, const void *d_reads, int64_t n, uint32_t flags, 
   return GTX_OK;
 }
 
-int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t n, uint32_t flags,
-             int64_t *offsets_out, int32_t *pairs_out, int64_t cap, gtx_count_info *info)
+} // extern "C"
+
+// the body of gtx_join / gtx_join_offsets: the queries in batches of batchReads, the pairs of each batch in chunks of at most
+// joinBuffer pairs.  on_chunk(q, b0, q0, q1, p0, len) runs when the pairs of the batch's queries [q0, q1) are in d_joinPairs (their
+// offsets relative to d_joinOff[q0]; p0: the position of the first among all pairs).  all_blocks: the queries' intervals go to
+// the device under GTX_JOIN_GAPS too.
+typedef std::function<int(const gtx::JoinQueries &, int64_t, int64_t, int64_t, int64_t, int64_t)> JoinChunk;
+static int join_batches(gtx_ctx *c, const char *who, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t n, uint32_t flags,
+                        bool all_blocks, int64_t *offsets_out, int64_t cap, gtx_count_info *info, const JoinChunk &on_chunk)
 {
+  const std::string w(who);
   if (!c) return GTX_E_ARG;
-  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_join: gtx_set_refs has not been called");
-  if (n < 0 || (n > 0 && !reads) || !offsets_out || cap < 0 || (cap > 0 && !pairs_out) || (first && (first[0] != 0 || (first[n] > 0 && !blocks))))
-    return fail(c, GTX_E_ARG, "gtx_join: bad argument");
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, (w + ": gtx_set_refs has not been called").c_str());
+  if (n < 0 || (n > 0 && !reads) || !offsets_out || cap < 0 || (first && (first[0] != 0 || (first[n] > 0 && !blocks))))
+    return fail(c, GTX_E_ARG, (w + ": bad argument").c_str());
   HIPCHK(c, hipSetDevice(c->device));
   const int mode = join_mode(c, flags);
   gtx_count_info acc; memset(&acc, 0, sizeof acc); acc.first_unsorted = -1; acc.first_degenerate = -1;
@@ -1279,16 +1295,16 @@ int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32
     HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
     gtx::JoinQueries q{c->d_joinReads, nullptr, nullptr, m};
     std::vector<int2> qb, iv;
-    if (first && !(mode & gtx::JOIN_GAPS)) {
+    if (first && (all_blocks || !(mode & gtx::JOIN_GAPS))) {
       qb.resize((size_t)m);
       const int64_t i0 = first[b0];
-      if (first[b1] - i0 >= INT32_MAX) return fail(c, GTX_E_ARG, "gtx_join: too many intervals in one batch");
+      if (first[b1] - i0 >= INT32_MAX) return fail(c, GTX_E_ARG, (w + ": too many intervals in one batch").c_str());
       for (int64_t i = b0; i < b1; i++) {
         const int64_t cnt = first[i + 1] - first[i];
-        if (cnt < 1) return fail(c, GTX_E_ARG, "gtx_join: every query has at least one interval");
+        if (cnt < 1) return fail(c, GTX_E_ARG, (w + ": every query has at least one interval").c_str());
         const int32_t *b = blocks + 2 * first[i];
-        if (b[0] != reads[3 * i + 1] || b[2 * cnt - 1] != reads[3 * i + 2]) return fail(c, GTX_E_ARG, "gtx_join: a query's triple must be its envelope");
-        if (!blocks_monotone(b, cnt)) return fail(c, GTX_E_RANGE, "gtx_join: the intervals of a query must be sorted (starts and stops non-decreasing)");
+        if (b[0] != reads[3 * i + 1] || b[2 * cnt - 1] != reads[3 * i + 2]) return fail(c, GTX_E_ARG, (w + ": a query's triple must be its envelope").c_str());
+        if (!blocks_monotone(b, cnt)) return fail(c, GTX_E_RANGE, (w + ": the intervals of a query must be sorted (starts and stops non-decreasing)").c_str());
         qb[i - b0] = make_int2((int)(first[i] - i0), (int)cnt);
       }
       iv.resize((size_t)std::max<int64_t>(first[b1] - i0, 1));
@@ -1320,14 +1336,164 @@ int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32
         rc = grow(c, c->d_joinPairs, c->capJoinPairs, (size_t)len); if (rc) return rc;
         if (!c->joinMono) { rc = grow(c, c->d_joinScratch, c->capJoinScratch, (size_t)len); if (rc) return rc; }
         rc = join_emit(c, q, mode, c->d_joinOff, q0, q1, c->d_joinPairs, c->d_joinScratch); if (rc) return rc;
-        const int64_t keep = std::min(len, cap - p0);
-        HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
+        rc = on_chunk(q, b0, q0, q1, p0, len); if (rc) return rc;
       }
       q0 = q1;
     }
     base = offsets_out[b1];
   }
   if (info) *info = acc;
+  return GTX_OK;
+}
+
+extern "C" {
+
+int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t n, uint32_t flags,
+             int64_t *offsets_out, int32_t *pairs_out, int64_t cap, gtx_count_info *info)
+{
+  if (c && c->nRefs >= 0 && cap > 0 && !pairs_out) return fail(c, GTX_E_ARG, "gtx_join: bad argument");
+  return join_batches(c, "gtx_join", reads, first, blocks, n, flags, false, offsets_out, cap, info,
+                      [&](const gtx::JoinQueries &, int64_t, int64_t, int64_t, int64_t p0, int64_t len) {
+                        const int64_t keep = std::min(len, cap - p0);
+                        HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
+                        return GTX_OK;
+                      });
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// pair offsets (gtx_offset.hip)
+// ---------------------------------------------------------------------------------------------
+
+// the per-ordinal reference point (front / back interval) as of gtx_set_ref_blocks
+static int offset_prepare(gtx_ctx *c)
+{
+  if (c->d_offRef) return GTX_OK;
+  const size_t m = (size_t)std::max<int64_t>(c->nRefs, 1);
+  std::vector<int2> env(m, make_int2(0, 0));
+  for (int64_t k = 0; k < c->nRefs; k++) env[k] = make_int2(c->h_refS[k], c->h_refE[k]);
+  int2 *d_env = nullptr;
+  HIPCHK(c, hipMalloc(&d_env, sizeof(int2) * m));
+  HIPCHK(c, hipMalloc(&c->d_offRef, sizeof(int4) * m));
+  hipError_t e = hipMemcpy(d_env, env.data(), sizeof(int2) * m, hipMemcpyHostToDevice);
+  const gtx::RegionBlocks rb{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
+  if (e == hipSuccess) e = gtx::launch_ref_ends(d_env, rb, c->nRefs, c->d_offRef, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dfree(d_env);
+  HIPCHK(c, e);
+  return GTX_OK;
+}
+
+static int offset_op(int32_t op) { return op >= GTX_OFFSET_1 && op <= GTX_OFFSET_3P ? op : 0; }
+
+extern "C" {
+
+int gtx_set_ref_strands(gtx_ctx *c, const int8_t *strand)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_set_ref_strands: gtx_set_refs has not been called");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_refStrand);
+  if (!strand || c->nRefs == 0) return GTX_OK;
+  for (int64_t k = 0; k < c->nRefs; k++)
+    if (strand[k] != '+' && strand[k] != '-') return fail(c, GTX_E_ARG, "gtx_set_ref_strands: a strand is '+' or '-'");
+  HIPCHK(c, hipMalloc(&c->d_refStrand, (size_t)c->nRefs));
+  HIPCHK(c, hipMemcpy(c->d_refStrand, strand, (size_t)c->nRefs, hipMemcpyHostToDevice));
+  return GTX_OK;
+}
+
+int gtx_join_offsets(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32_t *blocks, const int8_t *read_strands, int64_t n,
+                     uint32_t flags, int32_t op, int64_t *offsets_out, int32_t *pairs_out, int64_t cap, int64_t *entry_offsets_out,
+                     int64_t *entries_out, int64_t entry_cap, int64_t *first_inverted_out, gtx_count_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_join_offsets: gtx_set_refs has not been called");
+  const int o = offset_op(op);
+  const bool skip = flags & GTX_OFFSET_SKIP_REF_GAPS, fromQuery = flags & GTX_OFFSET_FROM_QUERY;
+  if (!o || (skip && fromQuery) || cap < 0 || (cap > 0 && (!pairs_out || !entry_offsets_out)) || entry_cap < 0 || (entry_cap > 0 && !entries_out))
+    return fail(c, GTX_E_ARG, "gtx_join_offsets: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = offset_prepare(c); if (rc) return rc;
+  int64_t ebase = 0, inverted = -1, strandsOf = -1;            // entries before the chunk; the first inverted pair; the batch whose strands are up
+  if (cap > 0) entry_offsets_out[0] = 0;
+  if (!c->d_offInv) { HIPCHK(c, hipMalloc(&c->d_offInv, sizeof(long long))); }
+  rc = join_batches(c, "gtx_join_offsets", reads, first, blocks, n, flags, true, offsets_out, cap, info,
+    [&](const gtx::JoinQueries &q, int64_t b0, int64_t q0, int64_t q1, int64_t p0, int64_t len) -> int {
+      int r = GTX_OK;
+      const int64_t keep = std::min(len, cap - p0);
+      HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
+      gtx::OffsetArgs a{q, nullptr, c->d_offRef, c->d_refStrand, gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv}, o, fromQuery};
+      if (fromQuery && read_strands) {
+        if (strandsOf != b0) {
+          const int64_t m = std::min<int64_t>(n - b0, std::max<int64_t>(1, c->batchReads));
+          r = grow(c, c->d_offQStrand, c->capOffQStrand, (size_t)m); if (r) return r;
+          HIPCHK(c, hipMemcpy(c->d_offQStrand, read_strands + b0, (size_t)m, hipMemcpyHostToDevice));
+          strandsOf = b0;
+        }
+        a.qStrand = c->d_offQStrand;
+      }
+      r = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(q1 - q0 + 1)); if (r) return r;
+      int64_t nent = len;
+      if (!skip) {
+        r = grow(c, c->d_offOut, c->capOffOut, (size_t)(2 * len)); if (r) return r;
+        const long long none = INT64_MAX;
+        HIPCHK(c, hipMemcpyAsync(c->d_offInv, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, gtx::launch_pair_offsets(a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offOut, c->d_offInv, c->d_joinBig, c->stream));
+        long long inv = INT64_MAX;
+        HIPCHK(c, hipMemcpyAsync(&inv, c->d_offInv, sizeof inv, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (inverted < 0 && inv < keep) inverted = p0 + inv;
+        for (int64_t p = 1; p <= keep; p++) entry_offsets_out[p0 + p] = ebase + p;
+        nent = keep;
+      } else {
+        r = grow(c, c->d_offCnt, c->capOffCnt, (size_t)(len + 1)); if (r) return r;
+        r = grow(c, c->d_offPart, c->capOffPart, (size_t)gtx::join_scan_partials(len + 1)); if (r) return r;
+        HIPCHK(c, gtx::launch_pair_gaps_count(a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offCnt, c->d_joinBig, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_offCnt + len, 0, sizeof(long long), c->stream));
+        HIPCHK(c, gtx::launch_join_scan(c->d_offCnt, len + 1, c->d_offPart, c->stream));
+        std::vector<int64_t> eoff((size_t)len + 1);
+        HIPCHK(c, hipMemcpyAsync(eoff.data(), c->d_offCnt, sizeof(int64_t) * (len + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        nent = eoff[len];
+        r = grow(c, c->d_offOut, c->capOffOut, (size_t)(2 * nent)); if (r) return r;
+        if (nent > 0) HIPCHK(c, gtx::launch_pair_gaps_emit(a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offCnt, c->d_offOut, c->d_joinBig, c->stream));
+        for (int64_t p = 1; p <= keep; p++) entry_offsets_out[p0 + p] = ebase + eoff[p];
+        nent = eoff[keep];
+      }
+      const int64_t ekeep = std::max<int64_t>(0, std::min(nent, entry_cap - ebase));
+      if (ekeep > 0) HIPCHK(c, hipMemcpy(entries_out + 2 * ebase, c->d_offOut, sizeof(int64_t) * 2 * ekeep, hipMemcpyDeviceToHost));
+      ebase += nent;
+      return GTX_OK;
+    });
+  if (rc) return rc;
+  if (first_inverted_out) *first_inverted_out = inverted;
+  return GTX_OK;
+}
+
+int gtx_pair_offsets_device(gtx_ctx *c, const void *d_reads, int64_t n, const void *d_offsets, const void *d_pairs, int64_t n_pairs, int32_t op,
+                            void *d_out, int64_t *first_inverted_out)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_pair_offsets_device: gtx_set_refs has not been called");
+  const int o = offset_op(op);
+  if (!o || n < 0 || (n > 0 && (!d_reads || !d_offsets)) || n_pairs < 0 || (n_pairs > 0 && (!d_pairs || !d_out)))
+    return fail(c, GTX_E_ARG, "gtx_pair_offsets_device: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = offset_prepare(c); if (rc) return rc;
+  if (!c->d_offInv) { HIPCHK(c, hipMalloc(&c->d_offInv, sizeof(long long))); }
+  rc = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(n + 1)); if (rc) return rc;
+  const gtx::OffsetArgs a{gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n}, nullptr, c->d_offRef, c->d_refStrand,
+                          gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv}, o, false};
+  const long long none = INT64_MAX;
+  HIPCHK(c, hipMemcpyAsync(c->d_offInv, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_pair_offsets(a, 0, n, (const long long *)d_offsets, (const int *)d_pairs, n_pairs, (long long *)d_out, c->d_offInv,
+                                     c->d_joinBig, c->stream));
+  long long inv = INT64_MAX;
+  HIPCHK(c, hipMemcpyAsync(&inv, c->d_offInv, sizeof inv, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (first_inverted_out) *first_inverted_out = inv == INT64_MAX ? -1 : inv;
   return GTX_OK;
 }
 

@@ -18,6 +18,9 @@ ZERO_LENGTH_OK = 4
 GAPS_FORMULA = 8
 READS_UNSORTED = 16
 JOIN_GAPS = 32
+OFFSET_SKIP_REF_GAPS = 64
+OFFSET_FROM_QUERY = 128
+OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
 
@@ -140,6 +143,12 @@ ABI = {
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "gtx_join_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_set_ref_strands": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_join_offsets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_pair_offsets_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "gtx_profile_last": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_profile_count": (ctypes.c_int, [ctypes.c_void_p]),
@@ -177,6 +186,19 @@ def _ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(ctypes.c_void_p)
     return ctypes.c_void_p(int(a))          # raw device/host address
+
+
+def _strands(strand):
+    """'+' / '-' (str, bytes or characters), or 0 / 1, as the int8 characters of the C ABI"""
+    if isinstance(strand, (str, bytes)):
+        a = np.frombuffer(strand.encode() if isinstance(strand, str) else strand, dtype=np.int8)
+    else:
+        a = np.asarray(strand)
+        if a.dtype.kind in "US":
+            a = np.frombuffer("".join(a.tolist()).encode(), dtype=np.int8)
+        else:
+            a = np.where(a.astype(np.int64) != 0, ord("-"), ord("+")).astype(np.int8)
+    return np.ascontiguousarray(a, dtype=np.int8)
 
 
 def _triples(a):
@@ -331,6 +353,54 @@ class Engine:
         self._chk(self.lib.gtx_join_device(self.ctx, _ptr(d_reads), int(n_reads), int(flags), _ptr(d_offsets), _ptr(d_pairs), int(capacity),
                                            ctypes.byref(tot), ctypes.byref(done), ctypes.byref(info)))
         return tot.value, done.value, info.as_dict()
+
+    def set_ref_strands(self, strand=None):
+        """gtx_set_ref_strands: one of '+' / '-' (or 0 '+', 1 '-') per reference region; None: all '+'."""
+        if strand is None:
+            self._chk(self.lib.gtx_set_ref_strands(self.ctx, None))
+            return
+        strand = _strands(strand)
+        if len(strand) != self.n_refs:
+            raise GtxError("set_ref_strands: one strand per reference region")
+        self._chk(self.lib.gtx_set_ref_strands(self.ctx, _ptr(strand)))
+
+    def join_offsets(self, reads, op="5p", flags=0, first=None, blocks=None, strands=None):
+        """gtx_join_offsets: (offsets [n+1], pairs, entry offsets [pairs+1], entries [E, 2] int64, first inverted pair, info).
+        op: "1", "2", "5p", "3p" (or its GTX_OFFSET_* code); strands: the queries' (GTX_OFFSET_FROM_QUERY)."""
+        reads = _triples(reads)
+        n = reads.shape[0]
+        code = OFFSET_OPS[op] if isinstance(op, str) else int(op)
+        if first is not None:
+            first = np.ascontiguousarray(first, dtype=np.int64)
+            blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 2)
+            if len(first) != n + 1 or first[-1] != len(blocks):
+                raise GtxError("join_offsets: first must have n + 1 entries and end at len(blocks)")
+        st = None if strands is None else _strands(strands)
+        off = np.zeros(n + 1, dtype=np.int64)
+        eoff = np.zeros(1, dtype=np.int64)
+        inv = ctypes.c_int64(-1)
+        info = CountInfo()
+
+        def call(pairs, cap, eoff, entries, ecap):
+            self._chk(self.lib.gtx_join_offsets(self.ctx, _ptr(reads), _ptr(first), _ptr(blocks), _ptr(st), n, int(flags), code, _ptr(off),
+                                                _ptr(pairs), int(cap), _ptr(eoff), _ptr(entries), int(ecap), ctypes.byref(inv), ctypes.byref(info)))
+        call(None, 0, None, None, 0)                                           # sizes: the pairs, then their entries
+        cap = int(off[-1])
+        pairs = np.zeros(max(cap, 1), dtype=np.int32)
+        eoff = np.zeros(cap + 1, dtype=np.int64)
+        call(pairs, cap, eoff, None, 0)
+        ecap = int(eoff[-1])
+        entries = np.zeros((max(ecap, 1), 2), dtype=np.int64)
+        call(pairs, cap, eoff, entries, ecap)
+        return off, pairs[:cap], eoff, entries[:ecap], inv.value, info.as_dict()
+
+    def pair_offsets_device(self, d_reads, n_reads, d_offsets, d_pairs, n_pairs, d_out, op="5p"):
+        """gtx_pair_offsets_device on raw device addresses (the pairs gtx_join_device left): the first inverted pair (-1: none)."""
+        code = OFFSET_OPS[op] if isinstance(op, str) else int(op)
+        inv = ctypes.c_int64(-1)
+        self._chk(self.lib.gtx_pair_offsets_device(self.ctx, _ptr(d_reads), int(n_reads), _ptr(d_offsets), _ptr(d_pairs), int(n_pairs), code,
+                                                   _ptr(d_out), ctypes.byref(inv)))
+        return inv.value
 
     def coverage(self, reads, weights=None, flags=READS_SORTED):
         reads = _triples(reads)

@@ -231,6 +231,52 @@ int gtx_join_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_reads, u
                     void *d_pairs, int64_t pair_capacity, int64_t *n_pairs_out, int64_t *n_done_out,
                     gtx_count_info *info /* may be NULL */);
 
+/* ---- genomic_overlaps offset: pair offsets on the join ----------------------------------------- */
+
+/* genomic_overlaps offset (gtools/genomic_overlaps.cpp:545-670) prints, per (test region, reference region)
+ * pair of the join, where the one lies relative to a reference point of the other: GetOffsetFrom
+ * (genomic_intervals.cpp:646-667) takes the front or back interval of the point's region by op and strand
+ * (2, -5p and +3p: the back one), its coordinate (GetCoordinate :465-472: 1 start, 2 stop, 5p / 3p by
+ * strand), and returns {start - ref, stop - ref} of the other region's envelope, or {ref - stop, ref - start}
+ * for -5p and +3p.  The point's strand decides (within a pair the strands agree unless -i, and under -i the
+ * reference's is the one used).
+ *
+ * gtx_set_ref_strands: the strand of every reference region ('+' or '-'; NULL: all '+'), since classes carry
+ * none under -i; gtx_set_refs clears it.  The front / back intervals are those of gtx_set_ref_blocks (or the
+ * envelope of a single-interval region).
+ *
+ * gtx_join_offsets: gtx_join (same queries, flags, offsets_out, pairs_out, pair_capacity, info) plus, for each
+ * pair p of the first min(pairs, pair_capacity), its entries entries_out[2 e], [2 e + 1] (start, stop offset)
+ * for e in entry_offsets_out[p] .. entry_offsets_out[p + 1] (pair_capacity + 1 offsets); entries_out receives
+ * the first entry_capacity entries.  Without GTX_OFFSET_SKIP_REF_GAPS a pair has one entry, its offsets; with
+ * GTX_OFFSET_FROM_QUERY the query is the point (its intervals from first / blocks, its strand from
+ * read_strands, NULL: all '+') and the reference region's envelope is offset -- the sorted branch, where the
+ * merge's queries are the reference file.  With GTX_OFFSET_SKIP_REF_GAPS (CalcOffsetsWithoutGaps :6176-6199;
+ * not with GTX_OFFSET_FROM_QUERY) a pair has one entry per (reference interval k, query interval contained in
+ * it), k outer: that interval's offsets minus the gaps of the reference before interval k (after it for 2,
+ * +3p and -5p); a pair whose query or reference intervals are not sorted and disjoint has none.
+ * *first_inverted_out (may be NULL): the first pair, among those returned, whose start offset exceeds its stop
+ * offset (-1: none; never with GTX_OFFSET_SKIP_REF_GAPS).
+ *
+ * gtx_pair_offsets_device: the entries of the pairs gtx_join_device left in HBM -- n_reads single-interval
+ * queries (its n_done), d_offsets (int64[n_reads + 1], from 0), d_pairs (int32[n_pairs]) -- into d_out
+ * (int64[2 * n_pairs]), op as above, the reference region the point.  Returns with the work complete. */
+#define GTX_OFFSET_1        1    /* -op 1: the start of the front interval                                     */
+#define GTX_OFFSET_2        2    /* -op 2: the stop of the back interval                                       */
+#define GTX_OFFSET_5P       3    /* -op 5p: + the start of the front interval, - the stop of the back one      */
+#define GTX_OFFSET_3P       4    /* -op 3p: + the stop of the back interval, - the start of the front one      */
+#define GTX_OFFSET_SKIP_REF_GAPS 64u   /* gtx_join_offsets: --skip-ref-gaps                                     */
+#define GTX_OFFSET_FROM_QUERY   128u   /* gtx_join_offsets: the query is the reference point (offset -S)        */
+int gtx_set_ref_strands(gtx_ctx *ctx, const int8_t *strand /* n_refs of '+' / '-', or NULL = '+' */);
+int gtx_join_offsets(gtx_ctx *ctx, const int32_t *read_triples, const int64_t *first /* n + 1, or NULL */, const int32_t *blocks,
+                     const int8_t *read_strands /* n_reads, or NULL */, int64_t n_reads, uint32_t flags, int32_t op,
+                     int64_t *offsets_out /* n_reads + 1 */, int32_t *pairs_out, int64_t pair_capacity,
+                     int64_t *entry_offsets_out /* pair_capacity + 1 */, int64_t *entries_out /* 2 x entry_capacity */,
+                     int64_t entry_capacity, int64_t *first_inverted_out /* may be NULL */, gtx_count_info *info /* may be NULL */);
+int gtx_pair_offsets_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_reads, const void *d_offsets, const void *d_pairs,
+                            int64_t n_pairs, int32_t op, void *d_out /* int64[2 * n_pairs] */,
+                            int64_t *first_inverted_out /* may be NULL */);
+
 /* ---- genomic_overlaps coverage / density ------------------------------------------------- */
 
 /* Replaces GenomicRegionSetOverlaps::CalcIndexCoverage (genomic_intervals.cpp:5269-5285, decl
