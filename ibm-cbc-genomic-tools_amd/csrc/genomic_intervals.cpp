@@ -2150,3 +2150,117 @@ void GtxPrintOffsets(GenomicRegionSetOverlaps *ov, const char *op, bool skip_ref
   flush();
   ExitOnLoadError(err);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// genomic_apps profile / heatmap: the signal bins under the reference's per-query loop
+// ---------------------------------------------------------------------------------------------------
+unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *ov, const GtxSignalSpec &spec, std::vector<double> &bins)
+{
+  GenomicRegionSet *IS = ov->IndexSet;
+  if (!IS->load_in_memory) { fprintf(stderr, "Error: [GtxSignalBins] the reference set must be loaded in memory!\n"); exit(1); }
+  JoinIndex ix;
+  BuildJoinIndex(ov, spec.ignore_strand, "17,20,23,26", true, ix);
+  gtx_ctx *ctx = ix.ctx;
+  const long int M = ix.M, B = spec.n_bins;
+  ix.Chk(gtx_set_ref_blocks(ctx, ix.multi ? ix.first.data() : NULL, ix.blocks.data()));
+  std::vector<int8_t> strand((size_t)std::max<long int>(M, 1), '+');
+  for (long int k = 0; k < M; k++) strand[k] = IS->R[k]->I.front()->STRAND == '-' ? '-' : '+';
+  ix.Chk(gtx_set_ref_strands(ctx, strand.data()));
+  // ref_len: GetSize(SKIP_REF_GAPS) under --norm-ref-length (a size_t), else 1
+  std::vector<int64_t> ref_len((size_t)std::max<long int>(M, 1), 1);
+  if (spec.norm_ref_len) for (long int k = 0; k < M; k++) ref_len[k] = (int64_t)IS->R[k]->GetSize(spec.skip_ref_gaps);
+  ix.Chk(gtx_set_signal_bins(ctx, spec.bin_min, spec.bin_max, B, spec.norm_ref_len ? ref_len.data() : NULL));
+  const uint32_t flags = spec.per_ref ? GTX_SIGNAL_PER_REF : 0;
+  const size_t len = (size_t)std::max<long int>(0, (spec.per_ref ? M : 1) * B);
+
+  // integral weights accumulate exactly in int64 on the device; from the first fractional weight on (and under --skip-ref-gaps
+  // from the start) the host adds doubles in the reference's order, starting from the exact integer sums
+  std::vector<int64_t> ibins(len, 0);
+  bins.assign(len, 0.0);
+  bool host = spec.skip_ref_gaps;
+  int64_t abs_sum = 0;
+  const char *kInverted = "Error: start offset is greater than stop offest (this must be a bug)!\n";
+  auto add = [&](long int r, long int a, long int b, double w) {
+    const double x = (double)(a + b) / 2 / (size_t)ref_len[r] + spec.bin_min;
+    const double z = (double)(x - spec.bin_min) / (spec.bin_max - spec.bin_min);
+    if ((z >= 0) && (z < 1)) {
+      const int bin = (int)(B * z);
+      if (bin < B) bins[(spec.per_ref ? (size_t)r * B : 0) + bin] += w;   // bin == n_bins: past the reference's array, dropped
+    }
+  };
+
+  const size_t kBatch = 1 << 20;
+  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst(1, 0), qw, off, eoff, ent; std::vector<double> qwd;
+  std::vector<int32_t> pairs;
+  bool qmulti = false, qfrac = false;
+  unsigned long int n_signal_reg = 0;
+  auto flush = [&]() {
+    const int64_t n = (int64_t)qwd.size();
+    if (n == 0) return;
+    if (!host && qfrac) { host = true; for (size_t k = 0; k < len; k++) bins[k] = (double)ibins[k]; }
+    if (!host) {
+      int64_t inverted = -1; gtx_signal_info info;
+      ix.Chk(gtx_signal_bins(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), spec.max_label_value <= 1 ? NULL : qw.data(), n, flags,
+                             ibins.data(), &inverted, &info));
+      if (inverted >= 0) { fflush(stdout); fprintf(stderr, "%s", kInverted); exit(1); }
+      abs_sum += info.weight_abs_sum;
+      if (abs_sum >= (int64_t)1 << 53) { fprintf(stderr, "Error: the label values summed into the bins reach 2^53: this build bins them exactly only below that!\n"); exit(1); }
+    } else {
+      off.assign((size_t)n + 1, 0);
+      if (pairs.empty()) { pairs.resize(1 << 16); eoff.resize(pairs.size() + 1); ent.resize(2 * pairs.size()); }
+      if (!spec.skip_ref_gaps) {                                           // pairs only: the offsets of the front interval here
+        gtx_count_info info;
+        ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, 0, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
+        if (off[n] > (int64_t)pairs.size()) {
+          pairs.resize((size_t)off[n]);
+          ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, 0, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
+        }
+      } else {                                                             // CalcOffsetsWithoutGaps entries, in its loop order
+        int64_t inverted = -1;
+        auto join = [&]() {
+          ix.Chk(gtx_join_offsets(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), NULL, n, GTX_OFFSET_SKIP_REF_GAPS, GTX_OFFSET_5P,
+                                  off.data(), pairs.data(), (int64_t)pairs.size(), eoff.data(), ent.data(), (int64_t)ent.size() / 2, &inverted, NULL));
+        };
+        join();
+        const int64_t np = off[n];
+        if (np > (int64_t)pairs.size()) { pairs.resize((size_t)np); eoff.resize((size_t)np + 1); join(); }
+        if (eoff[np] > (int64_t)ent.size() / 2) { ent.resize(2 * (size_t)eoff[np]); join(); }
+      }
+      for (int64_t i = 0; i < n; i++) {
+        const int32_t *fq = qblk.data() + 2 * qfirst[i];                    // qreg->I.front()
+        for (int64_t p = off[i]; p < off[i + 1]; p++) {
+          const long int r = pairs[p];
+          if (spec.skip_ref_gaps) { for (int64_t e = eoff[p]; e < eoff[p + 1]; e++) add(r, ent[2 * e], ent[2 * e + 1], qwd[i]); continue; }
+          GenomicRegion *R = IS->R[r];
+          const bool minus = R->I.front()->STRAND == '-';
+          GenomicInterval *ri = minus ? R->I.back() : R->I.front();         // GetOffsetFrom(ireg, "5p")
+          long int a, b;
+          if (minus) { a = ri->STOP - fq[1]; b = ri->STOP - fq[0]; } else { a = fq[0] - ri->START; b = fq[1] - ri->START; }
+          if (a > b) { fflush(stdout); fprintf(stderr, "%s", kInverted); exit(1); }
+          add(r, a, b, qwd[i]);
+        }
+      }
+    }
+    qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qw.clear(); qwd.clear(); qmulti = false; qfrac = false;
+  };
+
+  LoadError err;
+  RunQueryLoop(ov, ix, err, [&](GenomicRegion *q) {
+    n_signal_reg++;
+    GenomicInterval *f = q->I.front();
+    for (GenomicInterval *i : q->I) { qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
+    if (q->I.size() > 1) qmulti = true;
+    qfirst.push_back((int64_t)qblk.size() / 2);
+    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
+    // GetLabelValue(double) (:1072-1076)
+    const double w = spec.max_label_value <= 1 ? 1 : std::min(spec.max_label_value, atof(q->LABEL));
+    const bool integral = w == w && fabs(w) <= 2147483647.0 && w == (double)(int64_t)w;
+    qwd.push_back(w); qw.push_back(integral ? (int64_t)w : 0);
+    if (!integral) qfrac = true;
+    if (qwd.size() >= kBatch) flush();
+  });
+  flush();
+  ExitOnLoadError(err);
+  if (!host) for (size_t k = 0; k < len; k++) bins[k] = (double)ibins[k];
+  return n_signal_reg;
+}

@@ -342,6 +342,21 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *overlaps, bool intersect, bool matc
 void GtxPrintOffsets(GenomicRegionSetOverlaps *overlaps, const char *op, bool skip_ref_gaps, bool fraction, bool center, bool print_labels,
                      bool match_gaps, bool ignore_strand, const char *bin_bits);
 
+// genomic_apps profile / heatmap (gtools/genomic_apps.cpp:560-605, :826-880): for every query of the overlaps object (an
+// UnsortedGenomicRegionSetOverlaps over a reference set loaded in memory and already shifted by the caller), every pair the bin
+// index hands out (match_gaps = false) adds GetLabelValue(max_label_value) to the bin of the 5' offset of the query's front
+// interval from the reference region; with per_ref the bins are one row of n_bins per reference region (by ordinal: the
+// reference's ireg->n_line - n_ref1 when no non-region line follows the first region).  The fused device pass
+// (gtx_signal_bins) takes integral weights; a fractional weight from there on, and --skip-ref-gaps throughout, take the join's
+// pairs (and offsets) to the host, which bins them in the reference's order.  The reference's errors end the run where they
+// would.  Returns the number of queries (n_signal_reg).
+struct GtxSignalSpec {
+  bool ignore_strand, skip_ref_gaps, norm_ref_len, per_ref;
+  double bin_min, bin_max, max_label_value;
+  long int n_bins;
+};
+unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *overlaps, const GtxSignalSpec &spec, std::vector<double> &bins);
+
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)
 void GtxFinish(int code);                                        // flush and leave without the teardown (see genomic_intervals.cpp)

@@ -19,6 +19,7 @@
 #include "gtx_pairs.h"
 #include "gtx_join.h"
 #include "gtx_offset.h"
+#include "gtx_signal.h"
 #include "gtx_text.h"
 #include "gtx_internal.h"
 
@@ -100,6 +101,11 @@ struct gtx_ctx {
   int4 *d_offRef = nullptr; int8_t *d_refStrand = nullptr; long long *d_offInv = nullptr;
   long long *d_offOut = nullptr, *d_offCnt = nullptr, *d_offPart = nullptr; size_t capOffOut = 0, capOffCnt = 0, capOffPart = 0;
   int8_t *d_offQStrand = nullptr; size_t capOffQStrand = 0;
+  // signal bins (gtx_signal.hip): the geometry of gtx_set_signal_bins, per-ordinal reference lengths, the info block, the host
+  // entry's bins and weights
+  bool sigSet = false; double sigMin = 0, sigMax = 0; int64_t sigBins = 0; long long *d_sigRefLen = nullptr;
+  gtx::SignalInfo *d_sigInfo = nullptr; unsigned long long *d_sigBins = nullptr; size_t capSigBins = 0;
+  long long *d_sigW = nullptr; size_t capSigW = 0;
 
   gtx::DevInfo *d_info = nullptr;       // 2 blocks: the finalize of one call resets the block of the next
   int infoCur = 0;
@@ -288,6 +294,7 @@ void gtx_destroy(gtx_ctx *c)
   dfree(c->d_joinKey); dfree(c->d_joinOff); dfree(c->d_joinPart); dfree(c->d_joinCut); dfree(c->d_joinPairs); dfree(c->d_joinScratch); dfree(c->d_joinBig);
   dfree(c->d_joinReads); dfree(c->d_joinQBlk); dfree(c->d_joinQIv); dfree(c->d_joinInfo);
   dfree(c->d_offRef); dfree(c->d_refStrand); dfree(c->d_offInv); dfree(c->d_offOut); dfree(c->d_offCnt); dfree(c->d_offPart); dfree(c->d_offQStrand);
+  dfree(c->d_sigRefLen); dfree(c->d_sigInfo); dfree(c->d_sigBins); dfree(c->d_sigW);
   if (c->h_info) (void)hipHostFree(c->h_info);
   for (auto &slot : c->evRing) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
   delete c;
@@ -518,6 +525,7 @@ int gtx_set_refs_ex(gtx_ctx *c, const int32_t *tri, int64_t m, int32_t nClasses,
   c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->pairUsed = false;
   dfree(c->d_joinKey); c->h_joinKey.clear(); c->joinMono = -1;
   dfree(c->d_offRef); dfree(c->d_refStrand);
+  dfree(c->d_sigRefLen); c->sigSet = false;
   c->nRefs = m; c->nValid = nv; c->nClasses = nClasses; c->histLen = histLen;
   c->h_seg = seg;
   c->shareOn = false; dfree(c->d_shareTiles); dfree(c->d_shareRegions); dfree(c->d_shareOwned); c->nShareTiles = 0; c->nShareRegions = 0; c->shareOffset = 0;
@@ -1270,6 +1278,32 @@ int gtx_join_device(gtx_ctx *c, const void *d_reads, int64_t n, uint32_t flags, 
 
 } // extern "C"
 
+// the intervals of queries [b0, b1) (first / blocks as gtx_join takes them) into d_joinQBlk / d_joinQIv, checked, and q pointed at
+// them; qb / iv hold the host copies until the stream has passed the copies
+static int join_query_blocks(gtx_ctx *c, const std::string &w, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t b0,
+                             int64_t b1, std::vector<int2> &qb, std::vector<int2> &iv, gtx::JoinQueries &q)
+{
+  qb.resize((size_t)(b1 - b0));
+  const int64_t i0 = first[b0];
+  if (first[b1] - i0 >= INT32_MAX) return fail(c, GTX_E_ARG, (w + ": too many intervals in one batch").c_str());
+  for (int64_t i = b0; i < b1; i++) {
+    const int64_t cnt = first[i + 1] - first[i];
+    if (cnt < 1) return fail(c, GTX_E_ARG, (w + ": every query has at least one interval").c_str());
+    const int32_t *b = blocks + 2 * first[i];
+    if (b[0] != reads[3 * i + 1] || b[2 * cnt - 1] != reads[3 * i + 2]) return fail(c, GTX_E_ARG, (w + ": a query's triple must be its envelope").c_str());
+    if (!blocks_monotone(b, cnt)) return fail(c, GTX_E_RANGE, (w + ": the intervals of a query must be sorted (starts and stops non-decreasing)").c_str());
+    qb[i - b0] = make_int2((int)(first[i] - i0), (int)cnt);
+  }
+  iv.resize((size_t)std::max<int64_t>(first[b1] - i0, 1));
+  for (int64_t j = i0; j < first[b1]; j++) iv[j - i0] = make_int2(blocks[2 * j], blocks[2 * j + 1]);
+  int rc = grow(c, c->d_joinQBlk, c->capJoinQBlk, qb.size()); if (rc) return rc;
+  rc = grow(c, c->d_joinQIv, c->capJoinQIv, iv.size()); if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_joinQBlk, qb.data(), sizeof(int2) * qb.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_joinQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice, c->stream));
+  q.blk = c->d_joinQBlk; q.iv = c->d_joinQIv;
+  return GTX_OK;
+}
+
 // the body of gtx_join / gtx_join_offsets: the queries in batches of batchReads, the pairs of each batch in chunks of at most
 // joinBuffer pairs.  on_chunk(q, b0, q0, q1, p0, len) runs when the pairs of the batch's queries [q0, q1) are in d_joinPairs (their
 // offsets relative to d_joinOff[q0]; p0: the position of the first among all pairs).  all_blocks: the queries' intervals go to
@@ -1295,26 +1329,7 @@ static int join_batches(gtx_ctx *c, const char *who, const int32_t *reads, const
     HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
     gtx::JoinQueries q{c->d_joinReads, nullptr, nullptr, m};
     std::vector<int2> qb, iv;
-    if (first && (all_blocks || !(mode & gtx::JOIN_GAPS))) {
-      qb.resize((size_t)m);
-      const int64_t i0 = first[b0];
-      if (first[b1] - i0 >= INT32_MAX) return fail(c, GTX_E_ARG, (w + ": too many intervals in one batch").c_str());
-      for (int64_t i = b0; i < b1; i++) {
-        const int64_t cnt = first[i + 1] - first[i];
-        if (cnt < 1) return fail(c, GTX_E_ARG, (w + ": every query has at least one interval").c_str());
-        const int32_t *b = blocks + 2 * first[i];
-        if (b[0] != reads[3 * i + 1] || b[2 * cnt - 1] != reads[3 * i + 2]) return fail(c, GTX_E_ARG, (w + ": a query's triple must be its envelope").c_str());
-        if (!blocks_monotone(b, cnt)) return fail(c, GTX_E_RANGE, (w + ": the intervals of a query must be sorted (starts and stops non-decreasing)").c_str());
-        qb[i - b0] = make_int2((int)(first[i] - i0), (int)cnt);
-      }
-      iv.resize((size_t)std::max<int64_t>(first[b1] - i0, 1));
-      for (int64_t j = i0; j < first[b1]; j++) iv[j - i0] = make_int2(blocks[2 * j], blocks[2 * j + 1]);
-      rc = grow(c, c->d_joinQBlk, c->capJoinQBlk, qb.size()); if (rc) return rc;
-      rc = grow(c, c->d_joinQIv, c->capJoinQIv, iv.size()); if (rc) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->d_joinQBlk, qb.data(), sizeof(int2) * qb.size(), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(c->d_joinQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice, c->stream));
-      q.blk = c->d_joinQBlk; q.iv = c->d_joinQIv;
-    }
+    if (first && (all_blocks || !(mode & gtx::JOIN_GAPS))) { rc = join_query_blocks(c, w, reads, first, blocks, b0, b1, qb, iv, q); if (rc) return rc; }
     rc = grow(c, c->d_joinOff, c->capJoinOff, (size_t)(m + 1)); if (rc) return rc;
     int64_t total = 0; gtx::JoinInfo hi;
     rc = join_count(c, q, mode, c->d_joinOff, &total, &hi); if (rc) return rc;      // (synchronises: qb / iv may go)
@@ -1494,6 +1509,131 @@ int gtx_pair_offsets_device(gtx_ctx *c, const void *d_reads, int64_t n, const vo
   HIPCHK(c, hipMemcpyAsync(&inv, c->d_offInv, sizeof inv, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (first_inverted_out) *first_inverted_out = inv == INT64_MAX ? -1 : inv;
+  return GTX_OK;
+}
+
+int gtx_set_signal_bins(gtx_ctx *c, double bin_min, double bin_max, int64_t n_bins, const int64_t *ref_len)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_set_signal_bins: gtx_set_refs has not been called");
+  if (n_bins < 0 || n_bins >= INT32_MAX) return fail(c, GTX_E_ARG, "gtx_set_signal_bins: n_bins must lie in [0, 2^31 - 1)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  dfree(c->d_sigRefLen);
+  if (ref_len && c->nRefs > 0) {
+    HIPCHK(c, hipMalloc(&c->d_sigRefLen, sizeof(long long) * (size_t)c->nRefs));
+    HIPCHK(c, hipMemcpy(c->d_sigRefLen, ref_len, sizeof(long long) * (size_t)c->nRefs, hipMemcpyHostToDevice));
+  }
+  c->sigMin = bin_min; c->sigMax = bin_max; c->sigBins = n_bins; c->sigSet = true;
+  return GTX_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// signal bins (gtx_signal.hip)
+// ---------------------------------------------------------------------------------------------
+
+static const uint32_t kSignalFlags = GTX_ZERO_LENGTH_OK | GTX_JOIN_GAPS | GTX_SIGNAL_PER_REF | GTX_READS_SORTED | GTX_READS_UNSORTED;
+
+// the index, the reference points and the info block of a call; a = everything but the reads and their weights
+static int signal_prepare(gtx_ctx *c, const char *who, uint32_t flags, gtx::SignalArgs &a)
+{
+  const std::string w(who);
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, (w + ": gtx_set_refs has not been called").c_str());
+  if (!c->sigSet) return fail(c, GTX_E_STATE, (w + ": gtx_set_signal_bins has not been called").c_str());
+  if (flags & ~kSignalFlags) return fail(c, GTX_E_ARG, (w + ": unknown flag").c_str());
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = join_prepare(c); if (rc) return rc;
+  rc = offset_prepare(c); if (rc) return rc;
+  if (!c->d_sigInfo) { HIPCHK(c, hipMalloc(&c->d_sigInfo, sizeof(gtx::SignalInfo))); }
+  a = gtx::SignalArgs{};
+  a.ix = c->pairAll.ix;
+  a.rb = gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
+  a.mode = join_mode(c, flags & (GTX_ZERO_LENGTH_OK | GTX_JOIN_GAPS));
+  a.refEnds = c->d_offRef; a.refStrand = (const signed char *)c->d_refStrand; a.refLen = c->d_sigRefLen;
+  a.binMin = c->sigMin; a.binMax = c->sigMax; a.nBins = c->sigBins;
+  a.perRef = (flags & GTX_SIGNAL_PER_REF) != 0;
+  return GTX_OK;
+}
+
+static int64_t signal_len(const gtx_ctx *c, uint32_t flags) { return ((flags & GTX_SIGNAL_PER_REF) ? std::max<int64_t>(c->nRefs, 0) : 1) * c->sigBins; }
+static int signal_cus(const gtx_ctx *c) { return (int)std::max<int64_t>(1, c->waveSlots / 32); }
+
+// the info block into *info / *first_inverted_out (read indices from base); waits for the stream
+static int signal_info(gtx_ctx *c, gtx_signal_info *info, long long *firstInv, int64_t base)
+{
+  gtx::SignalInfo h;
+  HIPCHK(c, hipMemcpyAsync(&h, c->d_sigInfo, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (info) {
+    info->n_pairs += (int64_t)h.pairs; info->n_binned += (int64_t)h.binned; info->n_dropped += (int64_t)h.dropped;
+    info->weight_abs_sum += (int64_t)h.absWeight; info->n_no_class += (int64_t)h.noClass; info->n_degenerate += (int64_t)h.degenerate;
+  }
+  if (h.firstInverted != INT64_MAX && *firstInv < 0) *firstInv = h.firstInverted + base;
+  return GTX_OK;
+}
+
+extern "C" {
+
+int gtx_signal_bins_device(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, uint32_t flags, void *d_bins,
+                           int64_t *first_inverted_out, gtx_signal_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  gtx::SignalArgs a;
+  int rc = signal_prepare(c, "gtx_signal_bins_device", flags, a); if (rc) return rc;
+  if (n < 0 || (n > 0 && !d_reads) || (signal_len(c, flags) > 0 && !d_bins)) return fail(c, GTX_E_ARG, "gtx_signal_bins_device: bad argument");
+  a.q = gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n};
+  a.w = (const long long *)d_weights;
+  if (info) memset(info, 0, sizeof *info);
+  const gtx::SignalInfo init = {0, 0, 0, 0, 0, 0, INT64_MAX};
+  HIPCHK(c, hipMemcpyAsync(c->d_sigInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_signal_bins(a, (unsigned long long *)d_bins, c->d_sigInfo, signal_cus(c), c->stream));
+  long long inv = -1;
+  rc = signal_info(c, info, &inv, 0); if (rc) return rc;
+  if (first_inverted_out) *first_inverted_out = inv;
+  return GTX_OK;
+}
+
+int gtx_signal_bins(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32_t *blocks, const int64_t *weights, int64_t n,
+                    uint32_t flags, int64_t *bins_out, int64_t *first_inverted_out, gtx_signal_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  gtx::SignalArgs a;
+  int rc = signal_prepare(c, "gtx_signal_bins", flags, a); if (rc) return rc;
+  const int64_t len = signal_len(c, flags);
+  if (n < 0 || (n > 0 && !reads) || (len > 0 && !bins_out) || (first && (first[0] != 0 || (first[n] > 0 && !blocks))))
+    return fail(c, GTX_E_ARG, "gtx_signal_bins: bad argument");
+  if (info) memset(info, 0, sizeof *info);
+  rc = grow(c, c->d_sigBins, c->capSigBins, (size_t)std::max<int64_t>(len, 1)); if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(c->d_sigBins, 0, sizeof(unsigned long long) * (size_t)std::max<int64_t>(len, 1), c->stream));
+  long long inv = -1;
+  const int64_t per = std::max<int64_t>(1, c->batchReads);
+  const std::string who("gtx_signal_bins");
+  for (int64_t b0 = 0; b0 < n; b0 += per) {
+    const int64_t b1 = std::min(n, b0 + per), m = b1 - b0;
+    rc = grow(c, c->d_joinReads, c->capJoinReads, (size_t)(3 * m)); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+    a.q = gtx::JoinQueries{c->d_joinReads, nullptr, nullptr, m};
+    std::vector<int2> qb, iv;
+    if (first) { rc = join_query_blocks(c, who, reads, first, blocks, b0, b1, qb, iv, a.q); if (rc) return rc; }
+    a.w = nullptr;
+    if (weights) {
+      rc = grow(c, c->d_sigW, c->capSigW, (size_t)m); if (rc) return rc;
+      HIPCHK(c, hipMemcpyAsync(c->d_sigW, weights + b0, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
+      a.w = c->d_sigW;
+    }
+    const gtx::SignalInfo init = {0, 0, 0, 0, 0, 0, INT64_MAX};
+    HIPCHK(c, hipMemcpyAsync(c->d_sigInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, gtx::launch_signal_bins(a, c->d_sigBins, c->d_sigInfo, signal_cus(c), c->stream));
+    rc = signal_info(c, info, &inv, b0); if (rc) return rc;                           // (synchronises: qb / iv may go)
+  }
+  if (len > 0) {
+    std::vector<int64_t> h((size_t)len);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_sigBins, sizeof(int64_t) * (size_t)len, hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < len; k++) bins_out[k] = (int64_t)((uint64_t)bins_out[k] + (uint64_t)h[k]);
+  }
+  if (first_inverted_out) *first_inverted_out = inv;
   return GTX_OK;
 }
 

@@ -31,6 +31,21 @@ struct OffsetArgs {
 
 constexpr int kOffSmallSeg = 32;
 
+// the reference point of a pair: front and back interval of a region and its strand
+struct Point { int2 front, back; bool minus; };
+
+// GenomicInterval::GetOffsetFrom(GenomicRegion *) of the interval [s, e] (genomic_intervals.cpp:646-667, GetCoordinate :465-472):
+// the strand of the point decides both the interval (front / back) and the direction (within a pair the two strands agree
+// unless -i, and under -i the reference's strand is the one used)
+__device__ __forceinline__ void offset_from(const Point &pt, int op, long long s, long long e, long long &a, long long &b)
+{
+  const bool back = op == OFF_2 || (pt.minus && op == OFF_5P) || (!pt.minus && op == OFF_3P);
+  const int2 iv = back ? pt.back : pt.front;
+  const long long ref = op == OFF_1 ? iv.x : op == OFF_2 ? iv.y : op == OFF_5P ? (pt.minus ? iv.y : iv.x) : (pt.minus ? iv.x : iv.y);
+  if ((pt.minus && op == OFF_5P) || (!pt.minus && op == OFF_3P)) { a = ref - e; b = ref - s; }
+  else { a = s - ref; b = e - ref; }
+}
+
 // the pairs of queries [q0, q1): out[2 p], out[2 p + 1] = {start offset, stop offset} of pair p (p relative to off[q0]);
 // *firstInverted = min over the pairs p < nPairs with start > stop (leave it at INT64_MAX beforehand).  big: q1 - q0 + 1 entries.
 hipError_t launch_pair_offsets(const OffsetArgs &a, long long q0, long long q1, const long long *off, const int *pairs, long long nPairs,

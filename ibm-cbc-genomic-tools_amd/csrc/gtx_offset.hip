@@ -5,9 +5,6 @@
 namespace gtx {
 namespace {
 
-// the reference point of a pair: front and back interval of a region and its strand
-struct Point { int2 front, back; bool minus; };
-
 __device__ __forceinline__ Point ref_point(const OffsetArgs &a, int r)
 {
   const int4 v = a.refEnds[r];
@@ -21,18 +18,6 @@ __device__ __forceinline__ Point query_point(const OffsetArgs &a, long long t)
   else { p.front = make_int2(a.q.tri[3 * t + 1], a.q.tri[3 * t + 2]); p.back = p.front; }
   p.minus = a.qStrand != nullptr && a.qStrand[t] == '-';
   return p;
-}
-
-// GenomicInterval::GetOffsetFrom(GenomicRegion *) of the interval [s, e] (genomic_intervals.cpp:646-667, GetCoordinate :465-472):
-// the strand of the point decides both the interval (front / back) and the direction (within a pair the two strands agree
-// unless -i, and under -i the reference's strand is the one used)
-__device__ __forceinline__ void offset_from(const Point &pt, int op, long long s, long long e, long long &a, long long &b)
-{
-  const bool back = op == OFF_2 || (pt.minus && op == OFF_5P) || (!pt.minus && op == OFF_3P);
-  const int2 iv = back ? pt.back : pt.front;
-  const long long ref = op == OFF_1 ? iv.x : op == OFF_2 ? iv.y : op == OFF_5P ? (pt.minus ? iv.y : iv.x) : (pt.minus ? iv.x : iv.y);
-  if ((pt.minus && op == OFF_5P) || (!pt.minus && op == OFF_3P)) { a = ref - e; b = ref - s; }
-  else { a = s - ref; b = e - ref; }
 }
 
 // IsCompatibleSortedAndNonoverlapping (:1139-1161) of an interval list: starts non-decreasing, each start after the last stop

@@ -20,6 +20,7 @@ READS_UNSORTED = 16
 JOIN_GAPS = 32
 OFFSET_SKIP_REF_GAPS = 64
 OFFSET_FROM_QUERY = 128
+SIGNAL_PER_REF = 256
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
@@ -34,6 +35,14 @@ class GtxError(RuntimeError):
 class CountInfo(ctypes.Structure):
     _fields_ = [("first_unsorted", ctypes.c_int64), ("n_no_class", ctypes.c_int64),
                 ("n_degenerate", ctypes.c_int64), ("first_degenerate", ctypes.c_int64), ("n_unplaced", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SignalInfo(ctypes.Structure):
+    _fields_ = [("n_pairs", ctypes.c_int64), ("n_binned", ctypes.c_int64), ("n_dropped", ctypes.c_int64),
+                ("weight_abs_sum", ctypes.c_int64), ("n_no_class", ctypes.c_int64), ("n_degenerate", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -149,6 +158,11 @@ ABI = {
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_pair_offsets_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_set_signal_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p]),
+    "gtx_signal_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_signal_bins_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "gtx_profile_last": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_profile_count": (ctypes.c_int, [ctypes.c_void_p]),
@@ -227,6 +241,7 @@ class Engine:
         if not self.ctx:
             raise GtxError(self.lib.gtx_last_error(None).decode())
         self.n_refs = 0
+        self._sig_bins = 0
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -401,6 +416,46 @@ class Engine:
         self._chk(self.lib.gtx_pair_offsets_device(self.ctx, _ptr(d_reads), int(n_reads), _ptr(d_offsets), _ptr(d_pairs), int(n_pairs), code,
                                                    _ptr(d_out), ctypes.byref(inv)))
         return inv.value
+
+    def set_signal_bins(self, bin_min, bin_max, n_bins, ref_len=None):
+        """gtx_set_signal_bins: the bin geometry; ref_len: one length per reference region (None: 1)."""
+        rl = None
+        if ref_len is not None:
+            rl = np.ascontiguousarray(ref_len, dtype=np.int64)
+            if len(rl) != self.n_refs:
+                raise GtxError("set_signal_bins: one length per reference region")
+        self._chk(self.lib.gtx_set_signal_bins(self.ctx, float(bin_min), float(bin_max), int(n_bins), _ptr(rl)))
+        self._sig_bins = int(n_bins)
+
+    def signal_bins(self, reads, weights=None, flags=0, first=None, blocks=None):
+        """gtx_signal_bins: (bins int64 -- [n_bins], or [n_refs, n_bins] with SIGNAL_PER_REF --, first inverted read, info).
+        weights: int64 per read (None: 1); first / blocks: the intervals of multi-interval reads (as join)."""
+        reads = _triples(reads)
+        n = reads.shape[0]
+        if first is not None:
+            first = np.ascontiguousarray(first, dtype=np.int64)
+            blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 2)
+            if len(first) != n + 1 or first[-1] != len(blocks):
+                raise GtxError("signal_bins: first must have n + 1 entries and end at len(blocks)")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int64)
+        if w is not None and len(w) != n:
+            raise GtxError("signal_bins: one weight per read")
+        rows = self.n_refs if flags & SIGNAL_PER_REF else 1
+        bins = np.zeros(max(rows * self._sig_bins, 1), dtype=np.int64)
+        inv = ctypes.c_int64(-1)
+        info = SignalInfo()
+        self._chk(self.lib.gtx_signal_bins(self.ctx, _ptr(reads), _ptr(first), _ptr(blocks), _ptr(w), n, int(flags), _ptr(bins),
+                                           ctypes.byref(inv), ctypes.byref(info)))
+        bins = bins[:rows * self._sig_bins]
+        return (bins.reshape(rows, self._sig_bins) if flags & SIGNAL_PER_REF else bins), inv.value, info.as_dict()
+
+    def signal_bins_device(self, d_reads, n_reads, d_bins, d_weights=None, flags=0):
+        """gtx_signal_bins_device on raw device addresses (d_bins int64, added to): (first inverted read, info)."""
+        inv = ctypes.c_int64(-1)
+        info = SignalInfo()
+        self._chk(self.lib.gtx_signal_bins_device(self.ctx, _ptr(d_reads), _ptr(d_weights), int(n_reads), int(flags), _ptr(d_bins),
+                                                  ctypes.byref(inv), ctypes.byref(info)))
+        return inv.value, info.as_dict()
 
     def coverage(self, reads, weights=None, flags=READS_SORTED):
         reads = _triples(reads)

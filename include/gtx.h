@@ -277,6 +277,51 @@ int gtx_pair_offsets_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_
                             int64_t n_pairs, int32_t op, void *d_out /* int64[2 * n_pairs] */,
                             int64_t *first_inverted_out /* may be NULL */);
 
+/* ---- genomic_apps profile / heatmap: signal binned around reference points ---------------------- */
+
+/* genomic_apps profile and heatmap (gtools/genomic_apps.cpp:560-605, :826-880) sum, for every (read, reference
+ * region) pair of the bin index, the read's weight into the bin of its offset from the region's 5' point: the
+ * start / stop offset {a, b} of the read's FRONT interval (GetOffsetFrom, genomic_intervals.cpp:646-667, op 5p),
+ *     x = (double)(a + b) / 2 / ref_len + bin_min,  z = (x - bin_min) / (bin_max - bin_min),
+ * and, when 0 <= z < 1, bins[(int)(n_bins * z)] += w -- each step in double, in that order, without fused
+ * multiply-adds.  The pairs are those of gtx_join with the same flags; the regions are the set of gtx_set_refs[_ex]
+ * with its gtx_set_ref_blocks intervals and gtx_set_ref_strands strands (the caller shifts them as the reference does
+ * before it builds its index).  The pairs are not materialised: one pass walks, offsets, bins and accumulates.
+ *
+ * gtx_set_signal_bins: the bin geometry, and ref_len (n_refs values, a size_t each; NULL = 1) for --norm-ref-length.
+ * n_bins in [0, 2^31).  gtx_set_refs clears it.
+ *
+ * Weights are int64 (NULL: 1 per read) and the bins int64 sums (wrap-around).  While every weight is an integer and
+ * no partial sum reaches 2^53 in magnitude, (double)bins[k] is bit-equal to the reference's sequential double sum;
+ * info->weight_abs_sum bounds every partial sum.  A pair with (int)(n_bins * z) == n_bins (rounding, e.g. under
+ * --norm-ref-length) is dropped and counted in n_dropped: the reference writes past its array there.
+ * *first_inverted_out (may be NULL): the first read with a pair whose start offset exceeds its stop offset (the
+ * reference's "this must be a bug" exit; such pairs are not binned), -1: none.
+ *
+ * Layout: one row of n_bins (profile), or with GTX_SIGNAL_PER_REF one row per reference ordinal (heatmap,
+ * n_refs x n_bins, row-major).
+ *
+ * gtx_signal_bins: reads from host memory (triples; multi-interval reads as in gtx_join: first / blocks, NULL when
+ * every read has one interval), in batches; bins_out (the layout above) is ADDED to.  gtx_signal_bins_device:
+ * single-interval triples and weights (int64, may be NULL) in HBM; d_bins (int64, the layout above) is added to.
+ * Both return with the work complete.  flags: GTX_ZERO_LENGTH_OK, GTX_JOIN_GAPS, GTX_SIGNAL_PER_REF. */
+#define GTX_SIGNAL_PER_REF 256u   /* gtx_signal_bins*: one row of bins per reference region (heatmap)          */
+typedef struct gtx_signal_info {
+  int64_t n_pairs;          /* pairs walked                                                           */
+  int64_t n_binned;         /* pairs that landed in a bin                                             */
+  int64_t n_dropped;        /* pairs with 0 <= z < 1 but bin == n_bins                                */
+  int64_t weight_abs_sum;   /* sum of |w| over the binned pairs                                       */
+  int64_t n_no_class;       /* reads whose class is outside [0, n_classes)                            */
+  int64_t n_degenerate;     /* reads with start > stop (+1 under GTX_ZERO_LENGTH_OK): no pairs         */
+} gtx_signal_info;
+int gtx_set_signal_bins(gtx_ctx *ctx, double bin_min, double bin_max, int64_t n_bins, const int64_t *ref_len /* n_refs, or NULL = 1 */);
+int gtx_signal_bins(gtx_ctx *ctx, const int32_t *read_triples, const int64_t *first /* n + 1, or NULL */, const int32_t *blocks,
+                    const int64_t *weights /* n_reads, or NULL = 1 */, int64_t n_reads, uint32_t flags, int64_t *bins_out,
+                    int64_t *first_inverted_out /* may be NULL */, gtx_signal_info *info /* may be NULL */);
+int gtx_signal_bins_device(gtx_ctx *ctx, const void *d_read_triples, const void *d_weights /* int64, may be NULL */, int64_t n_reads,
+                           uint32_t flags, void *d_bins, int64_t *first_inverted_out /* may be NULL */,
+                           gtx_signal_info *info /* may be NULL */);
+
 /* ---- genomic_overlaps coverage / density ------------------------------------------------- */
 
 /* Replaces GenomicRegionSetOverlaps::CalcIndexCoverage (genomic_intervals.cpp:5269-5285, decl
