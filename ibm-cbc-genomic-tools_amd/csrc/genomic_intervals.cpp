@@ -1862,6 +1862,76 @@ struct JoinIndex {
   void Chk(int rc) const { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(ctx)); exit(1); } }
 };
 
+const size_t kQueryBatch = 1 << 20;                                     // queries per device call of the drivers
+
+// the queries RunQueryLoop hands out, as gtx_join takes them, and the strand of each one's front interval
+struct QueryBatch {
+  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst = {0}; std::vector<int8_t> qstrand;
+  bool qmulti = false;                                                  // some query has more than one interval
+  void Add(const JoinIndex &ix, GenomicRegion *q)
+  {
+    GenomicInterval *f = q->I.front();
+    for (GenomicInterval *i : q->I) { qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
+    if (q->I.size() > 1) qmulti = true;
+    qfirst.push_back((int64_t)qblk.size() / 2);
+    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
+    qstrand.push_back(f->STRAND == '-' ? '-' : '+');
+  }
+  void Clear() { qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qstrand.clear(); qmulti = false; }
+  int64_t Size() const { return (int64_t)qstrand.size(); }
+  const int64_t *First() const { return qmulti ? qfirst.data() : NULL; }
+};
+
+// gtx_join of the batch into off / pairs; when the pairs did not fit, pairs grows to them and the join runs again
+void JoinPairs(const JoinIndex &ix, const QueryBatch &qb, uint32_t flags, std::vector<int64_t> &off, std::vector<int32_t> &pairs)
+{
+  const int64_t n = qb.Size();
+  off.assign((size_t)n + 1, 0);
+  if (pairs.empty()) pairs.resize(1 << 16);
+  gtx_count_info info;
+  auto join = [&]() { ix.Chk(gtx_join(ix.ctx, qb.qtri.data(), qb.First(), qb.qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info)); };
+  join();
+  if (off[n] > (int64_t)pairs.size()) { pairs.resize((size_t)off[n]); join(); }
+}
+
+// gtx_join_offsets of the batch into off / pairs / eoff / ent; returns the first inverted pair.  When the pairs did not fit, pairs
+// and eoff grow (and ent, one entry per pair, unless skipping gaps) and the call runs again; then the same for the entries.
+int64_t JoinOffsets(const JoinIndex &ix, const QueryBatch &qb, const int8_t *strands, uint32_t flags, int32_t op, std::vector<int64_t> &off,
+                    std::vector<int32_t> &pairs, std::vector<int64_t> &eoff, std::vector<int64_t> &ent)
+{
+  const int64_t n = qb.Size();
+  off.assign((size_t)n + 1, 0);
+  if (pairs.empty()) { pairs.resize(1 << 16); eoff.resize(pairs.size() + 1); ent.resize(2 * pairs.size()); }
+  int64_t inverted = -1;
+  auto join = [&]() {
+    ix.Chk(gtx_join_offsets(ix.ctx, qb.qtri.data(), qb.First(), qb.qblk.data(), strands, n, flags, op, off.data(), pairs.data(), (int64_t)pairs.size(),
+                            eoff.data(), ent.data(), (int64_t)ent.size() / 2, &inverted, NULL));
+  };
+  join();
+  const int64_t np = off[n];
+  if (np > (int64_t)pairs.size()) {
+    pairs.resize((size_t)np); eoff.resize((size_t)np + 1);
+    if (!(flags & GTX_OFFSET_SKIP_REF_GAPS)) ent.resize(2 * (size_t)np);
+    join();
+  }
+  if (eoff[np] > (int64_t)ent.size() / 2) { ent.resize(2 * (size_t)eoff[np]); join(); }
+  return inverted;
+}
+
+// gtx_set_ref_strands: the strand of each index region's front interval
+void SetRefStrands(const JoinIndex &ix)
+{
+  std::vector<int8_t> strand((size_t)std::max<long int>(ix.M, 1), '+');
+  for (long int k = 0; k < ix.M; k++) strand[k] = ix.IS->R[k]->I.front()->STRAND == '-' ? '-' : '+';
+  ix.Chk(gtx_set_ref_strands(ix.ctx, strand.data()));
+}
+
+// the text so far to stdout once it is longer than `above`
+void WriteOut(std::string &out, size_t above = 0)
+{
+  if (out.size() > above) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+}
+
 // the index set of the overlaps object on the device (gtx_set_refs_ex, gtx_set_ref_order; the caller sets the blocks).  With
 // single_if_invalid a region that is not compatible, sorted and non-overlapping is given its envelope alone: no pair of it can be
 // printed (the bin index raises its error at the first query, the merge treats it as below), and its intervals may not be what
@@ -1975,22 +2045,14 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
   const uint32_t flags = (ix.sorted ? GTX_ZERO_LENGTH_OK : 0) | (match_gaps ? GTX_JOIN_GAPS : 0);
 
   // ---- query side: batches of the queries the loop hands out, joined and printed in order ----
-  const size_t kBatch = 1 << 20;
   std::vector<PairQuery> batch; batch.reserve(4096);
-  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst(1, 0), off; std::vector<int32_t> pairs;
-  bool qmulti = false;
+  QueryBatch qb;
+  std::vector<int64_t> off; std::vector<int32_t> pairs;
   std::string out;
   auto flush = [&]() {
-    const int64_t n = (int64_t)batch.size();
+    const int64_t n = qb.Size();
     if (n == 0) return;
-    off.assign((size_t)n + 1, 0);
-    if (pairs.empty()) pairs.resize(1 << 16);
-    gtx_count_info info;
-    ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
-    if (off[n] > (int64_t)pairs.size()) {
-      pairs.resize((size_t)off[n]);
-      ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, flags, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
-    }
+    JoinPairs(ix, qb, flags, off, pairs);
     std::vector<long int> civ;
     for (int64_t i = 0; i < n; i++) {
       const PairQuery &q = batch[i];
@@ -2009,11 +2071,11 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
           PrintBed(out, q, civ, label, q.n_tokens >= 5 ? q.score : 0, q.n_tokens >= 7 ? std::max(q.thick_start, rs - 1) : rs - 1,
                    q.n_tokens >= 8 ? std::min(q.thick_end, re) : re);
         }
-        if (out.size() > (1u << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+        WriteOut(out, 1u << 22);
       }
     }
-    fwrite(out.data(), 1, out.size(), stdout); out.clear();
-    batch.clear(); qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qmulti = false;
+    WriteOut(out);
+    batch.clear(); qb.Clear();
   };
 
   LoadError err;
@@ -2023,12 +2085,10 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
     pq.chrom = f->CHROMOSOME; pq.strand = f->STRAND; pq.label = q->LABEL;
     pq.n_tokens = static_cast<GenomicRegionBED *>(q)->n_tokens;
     ParseTail(QS->CurrentLine(), pq);
-    for (GenomicInterval *i : q->I) { pq.iv.push_back(i->START); pq.iv.push_back(i->STOP); qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
-    if (q->I.size() > 1) qmulti = true;
-    qfirst.push_back((int64_t)qblk.size() / 2);
-    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
+    for (GenomicInterval *i : q->I) { pq.iv.push_back(i->START); pq.iv.push_back(i->STOP); }
+    qb.Add(ix, q);
     batch.push_back(std::move(pq));
-    if (batch.size() >= kBatch) flush();
+    if (batch.size() >= kQueryBatch) flush();
   });
   flush();                                                                // the pairs before an error are printed, then the error
   ExitOnLoadError(err);
@@ -2064,11 +2124,7 @@ void GtxPrintOffsets(GenomicRegionSetOverlaps *ov, const char *op, bool skip_ref
   // the reference point's front / back intervals and strand: the index regions' unless -S, where the merge's queries are the
   // reference file (its branch :545-583) and the index regions' envelopes are offset
   ix.Chk(gtx_set_ref_blocks(ctx, ix.multi ? ix.first.data() : NULL, ix.blocks.data()));
-  {
-    std::vector<int8_t> strand((size_t)std::max<long int>(ix.M, 1), '+');
-    for (long int k = 0; k < ix.M; k++) strand[k] = IS->R[k]->I.front()->STRAND == '-' ? '-' : '+';
-    ix.Chk(gtx_set_ref_strands(ctx, strand.data()));
-  }
+  SetRefStrands(ix);
   const std::string ops = op;
   const int32_t code = ops == "1" ? GTX_OFFSET_1 : ops == "2" ? GTX_OFFSET_2 : ops == "5p" ? GTX_OFFSET_5P : ops == "3p" ? GTX_OFFSET_3P : 0;
   const uint32_t flags = (sorted ? GTX_ZERO_LENGTH_OK | GTX_OFFSET_FROM_QUERY : 0) | (match_gaps ? GTX_JOIN_GAPS : 0) |
@@ -2084,30 +2140,18 @@ void GtxPrintOffsets(GenomicRegionSetOverlaps *ov, const char *op, bool skip_ref
   std::vector<size_t> isize((size_t)std::max<long int>(ix.M, 1));
   for (long int k = 0; k < ix.M; k++) isize[k] = ref_size(IS->R[k]);
 
-  const size_t kBatch = 1 << 20;
   std::vector<OffsetQuery> batch; batch.reserve(4096);
-  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst(1, 0), off, eoff, ent; std::vector<int32_t> pairs; std::vector<int8_t> qstrand;
-  bool qmulti = false;
+  QueryBatch qb;
+  std::vector<int64_t> off, eoff, ent; std::vector<int32_t> pairs;
   std::string out;
-  auto die = [&](const char *msg) { fwrite(out.data(), 1, out.size(), stdout); fflush(stdout); fprintf(stderr, "%s", msg); exit(1); };
+  auto die = [&](const char *msg) { WriteOut(out); fflush(stdout); fprintf(stderr, "%s", msg); exit(1); };
   auto die_line = [&](long int n_line, const char *msg) {
-    fwrite(out.data(), 1, out.size(), stdout); fflush(stdout); fprintf(stderr, "\nError: Line %ld: %s\n", n_line, msg); exit(1);
+    WriteOut(out); fflush(stdout); fprintf(stderr, "\nError: Line %ld: %s\n", n_line, msg); exit(1);
   };
   auto flush = [&]() {
-    const int64_t n = (int64_t)batch.size();
+    const int64_t n = qb.Size();
     if (n == 0) return;
-    off.assign((size_t)n + 1, 0);
-    if (pairs.empty()) { pairs.resize(1 << 16); eoff.resize(pairs.size() + 1); ent.resize(2 * pairs.size()); }
-    int64_t inverted = -1;
-    auto join = [&]() {
-      ix.Chk(gtx_join_offsets(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), sorted ? qstrand.data() : NULL, n, flags,
-                              code ? code : GTX_OFFSET_1, off.data(), pairs.data(), (int64_t)pairs.size(), eoff.data(), ent.data(),
-                              (int64_t)ent.size() / 2, &inverted, NULL));
-    };
-    join();
-    const int64_t np = off[n];
-    if (np > (int64_t)pairs.size()) { pairs.resize((size_t)np); eoff.resize((size_t)np + 1); if (!skip_ref_gaps) ent.resize(2 * (size_t)np); join(); }
-    if (eoff[np] > (int64_t)ent.size() / 2) { ent.resize(2 * (size_t)eoff[np]); join(); }
+    const int64_t inverted = JoinOffsets(ix, qb, sorted ? qb.qstrand.data() : NULL, flags, code ? code : GTX_OFFSET_1, off, pairs, eoff, ent);
     for (int64_t i = 0; i < n; i++) {
       const OffsetQuery &q = batch[i];
       for (int64_t p = off[i]; p < off[i + 1]; p++) {
@@ -2129,23 +2173,18 @@ void GtxPrintOffsets(GenomicRegionSetOverlaps *ov, const char *op, bool skip_ref
           AppendOffsets(out, ent[2 * eoff[p]], ent[2 * eoff[p] + 1], size, fraction, center);
         }
         out += '\n';
-        if (out.size() > (1u << 22)) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
+        WriteOut(out, 1u << 22);
       }
     }
-    fwrite(out.data(), 1, out.size(), stdout); out.clear();
-    batch.clear(); qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qstrand.clear(); qmulti = false;
+    WriteOut(out);
+    batch.clear(); qb.Clear();
   };
 
   LoadError err;
   RunQueryLoop(ov, ix, err, [&](GenomicRegion *q) {
-    GenomicInterval *f = q->I.front();
-    batch.push_back(OffsetQuery{q->LABEL, q->n_line, q->I.size(), f->START, q->I.back()->STOP});
-    for (GenomicInterval *i : q->I) { qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
-    if (q->I.size() > 1) qmulti = true;
-    qfirst.push_back((int64_t)qblk.size() / 2);
-    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
-    qstrand.push_back(f->STRAND == '-' ? '-' : '+');
-    if (batch.size() >= kBatch) flush();
+    batch.push_back(OffsetQuery{q->LABEL, q->n_line, q->I.size(), q->I.front()->START, q->I.back()->STOP});
+    qb.Add(ix, q);
+    if (batch.size() >= kQueryBatch) flush();
   });
   flush();
   ExitOnLoadError(err);
@@ -2163,9 +2202,7 @@ unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *ov, const GtxSignalSpe
   gtx_ctx *ctx = ix.ctx;
   const long int M = ix.M, B = spec.n_bins;
   ix.Chk(gtx_set_ref_blocks(ctx, ix.multi ? ix.first.data() : NULL, ix.blocks.data()));
-  std::vector<int8_t> strand((size_t)std::max<long int>(M, 1), '+');
-  for (long int k = 0; k < M; k++) strand[k] = IS->R[k]->I.front()->STRAND == '-' ? '-' : '+';
-  ix.Chk(gtx_set_ref_strands(ctx, strand.data()));
+  SetRefStrands(ix);
   // ref_len: GetSize(SKIP_REF_GAPS) under --norm-ref-length (a size_t), else 1
   std::vector<int64_t> ref_len((size_t)std::max<long int>(M, 1), 1);
   if (spec.norm_ref_len) for (long int k = 0; k < M; k++) ref_len[k] = (int64_t)IS->R[k]->GetSize(spec.skip_ref_gaps);
@@ -2189,45 +2226,28 @@ unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *ov, const GtxSignalSpe
     }
   };
 
-  const size_t kBatch = 1 << 20;
-  std::vector<int32_t> qtri, qblk; std::vector<int64_t> qfirst(1, 0), qw, off, eoff, ent; std::vector<double> qwd;
+  QueryBatch qb;
+  std::vector<int64_t> qw, off, eoff, ent; std::vector<double> qwd;
   std::vector<int32_t> pairs;
-  bool qmulti = false, qfrac = false;
+  bool qfrac = false;
   unsigned long int n_signal_reg = 0;
   auto flush = [&]() {
-    const int64_t n = (int64_t)qwd.size();
+    const int64_t n = qb.Size();
     if (n == 0) return;
     if (!host && qfrac) { host = true; for (size_t k = 0; k < len; k++) bins[k] = (double)ibins[k]; }
     if (!host) {
       int64_t inverted = -1; gtx_signal_info info;
-      ix.Chk(gtx_signal_bins(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), spec.max_label_value <= 1 ? NULL : qw.data(), n, flags,
+      ix.Chk(gtx_signal_bins(ctx, qb.qtri.data(), qb.First(), qb.qblk.data(), spec.max_label_value <= 1 ? NULL : qw.data(), n, flags,
                              ibins.data(), &inverted, &info));
       if (inverted >= 0) { fflush(stdout); fprintf(stderr, "%s", kInverted); exit(1); }
       abs_sum += info.weight_abs_sum;
       if (abs_sum >= (int64_t)1 << 53) { fprintf(stderr, "Error: the label values summed into the bins reach 2^53: this build bins them exactly only below that!\n"); exit(1); }
     } else {
-      off.assign((size_t)n + 1, 0);
-      if (pairs.empty()) { pairs.resize(1 << 16); eoff.resize(pairs.size() + 1); ent.resize(2 * pairs.size()); }
-      if (!spec.skip_ref_gaps) {                                           // pairs only: the offsets of the front interval here
-        gtx_count_info info;
-        ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, 0, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
-        if (off[n] > (int64_t)pairs.size()) {
-          pairs.resize((size_t)off[n]);
-          ix.Chk(gtx_join(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), n, 0, off.data(), pairs.data(), (int64_t)pairs.size(), &info));
-        }
-      } else {                                                             // CalcOffsetsWithoutGaps entries, in its loop order
-        int64_t inverted = -1;
-        auto join = [&]() {
-          ix.Chk(gtx_join_offsets(ctx, qtri.data(), qmulti ? qfirst.data() : NULL, qblk.data(), NULL, n, GTX_OFFSET_SKIP_REF_GAPS, GTX_OFFSET_5P,
-                                  off.data(), pairs.data(), (int64_t)pairs.size(), eoff.data(), ent.data(), (int64_t)ent.size() / 2, &inverted, NULL));
-        };
-        join();
-        const int64_t np = off[n];
-        if (np > (int64_t)pairs.size()) { pairs.resize((size_t)np); eoff.resize((size_t)np + 1); join(); }
-        if (eoff[np] > (int64_t)ent.size() / 2) { ent.resize(2 * (size_t)eoff[np]); join(); }
-      }
+      // pairs only: the offsets of the front interval here; under --skip-ref-gaps CalcOffsetsWithoutGaps entries, in its loop order
+      if (!spec.skip_ref_gaps) JoinPairs(ix, qb, 0, off, pairs);
+      else JoinOffsets(ix, qb, NULL, GTX_OFFSET_SKIP_REF_GAPS, GTX_OFFSET_5P, off, pairs, eoff, ent);
       for (int64_t i = 0; i < n; i++) {
-        const int32_t *fq = qblk.data() + 2 * qfirst[i];                    // qreg->I.front()
+        const int32_t *fq = qb.qblk.data() + 2 * qb.qfirst[i];              // qreg->I.front()
         for (int64_t p = off[i]; p < off[i + 1]; p++) {
           const long int r = pairs[p];
           if (spec.skip_ref_gaps) { for (int64_t e = eoff[p]; e < eoff[p + 1]; e++) add(r, ent[2 * e], ent[2 * e + 1], qwd[i]); continue; }
@@ -2241,23 +2261,19 @@ unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *ov, const GtxSignalSpe
         }
       }
     }
-    qtri.clear(); qblk.clear(); qfirst.assign(1, 0); qw.clear(); qwd.clear(); qmulti = false; qfrac = false;
+    qb.Clear(); qw.clear(); qwd.clear(); qfrac = false;
   };
 
   LoadError err;
   RunQueryLoop(ov, ix, err, [&](GenomicRegion *q) {
     n_signal_reg++;
-    GenomicInterval *f = q->I.front();
-    for (GenomicInterval *i : q->I) { qblk.push_back((int32_t)i->START); qblk.push_back((int32_t)i->STOP); }
-    if (q->I.size() > 1) qmulti = true;
-    qfirst.push_back((int64_t)qblk.size() / 2);
-    qtri.push_back(ix.ClassOf(f)); qtri.push_back((int32_t)f->START); qtri.push_back((int32_t)q->I.back()->STOP);
+    qb.Add(ix, q);
     // GetLabelValue(double) (:1072-1076)
     const double w = spec.max_label_value <= 1 ? 1 : std::min(spec.max_label_value, atof(q->LABEL));
     const bool integral = w == w && fabs(w) <= 2147483647.0 && w == (double)(int64_t)w;
     qwd.push_back(w); qw.push_back(integral ? (int64_t)w : 0);
     if (!integral) qfrac = true;
-    if (qwd.size() >= kBatch) flush();
+    if (qwd.size() >= kQueryBatch) flush();
   });
   flush();
   ExitOnLoadError(err);

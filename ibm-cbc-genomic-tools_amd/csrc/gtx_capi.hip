@@ -1050,6 +1050,9 @@ static bool blocks_monotone(const int32_t *b, int64_t cnt)
   return true;
 }
 
+// the reference regions' interval lists as the kernels take them (none: every region is its envelope)
+static gtx::RegionBlocks ref_blocks(const gtx_ctx *c) { return gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv}; }
+
 extern "C" {
 
 int gtx_set_ref_blocks(gtx_ctx *c, const int64_t *first, const int32_t *blocks)
@@ -1119,8 +1122,8 @@ int gtx_count_add_regions(gtx_ctx *c, const int32_t *env, const int32_t *weights
   HIPCHK(c, hipMemcpy(c->d_pairQ, q.data(), sizeof(int4) * (size_t)n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_pairQBlk, qb.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_pairQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, gtx::launch_pair_hit(c->d_pairQ, c->d_pairQBlk, c->d_pairQIv, n, c->pairAll.ix, gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv},
-                                 c->d_pairAcc, c->stream));
+  HIPCHK(c, gtx::launch_pair_hit(c->d_pairQ, c->d_pairQBlk, c->d_pairQIv, n, c->pairAll.ix, ref_blocks(c), c->d_pairAcc,
+                                 c->stream));
   c->pairUsed = true;
   return GTX_OK;
 }
@@ -1180,8 +1183,7 @@ static int join_count(gtx_ctx *c, const gtx::JoinQueries &q, int mode, long long
   rc = grow(c, c->d_joinPart, c->capJoinPart, (size_t)gtx::join_scan_partials(q.n + 1)); if (rc) return rc;
   const gtx::JoinInfo init = {0, 0, INT64_MAX, INT64_MAX, 0};
   HIPCHK(c, hipMemcpyAsync(c->d_joinInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-  const gtx::RegionBlocks rb{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
-  HIPCHK(c, gtx::launch_join_count(q, c->pairAll.ix, rb, mode, d_off, c->d_joinInfo, c->stream));
+  HIPCHK(c, gtx::launch_join_count(q, c->pairAll.ix, ref_blocks(c), mode, d_off, c->d_joinInfo, c->stream));
   HIPCHK(c, hipMemsetAsync(d_off + q.n, 0, sizeof(long long), c->stream));
   HIPCHK(c, gtx::launch_join_scan(d_off, q.n + 1, c->d_joinPart, c->stream));
   long long t = 0;
@@ -1195,8 +1197,7 @@ static int join_count(gtx_ctx *c, const gtx::JoinQueries &q, int mode, long long
 // the pairs of queries [q0, q1) into d_pairs (their offsets relative to d_off[q0]), sorted by key; scratch: a buffer as long
 static int join_emit(gtx_ctx *c, const gtx::JoinQueries &q, int mode, const long long *d_off, int64_t q0, int64_t q1, int *d_pairs, int *d_scratch)
 {
-  const gtx::RegionBlocks rb{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
-  HIPCHK(c, gtx::launch_join_emit(q, q0, q1, c->pairAll.ix, rb, mode, d_off, d_pairs, c->d_joinInfo, c->stream));
+  HIPCHK(c, gtx::launch_join_emit(q, q0, q1, c->pairAll.ix, ref_blocks(c), mode, d_off, d_pairs, c->d_joinInfo, c->stream));
   if (!c->joinMono) {
     int rc = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(q1 - q0 + 1)); if (rc) return rc;
     HIPCHK(c, gtx::launch_join_sort(d_off, q0, q1, c->d_joinKey, d_pairs, d_scratch, c->d_joinBig, c->stream));
@@ -1278,12 +1279,23 @@ int gtx_join_device(gtx_ctx *c, const void *d_reads, int64_t n, uint32_t flags, 
 
 } // extern "C"
 
-// the intervals of queries [b0, b1) (first / blocks as gtx_join takes them) into d_joinQBlk / d_joinQIv, checked, and q pointed at
-// them; qb / iv hold the host copies until the stream has passed the copies
-static int join_query_blocks(gtx_ctx *c, const std::string &w, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t b0,
-                             int64_t b1, std::vector<int2> &qb, std::vector<int2> &iv, gtx::JoinQueries &q)
+// n host queries as gtx_join takes them: triples, and interval lists (first / blocks) or none
+static bool queries_ok(const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t n)
 {
-  qb.resize((size_t)(b1 - b0));
+  return !(n < 0 || (n > 0 && !reads) || (first && (first[0] != 0 || (first[n] > 0 && !blocks))));
+}
+
+// queries [b0, b1) into d_joinReads and q pointed at them; with_blocks: their intervals too (when given) into d_joinQBlk /
+// d_joinQIv, checked.  qb / iv hold the host copies until the stream has passed the copies
+static int stage_queries(gtx_ctx *c, const std::string &w, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t b0,
+                         int64_t b1, bool with_blocks, std::vector<int2> &qb, std::vector<int2> &iv, gtx::JoinQueries &q)
+{
+  const int64_t m = b1 - b0;
+  int rc = grow(c, c->d_joinReads, c->capJoinReads, (size_t)(3 * m)); if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+  q = gtx::JoinQueries{c->d_joinReads, nullptr, nullptr, m};
+  if (!first || !with_blocks) return GTX_OK;
+  qb.resize((size_t)m);
   const int64_t i0 = first[b0];
   if (first[b1] - i0 >= INT32_MAX) return fail(c, GTX_E_ARG, (w + ": too many intervals in one batch").c_str());
   for (int64_t i = b0; i < b1; i++) {
@@ -1296,7 +1308,7 @@ static int join_query_blocks(gtx_ctx *c, const std::string &w, const int32_t *re
   }
   iv.resize((size_t)std::max<int64_t>(first[b1] - i0, 1));
   for (int64_t j = i0; j < first[b1]; j++) iv[j - i0] = make_int2(blocks[2 * j], blocks[2 * j + 1]);
-  int rc = grow(c, c->d_joinQBlk, c->capJoinQBlk, qb.size()); if (rc) return rc;
+  rc = grow(c, c->d_joinQBlk, c->capJoinQBlk, qb.size()); if (rc) return rc;
   rc = grow(c, c->d_joinQIv, c->capJoinQIv, iv.size()); if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_joinQBlk, qb.data(), sizeof(int2) * qb.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_joinQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice, c->stream));
@@ -1315,8 +1327,7 @@ static int join_batches(gtx_ctx *c, const char *who, const int32_t *reads, const
   const std::string w(who);
   if (!c) return GTX_E_ARG;
   if (c->nRefs < 0) return fail(c, GTX_E_STATE, (w + ": gtx_set_refs has not been called").c_str());
-  if (n < 0 || (n > 0 && !reads) || !offsets_out || cap < 0 || (first && (first[0] != 0 || (first[n] > 0 && !blocks))))
-    return fail(c, GTX_E_ARG, (w + ": bad argument").c_str());
+  if (!offsets_out || cap < 0 || !queries_ok(reads, first, blocks, n)) return fail(c, GTX_E_ARG, (w + ": bad argument").c_str());
   HIPCHK(c, hipSetDevice(c->device));
   const int mode = join_mode(c, flags);
   gtx_count_info acc; memset(&acc, 0, sizeof acc); acc.first_unsorted = -1; acc.first_degenerate = -1;
@@ -1325,11 +1336,9 @@ static int join_batches(gtx_ctx *c, const char *who, const int32_t *reads, const
   const int64_t per = std::max<int64_t>(1, c->batchReads);
   for (int64_t b0 = 0; b0 < n; b0 += per) {
     const int64_t b1 = std::min(n, b0 + per), m = b1 - b0;
-    int rc = grow(c, c->d_joinReads, c->capJoinReads, (size_t)(3 * m)); if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
-    gtx::JoinQueries q{c->d_joinReads, nullptr, nullptr, m};
+    gtx::JoinQueries q{};
     std::vector<int2> qb, iv;
-    if (first && (all_blocks || !(mode & gtx::JOIN_GAPS))) { rc = join_query_blocks(c, w, reads, first, blocks, b0, b1, qb, iv, q); if (rc) return rc; }
+    int rc = stage_queries(c, w, reads, first, blocks, b0, b1, all_blocks || !(mode & gtx::JOIN_GAPS), qb, iv, q); if (rc) return rc;
     rc = grow(c, c->d_joinOff, c->capJoinOff, (size_t)(m + 1)); if (rc) return rc;
     int64_t total = 0; gtx::JoinInfo hi;
     rc = join_count(c, q, mode, c->d_joinOff, &total, &hi); if (rc) return rc;      // (synchronises: qb / iv may go)
@@ -1392,8 +1401,7 @@ static int offset_prepare(gtx_ctx *c)
   HIPCHK(c, hipMalloc(&d_env, sizeof(int2) * m));
   HIPCHK(c, hipMalloc(&c->d_offRef, sizeof(int4) * m));
   hipError_t e = hipMemcpy(d_env, env.data(), sizeof(int2) * m, hipMemcpyHostToDevice);
-  const gtx::RegionBlocks rb{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
-  if (e == hipSuccess) e = gtx::launch_ref_ends(d_env, rb, c->nRefs, c->d_offRef, c->stream);
+  if (e == hipSuccess) e = gtx::launch_ref_ends(d_env, ref_blocks(c), c->nRefs, c->d_offRef, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   dfree(d_env);
   HIPCHK(c, e);
@@ -1401,6 +1409,20 @@ static int offset_prepare(gtx_ctx *c)
 }
 
 static int offset_op(int32_t op) { return op >= GTX_OFFSET_1 && op <= GTX_OFFSET_3P ? op : 0; }
+
+// the offsets of the pairs of queries [q0, q1) into d_out; *inv = the first inverted pair (relative to d_off[q0]), INT64_MAX if none.
+// Waits for the stream.
+static int pair_offsets(gtx_ctx *c, const gtx::OffsetArgs &a, int64_t q0, int64_t q1, const long long *d_off, const int *d_pairs, int64_t n_pairs,
+                        long long *d_out, long long *inv)
+{
+  const long long none = INT64_MAX;
+  HIPCHK(c, hipMemcpyAsync(c->d_offInv, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_pair_offsets(a, q0, q1, d_off, d_pairs, n_pairs, d_out, c->d_offInv, c->d_joinBig, c->stream));
+  *inv = INT64_MAX;
+  HIPCHK(c, hipMemcpyAsync(inv, c->d_offInv, sizeof *inv, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTX_OK;
+}
 
 extern "C" {
 
@@ -1439,7 +1461,7 @@ int gtx_join_offsets(gtx_ctx *c, const int32_t *reads, const int64_t *first, con
       int r = GTX_OK;
       const int64_t keep = std::min(len, cap - p0);
       HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
-      gtx::OffsetArgs a{q, nullptr, c->d_offRef, c->d_refStrand, gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv}, o, fromQuery};
+      gtx::OffsetArgs a{q, nullptr, c->d_offRef, c->d_refStrand, ref_blocks(c), o, fromQuery};
       if (fromQuery && read_strands) {
         if (strandsOf != b0) {
           const int64_t m = std::min<int64_t>(n - b0, std::max<int64_t>(1, c->batchReads));
@@ -1453,12 +1475,8 @@ int gtx_join_offsets(gtx_ctx *c, const int32_t *reads, const int64_t *first, con
       int64_t nent = len;
       if (!skip) {
         r = grow(c, c->d_offOut, c->capOffOut, (size_t)(2 * len)); if (r) return r;
-        const long long none = INT64_MAX;
-        HIPCHK(c, hipMemcpyAsync(c->d_offInv, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, gtx::launch_pair_offsets(a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offOut, c->d_offInv, c->d_joinBig, c->stream));
-        long long inv = INT64_MAX;
-        HIPCHK(c, hipMemcpyAsync(&inv, c->d_offInv, sizeof inv, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        long long inv;
+        r = pair_offsets(c, a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offOut, &inv); if (r) return r;
         if (inverted < 0 && inv < keep) inverted = p0 + inv;
         for (int64_t p = 1; p <= keep; p++) entry_offsets_out[p0 + p] = ebase + p;
         nent = keep;
@@ -1499,15 +1517,9 @@ int gtx_pair_offsets_device(gtx_ctx *c, const void *d_reads, int64_t n, const vo
   int rc = offset_prepare(c); if (rc) return rc;
   if (!c->d_offInv) { HIPCHK(c, hipMalloc(&c->d_offInv, sizeof(long long))); }
   rc = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(n + 1)); if (rc) return rc;
-  const gtx::OffsetArgs a{gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n}, nullptr, c->d_offRef, c->d_refStrand,
-                          gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv}, o, false};
-  const long long none = INT64_MAX;
-  HIPCHK(c, hipMemcpyAsync(c->d_offInv, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, gtx::launch_pair_offsets(a, 0, n, (const long long *)d_offsets, (const int *)d_pairs, n_pairs, (long long *)d_out, c->d_offInv,
-                                     c->d_joinBig, c->stream));
-  long long inv = INT64_MAX;
-  HIPCHK(c, hipMemcpyAsync(&inv, c->d_offInv, sizeof inv, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const gtx::OffsetArgs a{gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n}, nullptr, c->d_offRef, c->d_refStrand, ref_blocks(c), o, false};
+  long long inv;
+  rc = pair_offsets(c, a, 0, n, (const long long *)d_offsets, (const int *)d_pairs, n_pairs, (long long *)d_out, &inv); if (rc) return rc;
   if (first_inverted_out) *first_inverted_out = inv == INT64_MAX ? -1 : inv;
   return GTX_OK;
 }
@@ -1549,7 +1561,7 @@ static int signal_prepare(gtx_ctx *c, const char *who, uint32_t flags, gtx::Sign
   if (!c->d_sigInfo) { HIPCHK(c, hipMalloc(&c->d_sigInfo, sizeof(gtx::SignalInfo))); }
   a = gtx::SignalArgs{};
   a.ix = c->pairAll.ix;
-  a.rb = gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv};
+  a.rb = ref_blocks(c);
   a.mode = join_mode(c, flags & (GTX_ZERO_LENGTH_OK | GTX_JOIN_GAPS));
   a.refEnds = c->d_offRef; a.refStrand = (const signed char *)c->d_refStrand; a.refLen = c->d_sigRefLen;
   a.binMin = c->sigMin; a.binMax = c->sigMax; a.nBins = c->sigBins;
@@ -1560,9 +1572,13 @@ static int signal_prepare(gtx_ctx *c, const char *who, uint32_t flags, gtx::Sign
 static int64_t signal_len(const gtx_ctx *c, uint32_t flags) { return ((flags & GTX_SIGNAL_PER_REF) ? std::max<int64_t>(c->nRefs, 0) : 1) * c->sigBins; }
 static int signal_cus(const gtx_ctx *c) { return (int)std::max<int64_t>(1, c->waveSlots / 32); }
 
-// the info block into *info / *first_inverted_out (read indices from base); waits for the stream
-static int signal_info(gtx_ctx *c, gtx_signal_info *info, long long *firstInv, int64_t base)
+// the signal pass of a.q into d_bins with a fresh info block, then that block into *info / *firstInv (read indices from base);
+// waits for the stream
+static int signal_pass(gtx_ctx *c, const gtx::SignalArgs &a, unsigned long long *d_bins, gtx_signal_info *info, long long *firstInv, int64_t base)
 {
+  const gtx::SignalInfo init = {0, 0, 0, 0, 0, 0, INT64_MAX};
+  HIPCHK(c, hipMemcpyAsync(c->d_sigInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_signal_bins(a, d_bins, c->d_sigInfo, signal_cus(c), c->stream));
   gtx::SignalInfo h;
   HIPCHK(c, hipMemcpyAsync(&h, c->d_sigInfo, sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1586,11 +1602,8 @@ int gtx_signal_bins_device(gtx_ctx *c, const void *d_reads, const void *d_weight
   a.q = gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n};
   a.w = (const long long *)d_weights;
   if (info) memset(info, 0, sizeof *info);
-  const gtx::SignalInfo init = {0, 0, 0, 0, 0, 0, INT64_MAX};
-  HIPCHK(c, hipMemcpyAsync(c->d_sigInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, gtx::launch_signal_bins(a, (unsigned long long *)d_bins, c->d_sigInfo, signal_cus(c), c->stream));
   long long inv = -1;
-  rc = signal_info(c, info, &inv, 0); if (rc) return rc;
+  rc = signal_pass(c, a, (unsigned long long *)d_bins, info, &inv, 0); if (rc) return rc;
   if (first_inverted_out) *first_inverted_out = inv;
   return GTX_OK;
 }
@@ -1602,8 +1615,7 @@ int gtx_signal_bins(gtx_ctx *c, const int32_t *reads, const int64_t *first, cons
   gtx::SignalArgs a;
   int rc = signal_prepare(c, "gtx_signal_bins", flags, a); if (rc) return rc;
   const int64_t len = signal_len(c, flags);
-  if (n < 0 || (n > 0 && !reads) || (len > 0 && !bins_out) || (first && (first[0] != 0 || (first[n] > 0 && !blocks))))
-    return fail(c, GTX_E_ARG, "gtx_signal_bins: bad argument");
+  if ((len > 0 && !bins_out) || !queries_ok(reads, first, blocks, n)) return fail(c, GTX_E_ARG, "gtx_signal_bins: bad argument");
   if (info) memset(info, 0, sizeof *info);
   rc = grow(c, c->d_sigBins, c->capSigBins, (size_t)std::max<int64_t>(len, 1)); if (rc) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_sigBins, 0, sizeof(unsigned long long) * (size_t)std::max<int64_t>(len, 1), c->stream));
@@ -1612,21 +1624,15 @@ int gtx_signal_bins(gtx_ctx *c, const int32_t *reads, const int64_t *first, cons
   const std::string who("gtx_signal_bins");
   for (int64_t b0 = 0; b0 < n; b0 += per) {
     const int64_t b1 = std::min(n, b0 + per), m = b1 - b0;
-    rc = grow(c, c->d_joinReads, c->capJoinReads, (size_t)(3 * m)); if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
-    a.q = gtx::JoinQueries{c->d_joinReads, nullptr, nullptr, m};
     std::vector<int2> qb, iv;
-    if (first) { rc = join_query_blocks(c, who, reads, first, blocks, b0, b1, qb, iv, a.q); if (rc) return rc; }
+    rc = stage_queries(c, who, reads, first, blocks, b0, b1, true, qb, iv, a.q); if (rc) return rc;
     a.w = nullptr;
     if (weights) {
       rc = grow(c, c->d_sigW, c->capSigW, (size_t)m); if (rc) return rc;
       HIPCHK(c, hipMemcpyAsync(c->d_sigW, weights + b0, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
       a.w = c->d_sigW;
     }
-    const gtx::SignalInfo init = {0, 0, 0, 0, 0, 0, INT64_MAX};
-    HIPCHK(c, hipMemcpyAsync(c->d_sigInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, gtx::launch_signal_bins(a, c->d_sigBins, c->d_sigInfo, signal_cus(c), c->stream));
-    rc = signal_info(c, info, &inv, b0); if (rc) return rc;                           // (synchronises: qb / iv may go)
+    rc = signal_pass(c, a, c->d_sigBins, info, &inv, b0); if (rc) return rc;          // (synchronises: qb / iv may go)
   }
   if (len > 0) {
     std::vector<int64_t> h((size_t)len);

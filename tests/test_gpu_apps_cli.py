@@ -1,8 +1,8 @@
 """genomic_apps profile / heatmap (csrc/genomic_apps.cpp, GtxSignalBins in csrc/genomic_intervals.cpp, bins from the device).
 Expected output: the reference regions are shifted here as the reference shifts them in memory (ShiftPos,
 genomic_intervals.cpp:524-531) and written with unique labels; the oracle's `pairs` on that file gives the (signal line,
-reference label) pairs in the bin index's order; GetOffsetFrom, the x / z / bin arithmetic in IEEE doubles, the sums in that
-order and the %.6e output of gtools/genomic_apps.cpp:466-655 / :752-895 are restated below."""
+reference label) pairs in the bin index's order; GetOffsetFrom and the x / z / bin arithmetic in IEEE doubles come from
+oracle/restate.py, the sums in that order and the %.6e output of gtools/genomic_apps.cpp:466-655 / :752-895 are restated below."""
 import gzip
 import os
 import re
@@ -12,12 +12,12 @@ import numpy as np
 import pytest
 
 from oracle import orc
+from oracle.restate import NAMES, offset_from, offsets_without_gaps, parse, signal_bin
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "ibm-cbc-genomic-tools_amd", "csrc", "genomic_apps")
-NAMES = ["chr1", "chr2", "chr3"]
 
 
 def tool(args, cwd):
@@ -50,17 +50,6 @@ def bed_lines(rng, n, span, lmax, cols=6, multi=0.0, prefix="q", labels=None, so
     return out
 
 
-def parse(line):
-    t = line.split("\t")
-    start = int(t[1]) + 1
-    if len(t) == 12:
-        sizes = [int(x) for x in t[10].split(",") if x]; starts = [int(x) for x in t[11].split(",") if x]
-        iv = [(start + b, start + b + a - 1) for a, b in zip(sizes, starts)]
-    else:
-        iv = [(start, int(t[2]))]
-    return dict(chrom=t[0], label=t[3], strand=t[5] if len(t) > 5 else "+", iv=iv)
-
-
 def bed_of(chrom, label, strand, iv):
     s0 = iv[0][0] - 1
     cols = [chrom, str(s0), str(iv[-1][1]), label, "0", strand]
@@ -86,31 +75,6 @@ def shifted(ref_lines, up, down):
             iv[i5][0] -= up
             iv[i3][1] += down
         out.append(bed_of(r["chrom"], "ref%d" % k, r["strand"], [tuple(x) for x in iv]))
-    return out
-
-
-def offset_5p(riv, minus, s, e):
-    if minus:
-        ref = riv[-1][1]
-        return ref - e, ref - s
-    ref = riv[0][0]
-    return s - ref, e - ref
-
-
-def offsets_without_gaps(qiv, riv, minus):
-    gap = [0] * len(riv)
-    if not minus:
-        for k in range(1, len(riv)):
-            gap[k] = gap[k - 1] + riv[k][0] - riv[k - 1][1] - 1
-    else:
-        for k in range(len(riv) - 2, -1, -1):
-            gap[k] = gap[k + 1] + riv[k + 1][0] - riv[k][1] - 1
-    out = []
-    for k, (rs, re_) in enumerate(riv):
-        for qs, qe in qiv:
-            if qs >= rs and qe <= re_:
-                a, b = offset_5p(riv, minus, qs, qe)
-                out.append((a - gap[k], b - gap[k]))
     return out
 
 
@@ -151,14 +115,11 @@ def signal_bins(cwd, sig, shifted_file, shifted_lines, bin_min, bin_max, n_bins,
             ref_len = sum(b - a + 1 for a, b in r["iv"]) if skip else r["iv"][-1][1] - r["iv"][0][0] + 1
         else:
             ref_len = 1
-        ents = offsets_without_gaps(q["iv"], r["iv"], minus) if skip else [offset_5p(r["iv"], minus, *q["iv"][0])]
+        ents = offsets_without_gaps(q["iv"], r["iv"], minus, "5p") if skip else [offset_from(r["iv"], minus, "5p", *q["iv"][0])]
         for a, b in ents:
-            x = float(a + b) / 2 / ref_len + bin_min
-            z = (x - bin_min) / (bin_max - bin_min)
-            if 0 <= z < 1:
-                k = int(n_bins * z)
-                if k < n_bins:
-                    bins[(r["k"] * n_bins if per_ref else 0) + k] += w
+            k = signal_bin(a, b, ref_len, bin_min, bin_max, n_bins)
+            if k is not None and k < n_bins:
+                bins[(r["k"] * n_bins if per_ref else 0) + k] += w
     return bins, n_sig, len(rows)
 
 

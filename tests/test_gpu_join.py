@@ -11,89 +11,9 @@ import pytest
 
 import gtx
 from oracle import orc
+from oracle.restate import NAMES, bin_keys, concat, multi, regions, take, triples, write_bed
 
 pytestmark = pytest.mark.gpu
-
-NAMES = ["chr1", "chr2", "chr3"]
-
-
-def regions(rng, n, span, lmin, lmax, n_chrom=3, sort="pos", multi=0.0, wide=0):
-    """n regions as a dict of arrays: chrom, strand (0 '+', 1 '-'), 1-based inclusive s / e, and interval lists (first, blocks)."""
-    chrom = rng.integers(0, n_chrom, size=n)
-    strand = rng.integers(0, 2, size=n)
-    s = rng.integers(1, span, size=n)
-    length = rng.integers(lmin, lmax + 1, size=n)
-    if wide:
-        at = rng.choice(n, wide, replace=False)
-        length[at] = rng.integers(span // 3, span, size=wide)
-    first, blocks = [0], []
-    e = np.zeros(n, dtype=np.int64)
-    for i in range(n):
-        if rng.random() < multi:
-            at, iv = int(s[i]), []
-            for _ in range(int(rng.integers(2, 5))):
-                sz = int(rng.integers(5, 60)); iv.append((at, at + sz - 1)); at += sz + int(rng.integers(20, 400))
-        else:
-            iv = [(int(s[i]), int(s[i]) + int(length[i]) - 1)]
-        e[i] = iv[-1][1]; blocks += iv; first.append(len(blocks))
-    r = dict(chrom=chrom, strand=strand, s=s.astype(np.int64), e=e, first=np.array(first, dtype=np.int64),
-             blocks=np.array(blocks, dtype=np.int64).reshape(-1, 2))
-    if sort == "pos":
-        return take(r, np.lexsort((r["s"], r["chrom"])))
-    if sort == "strand":
-        return take(r, np.lexsort((r["s"], r["strand"], r["chrom"])))
-    return take(r, rng.permutation(n))
-
-
-def take(r, order):
-    cnt = np.diff(r["first"])[order]
-    first = np.concatenate(([0], np.cumsum(cnt))).astype(np.int64)
-    blocks = np.concatenate([r["blocks"][r["first"][i]:r["first"][i + 1]] for i in order]) if len(order) else r["blocks"][:0]
-    out = {k: np.asarray(r[k])[order] for k in ("chrom", "strand", "s", "e")}
-    out.update(first=first, blocks=blocks.reshape(-1, 2))
-    return out
-
-
-def concat(a, b):
-    r = {k: np.concatenate((a[k], b[k])) for k in ("chrom", "strand", "s", "e")}
-    r["blocks"] = np.concatenate((a["blocks"], b["blocks"]))
-    r["first"] = np.concatenate((a["first"], a["first"][-1] + b["first"][1:]))
-    return r
-
-
-def write_bed(path, r, prefix, names=NAMES):
-    with open(path, "w") as f:
-        for i in range(len(r["s"])):
-            b = r["blocks"][r["first"][i]:r["first"][i + 1]]
-            cols = [names[r["chrom"][i]], str(r["s"][i] - 1), str(r["e"][i]), "%s%d" % (prefix, i), "0", "+-"[r["strand"][i]]]
-            if len(b) > 1:
-                cols += [str(r["s"][i] - 1), str(r["e"][i]), "0", str(len(b)), ",".join(str(int(x[1] - x[0] + 1)) for x in b) + ",",
-                         ",".join(str(int(x[0] - r["s"][i])) for x in b) + ","]
-            f.write("\t".join(cols) + "\n")
-
-
-def triples(r, ignore_strand, n_known=len(NAMES)):
-    """class = chromosome (x2 + strand unless -i); a chromosome the reference set lacks gets a class outside [0, n_classes)"""
-    c = r["chrom"] * (1 if ignore_strand else 2) + (0 if ignore_strand else r["strand"])
-    c = np.where(r["chrom"] >= n_known, 10_000, c)
-    return np.stack([c, r["s"], r["e"]], axis=1).astype(np.int32)
-
-
-def multi(r):
-    return None if (np.diff(r["first"]) == 1).all() else (r["first"], r["blocks"].astype(np.int32))
-
-
-def bin_keys(r, bits="17,20,23,26"):
-    """the bin index's order as a key per region: (level, bin, -ordinal) ranked (genomic_intervals.cpp:5619-5674)"""
-    b = [int(x) for x in bits.split(",")] + [60]                               # the level after the last one given holds the rest
-    s = np.maximum(r["s"], 1); e = r["e"]
-    level = np.full(len(s), len(b), dtype=np.int64); bins = np.zeros(len(s), dtype=np.int64)
-    for li in range(len(b) - 1, -1, -1):
-        same = (s >> b[li]) == (e >> b[li])
-        level = np.where(same, li, level); bins = np.where(same, s >> b[li], bins)
-    order = np.lexsort((-np.arange(len(s)), bins, level))
-    key = np.empty(len(s), dtype=np.int64); key[order] = np.arange(len(s))
-    return key
 
 
 def oracle_rows(tmp, args):

@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 
 from oracle import orc
+from oracle.restate import NAMES, parse
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "ibm-cbc-genomic-tools_amd", "csrc", "genomic_overlaps")
-NAMES = ["chr1", "chr2", "chr3"]
 
 
 def tool(args, cwd, stdin=None):
@@ -44,20 +44,6 @@ def bed_lines(rng, n, span, lmax, cols=6, sort=True, multi=0.0, prefix="q"):
             cols_ += [str(s + 1), str(e - 1), "255,0,0", str(len(iv)), ",".join(str(b - a) for a, b in iv) + ",", ",".join(str(a - s) for a, _ in iv) + ","]
         out.append("\t".join(cols_[:cols]))
     return out
-
-
-def parse(line):
-    t = line.split("\t")
-    n = len(t)
-    chrom, start, stop = t[0], int(t[1]) + 1, int(t[2])
-    q = dict(n=n, chrom=chrom, label=t[3] if n > 3 else "_", score=int(t[4]) if n > 4 else 0, strand=t[5] if n > 5 else "+",
-             ts=int(t[6]) if n > 7 else 0, te=int(t[7]) if n > 7 else 0, rgb=t[8] if n > 8 else "")
-    if n == 12:
-        sizes = [int(x) for x in t[10].split(",") if x]; starts = [int(x) for x in t[11].split(",") if x]
-        q["iv"] = [(start + b, start + b + a - 1) for a, b in zip(sizes, starts)]
-    else:
-        q["iv"] = [(start, stop)]
-    return q
 
 
 def render(q, iv, label, score, ts, te):

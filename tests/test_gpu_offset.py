@@ -1,50 +1,22 @@
 """Pair offsets (gtx_join_offsets / gtx_pair_offsets_device, include/gtx.h; kernels in csrc/gtx_offset.hip).  Expected values:
 the oracle's `pairs` rows (oracle/gtx_oracle.c: the (query, index region) pairs in the reference's iteration order) restated
-through GenomicInterval::GetOffsetFrom (genomic_intervals.cpp:646-667) and CalcOffsetsWithoutGaps (:6154-6205) below.  Without
--S the index is the reference set and the point is the reference region; under -S (the oracle run as `pairs -S test.bed
-refs.bed`) the merge's queries are the reference regions and the point is the query."""
+through GenomicInterval::GetOffsetFrom (genomic_intervals.cpp:646-667) and CalcOffsetsWithoutGaps (:6154-6205) in
+oracle/restate.py.  Without -S the index is the reference set and the point is the reference region; under -S (the oracle run
+as `pairs -S test.bed refs.bed`) the merge's queries are the reference regions and the point is the query."""
+import functools
 import subprocess
 
 import numpy as np
 import pytest
 
 import gtx
-from oracle import orc
+from oracle import orc, restate
+from oracle.restate import NAMES, bin_keys, concat, multi, offset_from, offsets_without_gaps, take, triples, write_bed
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ["chr1", "chr2", "chr3"]
 OPS = ["1", "2", "5p", "3p"]
-
-
-def regions(rng, n, span, lmin, lmax, n_chrom=3, sort="pos", multi=0.0):
-    """n regions as a dict of arrays: chrom, strand (0 '+', 1 '-'), 1-based inclusive s / e, and interval lists (first, blocks)."""
-    chrom = rng.integers(0, n_chrom, size=n)
-    strand = rng.integers(0, 2, size=n)
-    s = rng.integers(1, span, size=n)
-    length = rng.integers(lmin, lmax + 1, size=n)
-    first, blocks = [0], []
-    e = np.zeros(n, dtype=np.int64)
-    for i in range(n):
-        if rng.random() < multi:
-            at, iv = int(s[i]), []
-            for _ in range(int(rng.integers(2, 5))):
-                sz = int(rng.integers(5, 400)); iv.append((at, at + sz - 1)); at += sz + int(rng.integers(20, 400))
-        else:
-            iv = [(int(s[i]), int(s[i]) + int(length[i]) - 1)]
-        e[i] = iv[-1][1]; blocks += iv; first.append(len(blocks))
-    r = dict(chrom=chrom, strand=strand, s=s.astype(np.int64), e=e, first=np.array(first, dtype=np.int64),
-             blocks=np.array(blocks, dtype=np.int64).reshape(-1, 2))
-    return take(r, np.lexsort((r["s"], r["chrom"])) if sort == "pos" else rng.permutation(n))
-
-
-def take(r, order):
-    cnt = np.diff(r["first"])[order]
-    first = np.concatenate(([0], np.cumsum(cnt))).astype(np.int64)
-    blocks = np.concatenate([r["blocks"][r["first"][i]:r["first"][i + 1]] for i in order]) if len(order) else r["blocks"][:0]
-    out = {k: np.asarray(r[k])[order] for k in ("chrom", "strand", "s", "e")}
-    out.update(first=first, blocks=blocks.reshape(-1, 2))
-    return out
+regions = functools.partial(restate.regions, block_max=400)
 
 
 def inside(rng, refs, n):
@@ -65,84 +37,8 @@ def inside(rng, refs, n):
     return take(r, np.lexsort((r["s"], r["chrom"])))
 
 
-def concat(a, b):
-    r = {k: np.concatenate((a[k], b[k])) for k in ("chrom", "strand", "s", "e")}
-    r["blocks"] = np.concatenate((a["blocks"], b["blocks"]))
-    r["first"] = np.concatenate((a["first"], a["first"][-1] + b["first"][1:]))
-    return take(r, np.lexsort((r["s"], r["chrom"])))
-
-
-def write_bed(path, r, prefix):
-    with open(path, "w") as f:
-        for i in range(len(r["s"])):
-            b = r["blocks"][r["first"][i]:r["first"][i + 1]]
-            cols = [NAMES[r["chrom"][i]], str(r["s"][i] - 1), str(r["e"][i]), "%s%d" % (prefix, i), "0", "+-"[r["strand"][i]]]
-            if len(b) > 1:
-                cols += [str(r["s"][i] - 1), str(r["e"][i]), "0", str(len(b)), ",".join(str(int(x[1] - x[0] + 1)) for x in b) + ",",
-                         ",".join(str(int(x[0] - r["s"][i])) for x in b) + ","]
-            f.write("\t".join(cols) + "\n")
-
-
-def triples(r, ignore_strand, n_known=len(NAMES)):
-    c = r["chrom"] * (1 if ignore_strand else 2) + (0 if ignore_strand else r["strand"])
-    c = np.where(r["chrom"] >= n_known, 10_000, c)
-    return np.stack([c, r["s"], r["e"]], axis=1).astype(np.int32)
-
-
-def multi(r):
-    return None if (np.diff(r["first"]) == 1).all() else (r["first"], r["blocks"].astype(np.int32))
-
-
-def bin_keys(r, bits="17,20,23,26"):
-    b = [int(x) for x in bits.split(",")] + [60]
-    s = np.maximum(r["s"], 1); e = r["e"]
-    level = np.full(len(s), len(b), dtype=np.int64); bins = np.zeros(len(s), dtype=np.int64)
-    for li in range(len(b) - 1, -1, -1):
-        same = (s >> b[li]) == (e >> b[li])
-        level = np.where(same, li, level); bins = np.where(same, s >> b[li], bins)
-    order = np.lexsort((-np.arange(len(s)), bins, level))
-    key = np.empty(len(s), dtype=np.int64); key[order] = np.arange(len(s))
-    return key
-
-
 def intervals(r, i):
     return [(int(a), int(b)) for a, b in r["blocks"][r["first"][i]:r["first"][i + 1]]]
-
-
-# ---- the reference, restated ----
-
-def offset_from(riv, minus, op, s, e):
-    """GenomicInterval::GetOffsetFrom(GenomicRegion *) of [s, e] from the region with intervals riv and this strand"""
-    back = op == "2" or (minus and op == "5p") or (not minus and op == "3p")
-    a, b = riv[-1] if back else riv[0]
-    ref = {"1": a, "2": b, "5p": b if minus else a, "3p": a if minus else b}[op]
-    if (minus and op == "5p") or (not minus and op == "3p"):
-        return ref - e, ref - s
-    return s - ref, e - ref
-
-
-def sorted_disjoint(iv):
-    return all(iv[k][0] >= iv[k - 1][0] and iv[k][0] > iv[k - 1][1] for k in range(1, len(iv)))
-
-
-def offsets_without_gaps(qiv, riv, minus, op):
-    """CalcOffsetsWithoutGaps: [] for the warning case"""
-    if not sorted_disjoint(qiv) or not sorted_disjoint(riv):
-        return []
-    gap = [0] * len(riv)
-    if op == "1" or (not minus and op == "5p") or (minus and op == "3p"):
-        for k in range(1, len(riv)):
-            gap[k] = gap[k - 1] + riv[k][0] - riv[k - 1][1] - 1
-    else:
-        for k in range(len(riv) - 2, -1, -1):
-            gap[k] = gap[k + 1] + riv[k + 1][0] - riv[k][1] - 1
-    out = []
-    for k, (rs, re_) in enumerate(riv):
-        for qs, qe in qiv:
-            if qs >= rs and qe <= re_:
-                a, b = offset_from(riv, minus, op, qs, qe)
-                out.append((a - gap[k], b - gap[k]))
-    return out
 
 
 def oracle_rows(tmp, args, index, queries):
@@ -229,6 +125,7 @@ def test_bed12_on_both_sides_and_gaps(engine, rng, tmp_path, sorted_):
 def test_skip_ref_gaps(engine, rng, tmp_path, op, ign):
     refs = regions(rng, 1500, 300_000, 1, 3000, multi=0.6)
     tests = concat(regions(rng, 6000, 300_000, 1, 200, multi=0.3), inside(rng, refs, 3000))
+    tests = take(tests, np.lexsort((tests["s"], tests["chrom"])))
     rows, want, (off, pairs, eoff, ent, inv, _) = run(engine, tmp_path, refs, tests, op, ign=ign, skip=True)
     assert got_rows(off, pairs) == rows
     assert got_entries(eoff, ent) == want
@@ -240,6 +137,7 @@ def test_skip_ref_gaps_in_chunks(engine, rng, tmp_path):
     """a join buffer of 500 pairs: the entry offsets run on across chunks"""
     refs = regions(rng, 1500, 300_000, 1, 3000, multi=0.6)
     tests = concat(regions(rng, 6000, 300_000, 1, 200, multi=0.3), inside(rng, refs, 3000))
+    tests = take(tests, np.lexsort((tests["s"], tests["chrom"])))
     rows, want, (off, pairs, eoff, ent, _, _) = run(engine, tmp_path, refs, tests, "5p", skip=True, buffer=500)
     assert len(rows) > 5000 and got_rows(off, pairs) == rows and got_entries(eoff, ent) == want
 

@@ -1,7 +1,7 @@
 """genomic_overlaps offset (csrc/genomic_overlaps.cpp, GtxPrintOffsets in csrc/genomic_intervals.cpp, offsets from the device).
 Expected output: the oracle's `pairs` rows in the reference's order (without -S `pairs REF TEST`, rows (test line, reference
 label); under -S `pairs -S TEST REF`, rows (reference line, test label)) rendered as gtools/genomic_overlaps.cpp:545-670 prints
-them, through a restatement of GetOffsetFrom / CalcOffsetsWithoutGaps and C's float arithmetic below.  Error and edge cases are
+them, through the restatement of GetOffsetFrom / CalcOffsetsWithoutGaps in oracle/restate.py and C's float arithmetic below.  Error and edge cases are
 small inputs whose bytes are derived by hand in the comments."""
 import gzip
 import os
@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 
 from oracle import orc
+from oracle.restate import NAMES, offset_from, offsets_without_gaps, parse
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "ibm-cbc-genomic-tools_amd", "csrc", "genomic_overlaps")
-NAMES = ["chr1", "chr2", "chr3"]
 
 
 def tool(args, cwd, stdin=None):
@@ -49,44 +49,7 @@ def bed_lines(rng, n, span, lmax, cols=6, sort=True, multi=0.0, prefix="q", zero
     return out
 
 
-def parse(line):
-    t = line.split("\t")
-    start = int(t[1]) + 1
-    if len(t) == 12:
-        sizes = [int(x) for x in t[10].split(",") if x]; starts = [int(x) for x in t[11].split(",") if x]
-        iv = [(start + b, start + b + a - 1) for a, b in zip(sizes, starts)]
-    else:
-        iv = [(start, int(t[2]))]
-    return dict(label=t[3], minus=t[5] == "-", iv=iv, s=iv[0][0], e=iv[-1][1])
-
-
 # ---- the reference, restated ----
-
-def offset_from(riv, minus, op, s, e):
-    back = op == "2" or (minus and op == "5p") or (not minus and op == "3p")
-    a, b = riv[-1] if back else riv[0]
-    ref = {"1": a, "2": b, "5p": b if minus else a, "3p": a if minus else b}[op]
-    if (minus and op == "5p") or (not minus and op == "3p"):
-        return ref - e, ref - s
-    return s - ref, e - ref
-
-
-def offsets_without_gaps(qiv, riv, minus, op):
-    gap = [0] * len(riv)
-    if op == "1" or (not minus and op == "5p") or (minus and op == "3p"):
-        for k in range(1, len(riv)):
-            gap[k] = gap[k - 1] + riv[k][0] - riv[k - 1][1] - 1
-    else:
-        for k in range(len(riv) - 2, -1, -1):
-            gap[k] = gap[k + 1] + riv[k + 1][0] - riv[k][1] - 1
-    out = []
-    for k, (rs, re_) in enumerate(riv):
-        for qs, qe in qiv:
-            if qs >= rs and qe <= re_:
-                a, b = offset_from(riv, minus, op, qs, qe)
-                out.append((a - gap[k], b - gap[k]))
-    return out
-
 
 def cfloat(x):
     """printf("%f") of a float (promoted to double); glibc prints a NaN's sign"""

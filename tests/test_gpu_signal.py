@@ -1,11 +1,12 @@
 """gtx_signal_bins / gtx_signal_bins_device (csrc/gtx_signal.hip) against a restatement of the reference's inner loop
 (gtools/genomic_apps.cpp:560-605 heatmap, :826-880 profile): every overlapping (read, region) pair -- found here by brute force
 over the regions' intervals, so independently of the device index -- adds its read's weight to the bin of the 5' offset of the
-read's front interval, x / z / bin in IEEE doubles.  Weights are integers, so the sums do not depend on the order of the pairs."""
+read's front interval, x / z / bin in IEEE doubles (the formulas of oracle/restate.py).  Weights are integers, so the sums do not depend on the order of the pairs."""
 import numpy as np
 import pytest
 
 import gtx
+from oracle.restate import offset_from, signal_bin
 
 pytestmark = pytest.mark.gpu
 
@@ -85,20 +86,17 @@ def expected(regs, reads, strands, weights, bin_min, bin_max, n_bins, per_ref, r
                 continue
             if not any(a <= y and b >= x for a, b in riv for x, y in iv):
                 continue
-            fs, fe = iv[0]
-            a, b = (riv[-1][1] - fe, riv[-1][1] - fs) if minus else (fs - riv[0][0], fe - riv[0][0])
+            a, b = offset_from(riv, minus, "5p", *iv[0])
             if a > b:
                 first_inv = i if first_inv < 0 else first_inv
                 continue
-            L = 1 if ref_len is None else ref_len[k]
-            x = float(a + b) / 2 / L + bin_min
-            z = (x - bin_min) / (bin_max - bin_min)
-            if 0 <= z < 1:
-                j = int(n_bins * z)
-                if j >= n_bins:
-                    dropped += 1
-                    continue
-                out[(k * n_bins if per_ref else 0) + j] += weights[i]
+            j = signal_bin(a, b, 1 if ref_len is None else ref_len[k], bin_min, bin_max, n_bins)
+            if j is None:
+                continue
+            if j >= n_bins:
+                dropped += 1
+                continue
+            out[(k * n_bins if per_ref else 0) + j] += weights[i]
     return (out.reshape(len(regs), n_bins) if per_ref else out), first_inv, dropped
 
 
