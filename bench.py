@@ -16,11 +16,14 @@ tiles and regions of ITS classes only, and its piece of the compact result vecto
 ncclSend / ncclRecv, on a stream of its own under the next step's kernels); member 0 restores file order.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the streaming count kernel of rank 0: algorithmic bytes (12 B per read)
-/ its mean duration measured with HIP events on the launch stream inside the timed loop.  `cpu_baseline` is the CPU
-oracle (sorted-merge restatement of the reference) on a bounded sample of the same reads, single thread, on this box's
-host cores; its counts are also compared with the GPU's (parity check of the sample).  At N = 1 the line also carries
-`host_to_result` (packed host arrays -> counts on the host, PCIe included) and `text_to_stdout` (the product CLI from BED
-text / a packed region file to its last output line) -- reported beside `value`, never part of it.
+/ its mean duration measured with HIP events on the launch stream inside the timed loop.
+
+A plain run does only what that line needs: set up, warm up, time the steps, write --dump-outputs, print.  With --full
+the line also carries `cpu_baseline`: the CPU oracle (sorted-merge restatement of the reference) on a bounded sample of
+the same reads, on one host thread and on a thread per chromosome; its counts are also compared with the GPU's (parity
+check of the sample).  With --full at N = 1 it also carries `host_to_result` (packed host arrays -> counts on the host, PCIe included)
+and `text_to_stdout` (the product CLI from BED text / a packed region file to its last output line) -- reported beside
+`value`, never part of it.  Without --full `cpu_baseline` is null.
 """
 import argparse
 import json
@@ -741,7 +744,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reads", type=int, default=100_000_000, help="reads in total (strong scaling, the default of the count workload) or per GPU (--scaling weak)")
     ap.add_argument("--refs", type=int, default=1_000_000)
-    ap.add_argument("--cpu-sample", type=int, default=100_000_000, help="reads given to the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline with its parity check "
+                         "(`cpu_baseline`, --cpu-sample) and, N = 1 count only, `host_to_result` and `text_to_stdout` (--no-e2e leaves "
+                         "those two out); a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="with --full: reads given to the CPU baseline (default 100000000; 0 = skip)")
     ap.add_argument("--workload", choices=["count", "scans", "permutation_test"], default="count",
                     help="count = BASELINE config 3 (the headline metric); scans = config 4: genomic_scans counts -i -w 1000 -d 1000; "
                          "permutation_test = the shuffle part of config 5")
@@ -749,7 +757,7 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None,
                     help="N > 1: strong = --reads in total (default for the count workload: the fixed shape BASELINE.json names), weak = N x "
                          "--reads in total; either way ONE global read set, sharded by chromosome with the product's LPT packing")
-    ap.add_argument("--no-e2e", action="store_true", help="N = 1: skip the host_to_result / text_to_stdout measurements")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full, N = 1: skip the host_to_result / text_to_stdout measurements")
     ap.add_argument("--two-streams", action="store_true",
                     help="count, N=1: after the timed region also time the same steps alternating two contexts on two HIP streams "
                          "(extra 'two_streams' object; off by default so that a kernel trace of the default command sees only the timed steps)")
@@ -759,6 +767,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.cpu_sample is None:
+        args.cpu_sample = 100_000_000 if args.full else 0
+    elif args.cpu_sample > 0 and not args.full:
+        ap.error("--cpu-sample N > 0 needs --full (a plain run does only what the headline figure needs)")
 
     if args.scaling is None:
         args.scaling = "strong" if args.workload == "count" else "weak"
@@ -986,7 +998,7 @@ def main():
 
     # ---- not part of `value`: the same job timed from the host side (SURVEY 8(d) ii, iii), N = 1 only ----------------------
     host_to_result = text_to_stdout = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if rank == 0 and world == 1 and args.full and not args.no_e2e:
         host_to_result = measure_host_to_result(eng, reads, n, hits, flags)
         text_to_stdout, text_cli = measure_text_to_stdout(n, len(refs))
         if cpu is not None and text_cli is not None:

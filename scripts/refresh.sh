@@ -11,10 +11,10 @@ want() { case " $parts " in *" $1 "*) return 0;; esac; return 1; }
 step() { echo "== $1"; }
 if want bench; then
 step "bench lines"
-python3 bench.py > $out/bench_line.json 2> $out/bench.err && echo "count ok" &&
-python3 bench.py --workload scans > $out/bench_scans_line.json 2>> $out/bench.err && echo "scans ok" &&
-python3 bench.py --workload permutation_test > $out/bench_perm_line.json 2>> $out/bench.err && echo "perm ok" &&
-python3 bench.py --reads 1000000000 --refs 2000000 --cpu-sample 20000000 --no-e2e > $out/bench_c5_line.json 2>> $out/bench.err && echo "c5 ok"
+python3 bench.py --full > $out/bench_line.json 2> $out/bench.err && echo "count ok" &&
+python3 bench.py --full --workload scans > $out/bench_scans_line.json 2>> $out/bench.err && echo "scans ok" &&
+python3 bench.py --full --workload permutation_test > $out/bench_perm_line.json 2>> $out/bench.err && echo "perm ok" &&
+python3 bench.py --full --reads 1000000000 --refs 2000000 --cpu-sample 20000000 --no-e2e > $out/bench_c5_line.json 2>> $out/bench.err && echo "c5 ok"
 fi
 if want stats; then
 step "kernel stats"
@@ -49,14 +49,14 @@ grep -h "bucket path\|coverage:\|coverage, \|scan -w" $out/bench_bucket.log $out
 fi
 if want scans; then
 step "genomic_scans only (bench line, kernel stats, geometries): after a change to the scan kernels"
-python3 bench.py --workload scans > $out/bench_scans_line.json 2>> $out/bench.err && echo "scans ok"
+python3 bench.py --full --workload scans > $out/bench_scans_line.json 2>> $out/bench.err && echo "scans ok"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_scans -- python3 bench.py --workload scans --cpu-sample 0 --steps 20 --warmup 3 > /dev/null 2>> $out/rocprof.err && echo "scans stats ok"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_scanfine -- python3 scripts/bench_scan.py > $out/bench_scan.log 2>&1 && echo "scan geometry stats ok"
 python3 scripts/bench_scan_shuffled.py > $out/bench_scanshuf.log 2>&1 && echo "scans (shuffled reads) ok"
 fi
 if want perm; then
 step "permutation test only (bench line, kernel stats, PMC passes): after a change to gtx_perm.hip"
-python3 bench.py --workload permutation_test > $out/bench_perm_line.json 2>> $out/bench.err && echo "perm ok"
+python3 bench.py --full --workload permutation_test > $out/bench_perm_line.json 2>> $out/bench.err && echo "perm ok"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_perm -- python3 bench.py --workload permutation_test --cpu-sample 0 > /dev/null 2>> $out/rocprof.err && echo "perm stats ok"
 pmc() { name=$1; ctr=$2; shift 2; rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $out/pmc_$name -- "$@" > $out/pmc_$name.log 2>&1 && echo "pmc $name ok"; }
 pmc perm_fetch FETCH_SIZE python3 bench.py --workload permutation_test --steps 3 --warmup 1 --cpu-sample 0
