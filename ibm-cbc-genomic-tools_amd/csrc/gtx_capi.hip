@@ -27,6 +27,127 @@ typedef unsigned long long u64;
 
 static thread_local std::string g_create_error;
 
+namespace {
+
+// A buffer of T in device memory (Pinned: in page-locked host memory) that frees itself; move-only.  cap = elements it holds.
+template <class T, bool Pinned> class Buf {
+ public:
+  size_t cap = 0;
+  Buf() = default;
+  Buf(Buf &&o) noexcept { *this = std::move(o); }
+  Buf &operator=(Buf &&o) noexcept { if (this != &o) { reset(); std::swap(cap, o.cap); std::swap(p_, o.p_); } return *this; }
+  ~Buf() { reset(); }
+  T *get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+  void reset() { if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; cap = 0; }
+  // exactly n elements (the one-shot tables); what it held is freed first
+  hipError_t alloc(size_t n)
+  {
+    reset();
+    const hipError_t e = Pinned ? hipHostMalloc((void **)&p_, sizeof(T) * n) : hipMalloc((void **)&p_, sizeof(T) * n);
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
+  // grown, never shrunk: when `need` elements are more than it holds, free, then allocate `room` (>= need) and count `need` as held
+  hipError_t reserve(size_t need, size_t room) { if (need <= cap) return hipSuccess; hipError_t e = alloc(room); if (e == hipSuccess) cap = need; return e; }
+  hipError_t reserve(size_t n) { return reserve(n, n); }
+  hipError_t grow(size_t n) { return reserve(std::max<size_t>(n, 1)); }   // ... and never empty
+ private:
+  T *p_ = nullptr;
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinBuf = Buf<T, true>;
+
+// direct placement at the start of a span (gtx::PlaceTable): per class {segment start, end, first cell, cells}; per cell the rank
+// of the cell's first position in the ends array and in the starts array
+struct PlaceTable {
+  DevBuf<int4> cls; DevBuf<int> rank; int shift = 0;
+  gtx::PlaceTable view() const { gtx::PlaceTable t; t.cls = cls.get(); t.rank = rank.get(); t.shift = shift; return t; }
+};
+
+// the direct-address bucket lookup of the partition path (gtx::BucketTable): posHi | eLo | eHi | sLo | sHi | cls (nB each) |
+// clsStart (nClasses+1) in `bkt`, the cells of each class, the first bucket of each cell.  nB = 0: no tables (the search kernel serves)
+struct BucketTables {
+  DevBuf<int> bkt; DevBuf<int4> clsCell; DevBuf<uint16_t> cellTab; int nB = 0, nCells = 0, cellShift = 0;
+  gtx::BucketTable view() const
+  {
+    gtx::BucketTable t;
+    const int *d = bkt.get();
+    t.posHi = d; t.eLo = d + nB; t.eHi = d + 2 * nB; t.sLo = d + 3 * nB; t.sHi = d + 4 * nB; t.cls = d + 5 * nB; t.clsStart = d + 6 * nB; t.nB = nB;
+    t.clsCell = clsCell.get(); t.cellTab = cellTab.get(); t.nCells = nCells; t.cellShift = cellShift;
+    return t;
+  }
+};
+
+// the cuts of a partition path's buckets: per bucket the largest read start it takes, its ranges of the two boundary arrays, its
+// class; per class its first bucket
+struct BucketCuts { std::vector<int32_t> posHi, eLo, eHi, sLo, sHi, cls, clsStart; };
+
+// histograms, tile sums, prefix arrays of one count call and the finalize_scan_chained_kernel's flags (one per tile and histogram)
+// with the call's epoch
+struct HistSet { DevBuf<u64> histA, histB, partA, partB, prefA, prefB; DevBuf<unsigned> flags; unsigned epoch = 0; unsigned long long draws = 0; };
+
+// What a reference set is made into, in four parts that gtx_set_refs_ex drops together (by assignment) before it makes them anew.
+// The count index: sorted boundary arrays, the search kernel's top levels, placement, the partition path's tables, the histograms
+struct CountIndex {
+  DevBuf<int> sortedE, sortedS, segStart, posE, posS, classBase;
+  DevBuf<int> sampE, sampS; int sampShift = 6, nSamp = 0;   // top level of the search kernel
+  DevBuf<int> topE, topS;                          // every 256th boundary: first hop of the streaming kernel's start-of-span search
+  PlaceTable place;
+  BucketTables bkt;                                // unsorted reads, partition path (gtx_bucket.hip)
+  HistSet hist;
+  // The group's device calls (gtxi_count_device_share_async) finalize call k on the group's exchange stream UNDER the streaming kernel
+  // of call k+1: more sets of histograms, tile sums, prefix arrays and chain flags in turn (never `hist`: the other entry points
+  // stay as they are), two info blocks per stream (a call's finalize step resets the other one)
+  HistSet alt[GTXI_SHARE_STREAMS];                 // (dropped with the set: the ring of info blocks restarts clean)
+  DevBuf<gtx::DevInfo> info3; unsigned shareSeq = 0; unsigned shareTurn[GTXI_SHARE_STREAMS] = {}; const gtx::DevInfo *lastShareInfo = nullptr;
+};
+
+// coverage (made on first use, cover_prepare): the merged threshold array of the regions (E_k and S_k - 1, sorted per class) with its
+// 4 histograms, 4 tile-sum arrays, 4 prefix arrays, and its own placement and partition tables
+struct CoverIndex {
+  DevBuf<u64> cov[12];
+  DevBuf<int> sortedT, segT, topT, posTE, posTS, classBaseT;
+  int64_t histLenT = 0;
+  PlaceTable place;
+  BucketTables bkt;
+  bool ready = false;
+};
+
+// the rest that hangs on the reference set: region coordinates in file order, the inverted regions, multi-interval regions, the
+// join's order keys, pair offsets' reference points and strands, signal bins' lengths
+struct RefExtras {
+  DevBuf<int> refS, refE, refC;
+  // sorted-merge semantics, intervals with start > end + 1 (gtx_special.hip): the K inverted reference regions and their sums
+  int nSpecial = 0; DevBuf<int4> specialRefs; DevBuf<int> specialIdx; DevBuf<u64> specialOut;
+  // count without -gaps over multi-interval regions (gtx_pairs.hip): envelope indexes over the multi-interval index regions
+  // (reads with one interval are checked against them batch by batch) and over all regions (made on the first multi-interval
+  // read), the regions' interval lists, and the two correction vectors add[nRefs] | sub[nRefs] (zero between calls)
+  struct PairIdx { DevBuf<int> mem; int n = 0; bool built = false; gtx::PairIndex ix = {}; } pairMulti, pairAll;
+  DevBuf<int2> blkOf, blkIv; bool refBlocks = false;
+  DevBuf<u64> pairAcc;
+  // the overlap join (gtx_join.hip) over the envelope index pairAll: the regions' order keys (host copy too), whether the index
+  // is already in key order (-1: not yet looked at)
+  DevBuf<long long> joinKey; std::vector<long long> h_joinKey; int joinMono = -1;
+  DevBuf<int4> offRef; DevBuf<int8_t> refStrand;   // pair offsets: per-ordinal front / back interval, strands (gtx_set_ref_strands)
+  // signal bins (gtx_signal.hip): the geometry of gtx_set_signal_bins, per-ordinal reference lengths
+  bool sigSet = false; double sigMin = 0, sigMax = 0; int64_t sigBins = 0; DevBuf<long long> sigRefLen;
+};
+
+// a group member's share of the finalize step (gtxi_set_share): tiles of its classes, its regions in the group's compact order
+struct Share { bool on = false; DevBuf<int> tiles; int nTiles = 0; DevBuf<int> regions; int64_t nRegions = 0, offset = 0; DevBuf<unsigned char> owned; };
+
+// a block of region text tokenised on the device (gtx_count_add_text)
+struct TextSlot {
+  DevBuf<char> text; DevBuf<unsigned> seg;
+  DevBuf<unsigned> nl; DevBuf<int> tri, w;                    // w (made last) holds the lines these are made for
+  DevBuf<int> tri2; DevBuf<unsigned> blk; DevBuf<int> w2;      // ... w2 those of the strand-aware outputs
+  DevBuf<int> flag; PinBuf<int> hostFlag; PinBuf<char> pin, seam; DevBuf<unsigned long long> sum;
+  hipEvent_t evParsed = nullptr, evConsumed = nullptr, evCopied = nullptr; bool busy = false;
+};
+
+} // namespace
+
 struct gtx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -35,112 +156,63 @@ struct gtx_ctx {
   // reference side
   int64_t nRefs = -1, nValid = 0;
   int nClasses = 0;
-  int *d_sortedE = nullptr, *d_sortedS = nullptr, *d_segStart = nullptr;
-  int *d_sampE = nullptr, *d_sampS = nullptr; int sampShift = 6, nSamp = 0;   // top level of the search kernel
-  int *d_topE = nullptr, *d_topS = nullptr;   // every 256th boundary: first hop of the streaming kernel's start-of-span search
-  // direct placement at the start of a span (gtx::PlaceTable): per class {segment start, end, first cell, cells}; per cell the rank
-  // of the cell's first position in the ends array and in the starts array
-  int4 *d_placeCls = nullptr; int *d_placeRank = nullptr; int placeShift = 0;
-  int4 *d_placeClsT = nullptr; int *d_placeRankT = nullptr; int placeShiftT = 0;      // ... over the coverage thresholds (cover_prepare)
   std::vector<int32_t> h_seg;                        // [nClasses+1] class segments of the sorted boundary arrays (host copy)
-  // a group member's share of the finalize step (gtxi_set_share): tiles of its classes, its regions in the group's compact order
-  bool shareOn = false; int *d_shareTiles = nullptr; int nShareTiles = 0; int *d_shareRegions = nullptr; int64_t nShareRegions = 0, shareOffset = 0; unsigned char *d_shareOwned = nullptr;
-  // unsorted reads, bucket path (gtx_bucket.hip): table built with the references, scratch sized by the largest call
-  void *d_clsCell = nullptr, *d_cellTab = nullptr; int nCells = 0, cellShift = 0;   // direct-address bucket lookup (BucketTable)
-  int *d_bktT = nullptr; void *d_clsCellT = nullptr, *d_cellTabT = nullptr; int nBT = 0, nCellsT = 0, cellShiftT = 0;   // the same tables over the coverage thresholds (cover_prepare)
-  int *d_bktS = nullptr; void *d_clsCellS = nullptr, *d_cellTabS = nullptr; int nBS = 0, nCellsS = 0, cellShiftS = 0;          // ... and over the positions of a scan geometry (scan_bucket_tables)
-  gtx::ScanPart *d_scanParts = nullptr; int nScanParts = 0; std::vector<long long> scanBktKey; gtx::DevInfo *d_scanInfo = nullptr;
+  CountIndex ix;                                     // made from the reference set (gtx_set_refs_ex)
+  CoverIndex cv;
+  RefExtras rx;
+  Share share;
   bool covTileSums = true;                           // false: a batch went through the partition path, the tile sums are rebuilt before the finalize step
-  int *d_bkt = nullptr; int nB = 0;                  // posHi | eLo | eHi | sLo | sHi | cls (nB each) | clsStart (nClasses+1)
-  unsigned *d_bktCnt = nullptr, *d_bktDir = nullptr; size_t capBktMatrix = 0;   // scratch of the bucket path (gtx::BucketWork)
-  void *d_bktReads = nullptr; int *d_bktWeights = nullptr; size_t capBkt = 0;
+  DevBuf<u64> bktReads; DevBuf<int> bktWeights; DevBuf<unsigned> bktDir, bktCnt;   // scratch of the partition path (gtx::BucketWork)
   int64_t bucketMinReads = 1 << 18;                  // below this the per-read search kernel is used (GTX_BUCKET_MIN_READS)
-  int *d_posE = nullptr, *d_posS = nullptr, *d_classBase = nullptr;
-  u64 *d_histA = nullptr, *d_histB = nullptr, *d_partA = nullptr, *d_partB = nullptr, *d_prefA = nullptr, *d_prefB = nullptr;
-  unsigned *d_chainFlags = nullptr; unsigned chainEpoch = 0; unsigned long long chainDraws = 0;    // finalize_scan_chained_kernel: a flag per tile and histogram, the call's epoch
-  // The group's device calls (gtxi_count_device_share_async) finalize call k on the group's exchange stream UNDER the streaming kernel
-  // of call k+1: two more sets of histograms, tile sums, prefix arrays and chain flags in turn (never set 0: the other entry points
-  // stay as they are), three info blocks (call k counts into block k % 3, its finalize resets block (k + 2) % 3 -- the one call k+1
-  // uses was reset by the finalize of call k-1, which the streaming kernel of call k+1 is made to wait for anyway).
-  struct HistSet { u64 *histA = nullptr, *histB = nullptr, *partA = nullptr, *partB = nullptr, *prefA = nullptr, *prefB = nullptr; unsigned *flags = nullptr; unsigned epoch = 0; unsigned long long draws = 0; } alt[GTXI_SHARE_STREAMS];
-  gtx::DevInfo *d_info3 = nullptr; unsigned shareSeq = 0; unsigned shareTurn[GTXI_SHARE_STREAMS] = {}; const gtx::DevInfo *lastShareInfo = nullptr;
   bool histDirty = false;              // a call was abandoned between begin and end
-  // coverage (allocated on first use): 8 histograms, 8 tile-sum arrays, 8 prefix arrays, region coordinates
-  // coverage (made on first use): the merged threshold array of the regions (E_k and S_k - 1, sorted per class) with its
-  // 4 histograms, 4 tile-sum arrays, 4 prefix arrays; region coordinates in file order
-  u64 *d_cov[12] = {}; int *d_refS = nullptr, *d_refE = nullptr; bool covReady = false, covDirty = false, covOpen = false;
-  int *d_sortedT = nullptr, *d_segT = nullptr, *d_topT = nullptr, *d_posTE = nullptr, *d_posTS = nullptr, *d_classBaseT = nullptr;
-  int64_t histLenT = 0;
+  bool covDirty = false, covOpen = false;
   std::vector<int32_t> h_refS, h_refE, h_refC;
-  // sorted-merge semantics, intervals with start > end + 1 (gtx_special.hip): the K inverted reference regions and their sums,
-  // the inverted reads the kernels set aside, the region columns the second pair kernel reads
+  // the inverted reads the kernels set aside (sorted-merge semantics)
   bool mergeRefs = false;               // the reference set was given with GTX_REFS_KEEP_ZERO_LENGTH
-  int nSpecial = 0; int4 *d_specialRefs = nullptr; int *d_specialIdx = nullptr; u64 *d_specialOut = nullptr;
-  int4 *d_side = nullptr; unsigned *d_sideCount = nullptr; int sideCap = 1 << 20; int *d_refC = nullptr; bool sideUsed = false;
+  DevBuf<int4> side; DevBuf<unsigned> sideCount; int sideCap = 1 << 20; bool sideUsed = false;
   int specialMode = 0;                  // value of a pair in the open call: 0 count, 2 the -gaps coverage formula
   bool tileSumsValid = true;           // every kernel since the last finalize maintained the tile sums
   int64_t histLen = 0;
-  // count without -gaps over multi-interval regions (gtx_pairs.hip): envelope indexes over the multi-interval index regions
-  // (reads with one interval are checked against them batch by batch) and over all regions (made on the first multi-interval
-  // read), the regions' interval lists, and the two correction vectors add[nRefs] | sub[nRefs] (zero between calls)
-  struct PairIdx { int *d_mem = nullptr; int n = 0; bool built = false; gtx::PairIndex ix = {}; };
-  PairIdx pairMulti, pairAll;
-  int2 *d_blkOf = nullptr, *d_blkIv = nullptr; bool refBlocks = false;
-  u64 *d_pairAcc = nullptr; bool pairUsed = false;
-  int4 *d_pairQ = nullptr; size_t capPairQ = 0, capPairIv = 0; int2 *d_pairQBlk = nullptr, *d_pairQIv = nullptr;
-  // the overlap join (gtx_join.hip) over the envelope index pairAll: the regions' order keys (host copy too), whether the index
-  // is already in key order (-1: not yet looked at), offsets / scan / pair buffers of the host-buffer entry, its queries
-  long long *d_joinKey = nullptr; std::vector<long long> h_joinKey; int joinMono = -1;
-  long long *d_joinOff = nullptr, *d_joinPart = nullptr, *d_joinCut = nullptr; size_t capJoinOff = 0, capJoinPart = 0;
-  int *d_joinPairs = nullptr, *d_joinScratch = nullptr; size_t capJoinPairs = 0, capJoinScratch = 0;
-  unsigned *d_joinBig = nullptr; size_t capJoinBig = 0;
-  int *d_joinReads = nullptr; size_t capJoinReads = 0; int2 *d_joinQBlk = nullptr, *d_joinQIv = nullptr; size_t capJoinQBlk = 0, capJoinQIv = 0;
-  gtx::JoinInfo *d_joinInfo = nullptr;
+  bool pairUsed = false;
+  DevBuf<int4> pairQ; DevBuf<int2> pairQBlk, pairQIv;
+  // the overlap join's offsets / scan / pair buffers of the host-buffer entry, its queries
+  DevBuf<long long> joinOff, joinPart, joinCut; DevBuf<int> joinPairs, joinScratch; DevBuf<unsigned> joinBig;
+  DevBuf<int> joinReads; DevBuf<int2> joinQBlk, joinQIv;
+  DevBuf<gtx::JoinInfo> joinInfo;
   int64_t joinBuffer = 1ll << 26;       // pairs per device chunk of gtx_join (gtx_set_join_buffer)
-  // pair offsets (gtx_offset.hip): per-ordinal front / back interval, strands (gtx_set_ref_strands), the host entry's buffers
-  int4 *d_offRef = nullptr; int8_t *d_refStrand = nullptr; long long *d_offInv = nullptr;
-  long long *d_offOut = nullptr, *d_offCnt = nullptr, *d_offPart = nullptr; size_t capOffOut = 0, capOffCnt = 0, capOffPart = 0;
-  int8_t *d_offQStrand = nullptr; size_t capOffQStrand = 0;
-  // signal bins (gtx_signal.hip): the geometry of gtx_set_signal_bins, per-ordinal reference lengths, the info block, the host
-  // entry's bins and weights
-  bool sigSet = false; double sigMin = 0, sigMax = 0; int64_t sigBins = 0; long long *d_sigRefLen = nullptr;
-  gtx::SignalInfo *d_sigInfo = nullptr; unsigned long long *d_sigBins = nullptr; size_t capSigBins = 0;
-  long long *d_sigW = nullptr; size_t capSigW = 0;
+  DevBuf<long long> offInv, offOut, offCnt, offPart; DevBuf<int8_t> offQStrand;   // the pair offsets' host entry
+  DevBuf<gtx::SignalInfo> sigInfo; DevBuf<unsigned long long> sigBins; DevBuf<long long> sigW;   // the signal bins' info block, the host entry's bins and weights
 
-  gtx::DevInfo *d_info = nullptr;       // 2 blocks: the finalize of one call resets the block of the next
+  DevBuf<gtx::DevInfo> d_info;          // 2 blocks: the finalize of one call resets the block of the next
   int infoCur = 0;
-  gtx::DevInfo *h_info = nullptr;       // pinned: [0] = readback, [1] = init pattern
+  PinBuf<gtx::DevInfo> h_info;          // [0] = readback, [1] = init pattern
 
   // staging for the host-buffer entry points: two device slots fed from two pinned host slots by a copy stream, so that
   // the host->device copy of batch i+1 runs under the kernels of batch i (Stage* functions below)
   hipStream_t copyStream = nullptr;
-  void *d_stage[2] = {nullptr, nullptr}; int *d_stageW[2] = {nullptr, nullptr}; size_t capStage = 0, capStageW = 0;
-  char *h_pin[2] = {nullptr, nullptr}; size_t capPin = 0;       // bytes per slot
+  DevBuf<char> stage[2]; DevBuf<int> stageW[2];   // (12 bytes per read)
+  PinBuf<char> pin[2];                            // bytes per slot
   hipEvent_t evCopied[2] = {nullptr, nullptr}, evConsumed[2] = {nullptr, nullptr}; bool slotBusy[2] = {false, false};
   long long stageSeq = 0; bool directPending = false;   // a DMA may still be reading the page-locked buffer of the last call
   int copyThreads = 8;                  // host threads that move a pageable batch into the pinned slot (GTX_COPY_THREADS)
-  u64 *d_out = nullptr; size_t capOut = 0;
-  char *d_scratch = nullptr; size_t capScratch = 0;   // gtxi_scratch
-  // region text tokenised on the device (gtx_count_add_text): two blocks in flight
-  struct TextSlot {
-    char *d_text = nullptr; size_t capText = 0; unsigned *d_seg = nullptr; size_t capSeg = 0;
-    unsigned *d_nl = nullptr; int *d_tri = nullptr, *d_w = nullptr, *d_tri2 = nullptr, *d_w2 = nullptr; unsigned *d_blk = nullptr; size_t capLines = 0, capLines2 = 0;
-    int *d_flag = nullptr, *h_flag = nullptr; char *h_pin = nullptr; size_t capPin = 0; char *h_seam = nullptr; unsigned long long *d_sum = nullptr;
-    hipEvent_t evParsed = nullptr, evConsumed = nullptr, evCopied = nullptr; bool busy = false;
-  } text[2];
+  DevBuf<u64> out;
+  DevBuf<char> scratch;                 // gtxi_scratch
+  TextSlot text[2];                     // region text tokenised on the device (gtx_count_add_text): two blocks in flight
   long long textSeq = 0;
-  int *d_textTable = nullptr; char *d_textNames = nullptr; size_t capTextNames = 0; unsigned textMask = 0, textBlobLen = 0;
+  DevBuf<int> textTable; DevBuf<char> textNames; unsigned textMask = 0, textBlobLen = 0;
   std::string textBlob;                               // the chromosome names the device tables were built from
 
   // scan state
-  u64 *d_micro = nullptr; size_t capMicro = 0;
-  long long *d_scanTab = nullptr; size_t capScanTab = 0;
+  DevBuf<u64> micro;
+  DevBuf<long long> scanTab;
   std::vector<long long> scanKey;       // geometry the tables on the device were built for
   int64_t scanTotalWindows = 0, scanTotalMicro = 0, scanTotalTiles = 0;
+  // unsorted reads: bucket tables over the positions of a scan geometry (scan_bucket_tables), the parts they are counted in
+  BucketTables bktS; DevBuf<gtx::ScanPart> scanParts; int nScanParts = 0; std::vector<long long> scanBktKey; DevBuf<gtx::DevInfo> scanInfo;
   // owner-computes scan of sorted reads (gtx_scanown.hip): block table for the current tile, bounds scratch, give-up flag;
   // reads of a host-buffer call held resident for its single launch
-  int64_t scanOwnBlocks = 0; long long *d_scanBounds = nullptr; size_t capScanBounds = 0; int *d_scanFlag = nullptr;
-  void *d_resReads = nullptr; int *d_resWeights = nullptr; size_t capRes = 0, capResW = 0; hipEvent_t evRes[2] = {nullptr, nullptr};
+  int64_t scanOwnBlocks = 0; DevBuf<long long> scanBounds; DevBuf<int> scanFlag;
+  DevBuf<char> resReads; DevBuf<int> resWeights; hipEvent_t evRes[2] = {nullptr, nullptr};
 
   // measurement
   static constexpr int kProfSlots = 64;   // ring: the last 64 profiled calls can be read back
@@ -153,7 +225,7 @@ struct gtx_ctx {
   bool streamOpen = false; int64_t streamSeen = 0; int32_t streamLast[2] = {0, 0};
   // gtx_scan_begin .. gtx_scan_end: the open scan's geometry and what its batches have added so far
   struct ScanOpen { bool open = false, weighted = false; gtx::ScanArgs a; std::vector<int32_t> classLen; int64_t extent = 0; char prep = '1'; uint32_t flags = 0;
-                    unsigned long long *d_labelSum = nullptr; } scan;
+                    DevBuf<unsigned long long> labelSum; } scan;
   int64_t seamUnsorted = INT64_MAX;    // first order violation found at a seam between batches (host-side check)
 
   int64_t batchReads = 8ll << 20;       // reads per device batch of the host-buffer entry points (96 MiB of triples: ~2 ms of PCIe)
@@ -167,22 +239,31 @@ struct gtx_ctx {
 
 static int fail(gtx_ctx *c, int code, const char *msg) { c->err = msg; return code; }
 
-template <class T> static void dfree(T *&p);
-static void free_alt_sets(gtx_ctx *c);
-
-template <class T> static void dfree(T *&p) { if (p) { (void)hipFree(p); p = nullptr; } }
-static void free_alt_sets(gtx_ctx *c)
+// b = the n elements of v, in a buffer of exactly n
+template <class T> static hipError_t upload(DevBuf<T> &b, const T *v, size_t n)
 {
-  for (auto &h : c->alt) { dfree(h.histA); dfree(h.histB); dfree(h.partA); dfree(h.partB); dfree(h.prefA); dfree(h.prefB); dfree(h.flags); h.epoch = 0; h.draws = 0; }
-  c->shareSeq = 0; c->lastShareInfo = nullptr; for (unsigned &t : c->shareTurn) t = 0;
-  dfree(c->d_info3);                              // (the ring restarts with clean blocks: the last calls' blocks are cleared by calls that never came)
+  hipError_t e = b.alloc(n);
+  return e == hipSuccess ? hipMemcpy(b.get(), v, sizeof(T) * n, hipMemcpyHostToDevice) : e;
+}
+
+// histograms, tile sums, prefix arrays and chain flags over histLen slots; histograms, tile sums and flags zero (the invariant between
+// calls: the finalize kernels leave them so)
+static int make_hist_set(gtx_ctx *c, HistSet &h, int64_t histLen)
+{
+  const size_t parts = (size_t)gtx::scan_tiles(histLen) + 2;
+  HIPCHK(c, h.histA.alloc(histLen)); HIPCHK(c, h.histB.alloc(histLen)); HIPCHK(c, h.partA.alloc(parts)); HIPCHK(c, h.partB.alloc(parts));
+  HIPCHK(c, h.prefA.alloc(histLen)); HIPCHK(c, h.prefB.alloc(histLen)); HIPCHK(c, h.flags.alloc(8 * parts));
+  for (DevBuf<u64> *b : {&h.histA, &h.histB, &h.partA, &h.partB}) HIPCHK(c, hipMemset(b->get(), 0, sizeof(u64) * b->cap));
+  HIPCHK(c, hipMemset(h.flags.get(), 0, sizeof(unsigned) * h.flags.cap));
+  h.epoch = 0; h.draws = 0;
+  return GTX_OK;
 }
 
 // direct placement (gtx::PlaceTable) over two boundary arrays with the class segments `seg` (the same array twice for the
 // coverage thresholds): cells of 2^sh positions, sh the smallest shift that keeps the table at about one cell per eight
 // boundaries; a cell's entries = how many boundaries of the class lie below the cell's first position in either array (cell 0: none)
 static int make_place_table(gtx_ctx *c, const std::vector<int32_t> &seg, const std::vector<int32_t> &arrA, const std::vector<int32_t> &arrB,
-                            int nClasses, int64_t nv, int4 **d_cls, int **d_rank, int *shift)
+                            int nClasses, int64_t nv, PlaceTable &out)
 {
   const int64_t budget = std::max<int64_t>(1024, nv / 8) + 2 * (int64_t)nClasses;
   auto cellsOf = [&](int cl, int sh) -> int64_t {
@@ -205,12 +286,60 @@ static int make_place_table(gtx_ctx *c, const std::vector<int32_t> &seg, const s
     }
   }
   rank.push_back(0); rank.push_back(0);
-  dfree(*d_cls); dfree(*d_rank);
-  HIPCHK(c, hipMalloc(d_cls, sizeof(int4) * pc.size()));
-  HIPCHK(c, hipMalloc(d_rank, sizeof(int32_t) * rank.size()));
-  HIPCHK(c, hipMemcpy(*d_cls, pc.data(), sizeof(int4) * pc.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(*d_rank, rank.data(), sizeof(int32_t) * rank.size(), hipMemcpyHostToDevice));
-  *shift = sh;
+  out.cls.reset(); out.rank.reset();
+  HIPCHK(c, out.cls.alloc(pc.size()));
+  HIPCHK(c, out.rank.alloc(rank.size()));
+  HIPCHK(c, hipMemcpy(out.cls.get(), pc.data(), sizeof(int4) * pc.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(out.rank.get(), rank.data(), sizeof(int32_t) * rank.size(), hipMemcpyHostToDevice));
+  out.shift = sh;
+  return GTX_OK;
+}
+
+// t = the tables of cuts k: cells over the span of each class's cuts, the shift that keeps all classes within 4096 cells, a cell's
+// first bucket relative to its class's; uploaded if they fit the LDS of the scatter kernel (32 B per bucket, 16 per class), t.nB = 0
+// otherwise.  sync: wait for the context's stream before the tables are made.
+static int build_bucket_tables(gtx_ctx *c, BucketTables &t, BucketCuts &k, int nClasses, bool sync = false)
+{
+  t.nB = 0;
+  const int nB = (int)k.posHi.size();
+  if (nB == 0) return GTX_OK;
+  const std::vector<int32_t> &posHi = k.posHi, &clsStart = k.clsStart;
+  const int kCells = 4096;
+  int sh = 0;
+  auto cellsAt = [&](int shift) {
+    int64_t total = 0;
+    for (int cl = 0; cl < nClasses; cl++) {
+      const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
+      total += b1 - b0 <= 1 ? b1 - b0 : ((((int64_t)posHi[b1 - 2] - posHi[b0]) >> shift) + 1);
+    }
+    return total;
+  };
+  while (sh < 40 && cellsAt(sh) > kCells) sh++;
+  std::vector<int32_t> clsCell(4 * (size_t)nClasses);
+  std::vector<uint16_t> cellTab;
+  for (int cl = 0; cl < nClasses; cl++) {
+    const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
+    const int32_t lo = b1 - b0 <= 1 ? 0 : posHi[b0];
+    const int64_t nc = b1 == b0 ? 0 : b1 - b0 == 1 ? 1 : ((((int64_t)posHi[b1 - 2] - lo) >> sh) + 1);   // 0 cells: a class without buckets
+    clsCell[4 * cl] = (int32_t)cellTab.size(); clsCell[4 * cl + 1] = lo; clsCell[4 * cl + 2] = (int32_t)nc; clsCell[4 * cl + 3] = b0;
+    int b = b0;
+    for (int64_t j = 0; j < nc; j++) {
+      const int64_t first = (int64_t)lo + (j << sh);
+      while (b < b1 - 1 && (int64_t)posHi[b] < first) b++;
+      cellTab.push_back((uint16_t)(b - b0));
+    }
+  }
+  t.nCells = (int)cellTab.size(); t.cellShift = sh;
+  if (!gtx::bucket_tables_fit(nClasses, nB, t.nCells)) return GTX_OK;
+  cellTab.push_back(0);
+  std::vector<int32_t> all;
+  for (auto *v : {&k.posHi, &k.eLo, &k.eHi, &k.sLo, &k.sHi, &k.cls, &k.clsStart}) all.insert(all.end(), v->begin(), v->end());
+  if (sync) HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, upload(t.bkt, all.data(), all.size()));
+  HIPCHK(c, t.clsCell.alloc((size_t)nClasses + 1));                // (16 bytes beyond the last class)
+  HIPCHK(c, hipMemcpy(t.clsCell.get(), clsCell.data(), sizeof(int32_t) * clsCell.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, upload(t.cellTab, cellTab.data(), cellTab.size()));
+  t.nB = nB;
   return GTX_OK;
 }
 
@@ -232,13 +361,14 @@ gtx_ctx *gtx_create(int device_id)
   gtx_ctx *c = new gtx_ctx();
   c->device = device_id;
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->waveSlots = 32ll * cus; }
-  if (hipMalloc(&c->d_info, 2 * sizeof(gtx::DevInfo)) != hipSuccess || hipHostMalloc(&c->h_info, 2 * sizeof(gtx::DevInfo)) != hipSuccess) {
+  if (c->d_info.alloc(2) != hipSuccess || c->h_info.alloc(2) != hipSuccess) {
     g_create_error = "gtx_create: allocation failed"; delete c; return nullptr;
   }
-  c->h_info[1].first_unsorted = INT64_MAX; c->h_info[1].n_no_class = 0; c->h_info[1].n_degenerate = 0; c->h_info[1].first_degenerate = INT64_MAX; c->h_info[1].n_unplaced = 0; c->h_info[1].fault = 0;
-  c->h_info[0] = c->h_info[1];
-  if (hipMemcpy(c->d_info, &c->h_info[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->d_info + 1, &c->h_info[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice) != hipSuccess) {
+  gtx::DevInfo *hi = c->h_info.get();
+  hi[1].first_unsorted = INT64_MAX; hi[1].n_no_class = 0; hi[1].n_degenerate = 0; hi[1].first_degenerate = INT64_MAX; hi[1].n_unplaced = 0; hi[1].fault = 0;
+  hi[0] = hi[1];
+  if (hipMemcpy(c->d_info.get(), &hi[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->d_info.get() + 1, &hi[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice) != hipSuccess) {
     g_create_error = "gtx_create: hipMemcpy failed"; delete c; return nullptr;
   }
   for (auto &slot : c->evRing) for (auto &ev : slot) if (hipEventCreate(&ev) != hipSuccess) { g_create_error = "gtx_create: hipEventCreate failed"; delete c; return nullptr; }
@@ -264,38 +394,11 @@ void gtx_destroy(gtx_ctx *c)
 {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  dfree(c->d_sortedE); dfree(c->d_sortedS); dfree(c->d_segStart); dfree(c->d_posE); dfree(c->d_posS); dfree(c->d_classBase);
-  dfree(c->d_bktReads); dfree(c->d_bktWeights); dfree(c->d_bktDir); dfree(c->d_sampE); dfree(c->d_sampS); dfree(c->d_topE); dfree(c->d_topS); dfree(c->d_bkt); dfree(c->d_clsCell); dfree(c->d_cellTab); dfree(c->d_bktT); dfree(c->d_clsCellT); dfree(c->d_cellTabT); c->nBT = 0;
-  dfree(c->d_placeCls); dfree(c->d_placeRank); dfree(c->d_placeClsT); dfree(c->d_placeRankT); dfree(c->d_shareTiles); dfree(c->d_shareRegions); dfree(c->d_shareOwned);
-  dfree(c->d_bktCnt); dfree(c->d_bktS); dfree(c->d_clsCellS); dfree(c->d_cellTabS); dfree(c->d_scanParts); dfree(c->d_scanInfo); c->nBS = 0;
-  dfree(c->d_histA); dfree(c->d_histB); dfree(c->d_partA); dfree(c->d_partB); dfree(c->d_prefA); dfree(c->d_prefB); dfree(c->d_info); dfree(c->d_chainFlags); free_alt_sets(c); dfree(c->d_info3); dfree(c->scan.d_labelSum);
   if (c->copyStream) (void)hipStreamSynchronize(c->copyStream);
-  for (int k = 0; k < 2; k++) {
-    dfree(c->d_stage[k]); dfree(c->d_stageW[k]);
-    if (c->h_pin[k]) (void)hipHostFree(c->h_pin[k]);
-    if (c->evCopied[k]) (void)hipEventDestroy(c->evCopied[k]);
-    if (c->evConsumed[k]) (void)hipEventDestroy(c->evConsumed[k]);
-    if (c->evRes[k]) (void)hipEventDestroy(c->evRes[k]);
-  }
+  for (int k = 0; k < 2; k++)
+    for (hipEvent_t e : {c->evCopied[k], c->evConsumed[k], c->evRes[k]}) if (e) (void)hipEventDestroy(e);
   if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
-  for (auto &t : c->text) {
-    dfree(t.d_text); dfree(t.d_seg); dfree(t.d_nl); dfree(t.d_tri); dfree(t.d_w); dfree(t.d_tri2); dfree(t.d_w2); dfree(t.d_blk); dfree(t.d_flag); dfree(t.d_sum);
-    if (t.h_flag) (void)hipHostFree(t.h_flag);
-    if (t.h_pin) (void)hipHostFree(t.h_pin);
-    if (t.h_seam) (void)hipHostFree(t.h_seam);
-    for (hipEvent_t e : {t.evParsed, t.evConsumed, t.evCopied}) if (e) (void)hipEventDestroy(e);
-  }
-  dfree(c->d_textTable); dfree(c->d_textNames);
-  dfree(c->d_out); dfree(c->d_scratch); dfree(c->d_micro); dfree(c->d_scanTab); dfree(c->d_scanBounds); dfree(c->d_scanFlag); dfree(c->d_resReads); dfree(c->d_resWeights);
-  for (auto &p : c->d_cov) dfree(p);
-  dfree(c->d_sortedT); dfree(c->d_segT); dfree(c->d_topT); dfree(c->d_posTE); dfree(c->d_posTS); dfree(c->d_classBaseT);
-  dfree(c->d_refS); dfree(c->d_refE); dfree(c->d_refC); dfree(c->d_specialRefs); dfree(c->d_specialIdx); dfree(c->d_specialOut); dfree(c->d_side); dfree(c->d_sideCount);
-  dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv); dfree(c->d_pairAcc); dfree(c->d_pairQ); dfree(c->d_pairQBlk); dfree(c->d_pairQIv);
-  dfree(c->d_joinKey); dfree(c->d_joinOff); dfree(c->d_joinPart); dfree(c->d_joinCut); dfree(c->d_joinPairs); dfree(c->d_joinScratch); dfree(c->d_joinBig);
-  dfree(c->d_joinReads); dfree(c->d_joinQBlk); dfree(c->d_joinQIv); dfree(c->d_joinInfo);
-  dfree(c->d_offRef); dfree(c->d_refStrand); dfree(c->d_offInv); dfree(c->d_offOut); dfree(c->d_offCnt); dfree(c->d_offPart); dfree(c->d_offQStrand);
-  dfree(c->d_sigRefLen); dfree(c->d_sigInfo); dfree(c->d_sigBins); dfree(c->d_sigW);
-  if (c->h_info) (void)hipHostFree(c->h_info);
+  for (auto &t : c->text) for (hipEvent_t e : {t.evParsed, t.evConsumed, t.evCopied}) if (e) (void)hipEventDestroy(e);
   for (auto &slot : c->evRing) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
   delete c;
 }
@@ -384,151 +487,80 @@ int gtx_set_refs_ex(gtx_ctx *c, const int32_t *tri, int64_t m, int32_t nClasses,
     classBase[itE[i].k] = seg[itE[i].cls] + itE[i].cls - 1;
   }
 
-  dfree(c->d_sortedE); dfree(c->d_sortedS); dfree(c->d_segStart); dfree(c->d_posE); dfree(c->d_posS); dfree(c->d_classBase);
-  dfree(c->d_sampE); dfree(c->d_sampS); dfree(c->d_topE); dfree(c->d_topS); dfree(c->d_bkt); dfree(c->d_clsCell); dfree(c->d_cellTab);
-  dfree(c->d_placeCls); dfree(c->d_placeRank);
-  dfree(c->d_bktT); dfree(c->d_clsCellT); dfree(c->d_cellTabT); c->nBT = 0;      // tables over the coverage thresholds: rebuilt by cover_prepare
-  dfree(c->d_histA); dfree(c->d_histB); dfree(c->d_partA); dfree(c->d_partB); dfree(c->d_prefA); dfree(c->d_prefB); dfree(c->d_chainFlags); free_alt_sets(c);
+  // everything made from the old set goes before the new set is made (never both at once)
   c->nRefs = -1;
+  c->ix = {}; c->cv = {}; c->rx = {}; c->share = {};
+  c->covDirty = false; c->pairUsed = false;
   const int64_t histLen = nv + nClasses;
-  const int nTiles = gtx::scan_tiles(histLen);
-  HIPCHK(c, hipMalloc(&c->d_sortedE, sizeof(int32_t) * (nv + 1)));
-  HIPCHK(c, hipMalloc(&c->d_sortedS, sizeof(int32_t) * (nv + 1)));
-  HIPCHK(c, hipMalloc(&c->d_segStart, sizeof(int32_t) * (nClasses + 1)));
-  HIPCHK(c, hipMalloc(&c->d_posE, sizeof(int32_t) * (m + 1)));
-  HIPCHK(c, hipMalloc(&c->d_posS, sizeof(int32_t) * (m + 1)));
-  HIPCHK(c, hipMalloc(&c->d_classBase, sizeof(int32_t) * (m + 1)));
-  HIPCHK(c, hipMalloc(&c->d_histA, sizeof(u64) * histLen));
-  HIPCHK(c, hipMalloc(&c->d_histB, sizeof(u64) * histLen));
-  HIPCHK(c, hipMalloc(&c->d_partA, sizeof(u64) * (nTiles + 2)));
-  HIPCHK(c, hipMalloc(&c->d_partB, sizeof(u64) * (nTiles + 2)));
-  HIPCHK(c, hipMalloc(&c->d_prefA, sizeof(u64) * histLen));
-  HIPCHK(c, hipMalloc(&c->d_prefB, sizeof(u64) * histLen));
-  // invariant between calls: histograms and tile sums are all zero (the finalize kernels leave them so)
-  HIPCHK(c, hipMemset(c->d_histA, 0, sizeof(u64) * histLen));
-  HIPCHK(c, hipMemset(c->d_histB, 0, sizeof(u64) * histLen));
-  HIPCHK(c, hipMemset(c->d_partA, 0, sizeof(u64) * (nTiles + 2)));
-  HIPCHK(c, hipMemset(c->d_partB, 0, sizeof(u64) * (nTiles + 2)));
-  HIPCHK(c, hipMalloc(&c->d_chainFlags, sizeof(unsigned) * 8 * (nTiles + 2)));
-  HIPCHK(c, hipMemset(c->d_chainFlags, 0, sizeof(unsigned) * 8 * (nTiles + 2)));
-  c->chainEpoch = 0; c->chainDraws = 0;
+  HIPCHK(c, c->ix.sortedE.alloc(nv + 1));
+  HIPCHK(c, c->ix.sortedS.alloc(nv + 1));
+  HIPCHK(c, c->ix.segStart.alloc(nClasses + 1));
+  HIPCHK(c, c->ix.posE.alloc(m + 1));
+  HIPCHK(c, c->ix.posS.alloc(m + 1));
+  HIPCHK(c, c->ix.classBase.alloc(m + 1));
+  { int rc = make_hist_set(c, c->ix.hist, histLen); if (rc) return rc; }
   c->histDirty = false; c->tileSumsValid = true;
-  HIPCHK(c, hipMemcpy(c->d_sortedE, sortedE.data(), sizeof(int32_t) * nv, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_sortedS, sortedS.data(), sizeof(int32_t) * nv, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_segStart, seg.data(), sizeof(int32_t) * (nClasses + 1), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ix.sortedE.get(), sortedE.data(), sizeof(int32_t) * nv, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ix.sortedS.get(), sortedS.data(), sizeof(int32_t) * nv, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->ix.segStart.get(), seg.data(), sizeof(int32_t) * (nClasses + 1), hipMemcpyHostToDevice));
   {
-    c->sampShift = gtx::search_sample_shift(nv);
-    c->nSamp = (int)((nv + (1ll << c->sampShift) - 1) >> c->sampShift);
-    std::vector<int32_t> sampE(c->nSamp + 1), sampS(c->nSamp + 1);
-    for (int i = 0; i < c->nSamp; i++) { sampE[i] = sortedE[(int64_t)i << c->sampShift]; sampS[i] = sortedS[(int64_t)i << c->sampShift]; }
-    HIPCHK(c, hipMalloc(&c->d_sampE, sizeof(int32_t) * (c->nSamp + 1)));
-    HIPCHK(c, hipMalloc(&c->d_sampS, sizeof(int32_t) * (c->nSamp + 1)));
-    HIPCHK(c, hipMemcpy(c->d_sampE, sampE.data(), sizeof(int32_t) * (c->nSamp + 1), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_sampS, sampS.data(), sizeof(int32_t) * (c->nSamp + 1), hipMemcpyHostToDevice));
+    c->ix.sampShift = gtx::search_sample_shift(nv);
+    c->ix.nSamp = (int)((nv + (1ll << c->ix.sampShift) - 1) >> c->ix.sampShift);
+    std::vector<int32_t> sampE(c->ix.nSamp + 1), sampS(c->ix.nSamp + 1);
+    for (int i = 0; i < c->ix.nSamp; i++) { sampE[i] = sortedE[(int64_t)i << c->ix.sampShift]; sampS[i] = sortedS[(int64_t)i << c->ix.sampShift]; }
+    HIPCHK(c, upload(c->ix.sampE, sampE.data(), sampE.size()));
+    HIPCHK(c, upload(c->ix.sampS, sampS.data(), sampS.size()));
     const int64_t nTop = (nv + 255) >> 8;
     std::vector<int32_t> topE(nTop + 1), topS(nTop + 1);
     for (int64_t i = 0; i < nTop; i++) { topE[i] = sortedE[i << 8]; topS[i] = sortedS[i << 8]; }
-    HIPCHK(c, hipMalloc(&c->d_topE, sizeof(int32_t) * (nTop + 1)));
-    HIPCHK(c, hipMalloc(&c->d_topS, sizeof(int32_t) * (nTop + 1)));
-    HIPCHK(c, hipMemcpy(c->d_topE, topE.data(), sizeof(int32_t) * (nTop + 1), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_topS, topS.data(), sizeof(int32_t) * (nTop + 1), hipMemcpyHostToDevice));
+    HIPCHK(c, upload(c->ix.topE, topE.data(), topE.size()));
+    HIPCHK(c, upload(c->ix.topS, topS.data(), topS.size()));
   }
-  { int rc = make_place_table(c, seg, sortedE, sortedS, nClasses, nv, &c->d_placeCls, &c->d_placeRank, &c->placeShift); if (rc) return rc; }
+  { int rc = make_place_table(c, seg, sortedE, sortedS, nClasses, nv, c->ix.place); if (rc) return rc; }
   {
     // bucket table of the unsorted path: cuts of the ends array every bucket_e_size() boundaries, never across classes
     const int kE = gtx::bucket_e_size(), kS = gtx::bucket_s_size();
-    std::vector<int32_t> posHi, eLo, eHi, sLo, sHi, cls, clsStart(nClasses + 1, 0);
+    BucketCuts k;
+    k.clsStart.assign(nClasses + 1, 0);
     for (int cl = 0; cl < nClasses; cl++) {
-      clsStart[cl] = (int32_t)posHi.size();
+      k.clsStart[cl] = (int32_t)k.posHi.size();
       const int32_t s0 = seg[cl], s1 = seg[cl + 1];
       for (int32_t e0 = s0; e0 < s1; e0 += kE) {
         const int32_t e1 = std::min<int64_t>((int64_t)e0 + kE, s1);
-        posHi.push_back(e1 == s1 ? INT32_MAX : sortedE[e1 - 1]);
-        eLo.push_back(e0); eHi.push_back(e1); cls.push_back(cl);
+        k.posHi.push_back(e1 == s1 ? INT32_MAX : sortedE[e1 - 1]);
+        k.eLo.push_back(e0); k.eHi.push_back(e1); k.cls.push_back(cl);
         // a read of this bucket starts above E[e0-1], so it ends at or above it: ranks in the starts array begin here
         const int32_t lo = e0 == s0 ? s0 : (int32_t)(std::upper_bound(sortedS.begin() + s0, sortedS.begin() + s1, sortedE[e0 - 1]) - sortedS.begin());
-        sLo.push_back(lo); sHi.push_back((int32_t)std::min<int64_t>((int64_t)lo + kS, s1));
+        k.sLo.push_back(lo); k.sHi.push_back((int32_t)std::min<int64_t>((int64_t)lo + kS, s1));
       }
     }
-    clsStart[nClasses] = (int32_t)posHi.size();
-    c->nB = (int)posHi.size();
-    if (c->nB > 8192 || nClasses > 2048) c->nB = 0;               // (certainly too many for the LDS tables of the scatter kernel; the exact test follows)
-    std::vector<int32_t> clsCell(4 * (size_t)nClasses);
-    std::vector<uint16_t> cellTab;
-    if (c->nB > 0) {
-      // cells over the span of each class's cuts: the shift that keeps all classes within kCells cells
-      const int kCells = 4096;
-      int sh = 0;
-      auto cellsAt = [&](int shift) {
-        int64_t total = 0;
-        for (int cl = 0; cl < nClasses; cl++) {
-          const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
-          total += b1 - b0 <= 1 ? b1 - b0 : ((((int64_t)posHi[b1 - 2] - posHi[b0]) >> shift) + 1);
-        }
-        return total;
-      };
-      while (sh < 40 && cellsAt(sh) > kCells) sh++;
-      for (int cl = 0; cl < nClasses; cl++) {
-        const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
-        const int32_t lo = b1 - b0 <= 1 ? 0 : posHi[b0];
-        const int64_t nc = b1 == b0 ? 0 : b1 - b0 == 1 ? 1 : ((((int64_t)posHi[b1 - 2] - lo) >> sh) + 1);   // 0 cells: a class without reference regions
-        clsCell[4 * cl] = (int32_t)cellTab.size(); clsCell[4 * cl + 1] = lo; clsCell[4 * cl + 2] = (int32_t)nc; clsCell[4 * cl + 3] = b0;
-        int b = b0;
-        for (int64_t k = 0; k < nc; k++) {
-          const int64_t first = (int64_t)lo + (k << sh);
-          while (b < b1 - 1 && (int64_t)posHi[b] < first) b++;
-          cellTab.push_back((uint16_t)(b - b0));                   // relative to the class's first bucket
-        }
-      }
-      c->nCells = (int)cellTab.size(); c->cellShift = sh;
-      if (!gtx::bucket_tables_fit(nClasses, c->nB, c->nCells)) c->nB = 0;     // 32 B per bucket, 16 per class: the search kernel serves
-    }
-    if (c->nB > 0) {
-      cellTab.push_back(0);
-      HIPCHK(c, hipMalloc(&c->d_clsCell, sizeof(int32_t) * clsCell.size() + 16));
-      HIPCHK(c, hipMemcpy(c->d_clsCell, clsCell.data(), sizeof(int32_t) * clsCell.size(), hipMemcpyHostToDevice));
-      HIPCHK(c, hipMalloc(&c->d_cellTab, sizeof(uint16_t) * cellTab.size()));
-      HIPCHK(c, hipMemcpy(c->d_cellTab, cellTab.data(), sizeof(uint16_t) * cellTab.size(), hipMemcpyHostToDevice));
-      std::vector<int32_t> all;
-      for (auto *v : {&posHi, &eLo, &eHi, &sLo, &sHi, &cls, &clsStart}) all.insert(all.end(), v->begin(), v->end());
-      HIPCHK(c, hipMalloc(&c->d_bkt, sizeof(int32_t) * all.size()));
-      HIPCHK(c, hipMemcpy(c->d_bkt, all.data(), sizeof(int32_t) * all.size(), hipMemcpyHostToDevice));
+    k.clsStart[nClasses] = (int32_t)k.posHi.size();
+    if (k.posHi.size() <= 8192 && nClasses <= 2048) {            // (else certainly too many for the LDS tables of the scatter kernel)
+      int rc = build_bucket_tables(c, c->ix.bkt, k, nClasses); if (rc) return rc;
     }
   }
   if (m > 0) {
-    HIPCHK(c, hipMemcpy(c->d_posE, posE.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_posS, posS.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_classBase, classBase.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->ix.posE.get(), posE.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->ix.posS.get(), posS.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->ix.classBase.get(), classBase.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
   }
-  for (auto &p : c->d_cov) dfree(p);
-  dfree(c->d_sortedT); dfree(c->d_segT); dfree(c->d_topT); dfree(c->d_posTE); dfree(c->d_posTS); dfree(c->d_classBaseT);
-  dfree(c->d_refS); dfree(c->d_refE); c->covReady = false; c->covDirty = false;
   c->h_refS.resize(m > 0 ? m : 1); c->h_refE.resize(m > 0 ? m : 1); c->h_refC.resize(m > 0 ? m : 1);
   for (int64_t k = 0; k < m; k++) { c->h_refC[k] = tri[3 * k]; c->h_refS[k] = tri[3 * k + 1]; c->h_refE[k] = tri[3 * k + 2]; }
-  dfree(c->d_refC); dfree(c->d_specialRefs); dfree(c->d_specialIdx); dfree(c->d_specialOut);
-  c->mergeRefs = keepZero; c->nSpecial = 0;
+  c->mergeRefs = keepZero;
   if (keepZero) {
     std::vector<int4> sp; std::vector<int32_t> spIdx;
     for (int64_t k = 0; k < m; k++)
       if (tri[3 * k] >= 0 && (int64_t)tri[3 * k + 1] > (int64_t)tri[3 * k + 2] + 1) { sp.push_back(make_int4(tri[3 * k], tri[3 * k + 1], tri[3 * k + 2], 0)); spIdx.push_back((int32_t)k); }
-    c->nSpecial = (int)sp.size();
-    if (c->nSpecial) {
-      HIPCHK(c, hipMalloc(&c->d_specialRefs, sizeof(int4) * sp.size()));
-      HIPCHK(c, hipMalloc(&c->d_specialIdx, sizeof(int32_t) * sp.size()));
-      HIPCHK(c, hipMalloc(&c->d_specialOut, sizeof(u64) * sp.size()));
-      HIPCHK(c, hipMemcpy(c->d_specialRefs, sp.data(), sizeof(int4) * sp.size(), hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(c->d_specialIdx, spIdx.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemset(c->d_specialOut, 0, sizeof(u64) * sp.size()));
+    c->rx.nSpecial = (int)sp.size();
+    if (c->rx.nSpecial) {
+      HIPCHK(c, upload(c->rx.specialRefs, sp.data(), sp.size()));
+      HIPCHK(c, upload(c->rx.specialIdx, spIdx.data(), spIdx.size()));
+      HIPCHK(c, c->rx.specialOut.alloc(sp.size()));
+      HIPCHK(c, hipMemset(c->rx.specialOut.get(), 0, sizeof(u64) * sp.size()));
     }
   }
-  dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv); dfree(c->d_pairAcc);
-  c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->pairUsed = false;
-  dfree(c->d_joinKey); c->h_joinKey.clear(); c->joinMono = -1;
-  dfree(c->d_offRef); dfree(c->d_refStrand);
-  dfree(c->d_sigRefLen); c->sigSet = false;
   c->nRefs = m; c->nValid = nv; c->nClasses = nClasses; c->histLen = histLen;
   c->h_seg = seg;
-  c->shareOn = false; dfree(c->d_shareTiles); dfree(c->d_shareRegions); dfree(c->d_shareOwned); c->nShareTiles = 0; c->nShareRegions = 0; c->shareOffset = 0;
   return GTX_OK;
 }
 
@@ -553,19 +585,22 @@ extern "C" int gtx_debug_trace_read(unsigned long long *out, long long nWaves)
 }
 #endif
 
-// hist32: the call is ONE launch of the streaming kernel over unweighted reads (a *_device call): 32-bit histogram slots
-// (CountArgs::hist32); the caller hands the same flag to launch_finalize
-static gtx::CountArgs count_args(gtx_ctx *c, uint32_t flags, int64_t nReads, int64_t indexBase = 0, const gtx_ctx::HistSet *set = nullptr, bool share = false,
+// who counts: any entry point, a group member (its classes only: CountArgs::owned), or a member's call on one of the group's streams
+// (gtxi_count_device_share_async)
+enum CountCall { COUNT_ANY, COUNT_SHARE, COUNT_SHARE_ASYNC };
+
+// the count kernels' arguments over histogram set h.  hist32: the call is ONE launch of the streaming kernel over unweighted reads
+// (a *_device call): 32-bit histogram slots (CountArgs::hist32); the caller hands the same flag to launch_finalize
+static gtx::CountArgs count_args(gtx_ctx *c, const HistSet &h, uint32_t flags, int64_t nReads, int64_t indexBase = 0, CountCall who = COUNT_ANY,
                                  bool hist32 = false)
 {
   gtx::CountArgs a;
   a.indexBase = indexBase;
   { static const bool off = (getenv("GTX_HIST32") && atoi(getenv("GTX_HIST32")) == 0) || (getenv("GTX_PF") && atoi(getenv("GTX_PF")));
     a.hist32 = hist32 && !off && nReads < (1ll << 32) && c->prefetch >= 4; }
-  a.owned = (share || set) && c->shareOn ? c->d_shareOwned : nullptr;
-  a.sortedE = c->d_sortedE; a.sortedS = c->d_sortedS; a.segStart = c->d_segStart;
-  a.histA = c->d_histA; a.histB = c->d_histB; a.partA = c->d_partA; a.partB = c->d_partB; a.info = c->d_info + c->infoCur;
-  if (set) { a.histA = set->histA; a.histB = set->histB; a.partA = set->partA; a.partB = set->partB; }
+  a.owned = who != COUNT_ANY && c->share.on ? c->share.owned.get() : nullptr;
+  a.sortedE = c->ix.sortedE.get(); a.sortedS = c->ix.sortedS.get(); a.segStart = c->ix.segStart.get();
+  a.histA = h.histA.get(); a.histB = h.histB.get(); a.partA = h.partA.get(); a.partB = h.partB.get(); a.info = c->d_info.get() + c->infoCur;
   a.nClasses = c->nClasses;
   // Large batches: the streaming kernel leaves the per-tile sums alone and the finalize step rebuilds them from the
   // histograms (tile_sums_kernel, one pass over 16 B per region: 6 us at 1 M regions).  Keeping them up to date costs two
@@ -588,15 +623,15 @@ static gtx::CountArgs count_args(gtx_ctx *c, uint32_t flags, int64_t nReads, int
   a.sched = gtx::span_schedule((nReads + 63) >> 6, a.chunksPerWave, r, c->waveSlots);
   a.checkSorted = (flags & GTX_CHECK_SORTED) ? 1 : 0; a.sortClassShift = 0; a.prefetch = c->prefetch;
   a.zeroLenOk = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
-  const bool merge = (flags & GTX_ZERO_LENGTH_OK) && c->mergeRefs && c->d_side;       // full sorted-merge semantics (see merge_prepare)
-  a.side = merge ? c->d_side : nullptr; a.sideCount = merge ? c->d_sideCount : nullptr; a.sideCap = c->sideCap; a.coverRule = 0; a.keyCenter = 0;
-  a.sampE = c->d_sampE; a.sampS = c->d_sampS; a.sampShift = c->sampShift; a.nSamp = c->nSamp;
-  a.topE = c->d_topE; a.topS = c->d_topS;
-  a.place.cls = c->d_placeCls; a.place.rank = c->d_placeRank; a.place.shift = c->placeShift;
+  const bool merge = (flags & GTX_ZERO_LENGTH_OK) && c->mergeRefs && c->side.get();       // full sorted-merge semantics (see merge_prepare)
+  a.side = merge ? c->side.get() : nullptr; a.sideCount = merge ? c->sideCount.get() : nullptr; a.sideCap = c->sideCap; a.coverRule = 0; a.keyCenter = 0;
+  a.sampE = c->ix.sampE.get(); a.sampS = c->ix.sampS.get(); a.sampShift = c->ix.sampShift; a.nSamp = c->ix.nSamp;
+  a.topE = c->ix.topE.get(); a.topS = c->ix.topS.get();
+  a.place = c->ix.place.view();
   // dense references (>= 4 boundaries per 256 reads and array): all boundaries of a window at once instead of the
   // per-boundary loop (100 M reads x 4 M regions: 0.41 -> 0.28 ms; at 1 M regions the loop is 3 % faster).  GTX_FLIP=0|1 forces.
-  // (a group member streams the reads of ITS classes only: their density is against its own regions, not the whole set's)
-  { static const char *fl = getenv("GTX_FLIP"); const int64_t regions = set && c->shareOn ? std::min<int64_t>(c->nValid, c->nShareRegions) : c->nValid;
+  // (a group member's async call streams the reads of ITS classes only: their density is against its own regions, not the whole set's)
+  { static const char *fl = getenv("GTX_FLIP"); const int64_t regions = who == COUNT_SHARE_ASYNC && c->share.on ? std::min<int64_t>(c->nValid, c->share.nRegions) : c->nValid;
     a.flip = fl ? atoi(fl) : (regions * 256 >= 4 * std::max<int64_t>(nReads, 1)); }
 #ifdef GTX_WAVE_TRACE
   a.trace = gtx_debug_trace_buffer();
@@ -607,46 +642,31 @@ static gtx::CountArgs count_args(gtx_ctx *c, uint32_t flags, int64_t nReads, int
 // scratch of the partition path for a call of plan p (grown, never shrunk), and the views the kernels take
 static int bucket_scratch(gtx_ctx *c, const gtx::BucketPlan &p, int nB, gtx::BucketWork *w)
 {
-  if (p.pairs > c->capBkt) {
-    dfree(c->d_bktReads); dfree(c->d_bktWeights); dfree(c->d_bktDir); c->capBkt = 0;
-    HIPCHK(c, hipMalloc(&c->d_bktReads, 8 * p.pairs));
-    HIPCHK(c, hipMalloc(&c->d_bktWeights, 4 * p.pairs));
-    HIPCHK(c, hipMalloc(&c->d_bktDir, 4 * 2 * p.chunks));             // directory | list
-    c->capBkt = p.pairs;
+  if (p.pairs > c->bktReads.cap || !c->bktDir) {                     // (bktDir made last: there, all three are)
+    c->bktReads.reset(); c->bktWeights.reset(); c->bktDir.reset();
+    HIPCHK(c, c->bktReads.alloc(p.pairs));
+    HIPCHK(c, c->bktWeights.alloc(p.pairs));
+    HIPCHK(c, c->bktDir.alloc(2 * p.chunks));                         // directory | list
   }
-  const size_t words = p.matrix + p.blocks + (size_t)nB + 1;         // chunkCount | arenaUsed | rowOff
-  if (words > c->capBktMatrix) {
-    dfree(c->d_bktCnt); c->capBktMatrix = 0;
-    HIPCHK(c, hipMalloc(&c->d_bktCnt, 4 * words));
-    c->capBktMatrix = words;
-  }
-  w->tmpReads = c->d_bktReads; w->tmpWeights = c->d_bktWeights; w->arenaPairs = (unsigned)p.arenaPairs;
-  w->dir = c->d_bktDir; w->list = c->d_bktDir + c->capBkt / 64; w->chunkCount = c->d_bktCnt; w->arenaUsed = c->d_bktCnt + p.matrix; w->rowOff = w->arenaUsed + p.blocks;
+  HIPCHK(c, c->bktCnt.reserve(p.matrix + p.blocks + (size_t)nB + 1));  // chunkCount | arenaUsed | rowOff
+  w->tmpReads = c->bktReads.get(); w->tmpWeights = c->bktWeights.get(); w->arenaPairs = (unsigned)p.arenaPairs;
+  w->dir = c->bktDir.get(); w->list = c->bktDir.get() + c->bktReads.cap / 64; w->chunkCount = c->bktCnt.get(); w->arenaUsed = c->bktCnt.get() + p.matrix; w->rowOff = w->arenaUsed + p.blocks;
   return GTX_OK;
-}
-
-static gtx::BucketTable bucket_table(const int *d_bkt, int nB, const void *clsCell, const void *cellTab, int nCells, int cellShift)
-{
-  gtx::BucketTable t;
-  t.posHi = d_bkt; t.eLo = d_bkt + nB; t.eHi = d_bkt + 2 * nB; t.sLo = d_bkt + 3 * nB; t.sHi = d_bkt + 4 * nB;
-  t.cls = d_bkt + 5 * nB; t.clsStart = d_bkt + 6 * nB; t.nB = nB;
-  t.clsCell = (const int4 *)clsCell; t.cellTab = (const unsigned short *)cellTab; t.nCells = nCells; t.cellShift = cellShift;
-  return t;
 }
 
 // reads in no particular order: bucket partition + LDS counting for large batches, per-read search kernel otherwise
 static int launch_unsorted(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, const gtx::CountArgs &a)
 {
-  if (c->nB == 0 || n < c->bucketMinReads || n >= (1ll << 31)) {
+  const BucketTables &t = c->ix.bkt;
+  if (t.nB == 0 || n < c->bucketMinReads || n >= (1ll << 31)) {
     HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, false, c->stream));
     return GTX_OK;
   }
-  const gtx::BucketPlan p = gtx::bucket_plan(n, a.nClasses, c->nB, c->nCells, d_weights != nullptr);
+  const gtx::BucketPlan p = gtx::bucket_plan(n, a.nClasses, t.nB, t.nCells, d_weights != nullptr);
   if (p.pairs >= (1ull << 32)) { HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, false, c->stream)); return GTX_OK; }
   gtx::BucketWork w;
-  { int rc = bucket_scratch(c, p, c->nB, &w); if (rc) return rc; }
-  const gtx::BucketTable t = bucket_table(c->d_bkt, c->nB, c->d_clsCell, c->d_cellTab, c->nCells, c->cellShift);
-  HIPCHK(c, gtx::launch_count_bucketed(d_reads, d_weights, n, a, t, w, p, c->stream));
+  { int rc = bucket_scratch(c, p, t.nB, &w); if (rc) return rc; }
+  HIPCHK(c, gtx::launch_count_bucketed(d_reads, d_weights, n, a, t.view(), w, p, c->stream));
   return GTX_OK;
 }
 
@@ -654,12 +674,12 @@ static int launch_unsorted(gtx_ctx *c, const void *d_reads, const void *d_weight
 // start > end + 1 take part by the merge's two comparisons (gtx_special.hip).  Buffers are made on first use.
 static int ref_columns(gtx_ctx *c)
 {
-  if (!c->d_refS) {
-    HIPCHK(c, hipMalloc(&c->d_refS, sizeof(int32_t) * (c->nRefs + 1)));
-    HIPCHK(c, hipMalloc(&c->d_refE, sizeof(int32_t) * (c->nRefs + 1)));
+  if (!c->rx.refE) {
+    HIPCHK(c, c->rx.refS.alloc(c->nRefs + 1));
+    HIPCHK(c, c->rx.refE.alloc(c->nRefs + 1));
     if (c->nRefs > 0) {
-      HIPCHK(c, hipMemcpy(c->d_refS, c->h_refS.data(), sizeof(int32_t) * c->nRefs, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(c->d_refE, c->h_refE.data(), sizeof(int32_t) * c->nRefs, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->rx.refS.get(), c->h_refS.data(), sizeof(int32_t) * c->nRefs, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->rx.refE.get(), c->h_refE.data(), sizeof(int32_t) * c->nRefs, hipMemcpyHostToDevice));
     }
   }
   return GTX_OK;
@@ -668,15 +688,15 @@ static int ref_columns(gtx_ctx *c)
 static int merge_prepare(gtx_ctx *c, uint32_t flags, int mode)
 {
   if (!(flags & GTX_ZERO_LENGTH_OK) || !c->mergeRefs) return GTX_OK;
-  if (!c->d_side) {
-    HIPCHK(c, hipMalloc(&c->d_side, sizeof(int4) * (size_t)c->sideCap));
-    HIPCHK(c, hipMalloc(&c->d_sideCount, sizeof(unsigned)));
-    HIPCHK(c, hipMemset(c->d_sideCount, 0, sizeof(unsigned)));
+  if (!c->sideCount) {
+    HIPCHK(c, c->side.alloc((size_t)c->sideCap));
+    HIPCHK(c, c->sideCount.alloc(1));
+    HIPCHK(c, hipMemset(c->sideCount.get(), 0, sizeof(unsigned)));
   }
-  if (!c->d_refC) {
+  if (!c->rx.refC) {
     int rc = ref_columns(c); if (rc) return rc;
-    HIPCHK(c, hipMalloc(&c->d_refC, sizeof(int32_t) * (c->nRefs + 1)));
-    if (c->nRefs > 0) HIPCHK(c, hipMemcpy(c->d_refC, c->h_refC.data(), sizeof(int32_t) * c->nRefs, hipMemcpyHostToDevice));
+    HIPCHK(c, c->rx.refC.alloc(c->nRefs + 1));
+    if (c->nRefs > 0) HIPCHK(c, hipMemcpy(c->rx.refC.get(), c->h_refC.data(), sizeof(int32_t) * c->nRefs, hipMemcpyHostToDevice));
   }
   c->sideUsed = true; c->specialMode = mode;
   return GTX_OK;
@@ -686,8 +706,8 @@ static int merge_prepare(gtx_ctx *c, uint32_t flags, int mode)
 // a gap of such a region was counted on the region's envelope -- off again
 static int pairs_batch(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n)
 {
-  if (c->pairMulti.n > 0) {
-    HIPCHK(c, gtx::launch_pair_miss(d_reads, d_weights, n, c->pairMulti.ix, gtx::RegionBlocks{c->d_blkOf, c->d_blkIv}, c->d_pairAcc + c->nRefs, c->stream));
+  if (c->rx.pairMulti.n > 0) {
+    HIPCHK(c, gtx::launch_pair_miss(d_reads, d_weights, n, c->rx.pairMulti.ix, gtx::RegionBlocks{c->rx.blkOf.get(), c->rx.blkIv.get()}, c->rx.pairAcc.get() + c->nRefs, c->stream));
     c->pairUsed = true;
   }
   return GTX_OK;
@@ -696,7 +716,7 @@ static int pairs_batch(gtx_ctx *c, const void *d_reads, const void *d_weights, i
 // after the kernels of one batch: the batch against the inverted reference regions
 static int merge_batch(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n)
 {
-  if (c->sideUsed && c->nSpecial) HIPCHK(c, gtx::launch_special_refs(d_reads, d_weights, n, c->d_specialRefs, c->nSpecial, c->specialMode, c->d_specialOut, c->stream));
+  if (c->sideUsed && c->rx.nSpecial) HIPCHK(c, gtx::launch_special_refs(d_reads, d_weights, n, c->rx.specialRefs.get(), c->rx.nSpecial, c->specialMode, c->rx.specialOut.get(), c->stream));
   return GTX_OK;
 }
 
@@ -705,13 +725,13 @@ static int merge_end(gtx_ctx *c, void *d_out)
 {
   if (c->pairUsed) {
     c->pairUsed = false;
-    HIPCHK(c, gtx::launch_pair_apply((u64 *)d_out, c->d_pairAcc, c->d_pairAcc + c->nRefs, c->nRefs, c->stream));
+    HIPCHK(c, gtx::launch_pair_apply((u64 *)d_out, c->rx.pairAcc.get(), c->rx.pairAcc.get() + c->nRefs, c->nRefs, c->stream));
   }
   if (!c->sideUsed) return GTX_OK;
   c->sideUsed = false;
-  HIPCHK(c, gtx::launch_side_reads(c->d_refC, c->d_refS, c->d_refE, c->nRefs, c->d_side, c->d_sideCount, c->sideCap, c->specialMode, (u64 *)d_out,
-                                   c->d_info + c->infoCur, c->stream));
-  HIPCHK(c, gtx::launch_special_scatter(c->d_specialIdx, c->d_specialOut, c->nSpecial, (u64 *)d_out, c->d_sideCount, c->stream));
+  HIPCHK(c, gtx::launch_side_reads(c->rx.refC.get(), c->rx.refS.get(), c->rx.refE.get(), c->nRefs, c->side.get(), c->sideCount.get(), c->sideCap, c->specialMode, (u64 *)d_out,
+                                   c->d_info.get() + c->infoCur, c->stream));
+  HIPCHK(c, gtx::launch_special_scatter(c->rx.specialIdx.get(), c->rx.specialOut.get(), c->rx.nSpecial, (u64 *)d_out, c->sideCount.get(), c->stream));
   return GTX_OK;
 }
 
@@ -719,37 +739,42 @@ static int merge_end(gtx_ctx *c, void *d_out)
 static int count_begin(gtx_ctx *c)
 {
   if (c->histDirty) {                             // only after an abandoned call
-    const int nTiles = gtx::scan_tiles(c->histLen);
-    HIPCHK(c, hipMemsetAsync(c->d_histA, 0, sizeof(u64) * c->histLen, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_histB, 0, sizeof(u64) * c->histLen, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_partA, 0, sizeof(u64) * (nTiles + 2), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_partB, 0, sizeof(u64) * (nTiles + 2), c->stream));
+    HistSet &h = c->ix.hist;
+    for (DevBuf<u64> *b : {&h.histA, &h.histB, &h.partA, &h.partB}) HIPCHK(c, hipMemsetAsync(b->get(), 0, sizeof(u64) * b->cap, c->stream));
   }
   // the info block is shared by count and coverage calls: an abandoned call of either kind leaves counts in it
-  if (c->histDirty || c->covDirty) HIPCHK(c, hipMemcpyAsync(c->d_info + c->infoCur, &c->h_info[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice, c->stream));
-  if ((c->histDirty || c->covDirty) && c->d_sideCount) {            // an abandoned call may have left inverted reads / sums behind
-    HIPCHK(c, hipMemsetAsync(c->d_sideCount, 0, sizeof(unsigned), c->stream));
-    if (c->nSpecial) HIPCHK(c, hipMemsetAsync(c->d_specialOut, 0, sizeof(u64) * c->nSpecial, c->stream));
+  if (c->histDirty || c->covDirty) HIPCHK(c, hipMemcpyAsync(c->d_info.get() + c->infoCur, &c->h_info.get()[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice, c->stream));
+  if ((c->histDirty || c->covDirty) && c->sideCount.get()) {            // an abandoned call may have left inverted reads / sums behind
+    HIPCHK(c, hipMemsetAsync(c->sideCount.get(), 0, sizeof(unsigned), c->stream));
+    if (c->rx.nSpecial) HIPCHK(c, hipMemsetAsync(c->rx.specialOut.get(), 0, sizeof(u64) * c->rx.nSpecial, c->stream));
   }
-  if (c->histDirty && c->d_pairAcc) HIPCHK(c, hipMemsetAsync(c->d_pairAcc, 0, sizeof(u64) * 2 * (size_t)std::max<int64_t>(c->nRefs, 1), c->stream));
+  if (c->histDirty && c->rx.pairAcc.get()) HIPCHK(c, hipMemsetAsync(c->rx.pairAcc.get(), 0, sizeof(u64) * 2 * (size_t)std::max<int64_t>(c->nRefs, 1), c->stream));
   c->sideUsed = false; c->pairUsed = false;
   c->histDirty = true; c->tileSumsValid = true;
-  c->lastShareInfo = nullptr;
+  c->ix.lastShareInfo = nullptr;
+  return GTX_OK;
+}
+
+// the finalize step of a count call over set h on stream s: counts of info, infoNext reset for the call after; fs: a group member's
+// classes only
+static int finalize_set(gtx_ctx *c, HistSet &h, bool sumsValid, u64 *d_hits, gtx::DevInfo *info, gtx::DevInfo *infoNext, hipStream_t s,
+                        const gtx::FinalizeShare *fs, bool hist32)
+{
+  if (++h.epoch == 0) { HIPCHK(c, hipMemsetAsync(h.flags.get(), 0, sizeof(unsigned) * h.flags.cap, s)); h.epoch = 1; h.draws = 0; }   // (after 2^32 calls: the flags start over)
+  HIPCHK(c, gtx::launch_finalize(h.histA.get(), h.histB.get(), c->histLen, h.partA.get(), h.partB.get(), sumsValid, h.prefA.get(), h.prefB.get(),
+                                 c->ix.posE.get(), c->ix.posS.get(), c->ix.classBase.get(), c->nRefs, d_hits, infoNext, s, fs, h.flags.get(), h.epoch, info,
+                                 &h.draws, hist32));
   return GTX_OK;
 }
 
 // share: the context is a group member -- finalize its classes only, d_hits receives its regions in the group's compact order
 static int count_end(gtx_ctx *c, void *d_hits, bool share = false, bool scatter = false, bool hist32 = false)
 {
-  gtx::FinalizeShare fs = {c->d_shareTiles, c->nShareTiles, c->d_shareRegions, c->nShareRegions, scatter};
-  if (++c->chainEpoch == 0) {                       // (after 2^32 calls: the flags start over)
-    HIPCHK(c, hipMemsetAsync(c->d_chainFlags, 0, sizeof(unsigned) * 8 * (gtx::scan_tiles(c->histLen) + 2), c->stream));
-    c->chainEpoch = 1; c->chainDraws = 0;
-  }
-  HIPCHK(c, gtx::launch_finalize(c->d_histA, c->d_histB, c->histLen, c->d_partA, c->d_partB, c->tileSumsValid, c->d_prefA, c->d_prefB,
-                                 c->d_posE, c->d_posS, c->d_classBase, c->nRefs, (u64 *)d_hits, c->d_info + (c->infoCur ^ 1), c->stream,
-                                 share ? &fs : nullptr, c->d_chainFlags, c->chainEpoch, c->d_info + c->infoCur, &c->chainDraws, hist32));
-  { int rc = merge_end(c, d_hits); if (rc) return rc; }
+  const gtx::FinalizeShare fs = {c->share.tiles.get(), c->share.nTiles, c->share.regions.get(), c->share.nRegions, scatter};
+  int rc = finalize_set(c, c->ix.hist, c->tileSumsValid, (u64 *)d_hits, c->d_info.get() + c->infoCur, c->d_info.get() + (c->infoCur ^ 1), c->stream,
+                        share ? &fs : nullptr, hist32);
+  if (rc) return rc;
+  rc = merge_end(c, d_hits); if (rc) return rc;
   c->histDirty = false;
   c->infoCur ^= 1;                                // the block just used stays readable until the call after next
   return GTX_OK;
@@ -770,11 +795,11 @@ int gtx_count_device(gtx_ctx *c, const void *d_reads, const void *d_weights, int
   if (!streaming) c->tileSumsValid = false;
   bool h32 = false;
   if (streaming) {
-    const gtx::CountArgs a = count_args(c, flags, n, 0, nullptr, false, d_weights == nullptr);
+    const gtx::CountArgs a = count_args(c, c->ix.hist, flags, n, 0, COUNT_ANY, d_weights == nullptr);
     h32 = a.hist32 != 0 && n > 0;
     HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, true, c->stream));
   }
-  else { rc = launch_unsorted(c, d_reads, d_weights, n, count_args(c, flags, n)); if (rc) return rc; }
+  else { rc = launch_unsorted(c, d_reads, d_weights, n, count_args(c, c->ix.hist, flags, n)); if (rc) return rc; }
   rc = merge_batch(c, d_reads, d_weights, n); if (rc) return rc;
   rc = pairs_batch(c, d_reads, d_weights, n); if (rc) return rc;
   if (c->profThis) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
@@ -801,10 +826,10 @@ int gtx_last_info(gtx_ctx *c, gtx_count_info *info)
 {
   if (!c || !info) return GTX_E_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpyAsync(&c->h_info[0], c->d_info + (c->infoCur ^ 1), sizeof(gtx::DevInfo), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&c->h_info.get()[0], c->d_info.get() + (c->infoCur ^ 1), sizeof(gtx::DevInfo), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  info_out(c->h_info[0], info, 0);
-  return fault_check(c, c->h_info[0]);
+  info_out(c->h_info.get()[0], info, 0);
+  return fault_check(c, c->h_info.get()[0]);
 }
 
 } // extern "C" (templates below)
@@ -835,24 +860,18 @@ static void parallel_copy(char *dst, const char *src, size_t bytes, int threads)
 
 static int stage_reserve(gtx_ctx *c, size_t nReads, bool weights, bool pinnedSlots)
 {
-  if (nReads > c->capStage || (weights && nReads > c->capStageW) || (pinnedSlots && nReads * 16 > c->capPin)) {
+  const size_t bytes = nReads * 12, nW = weights ? nReads : 0, pinBytes = pinnedSlots ? nReads * 16 : 0;
+  bool grows = false;
+  for (int k = 0; k < 2; k++) grows |= bytes > c->stage[k].cap || nW > c->stageW[k].cap || pinBytes > c->pin[k].cap;
+  if (grows) {
     // growing: nothing may still be in flight on the old buffers
     HIPCHK(c, hipStreamSynchronize(c->copyStream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->slotBusy[0] = c->slotBusy[1] = false;
   }
-  if (nReads > c->capStage) {
-    for (int k = 0; k < 2; k++) { dfree(c->d_stage[k]); HIPCHK(c, hipMalloc(&c->d_stage[k], nReads * 12)); }
-    c->capStage = nReads;
-  }
-  if (weights && nReads > c->capStageW) {
-    for (int k = 0; k < 2; k++) { dfree(c->d_stageW[k]); HIPCHK(c, hipMalloc(&c->d_stageW[k], nReads * 4)); }
-    c->capStageW = nReads;
-  }
-  if (pinnedSlots && nReads * 16 > c->capPin) {
-    for (int k = 0; k < 2; k++) { if (c->h_pin[k]) { (void)hipHostFree(c->h_pin[k]); c->h_pin[k] = nullptr; } HIPCHK(c, hipHostMalloc((void **)&c->h_pin[k], nReads * 16)); }
-    c->capPin = nReads * 16;
-  }
+  for (int k = 0; k < 2; k++) HIPCHK(c, c->stage[k].reserve(bytes));
+  for (int k = 0; k < 2; k++) HIPCHK(c, c->stageW[k].reserve(nW));
+  for (int k = 0; k < 2; k++) HIPCHK(c, c->pin[k].reserve(pinBytes));
   return GTX_OK;
 }
 
@@ -879,15 +898,15 @@ static int stage_batches(gtx_ctx *c, const int32_t *reads, const int32_t *weight
     }
     const char *srcR = (const char *)(reads + 3 * off), *srcW = (const char *)(weights ? weights + off : nullptr);
     if (!direct) {
-      parallel_copy(c->h_pin[slot], srcR, (size_t)cnt * 12, c->copyThreads);
-      if (weights) parallel_copy(c->h_pin[slot] + (size_t)cnt * 12, srcW, (size_t)cnt * 4, c->copyThreads);
-      srcR = c->h_pin[slot]; srcW = c->h_pin[slot] + (size_t)cnt * 12;
+      parallel_copy(c->pin[slot].get(), srcR, (size_t)cnt * 12, c->copyThreads);
+      if (weights) parallel_copy(c->pin[slot].get() + (size_t)cnt * 12, srcW, (size_t)cnt * 4, c->copyThreads);
+      srcR = c->pin[slot].get(); srcW = c->pin[slot].get() + (size_t)cnt * 12;
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_stage[slot], srcR, (size_t)cnt * 12, hipMemcpyHostToDevice, c->copyStream));
-    if (weights) HIPCHK(c, hipMemcpyAsync(c->d_stageW[slot], srcW, (size_t)cnt * 4, hipMemcpyHostToDevice, c->copyStream));
+    HIPCHK(c, hipMemcpyAsync(c->stage[slot].get(), srcR, (size_t)cnt * 12, hipMemcpyHostToDevice, c->copyStream));
+    if (weights) HIPCHK(c, hipMemcpyAsync(c->stageW[slot].get(), srcW, (size_t)cnt * 4, hipMemcpyHostToDevice, c->copyStream));
     HIPCHK(c, hipEventRecord(c->evCopied[slot], c->copyStream));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->evCopied[slot], 0));
-    rc = launch(c->d_stage[slot], weights ? c->d_stageW[slot] : nullptr, cnt, off); if (rc) return rc;
+    rc = launch(c->stage[slot].get(), weights ? c->stageW[slot].get() : nullptr, cnt, off); if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->evConsumed[slot], c->stream));
     c->slotBusy[slot] = true;
   }
@@ -898,7 +917,7 @@ extern "C" {
 
 static int ensure_out(gtx_ctx *c, size_t n)
 {
-  if (n > c->capOut) { dfree(c->d_out); c->capOut = 0; HIPCHK(c, hipMalloc(&c->d_out, (n + 1) * sizeof(u64))); c->capOut = n; }
+  HIPCHK(c, c->out.reserve(n, n + 1));
   return GTX_OK;
 }
 
@@ -937,8 +956,8 @@ int gtx_count_add(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int6
   rc = stage_batches(c, reads, weights, n, [&](const void *dR, const int *dW, int64_t cnt, int64_t off) -> int {
     // indices in the info block are positions in the whole stream (indexBase); the block accumulates over the batches
     if (!streaming) c->tileSumsValid = false;
-    if (streaming) HIPCHK(c, gtx::launch_count(dR, dW, cnt, count_args(c, flags, cnt, seen + off), true, c->stream));
-    else { int rcu = launch_unsorted(c, dR, dW, cnt, count_args(c, flags, cnt, seen + off)); if (rcu) return rcu; }
+    if (streaming) HIPCHK(c, gtx::launch_count(dR, dW, cnt, count_args(c, c->ix.hist, flags, cnt, seen + off), true, c->stream));
+    else { int rcu = launch_unsorted(c, dR, dW, cnt, count_args(c, c->ix.hist, flags, cnt, seen + off)); if (rcu) return rcu; }
     { int rcp = pairs_batch(c, dR, dW, cnt); if (rcp) return rcp; }
     return merge_batch(c, dR, dW, cnt);
   });
@@ -952,14 +971,14 @@ int gtx_count_add(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int6
 int gtxi_count_finish(gtx_ctx *c, void **d_out, int share)
 {
   if (!c->streamOpen) return fail(c, GTX_E_STATE, "gtx_count_end: gtx_count_begin has not been called");
-  if (share && !c->shareOn) return fail(c, GTX_E_STATE, "gtxi_count_finish: no share set");
-  if (share && (c->refBlocks || c->pairUsed)) return fail(c, GTX_E_STATE, "gtxi_count_finish: multi-interval regions are finalized over the whole vector");
+  if (share && !c->share.on) return fail(c, GTX_E_STATE, "gtxi_count_finish: no share set");
+  if (share && (c->rx.refBlocks || c->pairUsed)) return fail(c, GTX_E_STATE, "gtxi_count_finish: multi-interval regions are finalized over the whole vector");
   HIPCHK(c, hipSetDevice(c->device));
   c->streamOpen = false;
   int rc = ensure_out(c, (size_t)c->nRefs); if (rc) return rc;
-  u64 *dst = share ? c->d_out + c->shareOffset : c->d_out;
+  u64 *dst = share ? c->out.get() + c->share.offset : c->out.get();
   rc = count_end(c, dst, share != 0); if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(&c->h_info[0], c->d_info + (c->infoCur ^ 1), sizeof(gtx::DevInfo), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&c->h_info.get()[0], c->d_info.get() + (c->infoCur ^ 1), sizeof(gtx::DevInfo), hipMemcpyDeviceToHost, c->stream));
   *d_out = dst;
   return GTX_OK;
 }
@@ -967,7 +986,7 @@ int gtxi_count_finish(gtx_ctx *c, void **d_out, int share)
 // after gtxi_*_finish and a wait for the stream: what the call observed
 void gtxi_fetch_info(gtx_ctx *c, gtx_count_info *info)
 {
-  info_out(c->h_info[0], info, 0);
+  info_out(c->h_info.get()[0], info, 0);
   if (c->seamUnsorted != INT64_MAX && (info->first_unsorted < 0 || c->seamUnsorted < info->first_unsorted)) info->first_unsorted = c->seamUnsorted;
 }
 
@@ -981,7 +1000,7 @@ int gtx_count_end(gtx_ctx *c, uint64_t *hits, gtx_count_info *info)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->copyStream));
   if (info) gtxi_fetch_info(c, info);
-  return fault_check(c, c->h_info[0]);
+  return fault_check(c, c->h_info.get()[0]);
 }
 
 int gtx_count(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t n, uint32_t flags, uint64_t *hits, gtx_count_info *info)
@@ -1004,9 +1023,9 @@ int gtx_count(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t 
 // with start > stop or stop <= 0 never match); under the sorted merge's rules every region with a class does, inverted or not:
 // the envelope test below is the merge's own (CalcDirection == 0, genomic_intervals.cpp:1225-1236).
 template <class Pick>
-static int build_pair_index(gtx_ctx *c, gtx_ctx::PairIdx *out, Pick pick)
+static int build_pair_index(gtx_ctx *c, RefExtras::PairIdx *out, Pick pick)
 {
-  dfree(out->d_mem); *out = gtx_ctx::PairIdx();
+  *out = {};
   struct Item { int32_t cls, s, e, k; };
   std::vector<Item> it;
   for (int64_t k = 0; k < c->nRefs; k++) {
@@ -1026,9 +1045,8 @@ static int build_pair_index(gtx_ctx *c, gtx_ctx::PairIdx *out, Pick pick)
     pm[i] = (i > 0 && it[i - 1].cls == it[i].cls) ? std::max(pm[i - 1], it[i].e) : it[i].e;
     bm[i >> 6] = std::max(bm[i >> 6], it[i].e);
   }
-  HIPCHK(c, hipMalloc(&out->d_mem, sizeof(int32_t) * mem.size()));
-  HIPCHK(c, hipMemcpy(out->d_mem, mem.data(), sizeof(int32_t) * mem.size(), hipMemcpyHostToDevice));
-  int *d = out->d_mem;
+  HIPCHK(c, upload(out->mem, mem.data(), mem.size()));
+  const int *d = out->mem.get();
   out->ix = gtx::PairIndex{d, d + nc + 1, d + nc + 1 + n, d + nc + 1 + 2 * n, d + nc + 1 + 3 * n, d + nc + 1 + 3 * n + nb, c->nClasses};
   out->n = (int)n; out->built = true;
   return GTX_OK;
@@ -1036,10 +1054,10 @@ static int build_pair_index(gtx_ctx *c, gtx_ctx::PairIdx *out, Pick pick)
 
 static int pair_acc(gtx_ctx *c)
 {
-  if (c->d_pairAcc) return GTX_OK;
-  const size_t bytes = sizeof(u64) * 2 * (size_t)std::max<int64_t>(c->nRefs, 1);
-  HIPCHK(c, hipMalloc(&c->d_pairAcc, bytes));
-  HIPCHK(c, hipMemset(c->d_pairAcc, 0, bytes));
+  if (c->rx.pairAcc) return GTX_OK;
+  const size_t n = 2 * (size_t)std::max<int64_t>(c->nRefs, 1);
+  HIPCHK(c, c->rx.pairAcc.alloc(n));
+  HIPCHK(c, hipMemset(c->rx.pairAcc.get(), 0, sizeof(u64) * n));
   return GTX_OK;
 }
 
@@ -1051,7 +1069,7 @@ static bool blocks_monotone(const int32_t *b, int64_t cnt)
 }
 
 // the reference regions' interval lists as the kernels take them (none: every region is its envelope)
-static gtx::RegionBlocks ref_blocks(const gtx_ctx *c) { return gtx::RegionBlocks{c->refBlocks ? c->d_blkOf : nullptr, c->d_blkIv}; }
+static gtx::RegionBlocks ref_blocks(const gtx_ctx *c) { return gtx::RegionBlocks{c->rx.refBlocks ? c->rx.blkOf.get() : nullptr, c->rx.blkIv.get()}; }
 
 extern "C" {
 
@@ -1062,8 +1080,7 @@ int gtx_set_ref_blocks(gtx_ctx *c, const int64_t *first, const int32_t *blocks)
   if (c->streamOpen || c->covOpen) return fail(c, GTX_E_STATE, "gtx_set_ref_blocks: a call is open");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(c->pairMulti.d_mem); dfree(c->pairAll.d_mem); dfree(c->d_blkOf); dfree(c->d_blkIv);
-  c->pairMulti = gtx_ctx::PairIdx(); c->pairAll = gtx_ctx::PairIdx(); c->refBlocks = false; c->joinMono = -1; dfree(c->d_offRef);
+  c->rx.pairMulti = {}; c->rx.pairAll = {}; c->rx.blkOf.reset(); c->rx.blkIv.reset(); c->rx.refBlocks = false; c->rx.joinMono = -1; c->rx.offRef.reset();
   if (!first) return GTX_OK;                                   // back to single-interval regions
   const int64_t m = c->nRefs;
   if (first[0] != 0) return fail(c, GTX_E_ARG, "gtx_set_ref_blocks: first[0] must be 0");
@@ -1081,13 +1098,11 @@ int gtx_set_ref_blocks(gtx_ctx *c, const int64_t *first, const int32_t *blocks)
     for (int64_t j = 0; j < cnt; j++) iv.push_back(make_int2(b[2 * j], b[2 * j + 1]));
   }
   if (iv.empty()) return GTX_OK;                               // no multi-interval region: nothing to correct
-  HIPCHK(c, hipMalloc(&c->d_blkOf, sizeof(int2) * blkOf.size()));
-  HIPCHK(c, hipMalloc(&c->d_blkIv, sizeof(int2) * iv.size()));
-  HIPCHK(c, hipMemcpy(c->d_blkOf, blkOf.data(), sizeof(int2) * blkOf.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_blkIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice));
-  int rc = build_pair_index(c, &c->pairMulti, [&](int64_t k) { return blkOf[k].y > 0; }); if (rc) return rc;
+  HIPCHK(c, upload(c->rx.blkOf, blkOf.data(), blkOf.size()));
+  HIPCHK(c, upload(c->rx.blkIv, iv.data(), iv.size()));
+  int rc = build_pair_index(c, &c->rx.pairMulti, [&](int64_t k) { return blkOf[k].y > 0; }); if (rc) return rc;
   rc = pair_acc(c); if (rc) return rc;
-  c->refBlocks = true;
+  c->rx.refBlocks = true;
   return GTX_OK;
 }
 
@@ -1110,60 +1125,47 @@ int gtx_count_add_regions(gtx_ctx *c, const int32_t *env, const int32_t *weights
     qb[i] = make_int2((int)first[i], (int)cnt);
     for (int64_t j = 0; j < cnt; j++) iv[first[i] + j] = make_int2(b[2 * j], b[2 * j + 1]);
   }
-  if (!c->pairAll.built) { int rc = build_pair_index(c, &c->pairAll, [](int64_t) { return true; }); if (rc) return rc; }
+  if (!c->rx.pairAll.built) { int rc = build_pair_index(c, &c->rx.pairAll, [](int64_t) { return true; }); if (rc) return rc; }
   { int rc = pair_acc(c); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));                  // (the kernel of the previous call may still read the query buffers)
-  if ((size_t)n > c->capPairQ) {
-    dfree(c->d_pairQ); dfree(c->d_pairQBlk); c->capPairQ = 0;
-    HIPCHK(c, hipMalloc(&c->d_pairQ, sizeof(int4) * (size_t)n)); HIPCHK(c, hipMalloc(&c->d_pairQBlk, sizeof(int2) * (size_t)n));
-    c->capPairQ = (size_t)n;
-  }
-  if (iv.size() > c->capPairIv) { dfree(c->d_pairQIv); c->capPairIv = 0; HIPCHK(c, hipMalloc(&c->d_pairQIv, sizeof(int2) * iv.size())); c->capPairIv = iv.size(); }
-  HIPCHK(c, hipMemcpy(c->d_pairQ, q.data(), sizeof(int4) * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_pairQBlk, qb.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_pairQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, gtx::launch_pair_hit(c->d_pairQ, c->d_pairQBlk, c->d_pairQIv, n, c->pairAll.ix, ref_blocks(c), c->d_pairAcc,
+  if ((size_t)n > c->pairQBlk.cap) { c->pairQ.reset(); c->pairQBlk.reset(); HIPCHK(c, c->pairQ.alloc((size_t)n)); HIPCHK(c, c->pairQBlk.alloc((size_t)n)); }
+  HIPCHK(c, c->pairQIv.reserve(iv.size()));
+  HIPCHK(c, hipMemcpy(c->pairQ.get(), q.data(), sizeof(int4) * (size_t)n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->pairQBlk.get(), qb.data(), sizeof(int2) * (size_t)n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->pairQIv.get(), iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, gtx::launch_pair_hit(c->pairQ.get(), c->pairQBlk.get(), c->pairQIv.get(), n, c->rx.pairAll.ix, ref_blocks(c), c->rx.pairAcc.get(),
                                  c->stream));
   c->pairUsed = true;
   return GTX_OK;
 }
 
-int gtxi_pairs_on(gtx_ctx *c) { return c && (c->refBlocks || c->pairUsed) ? 1 : 0; }
+int gtxi_pairs_on(gtx_ctx *c) { return c && (c->rx.refBlocks || c->pairUsed) ? 1 : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // the overlap join (gtx_join.hip)
 // ---------------------------------------------------------------------------------------------
 } // extern "C"
 
-template <class T> static int grow(gtx_ctx *c, T *&p, size_t &cap, size_t n)
-{
-  if (n <= cap && p) return GTX_OK;
-  dfree(p); cap = 0;
-  HIPCHK(c, hipMalloc(&p, sizeof(T) * std::max<size_t>(n, 1)));
-  cap = std::max<size_t>(n, 1);
-  return GTX_OK;
-}
-
 // the envelope index over all regions, and whether a query's pairs come out of the walk already in key order: the emit pass
 // writes them by ascending index position, so that holds when (key, ordinal) ascends along the index inside every class --
 // ordinal keys on a position-sorted set (the sorted merge's) are the common case
 static int join_prepare(gtx_ctx *c)
 {
-  if (!c->pairAll.built) { c->joinMono = -1; int rc = build_pair_index(c, &c->pairAll, [](int64_t) { return true; }); if (rc) return rc; }
-  if (c->joinMono >= 0) return GTX_OK;
-  const int n = c->pairAll.n, nc = c->nClasses;
+  if (!c->rx.pairAll.built) { c->rx.joinMono = -1; int rc = build_pair_index(c, &c->rx.pairAll, [](int64_t) { return true; }); if (rc) return rc; }
+  if (c->rx.joinMono >= 0) return GTX_OK;
+  const int n = c->rx.pairAll.n, nc = c->nClasses;
   std::vector<int32_t> seg(nc + 1), id(std::max(n, 1));
-  HIPCHK(c, hipMemcpy(seg.data(), c->pairAll.ix.seg, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost));
-  if (n) HIPCHK(c, hipMemcpy(id.data(), c->pairAll.ix.id, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  const bool keyed = !c->h_joinKey.empty();
+  HIPCHK(c, hipMemcpy(seg.data(), c->rx.pairAll.ix.seg, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost));
+  if (n) HIPCHK(c, hipMemcpy(id.data(), c->rx.pairAll.ix.id, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  const bool keyed = !c->rx.h_joinKey.empty();
   bool mono = true;
   for (int cl = 0; cl < nc && mono; cl++)
     for (int i = seg[cl] + 1; i < seg[cl + 1] && mono; i++) {
       const int32_t a = id[i - 1], b = id[i];
-      const long long ka = keyed ? c->h_joinKey[a] : a, kb = keyed ? c->h_joinKey[b] : b;
+      const long long ka = keyed ? c->rx.h_joinKey[a] : a, kb = keyed ? c->rx.h_joinKey[b] : b;
       mono = ka < kb || (ka == kb && a < b);
     }
-  c->joinMono = mono ? 1 : 0;
+  c->rx.joinMono = mono ? 1 : 0;
   return GTX_OK;
 }
 
@@ -1178,17 +1180,17 @@ static int join_count(gtx_ctx *c, const gtx::JoinQueries &q, int mode, long long
 {
   HIPCHK(c, hipSetDevice(c->device));
   int rc = join_prepare(c); if (rc) return rc;
-  if (!c->d_joinInfo) { HIPCHK(c, hipMalloc(&c->d_joinInfo, sizeof(gtx::JoinInfo))); }
-  if (!c->d_joinCut) { HIPCHK(c, hipMalloc(&c->d_joinCut, sizeof(long long) * 2)); }
-  rc = grow(c, c->d_joinPart, c->capJoinPart, (size_t)gtx::join_scan_partials(q.n + 1)); if (rc) return rc;
+  if (!c->joinInfo) HIPCHK(c, c->joinInfo.alloc(1));
+  if (!c->joinCut) HIPCHK(c, c->joinCut.alloc(2));
+  HIPCHK(c, c->joinPart.grow((size_t)gtx::join_scan_partials(q.n + 1)));
   const gtx::JoinInfo init = {0, 0, INT64_MAX, INT64_MAX, 0};
-  HIPCHK(c, hipMemcpyAsync(c->d_joinInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, gtx::launch_join_count(q, c->pairAll.ix, ref_blocks(c), mode, d_off, c->d_joinInfo, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->joinInfo.get(), &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_join_count(q, c->rx.pairAll.ix, ref_blocks(c), mode, d_off, c->joinInfo.get(), c->stream));
   HIPCHK(c, hipMemsetAsync(d_off + q.n, 0, sizeof(long long), c->stream));
-  HIPCHK(c, gtx::launch_join_scan(d_off, q.n + 1, c->d_joinPart, c->stream));
+  HIPCHK(c, gtx::launch_join_scan(d_off, q.n + 1, c->joinPart.get(), c->stream));
   long long t = 0;
   HIPCHK(c, hipMemcpyAsync(&t, d_off + q.n, sizeof t, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(hi, c->d_joinInfo, sizeof *hi, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hi, c->joinInfo.get(), sizeof *hi, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *total = t;
   return GTX_OK;
@@ -1197,13 +1199,13 @@ static int join_count(gtx_ctx *c, const gtx::JoinQueries &q, int mode, long long
 // the pairs of queries [q0, q1) into d_pairs (their offsets relative to d_off[q0]), sorted by key; scratch: a buffer as long
 static int join_emit(gtx_ctx *c, const gtx::JoinQueries &q, int mode, const long long *d_off, int64_t q0, int64_t q1, int *d_pairs, int *d_scratch)
 {
-  HIPCHK(c, gtx::launch_join_emit(q, q0, q1, c->pairAll.ix, ref_blocks(c), mode, d_off, d_pairs, c->d_joinInfo, c->stream));
-  if (!c->joinMono) {
-    int rc = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(q1 - q0 + 1)); if (rc) return rc;
-    HIPCHK(c, gtx::launch_join_sort(d_off, q0, q1, c->d_joinKey, d_pairs, d_scratch, c->d_joinBig, c->stream));
+  HIPCHK(c, gtx::launch_join_emit(q, q0, q1, c->rx.pairAll.ix, ref_blocks(c), mode, d_off, d_pairs, c->joinInfo.get(), c->stream));
+  if (!c->rx.joinMono) {
+    HIPCHK(c, c->joinBig.grow((size_t)(q1 - q0 + 1)));
+    HIPCHK(c, gtx::launch_join_sort(d_off, q0, q1, c->rx.joinKey.get(), d_pairs, d_scratch, c->joinBig.get(), c->stream));
   }
   long long mismatch = 0;
-  HIPCHK(c, hipMemcpyAsync(&mismatch, &c->d_joinInfo->mismatch, sizeof mismatch, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&mismatch, &c->joinInfo.get()->mismatch, sizeof mismatch, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (mismatch) return fail(c, GTX_E_HIP, "gtx_join: the emit pass found another number of pairs than the count pass");
   return GTX_OK;
@@ -1212,9 +1214,9 @@ static int join_emit(gtx_ctx *c, const gtx::JoinQueries &q, int mode, const long
 // the longest run of queries from q0 whose pairs fit `cap`
 static int join_cut(gtx_ctx *c, const long long *d_off, int64_t q0, int64_t n, int64_t cap, int64_t *q1)
 {
-  HIPCHK(c, gtx::launch_join_cut(d_off, q0, n, cap, c->d_joinCut, c->stream));
+  HIPCHK(c, gtx::launch_join_cut(d_off, q0, n, cap, c->joinCut.get(), c->stream));
   long long v = 0;
-  HIPCHK(c, hipMemcpyAsync(&v, c->d_joinCut, sizeof v, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&v, c->joinCut.get(), sizeof v, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *q1 = v;
   return GTX_OK;
@@ -1236,11 +1238,10 @@ int gtx_set_ref_order(gtx_ctx *c, const int64_t *key)
   if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_set_ref_order: gtx_set_refs has not been called");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_joinKey); c->h_joinKey.clear(); c->joinMono = -1;
+  c->rx.joinKey.reset(); c->rx.h_joinKey.clear(); c->rx.joinMono = -1;
   if (!key || c->nRefs == 0) return GTX_OK;
-  c->h_joinKey.assign(key, key + c->nRefs);
-  HIPCHK(c, hipMalloc(&c->d_joinKey, sizeof(long long) * (size_t)c->nRefs));
-  HIPCHK(c, hipMemcpy(c->d_joinKey, key, sizeof(long long) * (size_t)c->nRefs, hipMemcpyHostToDevice));
+  c->rx.h_joinKey.assign(key, key + c->nRefs);
+  HIPCHK(c, upload(c->rx.joinKey, (const long long *)key, (size_t)c->nRefs));
   return GTX_OK;
 }
 
@@ -1268,8 +1269,8 @@ int gtx_join_device(gtx_ctx *c, const void *d_reads, int64_t n, uint32_t flags, 
   if (q1 > 0) {
     int64_t len = 0;
     if (q1 < n) HIPCHK(c, hipMemcpy(&len, off + q1, sizeof len, hipMemcpyDeviceToHost)); else len = total;
-    if (!c->joinMono) { rc = grow(c, c->d_joinScratch, c->capJoinScratch, (size_t)len); if (rc) return rc; }
-    rc = join_emit(c, q, mode, off, 0, q1, (int *)d_pairs, c->d_joinScratch); if (rc) return rc;
+    if (!c->rx.joinMono) { HIPCHK(c, c->joinScratch.grow((size_t)len)); }
+    rc = join_emit(c, q, mode, off, 0, q1, (int *)d_pairs, c->joinScratch.get()); if (rc) return rc;
   }
   if (n_pairs_out) *n_pairs_out = total;
   if (n_done_out) *n_done_out = q1;
@@ -1291,9 +1292,9 @@ static int stage_queries(gtx_ctx *c, const std::string &w, const int32_t *reads,
                          int64_t b1, bool with_blocks, std::vector<int2> &qb, std::vector<int2> &iv, gtx::JoinQueries &q)
 {
   const int64_t m = b1 - b0;
-  int rc = grow(c, c->d_joinReads, c->capJoinReads, (size_t)(3 * m)); if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->d_joinReads, reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
-  q = gtx::JoinQueries{c->d_joinReads, nullptr, nullptr, m};
+  HIPCHK(c, c->joinReads.grow((size_t)(3 * m)));
+  HIPCHK(c, hipMemcpyAsync(c->joinReads.get(), reads + 3 * b0, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+  q = gtx::JoinQueries{c->joinReads.get(), nullptr, nullptr, m};
   if (!first || !with_blocks) return GTX_OK;
   qb.resize((size_t)m);
   const int64_t i0 = first[b0];
@@ -1308,11 +1309,11 @@ static int stage_queries(gtx_ctx *c, const std::string &w, const int32_t *reads,
   }
   iv.resize((size_t)std::max<int64_t>(first[b1] - i0, 1));
   for (int64_t j = i0; j < first[b1]; j++) iv[j - i0] = make_int2(blocks[2 * j], blocks[2 * j + 1]);
-  rc = grow(c, c->d_joinQBlk, c->capJoinQBlk, qb.size()); if (rc) return rc;
-  rc = grow(c, c->d_joinQIv, c->capJoinQIv, iv.size()); if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->d_joinQBlk, qb.data(), sizeof(int2) * qb.size(), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->d_joinQIv, iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice, c->stream));
-  q.blk = c->d_joinQBlk; q.iv = c->d_joinQIv;
+  HIPCHK(c, c->joinQBlk.grow(qb.size()));
+  HIPCHK(c, c->joinQIv.grow(iv.size()));
+  HIPCHK(c, hipMemcpyAsync(c->joinQBlk.get(), qb.data(), sizeof(int2) * qb.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->joinQIv.get(), iv.data(), sizeof(int2) * iv.size(), hipMemcpyHostToDevice, c->stream));
+  q.blk = c->joinQBlk.get(); q.iv = c->joinQIv.get();
   return GTX_OK;
 }
 
@@ -1339,27 +1340,27 @@ static int join_batches(gtx_ctx *c, const char *who, const int32_t *reads, const
     gtx::JoinQueries q{};
     std::vector<int2> qb, iv;
     int rc = stage_queries(c, w, reads, first, blocks, b0, b1, all_blocks || !(mode & gtx::JOIN_GAPS), qb, iv, q); if (rc) return rc;
-    rc = grow(c, c->d_joinOff, c->capJoinOff, (size_t)(m + 1)); if (rc) return rc;
+    HIPCHK(c, c->joinOff.grow((size_t)(m + 1)));
     int64_t total = 0; gtx::JoinInfo hi;
-    rc = join_count(c, q, mode, c->d_joinOff, &total, &hi); if (rc) return rc;      // (synchronises: qb / iv may go)
+    rc = join_count(c, q, mode, c->joinOff.get(), &total, &hi); if (rc) return rc;      // (synchronises: qb / iv may go)
     if ((flags & GTX_CHECK_SORTED) && b0 > 0 && acc.first_unsorted < 0) {           // the seam between two batches comes before the batch's own
       const int32_t *p = reads + 3 * (b0 - 1), *r = reads + 3 * b0;
       if (r[0] < p[0] || (r[0] == p[0] && r[1] < p[1])) acc.first_unsorted = b0;
     }
     join_info_merge(&acc, hi, b0);
-    HIPCHK(c, hipMemcpy(offsets_out + b0, c->d_joinOff, sizeof(int64_t) * (m + 1), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(offsets_out + b0, c->joinOff.get(), sizeof(int64_t) * (m + 1), hipMemcpyDeviceToHost));
     for (int64_t i = b0; i <= b1; i++) offsets_out[i] += base;
     // pairs chunk by chunk: the longest run of queries that fits the device buffer, or one query alone in a buffer of its size
     const int64_t chunk = std::min<int64_t>(c->joinBuffer, std::max<int64_t>(total, 1));
     for (int64_t q0 = 0; q0 < m && offsets_out[b0 + q0] < cap;) {
       int64_t q1 = m;
-      if (offsets_out[b1] - offsets_out[b0 + q0] > chunk) { rc = join_cut(c, c->d_joinOff, q0, m, chunk, &q1); if (rc) return rc; }
+      if (offsets_out[b1] - offsets_out[b0 + q0] > chunk) { rc = join_cut(c, c->joinOff.get(), q0, m, chunk, &q1); if (rc) return rc; }
       if (q1 == q0) q1 = q0 + 1;
       const int64_t p0 = offsets_out[b0 + q0], len = offsets_out[b0 + q1] - p0;
       if (len > 0) {
-        rc = grow(c, c->d_joinPairs, c->capJoinPairs, (size_t)len); if (rc) return rc;
-        if (!c->joinMono) { rc = grow(c, c->d_joinScratch, c->capJoinScratch, (size_t)len); if (rc) return rc; }
-        rc = join_emit(c, q, mode, c->d_joinOff, q0, q1, c->d_joinPairs, c->d_joinScratch); if (rc) return rc;
+        HIPCHK(c, c->joinPairs.grow((size_t)len));
+        if (!c->rx.joinMono) { HIPCHK(c, c->joinScratch.grow((size_t)len)); }
+        rc = join_emit(c, q, mode, c->joinOff.get(), q0, q1, c->joinPairs.get(), c->joinScratch.get()); if (rc) return rc;
         rc = on_chunk(q, b0, q0, q1, p0, len); if (rc) return rc;
       }
       q0 = q1;
@@ -1379,7 +1380,7 @@ int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32
   return join_batches(c, "gtx_join", reads, first, blocks, n, flags, false, offsets_out, cap, info,
                       [&](const gtx::JoinQueries &, int64_t, int64_t, int64_t, int64_t p0, int64_t len) {
                         const int64_t keep = std::min(len, cap - p0);
-                        HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
+                        HIPCHK(c, hipMemcpy(pairs_out + p0, c->joinPairs.get(), sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
                         return GTX_OK;
                       });
 }
@@ -1393,18 +1394,16 @@ int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32
 // the per-ordinal reference point (front / back interval) as of gtx_set_ref_blocks
 static int offset_prepare(gtx_ctx *c)
 {
-  if (c->d_offRef) return GTX_OK;
+  if (c->rx.offRef) return GTX_OK;
   const size_t m = (size_t)std::max<int64_t>(c->nRefs, 1);
   std::vector<int2> env(m, make_int2(0, 0));
   for (int64_t k = 0; k < c->nRefs; k++) env[k] = make_int2(c->h_refS[k], c->h_refE[k]);
-  int2 *d_env = nullptr;
-  HIPCHK(c, hipMalloc(&d_env, sizeof(int2) * m));
-  HIPCHK(c, hipMalloc(&c->d_offRef, sizeof(int4) * m));
-  hipError_t e = hipMemcpy(d_env, env.data(), sizeof(int2) * m, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = gtx::launch_ref_ends(d_env, ref_blocks(c), c->nRefs, c->d_offRef, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(d_env);
-  HIPCHK(c, e);
+  DevBuf<int2> d_env;
+  HIPCHK(c, d_env.alloc(m));
+  HIPCHK(c, c->rx.offRef.alloc(m));
+  HIPCHK(c, hipMemcpy(d_env.get(), env.data(), sizeof(int2) * m, hipMemcpyHostToDevice));
+  HIPCHK(c, gtx::launch_ref_ends(d_env.get(), ref_blocks(c), c->nRefs, c->rx.offRef.get(), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));                   // (before d_env goes)
   return GTX_OK;
 }
 
@@ -1416,10 +1415,10 @@ static int pair_offsets(gtx_ctx *c, const gtx::OffsetArgs &a, int64_t q0, int64_
                         long long *d_out, long long *inv)
 {
   const long long none = INT64_MAX;
-  HIPCHK(c, hipMemcpyAsync(c->d_offInv, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, gtx::launch_pair_offsets(a, q0, q1, d_off, d_pairs, n_pairs, d_out, c->d_offInv, c->d_joinBig, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->offInv.get(), &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_pair_offsets(a, q0, q1, d_off, d_pairs, n_pairs, d_out, c->offInv.get(), c->joinBig.get(), c->stream));
   *inv = INT64_MAX;
-  HIPCHK(c, hipMemcpyAsync(inv, c->d_offInv, sizeof *inv, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(inv, c->offInv.get(), sizeof *inv, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return GTX_OK;
 }
@@ -1432,12 +1431,11 @@ int gtx_set_ref_strands(gtx_ctx *c, const int8_t *strand)
   if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_set_ref_strands: gtx_set_refs has not been called");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_refStrand);
+  c->rx.refStrand.reset();
   if (!strand || c->nRefs == 0) return GTX_OK;
   for (int64_t k = 0; k < c->nRefs; k++)
     if (strand[k] != '+' && strand[k] != '-') return fail(c, GTX_E_ARG, "gtx_set_ref_strands: a strand is '+' or '-'");
-  HIPCHK(c, hipMalloc(&c->d_refStrand, (size_t)c->nRefs));
-  HIPCHK(c, hipMemcpy(c->d_refStrand, strand, (size_t)c->nRefs, hipMemcpyHostToDevice));
+  HIPCHK(c, upload(c->rx.refStrand, strand, (size_t)c->nRefs));
   return GTX_OK;
 }
 
@@ -1455,48 +1453,48 @@ int gtx_join_offsets(gtx_ctx *c, const int32_t *reads, const int64_t *first, con
   int rc = offset_prepare(c); if (rc) return rc;
   int64_t ebase = 0, inverted = -1, strandsOf = -1;            // entries before the chunk; the first inverted pair; the batch whose strands are up
   if (cap > 0) entry_offsets_out[0] = 0;
-  if (!c->d_offInv) { HIPCHK(c, hipMalloc(&c->d_offInv, sizeof(long long))); }
+  if (!c->offInv) HIPCHK(c, c->offInv.alloc(1));
   rc = join_batches(c, "gtx_join_offsets", reads, first, blocks, n, flags, true, offsets_out, cap, info,
     [&](const gtx::JoinQueries &q, int64_t b0, int64_t q0, int64_t q1, int64_t p0, int64_t len) -> int {
       int r = GTX_OK;
       const int64_t keep = std::min(len, cap - p0);
-      HIPCHK(c, hipMemcpy(pairs_out + p0, c->d_joinPairs, sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
-      gtx::OffsetArgs a{q, nullptr, c->d_offRef, c->d_refStrand, ref_blocks(c), o, fromQuery};
+      HIPCHK(c, hipMemcpy(pairs_out + p0, c->joinPairs.get(), sizeof(int32_t) * keep, hipMemcpyDeviceToHost));
+      gtx::OffsetArgs a{q, nullptr, c->rx.offRef.get(), c->rx.refStrand.get(), ref_blocks(c), o, fromQuery};
       if (fromQuery && read_strands) {
         if (strandsOf != b0) {
           const int64_t m = std::min<int64_t>(n - b0, std::max<int64_t>(1, c->batchReads));
-          r = grow(c, c->d_offQStrand, c->capOffQStrand, (size_t)m); if (r) return r;
-          HIPCHK(c, hipMemcpy(c->d_offQStrand, read_strands + b0, (size_t)m, hipMemcpyHostToDevice));
+          HIPCHK(c, c->offQStrand.grow((size_t)m));
+          HIPCHK(c, hipMemcpy(c->offQStrand.get(), read_strands + b0, (size_t)m, hipMemcpyHostToDevice));
           strandsOf = b0;
         }
-        a.qStrand = c->d_offQStrand;
+        a.qStrand = c->offQStrand.get();
       }
-      r = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(q1 - q0 + 1)); if (r) return r;
+      HIPCHK(c, c->joinBig.grow((size_t)(q1 - q0 + 1)));
       int64_t nent = len;
       if (!skip) {
-        r = grow(c, c->d_offOut, c->capOffOut, (size_t)(2 * len)); if (r) return r;
+        HIPCHK(c, c->offOut.grow((size_t)(2 * len)));
         long long inv;
-        r = pair_offsets(c, a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offOut, &inv); if (r) return r;
+        r = pair_offsets(c, a, q0, q1, c->joinOff.get(), c->joinPairs.get(), len, c->offOut.get(), &inv); if (r) return r;
         if (inverted < 0 && inv < keep) inverted = p0 + inv;
         for (int64_t p = 1; p <= keep; p++) entry_offsets_out[p0 + p] = ebase + p;
         nent = keep;
       } else {
-        r = grow(c, c->d_offCnt, c->capOffCnt, (size_t)(len + 1)); if (r) return r;
-        r = grow(c, c->d_offPart, c->capOffPart, (size_t)gtx::join_scan_partials(len + 1)); if (r) return r;
-        HIPCHK(c, gtx::launch_pair_gaps_count(a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offCnt, c->d_joinBig, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_offCnt + len, 0, sizeof(long long), c->stream));
-        HIPCHK(c, gtx::launch_join_scan(c->d_offCnt, len + 1, c->d_offPart, c->stream));
+        HIPCHK(c, c->offCnt.grow((size_t)(len + 1)));
+        HIPCHK(c, c->offPart.grow((size_t)gtx::join_scan_partials(len + 1)));
+        HIPCHK(c, gtx::launch_pair_gaps_count(a, q0, q1, c->joinOff.get(), c->joinPairs.get(), len, c->offCnt.get(), c->joinBig.get(), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->offCnt.get() + len, 0, sizeof(long long), c->stream));
+        HIPCHK(c, gtx::launch_join_scan(c->offCnt.get(), len + 1, c->offPart.get(), c->stream));
         std::vector<int64_t> eoff((size_t)len + 1);
-        HIPCHK(c, hipMemcpyAsync(eoff.data(), c->d_offCnt, sizeof(int64_t) * (len + 1), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(eoff.data(), c->offCnt.get(), sizeof(int64_t) * (len + 1), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         nent = eoff[len];
-        r = grow(c, c->d_offOut, c->capOffOut, (size_t)(2 * nent)); if (r) return r;
-        if (nent > 0) HIPCHK(c, gtx::launch_pair_gaps_emit(a, q0, q1, c->d_joinOff, c->d_joinPairs, len, c->d_offCnt, c->d_offOut, c->d_joinBig, c->stream));
+        HIPCHK(c, c->offOut.grow((size_t)(2 * nent)));
+        if (nent > 0) HIPCHK(c, gtx::launch_pair_gaps_emit(a, q0, q1, c->joinOff.get(), c->joinPairs.get(), len, c->offCnt.get(), c->offOut.get(), c->joinBig.get(), c->stream));
         for (int64_t p = 1; p <= keep; p++) entry_offsets_out[p0 + p] = ebase + eoff[p];
         nent = eoff[keep];
       }
       const int64_t ekeep = std::max<int64_t>(0, std::min(nent, entry_cap - ebase));
-      if (ekeep > 0) HIPCHK(c, hipMemcpy(entries_out + 2 * ebase, c->d_offOut, sizeof(int64_t) * 2 * ekeep, hipMemcpyDeviceToHost));
+      if (ekeep > 0) HIPCHK(c, hipMemcpy(entries_out + 2 * ebase, c->offOut.get(), sizeof(int64_t) * 2 * ekeep, hipMemcpyDeviceToHost));
       ebase += nent;
       return GTX_OK;
     });
@@ -1515,9 +1513,9 @@ int gtx_pair_offsets_device(gtx_ctx *c, const void *d_reads, int64_t n, const vo
     return fail(c, GTX_E_ARG, "gtx_pair_offsets_device: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
   int rc = offset_prepare(c); if (rc) return rc;
-  if (!c->d_offInv) { HIPCHK(c, hipMalloc(&c->d_offInv, sizeof(long long))); }
-  rc = grow(c, c->d_joinBig, c->capJoinBig, (size_t)(n + 1)); if (rc) return rc;
-  const gtx::OffsetArgs a{gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n}, nullptr, c->d_offRef, c->d_refStrand, ref_blocks(c), o, false};
+  if (!c->offInv) HIPCHK(c, c->offInv.alloc(1));
+  HIPCHK(c, c->joinBig.grow((size_t)(n + 1)));
+  const gtx::OffsetArgs a{gtx::JoinQueries{(const int *)d_reads, nullptr, nullptr, n}, nullptr, c->rx.offRef.get(), c->rx.refStrand.get(), ref_blocks(c), o, false};
   long long inv;
   rc = pair_offsets(c, a, 0, n, (const long long *)d_offsets, (const int *)d_pairs, n_pairs, (long long *)d_out, &inv); if (rc) return rc;
   if (first_inverted_out) *first_inverted_out = inv == INT64_MAX ? -1 : inv;
@@ -1531,12 +1529,9 @@ int gtx_set_signal_bins(gtx_ctx *c, double bin_min, double bin_max, int64_t n_bi
   if (n_bins < 0 || n_bins >= INT32_MAX) return fail(c, GTX_E_ARG, "gtx_set_signal_bins: n_bins must lie in [0, 2^31 - 1)");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  dfree(c->d_sigRefLen);
-  if (ref_len && c->nRefs > 0) {
-    HIPCHK(c, hipMalloc(&c->d_sigRefLen, sizeof(long long) * (size_t)c->nRefs));
-    HIPCHK(c, hipMemcpy(c->d_sigRefLen, ref_len, sizeof(long long) * (size_t)c->nRefs, hipMemcpyHostToDevice));
-  }
-  c->sigMin = bin_min; c->sigMax = bin_max; c->sigBins = n_bins; c->sigSet = true;
+  c->rx.sigRefLen.reset();
+  if (ref_len && c->nRefs > 0) HIPCHK(c, upload(c->rx.sigRefLen, (const long long *)ref_len, (size_t)c->nRefs));
+  c->rx.sigMin = bin_min; c->rx.sigMax = bin_max; c->rx.sigBins = n_bins; c->rx.sigSet = true;
   return GTX_OK;
 }
 
@@ -1553,23 +1548,23 @@ static int signal_prepare(gtx_ctx *c, const char *who, uint32_t flags, gtx::Sign
 {
   const std::string w(who);
   if (c->nRefs < 0) return fail(c, GTX_E_STATE, (w + ": gtx_set_refs has not been called").c_str());
-  if (!c->sigSet) return fail(c, GTX_E_STATE, (w + ": gtx_set_signal_bins has not been called").c_str());
+  if (!c->rx.sigSet) return fail(c, GTX_E_STATE, (w + ": gtx_set_signal_bins has not been called").c_str());
   if (flags & ~kSignalFlags) return fail(c, GTX_E_ARG, (w + ": unknown flag").c_str());
   HIPCHK(c, hipSetDevice(c->device));
   int rc = join_prepare(c); if (rc) return rc;
   rc = offset_prepare(c); if (rc) return rc;
-  if (!c->d_sigInfo) { HIPCHK(c, hipMalloc(&c->d_sigInfo, sizeof(gtx::SignalInfo))); }
+  if (!c->sigInfo) HIPCHK(c, c->sigInfo.alloc(1));
   a = gtx::SignalArgs{};
-  a.ix = c->pairAll.ix;
+  a.ix = c->rx.pairAll.ix;
   a.rb = ref_blocks(c);
   a.mode = join_mode(c, flags & (GTX_ZERO_LENGTH_OK | GTX_JOIN_GAPS));
-  a.refEnds = c->d_offRef; a.refStrand = (const signed char *)c->d_refStrand; a.refLen = c->d_sigRefLen;
-  a.binMin = c->sigMin; a.binMax = c->sigMax; a.nBins = c->sigBins;
+  a.refEnds = c->rx.offRef.get(); a.refStrand = (const signed char *)c->rx.refStrand.get(); a.refLen = c->rx.sigRefLen.get();
+  a.binMin = c->rx.sigMin; a.binMax = c->rx.sigMax; a.nBins = c->rx.sigBins;
   a.perRef = (flags & GTX_SIGNAL_PER_REF) != 0;
   return GTX_OK;
 }
 
-static int64_t signal_len(const gtx_ctx *c, uint32_t flags) { return ((flags & GTX_SIGNAL_PER_REF) ? std::max<int64_t>(c->nRefs, 0) : 1) * c->sigBins; }
+static int64_t signal_len(const gtx_ctx *c, uint32_t flags) { return ((flags & GTX_SIGNAL_PER_REF) ? std::max<int64_t>(c->nRefs, 0) : 1) * c->rx.sigBins; }
 static int signal_cus(const gtx_ctx *c) { return (int)std::max<int64_t>(1, c->waveSlots / 32); }
 
 // the signal pass of a.q into d_bins with a fresh info block, then that block into *info / *firstInv (read indices from base);
@@ -1577,10 +1572,10 @@ static int signal_cus(const gtx_ctx *c) { return (int)std::max<int64_t>(1, c->wa
 static int signal_pass(gtx_ctx *c, const gtx::SignalArgs &a, unsigned long long *d_bins, gtx_signal_info *info, long long *firstInv, int64_t base)
 {
   const gtx::SignalInfo init = {0, 0, 0, 0, 0, 0, INT64_MAX};
-  HIPCHK(c, hipMemcpyAsync(c->d_sigInfo, &init, sizeof init, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, gtx::launch_signal_bins(a, d_bins, c->d_sigInfo, signal_cus(c), c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->sigInfo.get(), &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, gtx::launch_signal_bins(a, d_bins, c->sigInfo.get(), signal_cus(c), c->stream));
   gtx::SignalInfo h;
-  HIPCHK(c, hipMemcpyAsync(&h, c->d_sigInfo, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&h, c->sigInfo.get(), sizeof h, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (info) {
     info->n_pairs += (int64_t)h.pairs; info->n_binned += (int64_t)h.binned; info->n_dropped += (int64_t)h.dropped;
@@ -1617,8 +1612,8 @@ int gtx_signal_bins(gtx_ctx *c, const int32_t *reads, const int64_t *first, cons
   const int64_t len = signal_len(c, flags);
   if ((len > 0 && !bins_out) || !queries_ok(reads, first, blocks, n)) return fail(c, GTX_E_ARG, "gtx_signal_bins: bad argument");
   if (info) memset(info, 0, sizeof *info);
-  rc = grow(c, c->d_sigBins, c->capSigBins, (size_t)std::max<int64_t>(len, 1)); if (rc) return rc;
-  HIPCHK(c, hipMemsetAsync(c->d_sigBins, 0, sizeof(unsigned long long) * (size_t)std::max<int64_t>(len, 1), c->stream));
+  HIPCHK(c, c->sigBins.grow((size_t)std::max<int64_t>(len, 1)));
+  HIPCHK(c, hipMemsetAsync(c->sigBins.get(), 0, sizeof(unsigned long long) * (size_t)std::max<int64_t>(len, 1), c->stream));
   long long inv = -1;
   const int64_t per = std::max<int64_t>(1, c->batchReads);
   const std::string who("gtx_signal_bins");
@@ -1628,15 +1623,15 @@ int gtx_signal_bins(gtx_ctx *c, const int32_t *reads, const int64_t *first, cons
     rc = stage_queries(c, who, reads, first, blocks, b0, b1, true, qb, iv, a.q); if (rc) return rc;
     a.w = nullptr;
     if (weights) {
-      rc = grow(c, c->d_sigW, c->capSigW, (size_t)m); if (rc) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->d_sigW, weights + b0, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
-      a.w = c->d_sigW;
+      HIPCHK(c, c->sigW.grow((size_t)m));
+      HIPCHK(c, hipMemcpyAsync(c->sigW.get(), weights + b0, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
+      a.w = c->sigW.get();
     }
-    rc = signal_pass(c, a, c->d_sigBins, info, &inv, b0); if (rc) return rc;          // (synchronises: qb / iv may go)
+    rc = signal_pass(c, a, c->sigBins.get(), info, &inv, b0); if (rc) return rc;          // (synchronises: qb / iv may go)
   }
   if (len > 0) {
     std::vector<int64_t> h((size_t)len);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_sigBins, sizeof(int64_t) * (size_t)len, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h.data(), c->sigBins.get(), sizeof(int64_t) * (size_t)len, hipMemcpyDeviceToHost));
     for (int64_t k = 0; k < len; k++) bins_out[k] = (int64_t)((uint64_t)bins_out[k] + (uint64_t)h[k]);
   }
   if (first_inverted_out) *first_inverted_out = inv;
@@ -1653,63 +1648,26 @@ static int cover_bucket_tables(gtx_ctx *c, const std::vector<int32_t> &sortedT, 
 {
   const int nClasses = c->nClasses;
   const int kE = gtx::bucket_e_size(), kS = gtx::bucket_t_size();
-  std::vector<int32_t> posHi, eLo, eHi, sLo, sHi, cls, clsStart(nClasses + 1, 0);
+  BucketCuts k;
+  k.clsStart.assign(nClasses + 1, 0);
   for (int cl = 0; cl < nClasses; cl++) {
-    clsStart[cl] = (int32_t)posHi.size();
+    k.clsStart[cl] = (int32_t)k.posHi.size();
     const int32_t s0 = seg[cl], s1 = seg[cl + 1];
     for (int32_t e0 = s0; e0 < s1; e0 += kE) {
       const int32_t e1 = (int32_t)std::min<int64_t>((int64_t)e0 + kE, s1);
-      posHi.push_back(e1 == s1 ? INT32_MAX : sortedT[e1 - 1]);
-      eLo.push_back(e0); eHi.push_back(e1); cls.push_back(cl);
-      sLo.push_back(e0); sHi.push_back((int32_t)std::min<int64_t>((int64_t)e0 + kS, s1));
+      k.posHi.push_back(e1 == s1 ? INT32_MAX : sortedT[e1 - 1]);
+      k.eLo.push_back(e0); k.eHi.push_back(e1); k.cls.push_back(cl);
+      k.sLo.push_back(e0); k.sHi.push_back((int32_t)std::min<int64_t>((int64_t)e0 + kS, s1));
     }
   }
-  clsStart[nClasses] = (int32_t)posHi.size();
-  c->nBT = (int)posHi.size();
-  if (c->nBT > 8192 || nClasses > 2048) c->nBT = 0;
-  if (c->nBT == 0) return GTX_OK;
-  const int kCells = 4096;
-  int sh = 0;
-  auto cellsAt = [&](int shift) {
-    int64_t total = 0;
-    for (int cl = 0; cl < nClasses; cl++) {
-      const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
-      total += b1 - b0 <= 1 ? b1 - b0 : ((((int64_t)posHi[b1 - 2] - posHi[b0]) >> shift) + 1);
-    }
-    return total;
-  };
-  while (sh < 40 && cellsAt(sh) > kCells) sh++;
-  std::vector<int32_t> clsCell(4 * (size_t)nClasses);
-  std::vector<uint16_t> cellTab;
-  for (int cl = 0; cl < nClasses; cl++) {
-    const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
-    const int32_t lo = b1 - b0 <= 1 ? 0 : posHi[b0];
-    const int64_t nc = b1 == b0 ? 0 : b1 - b0 == 1 ? 1 : ((((int64_t)posHi[b1 - 2] - lo) >> sh) + 1);
-    clsCell[4 * cl] = (int32_t)cellTab.size(); clsCell[4 * cl + 1] = lo; clsCell[4 * cl + 2] = (int32_t)nc; clsCell[4 * cl + 3] = b0;
-    int b = b0;
-    for (int64_t k = 0; k < nc; k++) {
-      const int64_t first = (int64_t)lo + (k << sh);
-      while (b < b1 - 1 && (int64_t)posHi[b] < first) b++;
-      cellTab.push_back((uint16_t)(b - b0));
-    }
-  }
-  c->nCellsT = (int)cellTab.size(); c->cellShiftT = sh;
-  if (!gtx::bucket_tables_fit(nClasses, c->nBT, c->nCellsT)) { c->nBT = 0; return GTX_OK; }
-  cellTab.push_back(0);
-  std::vector<int32_t> all;
-  for (auto *v : {&posHi, &eLo, &eHi, &sLo, &sHi, &cls, &clsStart}) all.insert(all.end(), v->begin(), v->end());
-  HIPCHK(c, hipMalloc(&c->d_bktT, sizeof(int32_t) * all.size()));
-  HIPCHK(c, hipMemcpy(c->d_bktT, all.data(), sizeof(int32_t) * all.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMalloc(&c->d_clsCellT, sizeof(int32_t) * clsCell.size() + 16));
-  HIPCHK(c, hipMemcpy(c->d_clsCellT, clsCell.data(), sizeof(int32_t) * clsCell.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMalloc(&c->d_cellTabT, sizeof(uint16_t) * cellTab.size()));
-  HIPCHK(c, hipMemcpy(c->d_cellTabT, cellTab.data(), sizeof(uint16_t) * cellTab.size(), hipMemcpyHostToDevice));
-  return GTX_OK;
+  k.clsStart[nClasses] = (int32_t)k.posHi.size();
+  if (k.posHi.size() > 8192 || nClasses > 2048) { c->cv.bkt.nB = 0; return GTX_OK; }
+  return build_bucket_tables(c, c->cv.bkt, k, nClasses);
 }
 
 static int cover_prepare(gtx_ctx *c)
 {
-  if (c->covReady) return GTX_OK;
+  if (c->cv.ready) return GTX_OK;
   // the thresholds of every region that takes part (the rule of gtx_set_refs_ex): E_k and S_k - 1, sorted by (class, value)
   const int64_t m = c->nRefs;
   struct Item { int32_t cls, val, k2; };                      // k2 = 2 * region + (0: the E threshold, 1: the S - 1 threshold)
@@ -1735,33 +1693,33 @@ static int cover_prepare(gtx_ctx *c)
   const int64_t nTop = (nt + 255) >> 8;
   std::vector<int32_t> topT(nTop + 1);
   for (int64_t i = 0; i < nTop; i++) topT[i] = sortedT[i << 8];
-  c->histLenT = nt + c->nClasses;
-  const int nTiles = gtx::scan_tiles(c->histLenT);
-  HIPCHK(c, hipMalloc(&c->d_sortedT, sizeof(int32_t) * (nt + 1)));
-  HIPCHK(c, hipMalloc(&c->d_segT, sizeof(int32_t) * (c->nClasses + 1)));
-  HIPCHK(c, hipMalloc(&c->d_topT, sizeof(int32_t) * (nTop + 1)));
-  HIPCHK(c, hipMalloc(&c->d_posTE, sizeof(int32_t) * (m + 1)));
-  HIPCHK(c, hipMalloc(&c->d_posTS, sizeof(int32_t) * (m + 1)));
-  HIPCHK(c, hipMalloc(&c->d_classBaseT, sizeof(int32_t) * (m + 1)));
-  HIPCHK(c, hipMemcpy(c->d_sortedT, sortedT.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_segT, seg.data(), sizeof(int32_t) * (c->nClasses + 1), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_topT, topT.data(), sizeof(int32_t) * (nTop + 1), hipMemcpyHostToDevice));
+  c->cv.histLenT = nt + c->nClasses;
+  const int nTiles = gtx::scan_tiles(c->cv.histLenT);
+  HIPCHK(c, c->cv.sortedT.alloc(nt + 1));
+  HIPCHK(c, c->cv.segT.alloc(c->nClasses + 1));
+  HIPCHK(c, c->cv.topT.alloc(nTop + 1));
+  HIPCHK(c, c->cv.posTE.alloc(m + 1));
+  HIPCHK(c, c->cv.posTS.alloc(m + 1));
+  HIPCHK(c, c->cv.classBaseT.alloc(m + 1));
+  HIPCHK(c, hipMemcpy(c->cv.sortedT.get(), sortedT.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->cv.segT.get(), seg.data(), sizeof(int32_t) * (c->nClasses + 1), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->cv.topT.get(), topT.data(), sizeof(int32_t) * (nTop + 1), hipMemcpyHostToDevice));
   if (m > 0) {
-    HIPCHK(c, hipMemcpy(c->d_posTE, posTE.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_posTS, posTS.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_classBaseT, base.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->cv.posTE.get(), posTE.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->cv.posTS.get(), posTS.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->cv.classBaseT.get(), base.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice));
   }
   for (int q = 0; q < 4; q++) {
-    HIPCHK(c, hipMalloc(&c->d_cov[q], sizeof(u64) * c->histLenT));          // histograms
-    HIPCHK(c, hipMalloc(&c->d_cov[4 + q], sizeof(u64) * (nTiles + 2)));     // tile sums
-    HIPCHK(c, hipMalloc(&c->d_cov[8 + q], sizeof(u64) * c->histLenT));      // prefixes
-    HIPCHK(c, hipMemset(c->d_cov[q], 0, sizeof(u64) * c->histLenT));
-    HIPCHK(c, hipMemset(c->d_cov[4 + q], 0, sizeof(u64) * (nTiles + 2)));
+    HIPCHK(c, c->cv.cov[q].alloc(c->cv.histLenT));          // histograms
+    HIPCHK(c, c->cv.cov[4 + q].alloc(nTiles + 2));         // tile sums
+    HIPCHK(c, c->cv.cov[8 + q].alloc(c->cv.histLenT));      // prefixes
+    HIPCHK(c, hipMemset(c->cv.cov[q].get(), 0, sizeof(u64) * c->cv.histLenT));
+    HIPCHK(c, hipMemset(c->cv.cov[4 + q].get(), 0, sizeof(u64) * (nTiles + 2)));
   }
   { int rc = ref_columns(c); if (rc) return rc; }
   { int rc = cover_bucket_tables(c, sortedT, seg); if (rc) return rc; }
-  { int rc = make_place_table(c, seg, sortedT, sortedT, c->nClasses, nt, &c->d_placeClsT, &c->d_placeRankT, &c->placeShiftT); if (rc) return rc; }
-  c->covReady = true; c->covDirty = false;
+  { int rc = make_place_table(c, seg, sortedT, sortedT, c->nClasses, nt, c->cv.place); if (rc) return rc; }
+  c->cv.ready = true; c->covDirty = false;
   return GTX_OK;
 }
 
@@ -1769,11 +1727,11 @@ static gtx::CoverArgs cover_args(gtx_ctx *c, int64_t nReads, int64_t indexBase =
 {
   gtx::CoverArgs a;
   a.indexBase = indexBase;
-  a.sortedT = c->d_sortedT; a.segStartT = c->d_segT; a.topT = c->d_topT;
-  for (int q = 0; q < 4; q++) { a.hist[q] = c->d_cov[q]; a.part[q] = c->d_cov[4 + q]; }
-  a.info = c->d_info + c->infoCur; a.nClasses = c->nClasses;
-  const bool merge = (flags & GTX_ZERO_LENGTH_OK) && (flags & GTX_GAPS_FORMULA) && c->mergeRefs && c->d_side;
-  a.side = merge ? c->d_side : nullptr; a.sideCount = merge ? c->d_sideCount : nullptr; a.sideCap = c->sideCap;
+  a.sortedT = c->cv.sortedT.get(); a.segStartT = c->cv.segT.get(); a.topT = c->cv.topT.get();
+  for (int q = 0; q < 4; q++) { a.hist[q] = c->cv.cov[q].get(); a.part[q] = c->cv.cov[4 + q].get(); }
+  a.info = c->d_info.get() + c->infoCur; a.nClasses = c->nClasses;
+  const bool merge = (flags & GTX_ZERO_LENGTH_OK) && (flags & GTX_GAPS_FORMULA) && c->mergeRefs && c->side.get();
+  a.side = merge ? c->side.get() : nullptr; a.sideCount = merge ? c->sideCount.get() : nullptr; a.sideCap = c->sideCap;
   { static const bool wf = !(getenv("GTX_WEIGHTED_FAST") && atoi(getenv("GTX_WEIGHTED_FAST")) == 0); a.wfast = wf ? 1 : 0; }
   int64_t nChunks = (nReads + 63) >> 6;
   // span per wave: as count_args, a little longer (the start of a span costs more here: 100 M reads: 0.55 ms at 16 chunks, 0.44 at 32,
@@ -1781,7 +1739,7 @@ static gtx::CoverArgs cover_args(gtx_ctx *c, int64_t nReads, int64_t indexBase =
   a.chunksPerWave = c->chunksPerWave > 0 ? c->chunksPerWave : (int)std::min<int64_t>(64, std::max<int64_t>(8, nChunks / 24576));
   a.chunksPerWave = (a.chunksPerWave + 3) / 4 * 4;
   a.sched = gtx::span_schedule(nChunks, a.chunksPerWave, 4, c->waveSlots);
-  a.place.cls = c->d_placeClsT; a.place.rank = c->d_placeRankT; a.place.shift = c->placeShiftT;
+  a.place = c->cv.place.view();
   return a;
 }
 
@@ -1789,17 +1747,17 @@ static int cover_begin(gtx_ctx *c)
 {
   int rc = cover_prepare(c); if (rc) return rc;
   if (c->covDirty) {
-    const int nTiles = gtx::scan_tiles(c->histLenT);
+    const int nTiles = gtx::scan_tiles(c->cv.histLenT);
     for (int q = 0; q < 4; q++) {
-      HIPCHK(c, hipMemsetAsync(c->d_cov[q], 0, sizeof(u64) * c->histLenT, c->stream));
-      HIPCHK(c, hipMemsetAsync(c->d_cov[4 + q], 0, sizeof(u64) * (nTiles + 2), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->cv.cov[q].get(), 0, sizeof(u64) * c->cv.histLenT, c->stream));
+      HIPCHK(c, hipMemsetAsync(c->cv.cov[4 + q].get(), 0, sizeof(u64) * (nTiles + 2), c->stream));
     }
   }
   if (c->covDirty || c->histDirty) {
-    HIPCHK(c, hipMemcpyAsync(c->d_info + c->infoCur, &c->h_info[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice, c->stream));
-    if (c->d_sideCount) {
-      HIPCHK(c, hipMemsetAsync(c->d_sideCount, 0, sizeof(unsigned), c->stream));
-      if (c->nSpecial) HIPCHK(c, hipMemsetAsync(c->d_specialOut, 0, sizeof(u64) * c->nSpecial, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_info.get() + c->infoCur, &c->h_info.get()[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice, c->stream));
+    if (c->sideCount.get()) {
+      HIPCHK(c, hipMemsetAsync(c->sideCount.get(), 0, sizeof(unsigned), c->stream));
+      if (c->rx.nSpecial) HIPCHK(c, hipMemsetAsync(c->rx.specialOut.get(), 0, sizeof(u64) * c->rx.nSpecial, c->stream));
     }
   }
   c->sideUsed = false;
@@ -1812,16 +1770,16 @@ static int cover_begin(gtx_ctx *c)
 static int cover_launch(gtx_ctx *c, const void *dR, const int *dW, int64_t n, int64_t indexBase, uint32_t flags, bool unsorted)
 {
   const gtx::CoverArgs cv = cover_args(c, n, indexBase, flags);
-  if (unsorted && c->nBT > 0 && n >= c->bucketMinReads && n < (1ll << 31)) {
-    const gtx::BucketPlan p = gtx::bucket_plan(n, c->nClasses, c->nBT, c->nCellsT, dW != nullptr);
+  const BucketTables &t = c->cv.bkt;
+  if (unsorted && t.nB > 0 && n >= c->bucketMinReads && n < (1ll << 31)) {
+    const gtx::BucketPlan p = gtx::bucket_plan(n, c->nClasses, t.nB, t.nCells, dW != nullptr);
     if (p.pairs < (1ull << 32)) {
       gtx::BucketWork w;
-      { int rc = bucket_scratch(c, p, c->nBT, &w); if (rc) return rc; }
-      const gtx::BucketTable t = bucket_table(c->d_bktT, c->nBT, c->d_clsCellT, c->d_cellTabT, c->nCellsT, c->cellShiftT);
+      { int rc = bucket_scratch(c, p, t.nB, &w); if (rc) return rc; }
       gtx::CountArgs a = {};                                        // what the partition pass reads of it
       a.nClasses = c->nClasses; a.zeroLenOk = 0; a.coverRule = 1; a.info = cv.info; a.indexBase = indexBase;
       a.side = cv.side; a.sideCount = cv.sideCount; a.sideCap = cv.sideCap;
-      HIPCHK(c, gtx::launch_cover_bucketed(dR, dW, n, a, cv, t, w, p, c->stream));
+      HIPCHK(c, gtx::launch_cover_bucketed(dR, dW, n, a, cv, t.view(), w, p, c->stream));
       c->covTileSums = false;
       return GTX_OK;
     }
@@ -1846,11 +1804,11 @@ static bool host_reads_look_unsorted(const int32_t *tri, int64_t n)
 static int cover_end(gtx_ctx *c, void *d_cov_out)
 {
   gtx::CoverGather g;
-  for (int q = 0; q < 4; q++) { g.pref[q] = c->d_cov[8 + q]; g.part[q] = c->d_cov[4 + q]; }
-  g.posTE = c->d_posTE; g.posTS = c->d_posTS; g.classBaseT = c->d_classBaseT; g.refS = c->d_refS; g.refE = c->d_refE;
+  for (int q = 0; q < 4; q++) { g.pref[q] = c->cv.cov[8 + q].get(); g.part[q] = c->cv.cov[4 + q].get(); }
+  g.posTE = c->cv.posTE.get(); g.posTS = c->cv.posTS.get(); g.classBaseT = c->cv.classBaseT.get(); g.refS = c->rx.refS.get(); g.refE = c->rx.refE.get();
   if (!c->covTileSums)                                               // (the partition path does not keep them)
-    for (int q = 0; q < 4; q += 2) HIPCHK(c, gtx::launch_tile_sums(c->d_cov[q], c->d_cov[q + 1], c->histLenT, c->d_cov[4 + q], c->d_cov[5 + q], c->stream));
-  HIPCHK(c, gtx::launch_coverage_finalize(cover_args(c, 0), c->histLenT, g, c->nRefs, (u64 *)d_cov_out, c->d_info + (c->infoCur ^ 1), c->stream));
+    for (int q = 0; q < 4; q += 2) HIPCHK(c, gtx::launch_tile_sums(c->cv.cov[q].get(), c->cv.cov[q + 1].get(), c->cv.histLenT, c->cv.cov[4 + q].get(), c->cv.cov[5 + q].get(), c->stream));
+  HIPCHK(c, gtx::launch_coverage_finalize(cover_args(c, 0), c->cv.histLenT, g, c->nRefs, (u64 *)d_cov_out, c->d_info.get() + (c->infoCur ^ 1), c->stream));
   { int rc = merge_end(c, d_cov_out); if (rc) return rc; }
   c->covDirty = false;
   c->infoCur ^= 1;
@@ -1910,9 +1868,9 @@ int gtxi_coverage_finish(gtx_ctx *c, void **d_out)
   HIPCHK(c, hipSetDevice(c->device));
   c->covOpen = false; c->seamUnsorted = INT64_MAX;
   int rc = ensure_out(c, (size_t)c->nRefs); if (rc) return rc;
-  rc = cover_end(c, c->d_out); if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(&c->h_info[0], c->d_info + (c->infoCur ^ 1), sizeof(gtx::DevInfo), hipMemcpyDeviceToHost, c->stream));
-  *d_out = c->d_out;
+  rc = cover_end(c, c->out.get()); if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(&c->h_info.get()[0], c->d_info.get() + (c->infoCur ^ 1), sizeof(gtx::DevInfo), hipMemcpyDeviceToHost, c->stream));
+  *d_out = c->out.get();
   return GTX_OK;
 }
 
@@ -1973,19 +1931,19 @@ static int scan_prepare(gtx_ctx *c, const int32_t *classLen, int nClasses, int s
     }
     winOff[nClasses] = wo; tileOff[nClasses] = to; blkOff[nClasses] = bo;
     c->scanTotalTiles = to; c->scanOwnBlocks = bo;
-    if (tabLen > c->capScanTab) { dfree(c->d_scanTab); c->capScanTab = 0; HIPCHK(c, hipMalloc(&c->d_scanTab, tabLen * sizeof(long long))); c->capScanTab = tabLen; }
-    if ((size_t)mo + 1 > c->capMicro) { dfree(c->d_micro); c->capMicro = 0; HIPCHK(c, hipMalloc(&c->d_micro, ((size_t)mo + 3) * sizeof(u64))); c->capMicro = (size_t)mo + 1; }
-    if ((size_t)(2 * bo + 2) > c->capScanBounds) { dfree(c->d_scanBounds); c->capScanBounds = 0; HIPCHK(c, hipMalloc(&c->d_scanBounds, (size_t)(2 * bo + 2) * sizeof(long long))); c->capScanBounds = (size_t)(2 * bo + 2); }
-    if (!c->d_scanFlag) HIPCHK(c, hipMalloc(&c->d_scanFlag, sizeof(int)));
+    HIPCHK(c, c->scanTab.reserve(tabLen));
+    HIPCHK(c, c->micro.reserve((size_t)mo + 1, (size_t)mo + 3));
+    HIPCHK(c, c->scanBounds.reserve((size_t)(2 * bo + 2)));
+    if (!c->scanFlag) HIPCHK(c, c->scanFlag.alloc(1));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(c->d_scanTab, tab.data(), tabLen * sizeof(long long), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->scanTab.get(), tab.data(), tabLen * sizeof(long long), hipMemcpyHostToDevice));
     c->scanKey = key; c->scanTotalMicro = mo; c->scanTotalWindows = wo;
   }
-  out->micro = c->d_micro; out->microOff = c->d_scanTab; out->nMicro = c->d_scanTab + nClasses;
-  out->winOff = c->d_scanTab + 2 * nClasses; out->outOff = c->d_scanTab + 3 * nClasses + 1; out->tileOff = c->d_scanTab + 4 * nClasses + 1;
+  out->micro = c->micro.get(); out->microOff = c->scanTab.get(); out->nMicro = c->scanTab.get() + nClasses;
+  out->winOff = c->scanTab.get() + 2 * nClasses; out->outOff = c->scanTab.get() + 3 * nClasses + 1; out->tileOff = c->scanTab.get() + 4 * nClasses + 1;
   out->nClasses = nClasses; out->winStep = step; out->comb = size / step;
   out->winStepInv = step > 1 ? (unsigned)((1ull << 32) / (unsigned)step) : 0;
-  if (own) { own->blkOff = c->d_scanTab + 5 * nClasses + 2; own->tile = ownTile; own->totalBlocks = c->scanOwnBlocks; own->bounds = c->d_scanBounds; own->flag = c->d_scanFlag; }
+  if (own) { own->blkOff = c->scanTab.get() + 5 * nClasses + 2; own->tile = ownTile; own->totalBlocks = c->scanOwnBlocks; own->bounds = c->scanBounds.get(); own->flag = c->scanFlag.get(); }
   return GTX_OK;
 }
 
@@ -1996,70 +1954,37 @@ static int scan_bucket_tables(gtx_ctx *c, const int32_t *classLen, int nClasses,
 {
   std::vector<long long> key = c->scanKey; key.push_back(weighted ? 1 : 0);
   if (key == c->scanBktKey) return GTX_OK;
-  c->scanBktKey.clear(); c->nBS = 0; c->nScanParts = 0;
-  dfree(c->d_bktS); dfree(c->d_clsCellS); dfree(c->d_cellTabS); dfree(c->d_scanParts);
-  if (!c->d_scanInfo) HIPCHK(c, hipMalloc(&c->d_scanInfo, sizeof(gtx::DevInfo)));
+  c->scanBktKey.clear(); c->nScanParts = 0;
+  c->bktS = {}; c->scanParts.reset();
+  if (!c->scanInfo) HIPCHK(c, c->scanInfo.alloc(1));
   long long total = 0;
   for (int i = 0; i < nClasses; i++) total += classLen[i] < 0 ? 0 : classLen[i] / step;
   static const long long want = getenv("GTX_SCAN_BUCKETS") && atoll(getenv("GTX_SCAN_BUCKETS")) > 0 ? atoll(getenv("GTX_SCAN_BUCKETS")) : 2000;     // (100 M shuffled reads, -d 25: 500 -> 2.77 ms, 1000 -> 2.30, 2000 -> 2.15, 3000 -> 2.10)
   long long per = std::max<long long>(16384, (total + want - 1) / want);           // micro-windows per bucket
-  std::vector<int32_t> posHi, eLo, eHi, sLo, sHi, cls, clsStart(nClasses + 1, 0);
+  BucketCuts k;
+  k.clsStart.assign(nClasses + 1, 0);
   std::vector<gtx::ScanPart> parts;
   const int bins = gtx::scan_part_bins(weighted);
   if (per > bins) per = per / bins * bins;          // whole parts: every part of a bucket reads all of the bucket's chunks, a short last one as well
   for (int cl = 0; cl < nClasses; cl++) {
-    clsStart[cl] = (int32_t)posHi.size();
+    k.clsStart[cl] = (int32_t)k.posHi.size();
     const long long nm = classLen[cl] < 0 ? 0 : classLen[cl] / step;
     for (long long f = 0; f < nm; f += per) {
       const long long g = std::min(f + per, nm);
-      posHi.push_back(g == nm ? INT32_MAX : (int32_t)(g * step));                // positions <= g * step lie in micro-windows < g
-      eLo.push_back((int32_t)f); eHi.push_back((int32_t)g); sLo.push_back(0); sHi.push_back(0); cls.push_back(cl);
-      for (long long m = f; m < g; m += bins) parts.push_back({(int)posHi.size() - 1, (int)m, (int)std::min<long long>(bins, g - m), 0});
+      k.posHi.push_back(g == nm ? INT32_MAX : (int32_t)(g * step));                // positions <= g * step lie in micro-windows < g
+      k.eLo.push_back((int32_t)f); k.eHi.push_back((int32_t)g); k.sLo.push_back(0); k.sHi.push_back(0); k.cls.push_back(cl);
+      for (long long m = f; m < g; m += bins) parts.push_back({(int)k.posHi.size() - 1, (int)m, (int)std::min<long long>(bins, g - m), 0});
     }
   }
-  clsStart[nClasses] = (int32_t)posHi.size();
-  const int nB = (int)posHi.size();
-  if (nB == 0 || nB > 4096 || nClasses > 2048 || total >= (1ll << 31)) { c->scanBktKey = key; return GTX_OK; }   // (nBS == 0: the general kernels serve)
-  const int kCells = 4096;
-  int sh = 0;
-  auto cellsAt = [&](int shift) {
-    int64_t tot = 0;
-    for (int cl = 0; cl < nClasses; cl++) {
-      const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
-      tot += b1 - b0 <= 1 ? b1 - b0 : ((((int64_t)posHi[b1 - 2] - posHi[b0]) >> shift) + 1);
-    }
-    return tot;
-  };
-  while (sh < 40 && cellsAt(sh) > kCells) sh++;
-  std::vector<int32_t> clsCell(4 * (size_t)nClasses);
-  std::vector<uint16_t> cellTab;
-  for (int cl = 0; cl < nClasses; cl++) {
-    const int b0 = clsStart[cl], b1 = clsStart[cl + 1];
-    const int32_t lo = b1 - b0 <= 1 ? 0 : posHi[b0];
-    const int64_t nc = b1 == b0 ? 0 : b1 - b0 == 1 ? 1 : ((((int64_t)posHi[b1 - 2] - lo) >> sh) + 1);
-    clsCell[4 * cl] = (int32_t)cellTab.size(); clsCell[4 * cl + 1] = lo; clsCell[4 * cl + 2] = (int32_t)nc; clsCell[4 * cl + 3] = b0;
-    int b = b0;
-    for (int64_t k = 0; k < nc; k++) {
-      const int64_t first = (int64_t)lo + (k << sh);
-      while (b < b1 - 1 && (int64_t)posHi[b] < first) b++;
-      cellTab.push_back((uint16_t)(b - b0));
-    }
+  k.clsStart[nClasses] = (int32_t)k.posHi.size();
+  const int nB = (int)k.posHi.size();
+  if (nB == 0 || nB > 4096 || nClasses > 2048 || total >= (1ll << 31)) { c->scanBktKey = key; return GTX_OK; }   // (bktS.nB == 0: the general kernels serve)
+  int rc = build_bucket_tables(c, c->bktS, k, nClasses, true); if (rc) return rc;
+  if (c->bktS.nB > 0) {
+    HIPCHK(c, upload(c->scanParts, parts.data(), parts.size()));
+    c->nScanParts = (int)parts.size();
   }
-  if (!gtx::bucket_tables_fit(nClasses, nB, (int)cellTab.size())) { c->scanBktKey = key; return GTX_OK; }
-  c->nCellsS = (int)cellTab.size(); c->cellShiftS = sh;
-  cellTab.push_back(0);
-  std::vector<int32_t> all;
-  for (auto *v : {&posHi, &eLo, &eHi, &sLo, &sHi, &cls, &clsStart}) all.insert(all.end(), v->begin(), v->end());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMalloc(&c->d_bktS, sizeof(int32_t) * all.size()));
-  HIPCHK(c, hipMemcpy(c->d_bktS, all.data(), sizeof(int32_t) * all.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMalloc(&c->d_clsCellS, sizeof(int32_t) * clsCell.size() + 16));
-  HIPCHK(c, hipMemcpy(c->d_clsCellS, clsCell.data(), sizeof(int32_t) * clsCell.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMalloc(&c->d_cellTabS, sizeof(uint16_t) * cellTab.size()));
-  HIPCHK(c, hipMemcpy(c->d_cellTabS, cellTab.data(), sizeof(uint16_t) * cellTab.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMalloc(&c->d_scanParts, sizeof(gtx::ScanPart) * parts.size()));
-  HIPCHK(c, hipMemcpy(c->d_scanParts, parts.data(), sizeof(gtx::ScanPart) * parts.size(), hipMemcpyHostToDevice));
-  c->nBS = nB; c->nScanParts = (int)parts.size(); c->scanBktKey = key;
+  c->scanBktKey = key;
   return GTX_OK;
 }
 
@@ -2071,7 +1996,7 @@ static int scan_takes_buckets(gtx_ctx *c, const int *dW, int64_t n, const gtx::S
   *yes = false;
   if (!(unsorted && !a.sortedRule && n >= c->bucketMinReads && n < (1ll << 31))) return GTX_OK;
   int rc = scan_bucket_tables(c, classLen, a.nClasses, a.winStep, dW != nullptr); if (rc) return rc;
-  *yes = c->nBS > 0 && gtx::bucket_plan(n, a.nClasses, c->nBS, c->nCellsS, dW != nullptr).pairs < (1ull << 32);
+  *yes = c->bktS.nB > 0 && gtx::bucket_plan(n, a.nClasses, c->bktS.nB, c->bktS.nCells, dW != nullptr).pairs < (1ull << 32);
   return GTX_OK;
 }
 
@@ -2080,15 +2005,15 @@ static int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, c
 {
   if (unsorted && !a.sortedRule && n >= c->bucketMinReads && n < (1ll << 31)) {
     int rc = scan_bucket_tables(c, classLen, a.nClasses, a.winStep, dW != nullptr); if (rc) return rc;
-    if (c->nBS > 0) {
-      const gtx::BucketPlan p = gtx::bucket_plan(n, a.nClasses, c->nBS, c->nCellsS, dW != nullptr);
+    const BucketTables &t = c->bktS;
+    if (t.nB > 0) {
+      const gtx::BucketPlan p = gtx::bucket_plan(n, a.nClasses, t.nB, t.nCells, dW != nullptr);
       if (p.pairs < (1ull << 32)) {
         gtx::BucketWork w;
-        rc = bucket_scratch(c, p, c->nBS, &w); if (rc) return rc;
-        const gtx::BucketTable t = bucket_table(c->d_bktS, c->nBS, c->d_clsCellS, c->d_cellTabS, c->nCellsS, c->cellShiftS);
+        rc = bucket_scratch(c, p, t.nB, &w); if (rc) return rc;
         gtx::CountArgs ca = {};                                      // what the partition pass reads of it; its counts of dropped reads go nowhere
-        ca.nClasses = a.nClasses; ca.zeroLenOk = 0; ca.coverRule = 1; ca.keyCenter = a.center; ca.info = c->d_scanInfo; ca.indexBase = 0;
-        HIPCHK(c, gtx::launch_scan_bucketed(dR, dW, n, ca, a, t, w, p, c->d_scanParts, c->nScanParts, c->stream, d_windows));
+        ca.nClasses = a.nClasses; ca.zeroLenOk = 0; ca.coverRule = 1; ca.keyCenter = a.center; ca.info = c->scanInfo.get(); ca.indexBase = 0;
+        HIPCHK(c, gtx::launch_scan_bucketed(dR, dW, n, ca, a, t.view(), w, p, c->scanParts.get(), c->nScanParts, c->stream, d_windows));
         return GTX_OK;
       }
     }
@@ -2115,12 +2040,12 @@ static int scan_launch(gtx_ctx *c, const void *d_reads, const void *d_weights, i
   const size_t microBytes = (size_t)c->scanTotalMicro * (micro64 ? 8 : 4);
   const int *runIf = nullptr;
   if (tile > 0 && own.totalBlocks > 0) {
-    HIPCHK(c, hipMemsetAsync(c->d_scanFlag, 0, sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->scanFlag.get(), 0, sizeof(int), c->stream));
     if (profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     HIPCHK(c, gtx::launch_scan_own(d_reads, d_weights, n, a, own, (u64 *)d_out, c->stream));
     if (profile) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    runIf = c->d_scanFlag;
-    if (microBytes) HIPCHK(c, gtx::launch_scan_zero(c->d_micro, (long long)microBytes, runIf, c->stream));
+    runIf = c->scanFlag.get();
+    if (microBytes) HIPCHK(c, gtx::launch_scan_zero(c->micro.get(), (long long)microBytes, runIf, c->stream));
     HIPCHK(c, gtx::launch_scan_hist(d_reads, d_weights, n, a, c->stream, runIf));
   } else {
     // reads in no order through the partition path: its parts write the windows themselves (no micro-window array, no window pass)
@@ -2135,12 +2060,12 @@ static int scan_launch(gtx_ctx *c, const void *d_reads, const void *d_weights, i
       if (profile) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
       return GTX_OK;
     }
-    if (microBytes) HIPCHK(c, hipMemsetAsync(c->d_micro, 0, microBytes, c->stream));
+    if (microBytes) HIPCHK(c, hipMemsetAsync(c->micro.get(), 0, microBytes, c->stream));
     if (profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
     rc = scan_hist_any(c, d_reads, (const int *)d_weights, n, a, classLen, (flags & GTX_READS_UNSORTED) != 0); if (rc) return rc;
     if (profile) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
   }
-  HIPCHK(c, gtx::launch_scan_windows(c->d_micro, micro64, a, c->scanTotalTiles, (u64 *)d_out, c->stream, runIf));
+  HIPCHK(c, gtx::launch_scan_windows(c->micro.get(), micro64, a, c->scanTotalTiles, (u64 *)d_out, c->stream, runIf));
   return GTX_OK;
 }
 
@@ -2149,18 +2074,19 @@ static int scan_launch(gtx_ctx *c, const void *d_reads, const void *d_weights, i
 static int stage_resident(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t n, void **dR, int **dW)
 {
   if (c->directPending) { HIPCHK(c, hipStreamSynchronize(c->copyStream)); c->directPending = false; }
-  if ((size_t)n > c->capRes || (weights && (size_t)n > c->capResW)) {
+  const size_t bytes = (size_t)n * 12, nW = weights ? (size_t)n : 0;
+  if (bytes > c->resReads.cap || nW > c->resWeights.cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->copyStream));
-    if ((size_t)n > c->capRes) { dfree(c->d_resReads); c->capRes = 0; HIPCHK(c, hipMalloc(&c->d_resReads, (size_t)n * 12)); c->capRes = (size_t)n; }
-    if (weights && (size_t)n > c->capResW) { dfree(c->d_resWeights); c->capResW = 0; HIPCHK(c, hipMalloc(&c->d_resWeights, (size_t)n * 4)); c->capResW = (size_t)n; }
+    HIPCHK(c, c->resReads.reserve(bytes));
+    HIPCHK(c, c->resWeights.reserve(nW));
   }
   const bool direct = is_pinned(reads) && (!weights || is_pinned(weights));
   const int64_t batch = c->batchReads;
   const size_t slotBytes = (size_t)std::min<int64_t>(n, batch) * 16;
-  if (!direct && slotBytes > c->capPin) {
+  if (!direct && (slotBytes > c->pin[0].cap || slotBytes > c->pin[1].cap)) {
     HIPCHK(c, hipStreamSynchronize(c->copyStream));
-    for (int k = 0; k < 2; k++) { if (c->h_pin[k]) { (void)hipHostFree(c->h_pin[k]); c->h_pin[k] = nullptr; } HIPCHK(c, hipHostMalloc((void **)&c->h_pin[k], slotBytes)); }
-    c->capPin = slotBytes; c->slotBusy[0] = c->slotBusy[1] = false;
+    for (int k = 0; k < 2; k++) HIPCHK(c, c->pin[k].reserve(slotBytes));
+    c->slotBusy[0] = c->slotBusy[1] = false;
   }
   // the kernels of the previous call (the context's stream) may still be reading the resident buffer
   HIPCHK(c, hipEventRecord(c->evRes[0], c->stream));
@@ -2172,18 +2098,18 @@ static int stage_resident(gtx_ctx *c, const int32_t *reads, const int32_t *weigh
     if (!direct) {
       slot = (int)(c->stageSeq++ & 1);
       if (c->slotBusy[slot]) HIPCHK(c, hipEventSynchronize(c->evCopied[slot]));      // the DMA out of this page-locked slot is done
-      parallel_copy(c->h_pin[slot], srcR, (size_t)cnt * 12, c->copyThreads);
-      if (weights) parallel_copy(c->h_pin[slot] + (size_t)cnt * 12, srcW, (size_t)cnt * 4, c->copyThreads);
-      srcR = c->h_pin[slot]; srcW = c->h_pin[slot] + (size_t)cnt * 12;
+      parallel_copy(c->pin[slot].get(), srcR, (size_t)cnt * 12, c->copyThreads);
+      if (weights) parallel_copy(c->pin[slot].get() + (size_t)cnt * 12, srcW, (size_t)cnt * 4, c->copyThreads);
+      srcR = c->pin[slot].get(); srcW = c->pin[slot].get() + (size_t)cnt * 12;
     }
-    HIPCHK(c, hipMemcpyAsync((char *)c->d_resReads + (size_t)off * 12, srcR, (size_t)cnt * 12, hipMemcpyHostToDevice, c->copyStream));
-    if (weights) HIPCHK(c, hipMemcpyAsync(c->d_resWeights + off, srcW, (size_t)cnt * 4, hipMemcpyHostToDevice, c->copyStream));
+    HIPCHK(c, hipMemcpyAsync((char *)c->resReads.get() + (size_t)off * 12, srcR, (size_t)cnt * 12, hipMemcpyHostToDevice, c->copyStream));
+    if (weights) HIPCHK(c, hipMemcpyAsync(c->resWeights.get() + off, srcW, (size_t)cnt * 4, hipMemcpyHostToDevice, c->copyStream));
     if (slot >= 0) { HIPCHK(c, hipEventRecord(c->evCopied[slot], c->copyStream)); c->slotBusy[slot] = true; }
   }
   c->directPending = direct;
   HIPCHK(c, hipEventRecord(c->evRes[1], c->copyStream));                              // everything has arrived before the scan starts
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->evRes[1], 0));
-  *dR = c->d_resReads; *dW = weights ? c->d_resWeights : nullptr;
+  *dR = c->resReads.get(); *dW = weights ? c->resWeights.get() : nullptr;
   return GTX_OK;
 }
 
@@ -2216,26 +2142,26 @@ int gtxi_scan_enqueue(gtx_ctx *c, const int32_t *reads, const int32_t *weights, 
   int64_t extent = 0;
   for (int i = 0; i < nClasses; i++) extent = std::max<int64_t>(extent, classOff[i] + gtx_scan_n_windows(classLen[i] < 0 ? 0 : classLen[i], step, size));
   int rc = ensure_out(c, (size_t)extent); if (rc) return rc;
-  if (extent > 0) HIPCHK(c, hipMemsetAsync(c->d_out, 0, (size_t)extent * sizeof(u64), c->stream));
+  if (extent > 0) HIPCHK(c, hipMemsetAsync(c->out.get(), 0, (size_t)extent * sizeof(u64), c->stream));
   if ((flags & GTX_READS_SORTED) && prep == '1' && n > 0) {
     // sorted reads: all of them resident, one owner-computes launch (gtx_scanown.hip)
     void *dR = nullptr; int *dW = nullptr;
     rc = stage_resident(c, reads, weights, n, &dR, &dW); if (rc) return rc;
-    rc = scan_launch(c, dR, dW, n, classLen, nClasses, step, size, prep, flags, classOff, c->d_out, false); if (rc) return rc;
+    rc = scan_launch(c, dR, dW, n, classLen, nClasses, step, size, prep, flags, classOff, c->out.get(), false); if (rc) return rc;
   } else {
     gtx::ScanArgs a;
     rc = scan_prepare(c, classLen, nClasses, step, size, classOff, &a); if (rc) return rc;
     a.center = prep == 'c'; a.sortedRule = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
     const bool micro64 = weights != nullptr;
-    if (c->scanTotalMicro > 0) HIPCHK(c, hipMemsetAsync(c->d_micro, 0, (size_t)c->scanTotalMicro * (micro64 ? 8 : 4), c->stream));
+    if (c->scanTotalMicro > 0) HIPCHK(c, hipMemsetAsync(c->micro.get(), 0, (size_t)c->scanTotalMicro * (micro64 ? 8 : 4), c->stream));
     rc = stage_batches(c, reads, weights, n, [&](const void *dR, const int *dW, int64_t cnt, int64_t off) -> int {
       const bool unsorted = (flags & GTX_READS_UNSORTED) || host_reads_look_unsorted(reads + 3 * off, cnt);
       return scan_hist_any(c, dR, dW, cnt, a, classLen, unsorted);
     });
     if (rc) return rc;
-    HIPCHK(c, gtx::launch_scan_windows(c->d_micro, micro64, a, c->scanTotalTiles, c->d_out, c->stream));
+    HIPCHK(c, gtx::launch_scan_windows(c->micro.get(), micro64, a, c->scanTotalTiles, c->out.get(), c->stream));
   }
-  *d_out = c->d_out; *extent_out = extent;
+  *d_out = c->out.get(); *extent_out = extent;
   return GTX_OK;
 }
 
@@ -2268,14 +2194,14 @@ int gtx_scan_begin(gtx_ctx *c, const int32_t *classLen, int32_t nClasses, int32_
   int64_t extent = 0;
   for (int i = 0; i < nClasses; i++) extent = std::max<int64_t>(extent, classOff[i] + gtx_scan_n_windows(classLen[i] < 0 ? 0 : classLen[i], step, size));
   int rc = ensure_out(c, (size_t)extent); if (rc) return rc;
-  if (extent > 0) HIPCHK(c, hipMemsetAsync(c->d_out, 0, (size_t)extent * sizeof(u64), c->stream));
+  if (extent > 0) HIPCHK(c, hipMemsetAsync(c->out.get(), 0, (size_t)extent * sizeof(u64), c->stream));
   gtx_ctx::ScanOpen &s = c->scan;
   rc = scan_prepare(c, classLen, nClasses, step, size, classOff, &s.a); if (rc) return rc;
   s.a.center = prep == 'c'; s.a.sortedRule = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
   s.weighted = weighted != 0; s.classLen.assign(classLen, classLen + nClasses); s.extent = extent; s.prep = prep; s.flags = flags;
-  if (c->scanTotalMicro > 0) HIPCHK(c, hipMemsetAsync(c->d_micro, 0, (size_t)c->scanTotalMicro * (s.weighted ? 8 : 4), c->stream));
-  if (!s.d_labelSum) HIPCHK(c, hipMalloc(&s.d_labelSum, sizeof(unsigned long long)));
-  HIPCHK(c, hipMemsetAsync(s.d_labelSum, 0, sizeof(unsigned long long), c->stream));
+  if (c->scanTotalMicro > 0) HIPCHK(c, hipMemsetAsync(c->micro.get(), 0, (size_t)c->scanTotalMicro * (s.weighted ? 8 : 4), c->stream));
+  if (!s.labelSum) HIPCHK(c, s.labelSum.alloc(1));
+  HIPCHK(c, hipMemsetAsync(s.labelSum.get(), 0, sizeof(unsigned long long), c->stream));
   s.open = true;
   return GTX_OK;
 }
@@ -2301,10 +2227,10 @@ int gtx_scan_end(gtx_ctx *c, uint64_t *out, int64_t *labelSum)
   s.open = false;
   if (s.extent > 0 && !out) return fail(c, GTX_E_ARG, "gtx_scan_end: null output");
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, gtx::launch_scan_windows(c->d_micro, s.weighted, s.a, c->scanTotalTiles, c->d_out, c->stream));
-  if (s.extent > 0) HIPCHK(c, hipMemcpyAsync(out, c->d_out, (size_t)s.extent * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, gtx::launch_scan_windows(c->micro.get(), s.weighted, s.a, c->scanTotalTiles, c->out.get(), c->stream));
+  if (s.extent > 0) HIPCHK(c, hipMemcpyAsync(out, c->out.get(), (size_t)s.extent * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   unsigned long long sum = 0;
-  HIPCHK(c, hipMemcpyAsync(&sum, s.d_labelSum, sizeof sum, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&sum, s.labelSum.get(), sizeof sum, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->copyStream));
   if (labelSum) *labelSum = (int64_t)sum;
@@ -2327,25 +2253,24 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
     { c->err = std::string(who) + ": bad argument"; return GTX_E_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   const int slot = (int)(c->textSeq & 1);
-  gtx_ctx::TextSlot &t = c->text[slot];
+  TextSlot &t = c->text[slot];
   *ticket = slot;
   if (!t.evParsed) {
     HIPCHK(c, hipEventCreateWithFlags(&t.evParsed, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&t.evConsumed, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&t.evCopied, hipEventDisableTiming));
-    HIPCHK(c, hipMalloc(&t.d_flag, sizeof(int))); HIPCHK(c, hipHostMalloc((void **)&t.h_flag, sizeof(int))); HIPCHK(c, hipHostMalloc((void **)&t.h_seam, 4096));
-    HIPCHK(c, hipMalloc(&t.d_sum, sizeof(unsigned long long))); HIPCHK(c, hipMemset(t.d_sum, 0, sizeof(unsigned long long)));
+    HIPCHK(c, t.flag.alloc(1)); HIPCHK(c, t.hostFlag.alloc(1)); HIPCHK(c, t.seam.alloc(4096));
+    HIPCHK(c, t.sum.alloc(1)); HIPCHK(c, hipMemset(t.sum.get(), 0, sizeof(unsigned long long)));
   }
   if (t.busy) { HIPCHK(c, hipEventSynchronize(t.evConsumed)); t.busy = false; }          // the block before last has been counted: its buffers are free
   c->textSeq++;
-  if (nLines == 0 || bytes == 0) { *t.h_flag = 0; HIPCHK(c, hipEventRecord(t.evParsed, c->stream)); return GTX_OK; }
+  if (nLines == 0 || bytes == 0) { *t.hostFlag.get() = 0; HIPCHK(c, hipEventRecord(t.evParsed, c->stream)); return GTX_OK; }
   const size_t nSeg = (bytes + 1023) / 1024;
-  if (bytes + 64 > t.capText) { dfree(t.d_text); t.capText = 0; HIPCHK(c, hipMalloc(&t.d_text, bytes + (bytes >> 3) + 4096)); t.capText = bytes + (bytes >> 3) + 4096 - 64; }
-  if (nSeg + 2 > t.capSeg) { dfree(t.d_seg); t.capSeg = 0; HIPCHK(c, hipMalloc(&t.d_seg, sizeof(unsigned) * (nSeg + (nSeg >> 3) + 16))); t.capSeg = nSeg + (nSeg >> 3) + 14; }
-  if ((size_t)nLines > t.capLines) {
-    dfree(t.d_nl); dfree(t.d_tri); dfree(t.d_w); t.capLines = 0;
+  if (bytes + 128 > t.text.cap) HIPCHK(c, t.text.alloc(bytes + (bytes >> 3) + 4096));              // (128 bytes beyond the block kept free)
+  if (nSeg + 4 > t.seg.cap) HIPCHK(c, t.seg.alloc(nSeg + (nSeg >> 3) + 16));
+  if ((size_t)nLines > t.w.cap) {
+    t.nl.reset(); t.tri.reset(); t.w.reset();
     const size_t cap = (size_t)nLines + ((size_t)nLines >> 3) + 1024;
-    HIPCHK(c, hipMalloc(&t.d_nl, sizeof(unsigned) * cap)); HIPCHK(c, hipMalloc(&t.d_tri, sizeof(int) * 3 * cap)); HIPCHK(c, hipMalloc(&t.d_w, sizeof(int) * cap));
-    t.capLines = cap;
+    HIPCHK(c, t.nl.alloc(cap)); HIPCHK(c, t.tri.alloc(3 * cap)); HIPCHK(c, t.w.alloc(cap));
   }
   // the names' tables: per set of names (rebuilt when they change)
   {
@@ -2353,51 +2278,50 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
     size_t total = 0; for (int i = 0; i < r->n_chrom; i++) total += strlen(r->chrom_names[i]) + 1;
     std::string key; key.reserve(total);
     for (int i = 0; i < r->n_chrom; i++) { key += r->chrom_names[i]; key += '\n'; }
-    if (key != c->textBlob || !c->d_textTable) {
+    if (key != c->textBlob || !c->textNames) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
       gtxtext::build_tables(*r, &table, &mask, &blob);
-      dfree(c->d_textTable); dfree(c->d_textNames);
-      HIPCHK(c, hipMalloc(&c->d_textTable, sizeof(int32_t) * table.size()));
-      HIPCHK(c, hipMalloc(&c->d_textNames, blob.size() + 4096 * 2 + 16));
-      HIPCHK(c, hipMemcpy(c->d_textTable, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
-      if (!blob.empty()) HIPCHK(c, hipMemcpy(c->d_textNames, blob.data(), blob.size(), hipMemcpyHostToDevice));
+      c->textTable.reset(); c->textNames.reset();
+      HIPCHK(c, c->textTable.alloc(table.size()));
+      HIPCHK(c, c->textNames.alloc(blob.size() + 4096 * 2 + 16));
+      HIPCHK(c, hipMemcpy(c->textTable.get(), table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
+      if (!blob.empty()) HIPCHK(c, hipMemcpy(c->textNames.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
       c->textMask = mask; c->textBlobLen = (unsigned)blob.size(); c->textBlob = key;
     }
   }
-  gtxtext::TextTables tabs; tabs.table = c->d_textTable; tabs.tableMask = c->textMask; tabs.names = c->d_textNames; tabs.prevOff = 0; tabs.prevLen = 0;
+  gtxtext::TextTables tabs; tabs.table = c->textTable.get(); tabs.tableMask = c->textMask; tabs.names = c->textNames.get(); tabs.prevOff = 0; tabs.prevLen = 0;
   if (r->have_prev && r->prev_chrom) {
     const size_t len = strlen(r->prev_chrom);
     if (len > 0 && len < 4096) {                                       // the seam's name behind the names, one place per slot
-      memcpy(t.h_seam, r->prev_chrom, len);
+      memcpy(t.seam.get(), r->prev_chrom, len);
       tabs.prevOff = c->textBlobLen + (unsigned)slot * 4096; tabs.prevLen = (unsigned)len;
-      HIPCHK(c, hipMemcpyAsync(c->d_textNames + tabs.prevOff, t.h_seam, len, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->textNames.get() + tabs.prevOff, t.seam.get(), len, hipMemcpyHostToDevice, c->stream));
     }
   }
   // the text: page-locked memory is read where it is, anything else goes through a page-locked slot of the context
   const char *src = text;
   if (!is_pinned(text)) {
-    if (bytes > t.capPin) { if (t.h_pin) (void)hipHostFree(t.h_pin); t.h_pin = nullptr; t.capPin = 0; HIPCHK(c, hipHostMalloc((void **)&t.h_pin, bytes + (bytes >> 3))); t.capPin = bytes + (bytes >> 3); }
-    parallel_copy(t.h_pin, text, bytes, c->copyThreads);
-    src = t.h_pin;
+    if (bytes > t.pin.cap) HIPCHK(c, t.pin.alloc(bytes + (bytes >> 3)));
+    parallel_copy(t.pin.get(), text, bytes, c->copyThreads);
+    src = t.pin.get();
   }
-  HIPCHK(c, hipMemcpyAsync(t.d_text, src, bytes, hipMemcpyHostToDevice, c->copyStream));
+  HIPCHK(c, hipMemcpyAsync(t.text.get(), src, bytes, hipMemcpyHostToDevice, c->copyStream));
   HIPCHK(c, hipEventRecord(t.evCopied, c->copyStream));
   HIPCHK(c, hipStreamWaitEvent(c->stream, t.evCopied, 0));
-  HIPCHK(c, hipMemsetAsync(t.d_flag, 0, sizeof(int), c->stream));
-  if (r->strand_aware && (size_t)nLines > t.capLines2) {
-    dfree(t.d_tri2); dfree(t.d_w2); dfree(t.d_blk); t.capLines2 = 0;
-    HIPCHK(c, hipMalloc(&t.d_tri2, sizeof(int) * 3 * t.capLines)); HIPCHK(c, hipMalloc(&t.d_w2, sizeof(int) * t.capLines)); HIPCHK(c, hipMalloc(&t.d_blk, sizeof(unsigned) * (t.capLines / 128 + 4)));
-    t.capLines2 = t.capLines;
+  HIPCHK(c, hipMemsetAsync(t.flag.get(), 0, sizeof(int), c->stream));
+  if (r->strand_aware && (size_t)nLines > t.w2.cap) {
+    t.tri2.reset(); t.blk.reset(); t.w2.reset();
+    HIPCHK(c, t.tri2.alloc(3 * t.w.cap)); HIPCHK(c, t.blk.alloc(t.w.cap / 128 + 4)); HIPCHK(c, t.w2.alloc(t.w.cap));
   }
-  gtxtext::TextDevice d; d.text = t.d_text; d.segCount = t.d_seg; d.nl = t.d_nl; d.tri = t.d_tri; d.w = t.d_w; d.flag = t.d_flag;
-  d.tri2 = r->strand_aware ? t.d_tri2 : nullptr; d.w2 = r->strand_aware ? t.d_w2 : nullptr; d.blkMinus = r->strand_aware ? t.d_blk : nullptr;
-  const int *triOut = r->strand_aware ? t.d_tri2 : t.d_tri;
-  d.labelSum = mode == TEXT_SCAN ? c->scan.d_labelSum : nullptr; d.blockSum = t.d_sum;
+  gtxtext::TextDevice d; d.text = t.text.get(); d.segCount = t.seg.get(); d.nl = t.nl.get(); d.tri = t.tri.get(); d.w = t.w.get(); d.flag = t.flag.get();
+  d.tri2 = r->strand_aware ? t.tri2.get() : nullptr; d.w2 = r->strand_aware ? t.w2.get() : nullptr; d.blkMinus = r->strand_aware ? t.blk.get() : nullptr;
+  const int *triOut = r->strand_aware ? t.tri2.get() : t.tri.get();
+  d.labelSum = mode == TEXT_SCAN ? c->scan.labelSum.get() : nullptr; d.blockSum = t.sum.get();
   HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, mode == TEXT_SCAN ? (c->scan.a.sortedRule ? 2 : 1) : 0));
-  HIPCHK(c, hipMemcpyAsync(t.h_flag, t.d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
   // ... and counted where the triples are
-  const int *dW = r->max_label_value > 1 ? (r->strand_aware ? t.d_w2 : t.d_w) : nullptr;
+  const int *dW = r->max_label_value > 1 ? (r->strand_aware ? t.w2.get() : t.w.get()) : nullptr;
   const int64_t seen = c->streamSeen;
   int rc = GTX_OK;
   if (mode == TEXT_SCAN) {
@@ -2414,8 +2338,8 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
     rc = merge_prepare(c, flags, 0); if (rc) return rc;
     const bool streaming = (flags & (GTX_READS_SORTED | GTX_CHECK_SORTED)) != 0;
     if (!streaming) c->tileSumsValid = false;
-    if (streaming) HIPCHK(c, gtx::launch_count(triOut, dW, nLines, count_args(c, flags & ~GTX_CHECK_SORTED, nLines, seen), true, c->stream));
-    else { rc = launch_unsorted(c, triOut, dW, nLines, count_args(c, flags, nLines, seen)); if (rc) return rc; }
+    if (streaming) HIPCHK(c, gtx::launch_count(triOut, dW, nLines, count_args(c, c->ix.hist, flags & ~GTX_CHECK_SORTED, nLines, seen), true, c->stream));
+    else { rc = launch_unsorted(c, triOut, dW, nLines, count_args(c, c->ix.hist, flags, nLines, seen)); if (rc) return rc; }
     rc = pairs_batch(c, triOut, dW, nLines); if (rc) return rc;
   }
   rc = merge_batch(c, triOut, dW, nLines); if (rc) return rc;
@@ -2435,11 +2359,11 @@ int gtx_scan_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t n_line
 int gtx_text_result(gtx_ctx *c, int ticket, int *needs_host)
 {
   if (!c || !needs_host || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_text_result: bad argument") : GTX_E_ARG;
-  gtx_ctx::TextSlot &t = c->text[ticket];
+  TextSlot &t = c->text[ticket];
   if (!t.evParsed) return fail(c, GTX_E_STATE, "gtx_text_result: no such block");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(t.evParsed));
-  *needs_host = *t.h_flag;
+  *needs_host = *t.hostFlag.get();
   return GTX_OK;
 }
 }
@@ -2464,28 +2388,28 @@ int gtxi_set_share(gtx_ctx *c, const uint8_t *owned, int32_t nClasses, const int
   }
   std::vector<int32_t> tiles;
   for (int t = 0; t < nTilesAll; t++) if (mark[t]) tiles.push_back(t);
-  dfree(c->d_shareTiles); dfree(c->d_shareRegions); dfree(c->d_shareOwned);
+  c->share.tiles.reset(); c->share.regions.reset(); c->share.owned.reset();
   {
     std::vector<uint8_t> own((size_t)std::max(c->nClasses, 1), 0);
     for (int cl = 0; cl < c->nClasses && cl < nClasses; cl++) own[cl] = owned[cl] ? 1 : 0;
-    HIPCHK(c, hipMalloc(&c->d_shareOwned, own.size()));
-    HIPCHK(c, hipMemcpy(c->d_shareOwned, own.data(), own.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, c->share.owned.alloc(own.size()));
+    HIPCHK(c, hipMemcpy(c->share.owned.get(), own.data(), own.size(), hipMemcpyHostToDevice));
   }
-  HIPCHK(c, hipMalloc(&c->d_shareTiles, sizeof(int32_t) * (tiles.size() + 1)));
-  HIPCHK(c, hipMalloc(&c->d_shareRegions, sizeof(int32_t) * (size_t)(nRegions + 1)));
-  if (!tiles.empty()) HIPCHK(c, hipMemcpy(c->d_shareTiles, tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice));
-  if (nRegions > 0) HIPCHK(c, hipMemcpy(c->d_shareRegions, regions, sizeof(int32_t) * (size_t)nRegions, hipMemcpyHostToDevice));
-  c->nShareTiles = (int)tiles.size(); c->nShareRegions = nRegions; c->shareOffset = offset; c->shareOn = true;
+  HIPCHK(c, c->share.tiles.alloc(tiles.size() + 1));
+  HIPCHK(c, c->share.regions.alloc((size_t)(nRegions + 1)));
+  if (!tiles.empty()) HIPCHK(c, hipMemcpy(c->share.tiles.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice));
+  if (nRegions > 0) HIPCHK(c, hipMemcpy(c->share.regions.get(), regions, sizeof(int32_t) * (size_t)nRegions, hipMemcpyHostToDevice));
+  c->share.nTiles = (int)tiles.size(); c->share.nRegions = nRegions; c->share.offset = offset; c->share.on = true;
   return ensure_out(c, GTXI_SHARE_SLOTS * (size_t)c->nRefs);     // the compact vectors gtxi_count_device_share[_async] takes in turn (slot)
 }
 
 // gtx_count_device for a group member: the reads (of the member's classes, resident on its device) are counted and the member's
-// regions finalized into its piece of compact vector `slot` (0 | 1), c->d_out + slot * nRefs + shareOffset.  Enqueued on the
+// regions finalized into its piece of compact vector `slot` (0 | 1), c->out.get() + slot * nRefs + shareOffset.  Enqueued on the
 // context's stream.
 int gtxi_count_device_share(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, uint32_t flags, int slot, void *direct_out, void **d_piece, int64_t *pieceLen)
 {
-  if (!c->shareOn) return fail(c, GTX_E_STATE, "gtxi_count_device_share: no share set");
-  if (c->refBlocks) return fail(c, GTX_E_STATE, "gtx_group_count_device: multi-interval regions (gtx_set_ref_blocks) are outside the members' shares");
+  if (!c->share.on) return fail(c, GTX_E_STATE, "gtxi_count_device_share: no share set");
+  if (c->rx.refBlocks) return fail(c, GTX_E_STATE, "gtx_group_count_device: multi-interval regions (gtx_set_ref_blocks) are outside the members' shares");
   if (n < 0 || (n > 0 && !d_reads)) return fail(c, GTX_E_ARG, "gtx_group_count_device: bad argument");
   if (flags & GTX_ZERO_LENGTH_OK) return fail(c, GTX_E_ARG, "gtx_group_count_device: GTX_ZERO_LENGTH_OK (sorted-merge semantics with their host-side corrections) is served by the host-buffer group calls only");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2495,14 +2419,14 @@ int gtxi_count_device_share(gtx_ctx *c, const void *d_reads, const void *d_weigh
   const bool streaming = (flags & (GTX_READS_SORTED | GTX_CHECK_SORTED)) != 0;
   if (!streaming) c->tileSumsValid = false;
   if (n > 0) {
-    if (streaming) HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, count_args(c, flags, n, 0, nullptr, true), true, c->stream));
-    else { rc = launch_unsorted(c, d_reads, d_weights, n, count_args(c, flags, n, 0, nullptr, true)); if (rc) return rc; }
+    if (streaming) HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, count_args(c, c->ix.hist, flags, n, 0, COUNT_SHARE), true, c->stream));
+    else { rc = launch_unsorted(c, d_reads, d_weights, n, count_args(c, c->ix.hist, flags, n, 0, COUNT_SHARE)); if (rc) return rc; }
   }
   if (c->profThis) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  u64 *dst = direct_out ? (u64 *)direct_out : c->d_out + (size_t)(slot % GTXI_SHARE_SLOTS) * c->nRefs + c->shareOffset;
+  u64 *dst = direct_out ? (u64 *)direct_out : c->out.get() + (size_t)(slot % GTXI_SHARE_SLOTS) * c->nRefs + c->share.offset;
   rc = count_end(c, dst, true, direct_out != nullptr); if (rc) return rc;
   if (c->profThis) { if (c->profEvery <= 1) HIPCHK(c, hipEventRecord(c->ev[3], c->stream)); c->profCalls++; }
-  *d_piece = dst; *pieceLen = c->nShareRegions;
+  *d_piece = dst; *pieceLen = c->share.nRegions;
   return GTX_OK;
 }
 
@@ -2515,82 +2439,68 @@ static constexpr int kInfoRing = 2 * GTXI_SHARE_STREAMS;
 int gtxi_count_device_share_async(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, uint32_t flags, int slot, int set, hipStream_t run,
                                   void *direct_out, void **d_piece, int64_t *pieceLen)
 {
-  if (!c->shareOn) return fail(c, GTX_E_STATE, "gtxi_count_device_share_async: no share set");
-  if (c->refBlocks || (flags & GTX_ZERO_LENGTH_OK) || !(flags & GTX_READS_SORTED) || n < 0 || (n > 0 && !d_reads))
+  if (!c->share.on) return fail(c, GTX_E_STATE, "gtxi_count_device_share_async: no share set");
+  if (c->rx.refBlocks || (flags & GTX_ZERO_LENGTH_OK) || !(flags & GTX_READS_SORTED) || n < 0 || (n > 0 && !d_reads))
     return fail(c, GTX_E_ARG, "gtxi_count_device_share_async: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
-  gtx_ctx::HistSet &h = c->alt[set % GTXI_SHARE_STREAMS];
-  const int nTiles = gtx::scan_tiles(c->histLen);
-  if (!h.histA) {
-    u64 **arr[] = {&h.histA, &h.histB, &h.prefA, &h.prefB};
-    for (u64 **p : arr) HIPCHK(c, hipMalloc(p, sizeof(u64) * c->histLen));
-    HIPCHK(c, hipMalloc(&h.partA, sizeof(u64) * (nTiles + 2))); HIPCHK(c, hipMalloc(&h.partB, sizeof(u64) * (nTiles + 2)));
-    HIPCHK(c, hipMalloc(&h.flags, sizeof(unsigned) * 8 * (nTiles + 2)));
-    HIPCHK(c, hipMemset(h.histA, 0, sizeof(u64) * c->histLen)); HIPCHK(c, hipMemset(h.histB, 0, sizeof(u64) * c->histLen));
-    HIPCHK(c, hipMemset(h.partA, 0, sizeof(u64) * (nTiles + 2))); HIPCHK(c, hipMemset(h.partB, 0, sizeof(u64) * (nTiles + 2)));
-    HIPCHK(c, hipMemset(h.flags, 0, sizeof(unsigned) * 8 * (nTiles + 2)));
-    h.epoch = 0; h.draws = 0;
-  }
-  if (!c->d_info3) {
-    HIPCHK(c, hipMalloc(&c->d_info3, kInfoRing * sizeof(gtx::DevInfo)));
-    for (int k = 0; k < kInfoRing; k++) HIPCHK(c, hipMemcpy(c->d_info3 + k, &c->h_info[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice));
+  HistSet &h = c->ix.alt[set % GTXI_SHARE_STREAMS];
+  if (!h.flags) { int rc = make_hist_set(c, h, c->histLen); if (rc) return rc; }
+  if (!c->ix.info3) {
+    HIPCHK(c, c->ix.info3.alloc(kInfoRing));
+    for (int k = 0; k < kInfoRing; k++) HIPCHK(c, hipMemcpy(c->ix.info3.get() + k, &c->h_info.get()[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice));
   }
   // info blocks: the calls on stream `set` take two blocks in turn; a call's finalize step clears the other one -- the block of the
   // call that ran on this stream before, for the call that runs on it next
   const int st = set % GTXI_SHARE_STREAMS;
-  const unsigned turn = c->shareTurn[st]++;
-  c->shareSeq++;
-  gtx::DevInfo *info = c->d_info3 + 2 * st + (turn & 1), *infoNext = c->d_info3 + 2 * st + ((turn + 1) & 1);
+  const unsigned turn = c->ix.shareTurn[st]++;
+  c->ix.shareSeq++;
+  gtx::DevInfo *info = c->ix.info3.get() + 2 * st + (turn & 1), *infoNext = c->ix.info3.get() + 2 * st + ((turn + 1) & 1);
   c->profThis = c->prof && (c->profEvery <= 1 || (c->profSeq++ % c->profEvery) == 0);
   if (c->profThis) { c->ev = c->evRing[c->profCalls % gtx_ctx::kProfSlots]; HIPCHK(c, hipEventRecord(c->ev[1], run)); }
   const bool keepDefault = c->tileSumsValid;
   c->tileSumsValid = true;
-  gtx::CountArgs a = count_args(c, flags, n, 0, &h, false, d_weights == nullptr);   // (clears c->tileSumsValid when the kernel leaves the tile sums to the finalize step)
+  gtx::CountArgs a = count_args(c, h, flags, n, 0, COUNT_SHARE_ASYNC, d_weights == nullptr);   // (clears c->tileSumsValid when the kernel leaves the tile sums to the finalize step)
   a.info = info;
   const bool sumsValid = c->tileSumsValid;
   c->tileSumsValid = keepDefault;
   if (n > 0) HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, true, run));
   if (c->profThis) HIPCHK(c, hipEventRecord(c->ev[2], run));
   // direct_out (may be null): the caller's result vector in file order (n_refs entries) -- the member's regions go to their places in it
-  u64 *dst = direct_out ? (u64 *)direct_out : c->d_out + (size_t)(slot % GTXI_SHARE_SLOTS) * c->nRefs + c->shareOffset;
-  gtx::FinalizeShare fs = {c->d_shareTiles, c->nShareTiles, c->d_shareRegions, c->nShareRegions, direct_out != nullptr};
-  if (++h.epoch == 0) { HIPCHK(c, hipMemsetAsync(h.flags, 0, sizeof(unsigned) * 8 * (nTiles + 2), run)); h.epoch = 1; h.draws = 0; }
-  HIPCHK(c, gtx::launch_finalize(h.histA, h.histB, c->histLen, h.partA, h.partB, sumsValid, h.prefA, h.prefB, c->d_posE, c->d_posS, c->d_classBase,
-                                 c->nRefs, dst, infoNext, run, &fs, h.flags, h.epoch, info, &h.draws, a.hist32 != 0 && n > 0));
+  u64 *dst = direct_out ? (u64 *)direct_out : c->out.get() + (size_t)(slot % GTXI_SHARE_SLOTS) * c->nRefs + c->share.offset;
+  const gtx::FinalizeShare fs = {c->share.tiles.get(), c->share.nTiles, c->share.regions.get(), c->share.nRegions, direct_out != nullptr};
+  int rc = finalize_set(c, h, sumsValid, dst, info, infoNext, run, &fs, a.hist32 != 0 && n > 0); if (rc) return rc;
   if (c->profThis) { if (c->profEvery <= 1) HIPCHK(c, hipEventRecord(c->ev[3], run)); c->profCalls++; }
-  c->lastShareInfo = info;
-  *d_piece = dst; *pieceLen = c->nShareRegions;
+  c->ix.lastShareInfo = info;
+  *d_piece = dst; *pieceLen = c->share.nRegions;
   return GTX_OK;
 }
 
 // what the last gtxi_count_device_share_async call observed (the caller has waited for its streams)
 int gtxi_last_share_info(gtx_ctx *c, gtx_count_info *info)
 {
-  if (!c->lastShareInfo) return gtx_last_info(c, info);
+  if (!c->ix.lastShareInfo) return gtx_last_info(c, info);
   HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpy(&c->h_info[0], c->lastShareInfo, sizeof(gtx::DevInfo), hipMemcpyDeviceToHost));
-  info_out(c->h_info[0], info, 0);
-  return fault_check(c, c->h_info[0]);
+  HIPCHK(c, hipMemcpy(&c->h_info.get()[0], c->ix.lastShareInfo, sizeof(gtx::DevInfo), hipMemcpyDeviceToHost));
+  info_out(c->h_info.get()[0], info, 0);
+  return fault_check(c, c->h_info.get()[0]);
 }
 
-void *gtxi_out_buffer(gtx_ctx *c) { return c->d_out; }
+void *gtxi_out_buffer(gtx_ctx *c) { return c->out.get(); }
 int gtxi_ensure_out(gtx_ctx *c, int64_t n)
 {
   HIPCHK(c, hipSetDevice(c->device));
-  if ((size_t)n > c->capOut) HIPCHK(c, hipStreamSynchronize(c->stream));      // (the old vector may still be read)
+  if ((size_t)n > c->out.cap) HIPCHK(c, hipStreamSynchronize(c->stream));      // (the old vector may still be read)
   return ensure_out(c, (size_t)std::max<int64_t>(n, 0));
 }
 // a second device buffer of the context (grown, never shrunk): where a group's member 0 assembles a result
 int gtxi_scratch(gtx_ctx *c, size_t bytes, void **p)
 {
   HIPCHK(c, hipSetDevice(c->device));
-  if (bytes > c->capScratch) {
+  if (bytes > c->scratch.cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dfree(c->d_scratch); c->capScratch = 0;
-    HIPCHK(c, hipMalloc(&c->d_scratch, bytes));
-    c->capScratch = bytes;
+    HIPCHK(c, c->scratch.reserve(bytes));
   }
-  *p = c->d_scratch;
+  *p = c->scratch.get();
   return GTX_OK;
 }
 

@@ -1,6 +1,7 @@
 """The C ABI's error contract on a live device: status codes + gtx_last_error text for bad arguments, wrong call
 order and out-of-range data; a context stays usable after an error; reference sets can be replaced at will."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -8,6 +9,9 @@ import pytest
 import gtx
 from gtx import perm, synth
 from oracle import orc, porc
+from oracle.restate import regions
+from test_gpu_join import join_rows, run as join_run
+from test_gpu_pairs import make_set, oracle_counts, split
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +81,40 @@ def test_reference_sets_can_be_replaced(engine):
             np.testing.assert_array_equal(got, orc.count(refs, reads, algo=orc.BIN_INDEX))
         cov, _ = engine.coverage(reads)
         np.testing.assert_array_equal(cov, orc.coverage(refs, reads, algo=orc.BIN_INDEX))
+
+
+def test_reference_sets_can_be_replaced_on_every_path(tmp_path):
+    """Each replacement of the reference set on one context: every path that keeps tables made from the set answers for the new
+    one -- shuffled count and coverage through the partition path, a count over multi-interval regions, a join."""
+    os.environ["GTX_BUCKET_MIN_READS"] = "1"                                  # (every unsorted batch through the partition path)
+    try:
+        e = gtx.Engine(0)
+    finally:
+        del os.environ["GTX_BUCKET_MIN_READS"]
+    rng = np.random.default_rng(17)
+    try:
+        for m, n_reads, n_genes, n_join in ((3000, 60_000, 800, 2000), (1, 500, 5, 20), (60_000, 300_000, 3000, 4000), (200, 5000, 40, 300)):
+            refs = synth.genome_intervals(m, 7 + m % 5, 50, 3000)
+            reads = synth.genome_intervals(n_reads, 8, 40, 41)
+            reads = reads[rng.permutation(len(reads))]
+            e.set_refs(refs, synth.n_classes())
+            got, _ = e.count(reads, None, 0)
+            np.testing.assert_array_equal(got, orc.count(refs, reads, algo=orc.BIN_INDEX))
+            cov, _ = e.coverage(reads, None, gtx.READS_UNSORTED)
+            np.testing.assert_array_equal(cov, orc.coverage(refs, reads, algo=orc.BIN_INDEX))
+            genes = make_set(rng, n_genes, 300_000, 0.7, (50, 300), (100, 5000), 8, 2000)
+            greads = make_set(rng, 10 * n_genes, 300_000, 0.3, (10, 80), (50, 2000), 3, 120)
+            e.set_refs(genes[0], 3)
+            e.set_ref_blocks(genes[1], genes[2])
+            single, mq = split(greads)
+            hits, _ = e.count_stream([(single, None)], 0, regions=[(mq[0], None, mq[1], mq[2])])
+            np.testing.assert_array_equal(hits, oracle_counts(tmp_path, genes, greads))
+            jr = regions(rng, n_join, 300_000, 1, 3000, multi=0.5)
+            jq = regions(rng, 4 * n_join, 300_000, 1, 200, multi=0.3)
+            want, off, pairs, _ = join_run(e, tmp_path, jr, jq)
+            assert join_rows(off, pairs) == want
+    finally:
+        e.close()
 
 
 def test_permutation_abi_errors():
