@@ -293,8 +293,10 @@ int gtx_pair_offsets_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_
  *
  * Weights are int64 (NULL: 1 per read) and the bins int64 sums (wrap-around).  While every weight is an integer and
  * no partial sum reaches 2^53 in magnitude, (double)bins[k] is bit-equal to the reference's sequential double sum;
- * info->weight_abs_sum bounds every partial sum.  A pair with (int)(n_bins * z) == n_bins (rounding, e.g. under
- * --norm-ref-length) is dropped and counted in n_dropped: the reference writes past its array there.
+ * info->weight_abs_sum bounds every partial sum.  A pair with (int)(n_bins * z) == n_bins is dropped and counted in
+ * n_dropped (the reference would write past its array there).  With IEEE doubles that cannot happen: for an integer
+ * n_bins < 2^53 and z <= 1 - 2^-53, n_bins * z rounds below n_bins (tests/test_switch_points_cpu.py), so the guard is
+ * free and n_dropped stays 0.
  * *first_inverted_out (may be NULL): the first read with a pair whose start offset exceeds its stop offset (the
  * reference's "this must be a bug" exit; such pairs are not binned), -1: none.
  *
