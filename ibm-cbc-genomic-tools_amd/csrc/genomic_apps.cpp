@@ -112,6 +112,7 @@ static void PlotNote() { fprintf(stderr, "Plot step skipped: this build writes t
 
 int main(int argc, char *argv[])
 {
+  GtxAcceptSAM(false);                                        // (SAM input stays unsupported here)
   if (argc < 2) {
     fprintf(stderr, "\nUSAGE: \n  %s OPERATION [OPTIONS] INPUT-FILES\n\nOPERATIONS (MI355X path): \n"
                     "  heatmap    Create heatmap profile of signal region in reference region.\n"

@@ -261,10 +261,31 @@ GenomicRegionBED::GenomicRegionBED(char *inp, long int n_line)
   if (I.empty()) PrintError("BED12 line without blocks!");
 }
 
+GenomicRegionSAM::GenomicRegionSAM(char *inp, long int n_line)
+{
+  this->n_line = n_line;
+  CIGAR = RNEXT = SEQ = QUAL = OPTIONAL = NULL;
+  gtxhost::SamFields f; std::vector<long> iv; std::string msg;
+  if (gtxhost::ParseSamLine(inp, &f, &iv, &msg) != gtxhost::SAM_OK) PrintError(msg);
+  n_tokens = f.n_tokens;
+  LABEL = CopyString(f.qname);
+  FLAG = f.flag; MAPQ = f.mapq; PNEXT = f.pnext; TLEN = f.tlen;
+  CIGAR = CopyString(f.cigar_text.c_str()); RNEXT = CopyString(f.rnext); SEQ = CopyString(f.seq); QUAL = CopyString(f.qual);
+  OPTIONAL = f.optional ? CopyString(f.optional) : NULL;
+  for (size_t k = 0; k + 1 < iv.size(); k += 2) I.push_back(new GenomicInterval(f.rname, f.strand, iv[k], iv[k + 1], n_line));
+}
+
+GenomicRegionSAM::~GenomicRegionSAM()
+{
+  GtxRegionFree(CIGAR); GtxRegionFree(RNEXT); GtxRegionFree(SEQ); GtxRegionFree(QUAL); GtxRegionFree(OPTIONAL);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // GenomicRegionSet
 // ---------------------------------------------------------------------------------------------------
 void StdoutIsOurs();   // (below, with the GPU start-up)
+static bool g_accept_sam = true;
+void GtxAcceptSAM(bool on) { g_accept_sam = on; }
 
 GenomicRegionSet::GenomicRegionSet(char *file, unsigned long int buffer_size, bool verbose, bool load_in_memory, bool hide_header)
 {
@@ -312,7 +333,8 @@ void GenomicRegionSet::PrintError(std::string error_msg)
   exit(1);
 }
 
-// genomic_intervals.cpp:3736-3759: by the number of TAB-separated tokens of the first data line
+// genomic_intervals.cpp:3736-3759: by the number of TAB-separated tokens of the first data line (SAM: 11 or more, a 6th token
+// without '+' or '-')
 void GenomicRegionSet::DetectFormat(const char *line)
 {
   if (line[0] == '>' || line[0] == '@' || (line[0] == '#' && line[1] == '#')) PrintError("unsupported input format!\n");
@@ -325,8 +347,15 @@ void GenomicRegionSet::DetectFormat(const char *line)
     std::string tok(p, strcspn(p, "\t"));
     bed = tok.find('+') != std::string::npos || tok.find('-') != std::string::npos;
   }
-  if (!bed) PrintError("unsupported input format!\n");     // REG / SAM / GFF are outside the path
+  if (!bed && g_accept_sam && gtxhost::LooksLikeSam(line)) { format = "SAM"; return; }
+  if (!bed) PrintError("unsupported input format!\n");     // REG / GFF are outside the path
   format = "BED";
+}
+
+GenomicRegion *GenomicRegionSet::CreateRegion(char *line, long int n_line)
+{
+  if (format == "SAM") return new GenomicRegionSAM(line, n_line);
+  return new GenomicRegionBED(line, n_line);
 }
 
 void GtxWarmUp();
@@ -356,11 +385,20 @@ void GenomicRegionSet::Init()
   src = file_ptr ? LineSource::FromFile(file_ptr) : LineSource::Open(file, &err);
   if (!src) { fprintf(stderr, "%s\n", err.c_str()); exit(1); }
   char *line = src->Next();
-  while (line && (strncmp(line, "browser ", 8) == 0 || strncmp(line, "track ", 6) == 0)) {
+  bool sam_header = false;
+  if (line && line[0] == '@' && g_accept_sam) {                 // a SAM header (ProcessFileHeader :3721-3724): echoed unless hidden
+    sam_header = true;
+    while (line && line[0] == '@') {
+      if (!hide_header) { StdoutIsOurs(); printf("%s\n", line); }
+      line = src->Next();
+    }
+  }
+  while (!sam_header && line && (strncmp(line, "browser ", 8) == 0 || strncmp(line, "track ", 6) == 0)) {
     if (!hide_header) { StdoutIsOurs(); printf("%s\n", line); }
     line = src->Next();
   }
   if (!line) { format = "EMPTY"; n_regions = 0; }
+  else if (sam_header) format = "SAM";
   else DetectFormat(line);
 
   if (load_in_memory) {
@@ -369,7 +407,7 @@ void GenomicRegionSet::Init()
     // (1 M regions: 0.23 s on one thread).  The set is the same objects in the same order; a malformed line is reported as the
     // line-by-line reader would have met it -- the first one in the file.
     std::vector<GenomicRegion *> regs;
-    if (line) regs.push_back(new GenomicRegionBED(line, src->line_no()));
+    if (line) regs.push_back(CreateRegion(line, src->line_no()));
     // Four threads, not all of them: this runs while the start-up thread brings up the HIP runtime, and a process that had many
     // threads running then takes 0.15-0.2 s longer to go away at exit (measured on the MI355X boxes, 16 threads against 4: every
     // run against none; where the time goes inside the driver's teardown was not found).  Four are enough: the runtime is what the
@@ -402,7 +440,7 @@ void GenomicRegionSet::Init()
             char *nl = (char *)memchr(q, '\n', (size_t)(p.e - q));
             if (!nl) break;                                                // (cannot happen: pieces end at line ends)
             *nl = 0;
-            p.out.push_back(new GenomicRegionBED(q, no));
+            p.out.push_back(CreateRegion(q, no));
             q = nl + 1;
           }
         } catch (const LoadAbort &) {}
@@ -435,7 +473,7 @@ void GenomicRegionSet::Init()
     n_regions = 1;
     cur_raw = line;
     R = new GenomicRegion *[1];
-    R[0] = new GenomicRegionBED(line, src->line_no());
+    R[0] = CreateRegion(line, src->line_no());
   }
   if (verbose) {
     std::cerr << "Reading from '" << (file == NULL ? "<standard input>" : file) << "'; ";
@@ -489,7 +527,7 @@ GenomicRegion *GenomicRegionSet::Next(bool retain_current)
   if (!line) return NULL;
   if (R[0] && !retain_current) delete R[0];
   cur_raw = line;
-  R[0] = new GenomicRegionBED(line, src->line_no());
+  R[0] = CreateRegion(line, src->line_no());
   return R[0];
 }
 
@@ -648,7 +686,7 @@ static std::atomic<bool> g_drain_stop(false);                 // set by a sink t
 // anything else in it comes back and is packed here, with the reference's reading of it and the reference's errors.
 struct TextSink {
   std::function<bool()> usable;                                   // (asked behind prep(): one GPU)
-  std::function<int(const char *, size_t, int64_t, const gtx_text_rules &)> add;
+  std::function<int(const char *, size_t, int64_t, const gtx_text_rules &, uint32_t)> add;   // (the last argument: GTX_TEXT_SAM or 0, to go with the call's flags)
   std::function<bool(int)> needs_host;
 };
 
@@ -656,7 +694,7 @@ static bool TextOnDevice(GenomicRegionSet *set, const PackOptions &opt, const Te
 {
   static const char *e = getenv("GTX_TEXT_ON_DEVICE");        // 0: never; 1: whenever the input qualifies (tests); default: files of 32 MB or more
   if (!ts || (e && atoi(e) == 0)) return false;
-  if (set->load_in_memory || set->format != "BED") return false;
+  if (set->load_in_memory || (set->format != "BED" && set->format != "SAM")) return false;
   if (opt.guard || opt.collect_zero_length) return false;                 // (explode_blocks: a 12-column line sends its block back to the packer, which does it)
   if (!g_pool.buf[0] || !g_pool.buf[1] || !ts->usable()) return false;
   // a regular uncompressed file: worth it from 32 MB on.  A stream (stdin / a pipe, a .gz file, a FILE* of the caller's: -1) has no
@@ -672,6 +710,7 @@ static void DrainSet(GenomicRegionSet *set, PackOptions opt, Prep prep, Sink sin
                      const std::function<void(const PackError &)> &on_error = std::function<void(const PackError &)>())
 {
   g_drain_stop = false;
+  opt.sam = set->format == "SAM";
   const size_t batch_reads = kBatchReads;
   PackedBatch two[2]; PackError err;
   // (a scanner's batch without a single region for the windows still carries the label values of its lines)
@@ -726,7 +765,7 @@ static void DrainSet(GenomicRegionSet *set, PackOptions opt, Prep prep, Sink sin
         continue;
       }
       rules.have_prev = b.have_prev; rules.prev_chrom = b.prev_chrom.c_str(); rules.prev_strand = b.prev_strand; rules.prev_start = b.prev_start;
-      ticket[cur] = text_sink->add(b.text, b.bytes, b.n_lines, rules);
+      ticket[cur] = text_sink->add(b.text, b.bytes, b.n_lines, rules, opt.sam ? GTX_TEXT_SAM : 0u);
       if (on_error) settle(cur);                                 // (a caller that goes on after an error wants nothing behind the offending line counted: one block at a time)
     }
     settle(0); settle(1);
@@ -825,12 +864,16 @@ static bool LooksSorted(const gtxhost::RawVec &tri)
 }
 
 // the same hint from the text of a block: pairs of adjacent lines at ~4096 places, (chromosome token, column 2) compared
-static bool TextLooksSorted(const char *text, size_t bytes)
+static bool TextLooksSorted(const char *text, size_t bytes, bool sam = false)
 {
   if (bytes < 64) return true;
   const size_t stride = bytes > (4096u * 64u) ? bytes / 4096 : 64;
   int descents = 0;
   auto key = [&](const char *l, const char *e, const char **tok, size_t *len, long *start) {
+    if (sam) {                                                     // SAM: (RNAME, POS), columns 3 and 4
+      for (int k = 0; k < 2 && l; k++) { l = (const char *)memchr(l, '\t', (size_t)(e - l)); if (l) l++; }
+      if (!l) return false;
+    }
     const char *t = (const char *)memchr(l, '\t', (size_t)(e - l));
     if (!t) return false;
     *tok = l; *len = (size_t)(t - l); *start = atol(t + 1);
@@ -1034,9 +1077,9 @@ unsigned long int *GenomicRegionSetOverlaps::Reduce(bool coverage, bool match_ga
   if (coverage) {
     // zero-length reads (sorted rules let them through) and zero-length regions contribute 0: the device leaves them out
     const uint32_t cflags = sorted ? (GTX_ZERO_LENGTH_OK | (match_gaps ? GTX_GAPS_FORMULA : 0u)) : 0u;
-    text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules) {
+    text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules, uint32_t text_flags) {
       int ticket = -1;
-      CheckGrp(grp, gtx_group_coverage_add_text(grp, text, bytes, lines, &rules, cflags | (sorted ? GTX_READS_SORTED : 0u), &ticket));
+      CheckGrp(grp, gtx_group_coverage_add_text(grp, text, bytes, lines, &rules, cflags | text_flags | (sorted ? GTX_READS_SORTED : 0u), &ticket));
       return ticket;
     };
     DrainSet(QuerySet, opt, [&] { device_side(true); }, [&](const PackedBatch &b) {
@@ -1054,10 +1097,10 @@ unsigned long int *GenomicRegionSetOverlaps::Reduce(bool coverage, bool match_ga
     return hits;
   }
   const uint32_t mode_flags = sorted ? GTX_ZERO_LENGTH_OK : 0;
-  text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules) {
+  text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules, uint32_t text_flags) {
     int ticket = -1;
     // (the sorted merge's input is in order, or the block comes back; the bin index takes any order: a look at the text decides the kernel)
-    const uint32_t flags = mode_flags | ((sorted || TextLooksSorted(text, bytes)) ? GTX_READS_SORTED : 0);
+    const uint32_t flags = mode_flags | text_flags | ((sorted || TextLooksSorted(text, bytes, (text_flags & GTX_TEXT_SAM) != 0)) ? GTX_READS_SORTED : 0);
     CheckGrp(grp, gtx_group_count_add_text(grp, text, bytes, lines, &rules, flags, &ticket));
     return ticket;
   };
@@ -1418,10 +1461,10 @@ void GenomicRegionSetScanner::Compute(bool sorted_rules)
   TextSink text_sink;
   text_sink.usable = [&] { return one != NULL; };
   text_sink.needs_host = [&](int ticket) { int redo = 0; check_one(gtx_text_result(one, ticket, &redo)); return redo != 0; };
-  text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules) {
+  text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules, uint32_t text_flags) {
     if (!preprocess_ok) { bad_preprocess = true; g_drain_stop = true; return -1; }
     int ticket = -1;
-    check_one(gtx_scan_add_text(one, text, bytes, lines, &rules, (sorted_rules || TextLooksSorted(text, bytes)) ? 0u : GTX_READS_UNSORTED, &ticket));
+    check_one(gtx_scan_add_text(one, text, bytes, lines, &rules, text_flags | ((sorted_rules || TextLooksSorted(text, bytes, (text_flags & GTX_TEXT_SAM) != 0)) ? 0u : GTX_READS_UNSORTED), &ticket));
     return ticket;
   };
   DrainSet(R, opt, device_side, [&](const PackedBatch &b) {
@@ -1938,6 +1981,9 @@ void WriteOut(std::string &out, size_t above = 0)
 // gtx_set_ref_blocks accepts.
 void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char *bin_bits, bool single_if_invalid, JoinIndex &ix)
 {
+  // the per-pair operations print query lines as BED text (and read their BED columns back): a SAM set of the class API's is refused
+  // here, with the message the CLIs give for it (GtxAcceptSAM)
+  if (ov->QuerySet->format == "SAM" || ov->IndexSet->format == "SAM") ov->QuerySet->PrintError("unsupported input format!\n");
   GenomicRegionSet *IS = ov->IndexSet;
   const long int M = IS->n_regions;
   ix.IS = IS; ix.M = M; ix.ignore_strand = ignore_strand;

@@ -11,9 +11,10 @@
 // reductions here; without a GPU they fail with an error message and exit(1), like every other
 // error of the reference (genomic_intervals.cpp:1001-1006).
 //
-// Scope: BED3..BED12 regions (BED12 blocks as multi-interval regions), the
+// Scope: BED3..BED12 regions (BED12 blocks as multi-interval regions) and SAM
+// alignments (a spliced read as a multi-interval region), the
 // reductions of count / rpkm / coverage / density and the scanners, and the per-pair iteration
-// (GetQuery / GetOverlap / NextOverlap) on the host.  REG/SAM/GFF/SEQ input, the ~45 Run*/Print*
+// (GetQuery / GetOverlap / NextOverlap) on the host.  REG/GFF/SEQ input, the ~45 Run*/Print*
 // text transforms of GenomicRegionSet and GenomicRegionSetIndex beyond the "does anything overlap"
 // query of the scanners' reference filter are outside the path; the device-side pair join is the
 // C ABI's gtx_join (include/gtx.h).
@@ -105,6 +106,19 @@ class GenomicRegionBED : public GenomicRegion
   long int n_tokens;
 };
 
+class GenomicRegionSAM : public GenomicRegion
+{
+ public:
+  // parses one SAM alignment (the line is modified); genomic_intervals.cpp:2771-2812.  A CIGAR with 'N' operations makes a region
+  // of several intervals; one without any interval on the reference (no M, D, X or N of positive length) is an input error here
+  GenomicRegionSAM(char *inp, long int n_line);
+  ~GenomicRegionSAM();
+  long int n_tokens;
+  unsigned long int FLAG;
+  long int MAPQ, PNEXT, TLEN;
+  char *CIGAR, *RNEXT, *SEQ, *QUAL, *OPTIONAL;                    // OPTIONAL: NULL for an 11-column line
+};
+
 // ---- GenomicRegionSet (genomic_intervals.h:1828) ------------------------------------------------------
 class GenomicRegionSet
 {
@@ -133,7 +147,7 @@ class GenomicRegionSet
   const std::string &CurrentLine() const { return cur_raw; }      // MI355X path: the unparsed line of the current region of a streamed text set
   long int StreamBytesLeft();                     // size of a streamed regular text file, -1 otherwise (MI355X build: the device-side tokenizer's test)
   long int n_regions;
-  std::string format;                                              // "BED", "EMPTY" or "GTX" (a packed region file, gtx_bed.h)
+  std::string format;                                              // "BED", "SAM", "EMPTY" or "GTX" (a packed region file, gtx_bed.h)
   GenomicRegion **R;
 
  private:
@@ -143,6 +157,7 @@ class GenomicRegionSet
   gtxhost::GtxView *packed;                                        // format "GTX"
   std::vector<std::pair<void *, size_t> > blocks_;                  // memory of the region objects built in parallel (GtxRegionAlloc)
   GenomicRegion *PackedRegion(long int record);                    // region object of one record of the packed file
+  GenomicRegion *CreateRegion(char *line, long int n_line);        // GenomicRegionBED or GenomicRegionSAM, by the set's format
   std::string cur_raw;                                             // unparsed copy of the current line (streaming mode)
   long int r_index;
 };
@@ -358,6 +373,7 @@ struct GtxSignalSpec {
 unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *overlaps, const GtxSignalSpec &spec, std::vector<double> &bins);
 
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
+void GtxAcceptSAM(bool on);                                      // false: a SAM file is "unsupported input format!" (drivers that print query lines; default true)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)
 void GtxFinish(int code);                                        // flush and leave without the teardown (see genomic_intervals.cpp)
 

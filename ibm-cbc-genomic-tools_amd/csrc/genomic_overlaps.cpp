@@ -36,6 +36,7 @@ int main(int argc, char *argv[])
   for (const char *o : others) if (op == o) { fprintf(stderr, "Operation '%s' is outside the MI355X counting path of this build (count, coverage, density, rpkm)!\n", o); return 1; }
   if (op != "count" && op != "rpkm" && op != "coverage" && op != "density" && op != "overlap" && op != "intersect" && op != "offset") { fprintf(stderr, "Unknown operation '%s'!\n", op.c_str()); return 1; }
   const bool per_pair = op == "overlap" || op == "intersect";
+  if (per_pair || op == "offset") GtxAcceptSAM(false);        // (they print query lines in their own format: SAM stays unsupported there)
 
   bool HELP, HELP2, VERBOSE, IS_SORTED, SORTED_BY_STRAND, IGNORE_STRAND, MATCH_GAPS;
   const char *BIN_BITS; long MAX_LABEL_VALUE; unsigned long MIN_COUNT = 0; double MIN_RPKM, MIN_DENSITY = 0.0;

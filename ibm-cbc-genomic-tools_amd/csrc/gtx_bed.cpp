@@ -396,6 +396,74 @@ BedStatus ParseBedLine(char *line, BedFields *o, char **bad)
   return BED_OK;
 }
 
+SamStatus ParseSamLine(char *line, SamFields *o, std::vector<long> *iv, std::string *msg)
+{
+  iv->clear();
+  o->n_tokens = CountTokensLike(line, '\t');
+  if (o->n_tokens < 11) { *msg = "number of tokens should be at least 11 for SAM format!"; return SAM_TOO_FEW_TOKENS; }
+  char *cur = line;
+  o->qname = TakeToken(&cur, '\t');
+  o->flag = (unsigned long)FastAtol(TakeToken(&cur, '\t'));
+  o->rname = TakeToken(&cur, '\t');
+  o->pos = FastAtol(TakeToken(&cur, '\t'));
+  o->mapq = FastAtol(TakeToken(&cur, '\t'));
+  o->cigar = TakeToken(&cur, '\t');
+  o->rnext = TakeToken(&cur, '\t');
+  o->pnext = FastAtol(TakeToken(&cur, '\t'));
+  o->tlen = FastAtol(TakeToken(&cur, '\t'));
+  o->seq = TakeToken(&cur, '\t');
+  o->qual = TakeToken(&cur, '\t');
+  o->optional = o->n_tokens > 11 ? TakeToken(&cur, '\n') : nullptr;
+  o->strand = (o->flag & 0x10) ? '-' : '+';
+  const long seq_len = (long)strlen(o->seq);
+  o->cigar_text = strcmp(o->cigar, "*") == 0 ? std::to_string(seq_len) + "M" : std::string(o->cigar);
+  // TokenizeCIGAR / GetNextTokenOfCIGAR (:2888-2920).  (Digits at the very end make an operation of type NUL, which strchr finds in
+  // every set; the reference then reads on behind the string -- here the CIGAR ends there.)
+  std::vector<std::pair<long, char>> ops;
+  for (const char *p = o->cigar_text.c_str(); *p;) {
+    const char *d = p;
+    while (*p >= '0' && *p <= '9') p++;
+    const char type = *p;
+    const long len = FastAtolTo(d, p);
+    if (type != 0 && !strchr("MIDNSHP-X", type)) { *msg = std::string("unknown CIGAR operation type '") + type + "'!"; return SAM_BAD_CIGAR_OP; }
+    ops.emplace_back(len, type);
+    if (type == 0) break;
+    p++;
+  }
+  auto in = [](const char *set, char t) { return t == 0 || strchr(set, t) != nullptr; };
+  if (strcmp(o->seq, "*") != 0) {
+    long frag = 0;
+    for (auto &op : ops) if (in("MIS=X", op.second)) frag += op.first;
+    if (seq_len != frag) {
+      *msg = std::string("length of aligned fragment does not match CIGAR string: \n  LABEL = ") + o->qname + "\n  CIGAR = " + o->cigar_text +
+             "\n  length(SEQ) = " + std::to_string(seq_len) + "\n";
+      return SAM_FRAGMENT_MISMATCH;
+    }
+  }
+  long start = o->pos, ref = 0;
+  for (auto &op : ops) {
+    if (op.second != 'N') { if (in("MD=X", op.second)) ref += op.first; continue; }
+    iv->push_back(start); iv->push_back(start + ref - 1);
+    start += ref + op.first; ref = 0;
+  }
+  if (ref > 0) { iv->push_back(start); iv->push_back(start + ref - 1); }
+  // the reference goes on with a region of no interval and dereferences I.front() (undefined behaviour): an input error here
+  if (iv->empty()) { *msg = "SAM alignment without a reference interval (its CIGAR string has no M, D, X or N operation of positive length)!"; return SAM_NO_INTERVAL; }
+  return SAM_OK;
+}
+
+bool LooksLikeSam(const char *line)
+{
+  if (line[0] == '@') return true;
+  const int nt = CountTokensLike(line, '\t');
+  if (nt < 11) return false;
+  const char *p = line; int tabs = 0;
+  while (*p && tabs < 5) { if (*p == '\t') tabs++; p++; }
+  while (*p == ' ') p++;
+  const size_t n = strcspn(p, "\t");
+  return memchr(p, '+', n) == nullptr && memchr(p, '-', n) == nullptr;
+}
+
 void BedBlocks(const BedFields &f, std::vector<long> *iv)
 {
   iv->clear();
@@ -520,17 +588,26 @@ GtxView *GtxView::Open(const char *path, std::string *err)
 
 GtxView::~GtxView() { if (map_) munmap(map_, map_len_); }
 
-bool WriteGtx(LineSource *src, const char *out_path, PackError *err)
+bool WriteGtx(LineSource *src, const char *out_path, PackError *err, bool sam)
 {
   std::vector<std::string> names; std::vector<uint16_t> cidx; std::vector<int32_t> st, en, lab; std::vector<uint8_t> minus;
   std::string last; int last_id = -1;
   bool any_label = false, top = true;
   uint64_t n = 0;
+  std::vector<long> iv;
   for (char *line = src->Next(); line; line = src->Next()) {
     if (top && (strncmp(line, "browser ", 8) == 0 || strncmp(line, "track ", 6) == 0)) continue;   // genomic_intervals.cpp:3713-3720
+    if (top && sam && line[0] == '@') continue;                                                  // the SAM header (:3721-3724)
     top = false;
     BedFields f; char *bad = nullptr;
-    const BedStatus s = ParseBedLine(line, &f, &bad);
+    BedStatus s = BED_OK;
+    if (sam) {
+      SamFields sf; std::string msg;
+      if (ParseSamLine(line, &sf, &iv, &msg) != SAM_OK) { SetErrPublic(err, src->line_no(), msg, false); return false; }
+      if (iv.size() > 2) { SetErrPublic(err, src->line_no(), "a spliced SAM alignment (a region of several intervals) cannot be kept in a packed region file!", false); return false; }
+      f.chrom = sf.rname; f.label = sf.qname; f.strand = sf.strand; f.start = iv[0]; f.stop = iv[1];
+      f.n_tokens = 6;                                              // (one interval: what a BED6 line holds, whatever the number of SAM columns)
+    } else s = ParseBedLine(line, &f, &bad);
     if (s == BED_TOO_FEW_TOKENS) { SetErrPublic(err, src->line_no(), "number of tokens should be at least 3 for BED format!", false); return false; }
     if (s == BED_BAD_STRAND) { SetErrPublic(err, src->line_no(), std::string("Error: invalid strand '") + bad + "'!", true); return false; }
     if (f.n_tokens == 12) { SetErrPublic(err, src->line_no(), "multi-interval (BED12) regions are outside the MI355X counting path!", false); return false; }
@@ -757,32 +834,50 @@ void ParsePiece(Piece *p, const PackOptions &o)
   char *cur = p->begin;
   size_t est = (size_t)(p->end - p->begin) / 20 + 16;
   if (!p->dtri) { p->tri.reserve(est * 3); if (weighted) p->w.reserve(est); }
+  std::vector<long> iv;
   while (cur < p->end) {
     BedFields f; char *bad = nullptr;
     BedStatus st = BED_OK;
     static const bool fast_lines = getenv("GTX_NO_FAST_PARSE") == nullptr;      // (the tests compare both ways)
     size_t chrom_len = 0;
-    char *next = fast_lines ? ParseTabbedLine(cur, p->end, &f, &chrom_len) : nullptr;
-    if (next) { cur = next; line_no++; }
-    else {
+    bool multi = false;                                            // a region of several intervals (BED12, a spliced SAM read): iv holds them
+    if (o.sam) {
       char *nl = (char *)memchr(cur, '\n', (size_t)(p->end - cur));
       if (!nl) break;
       *nl = 0;
       char *line = cur;
       cur = nl + 1;
       line_no++;
-      st = ParseBedLine(line, &f, &bad);
-      if (st == BED_OK) chrom_len = strlen(f.chrom);
+      SamFields s; std::string msg;
+      if (ParseSamLine(line, &s, &iv, &msg) != SAM_OK) { SetErr(&p->err, line_no, msg); break; }
+      f.chrom = s.rname; f.label = s.qname; f.strand = s.strand; f.n_tokens = s.n_tokens;
+      f.start = iv.front(); f.stop = iv.back();
+      chrom_len = strlen(s.rname);
+      multi = iv.size() > 2;                                       // (one interval: a read like a BED6 line)
+    } else {
+      char *next = fast_lines ? ParseTabbedLine(cur, p->end, &f, &chrom_len) : nullptr;
+      if (next) { cur = next; line_no++; }
+      else {
+        char *nl = (char *)memchr(cur, '\n', (size_t)(p->end - cur));
+        if (!nl) break;
+        *nl = 0;
+        char *line = cur;
+        cur = nl + 1;
+        line_no++;
+        st = ParseBedLine(line, &f, &bad);
+        if (st == BED_OK) chrom_len = strlen(f.chrom);
+      }
+      multi = st == BED_OK && f.n_tokens == 12;
     }
     if (st == BED_TOO_FEW_TOKENS) { SetErr(&p->err, line_no, "number of tokens should be at least 3 for BED format!"); break; }
     if (st == BED_BAD_STRAND) { SetErr(&p->err, line_no, std::string("Error: invalid strand '") + bad + "'!", true); break; }
     const long label_value = f.label ? FastAtol(f.label) : 0;      // (before the block lists are cut into tokens)
-    if (f.n_tokens == 12) {
+    if (multi) {
       // a multi-interval region: under -gaps it is matched on its envelope [first interval's start, last interval's stop]
       // (genomic_intervals.cpp:5226, :5752, :5278); its intervals must be sorted and disjoint (:1153-1161, checked at :5709, :5880)
       const bool overlaps = o.mode == PACK_OVERLAPS_SORTED || o.mode == PACK_OVERLAPS_UNSORTED;
-      if (!overlaps || !(o.match_gaps || o.explode_blocks || o.collect_blocks) || f.n_blocks < 1) { SetErr(&p->err, line_no, "multi-interval (BED12) regions are outside the MI355X counting path (except genomic_overlaps count, coverage and density)!"); break; }
-      std::vector<long> iv; BedBlocks(f, &iv);
+      if (!overlaps || !(o.match_gaps || o.explode_blocks || o.collect_blocks) || (!o.sam && f.n_blocks < 1)) { SetErr(&p->err, line_no, "multi-interval (BED12) regions are outside the MI355X counting path (except genomic_overlaps count, coverage and density)!"); break; }
+      if (!o.sam) BedBlocks(f, &iv);
       bool ok = true;
       for (size_t k = 2; k < iv.size(); k += 2) if (iv[k] < iv[k - 2] || iv[k] <= iv[k - 1]) ok = false;
       if (!ok) { SetErr(&p->err, line_no, "query regions should be compatible, sorted and non-overlapping!"); break; }
@@ -1083,7 +1178,12 @@ bool BedPacker::NextTextBlock(TextBlock *b)
     while (s > b->text && s[-1] != '\n') s--;
     std::string line(s, e);
     BedFields f; char *bad = nullptr;
-    if (!line.empty() && line.find('\0') == std::string::npos && ParseBedLine(&line[0], &f, &bad) == BED_OK && f.n_tokens != 12) {
+    SamFields sf; std::vector<long> iv; std::string msg;
+    if (opt_.sam) {                                                  // (a spliced read's key is its first interval's: POS)
+      if (!line.empty() && line.find('\0') == std::string::npos && ParseSamLine(&line[0], &sf, &iv, &msg) == SAM_OK) {
+        seam_have_ = true; seam_chrom_ = sf.rname; seam_strand_ = sf.strand; seam_start_ = iv.front();
+      } else seam_ok_ = false;
+    } else if (!line.empty() && line.find('\0') == std::string::npos && ParseBedLine(&line[0], &f, &bad) == BED_OK && f.n_tokens != 12) {
       seam_have_ = true; seam_chrom_ = f.chrom; seam_strand_ = f.strand; seam_start_ = f.start;
     } else seam_ok_ = false;
   }

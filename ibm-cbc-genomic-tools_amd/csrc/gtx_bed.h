@@ -85,6 +85,26 @@ BedStatus ParseBedLine(char *line, BedFields *out, char **bad);
 // Number of `delim`-separated tokens as the reference counts them (core.cpp:577-593).
 int CountTokensLike(const char *s, char delim);
 
+// ---- one SAM line (GenomicRegionSAM::Read, genomic_intervals.cpp:2771-2812) --------------------------------
+// TAB-separated, blanks before a token skipped; QNAME is the label, RNAME the chromosome, the strand '-' iff FLAG & 0x10.  A CIGAR
+// of "*" reads as "<strlen(SEQ)>M".  The CIGAR's operations come from "MIDNSHP-X" (a run of digits, possibly empty, then the
+// operation; '=' is refused, as the reference's tokenizer does); the ones in "MD=X" make up the reference length, an 'N' closes
+// an interval [start, start + reference length - 1] and moves start on by the reference length and its own; the interval after
+// the last 'N' is kept when its reference length is > 0.  iv receives the intervals as (start, stop) pairs, 1-based inclusive.
+struct SamFields {
+  char *qname, *rname, *cigar, *rnext, *seq, *qual;
+  char *optional;                    // the rest of the line behind QUAL, NULL for an 11-column line
+  unsigned long flag; long pos, mapq, pnext, tlen;
+  char strand;
+  int n_tokens;
+  std::string cigar_text;            // the CIGAR as the reference keeps it ("*" replaced)
+};
+enum SamStatus { SAM_OK = 0, SAM_TOO_FEW_TOKENS, SAM_BAD_CIGAR_OP, SAM_FRAGMENT_MISMATCH, SAM_NO_INTERVAL };
+// Parses in place (the line is cut into tokens).  On an error *msg receives what follows "Error: Line N: ".
+SamStatus ParseSamLine(char *line, SamFields *out, std::vector<long> *iv, std::string *msg);
+// the first data line of a file is SAM (GenomicRegionSet::DetectFileFormat, genomic_intervals.cpp:3736-3759)
+bool LooksLikeSam(const char *line);
+
 // ---- chromosome table: names in strcmp order, id = rank ------------------------------------------
 class ChromTable {
  public:
@@ -149,6 +169,7 @@ struct PackOptions {
                                      // every interval of a region goes out as a read of its own with the region's label value
   bool collect_blocks = false;       // ... count without -gaps: "some interval overlaps some interval" (:1167-1172) -- a region with several
                                      // intervals goes out on its own list (PackedBatch::m_*), after the same checks as any other region
+  bool sam = false;                  // the lines are SAM alignments (ParseSamLine): a spliced read is a multi-interval region, as a BED12 line is
   int threads = 0;                   // 0 = hardware concurrency
   IndexGuard *guard = nullptr;       // PACK_OVERLAPS_SORTED with an out-of-order index set (forces one thread)
   bool keep_prefix_on_error = false; // an error leaves the regions of the lines in front of it in the batch (the sorted scanner streams: what it
@@ -206,7 +227,7 @@ struct PackedBatch {
 };
 
 // text -> packed file; lines are validated like GenomicRegionBED (token count, strand); returns false with *err set
-bool WriteGtx(LineSource *src, const char *out_path, PackError *err);
+bool WriteGtx(LineSource *src, const char *out_path, PackError *err, bool sam = false);
 // the same file from columns the caller holds (minus: one bit per record; lab may be NULL)
 bool WriteGtxColumns(const char *out_path, const std::vector<std::string> &names, uint64_t n, const uint16_t *cidx, const int32_t *st, const int32_t *en,
                      const uint8_t *minus, const int32_t *lab, PackError *err);

@@ -2251,6 +2251,8 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
   if (mode == TEXT_SCAN && r && (r->max_label_value > 1) != c->scan.weighted) return fail(c, GTX_E_ARG, "gtx_scan_add_text: the rules' label weights do not match gtx_scan_begin's");
   if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names))
     { c->err = std::string(who) + ": bad argument"; return GTX_E_ARG; }
+  const bool sam = (flags & GTX_TEXT_SAM) != 0;                  // (the format of the text, not a flag of the count)
+  flags &= ~GTX_TEXT_SAM;
   HIPCHK(c, hipSetDevice(c->device));
   const int slot = (int)(c->textSeq & 1);
   TextSlot &t = c->text[slot];
@@ -2317,7 +2319,7 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
   d.tri2 = r->strand_aware ? t.tri2.get() : nullptr; d.w2 = r->strand_aware ? t.w2.get() : nullptr; d.blkMinus = r->strand_aware ? t.blk.get() : nullptr;
   const int *triOut = r->strand_aware ? t.tri2.get() : t.tri.get();
   d.labelSum = mode == TEXT_SCAN ? c->scan.labelSum.get() : nullptr; d.blockSum = t.sum.get();
-  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, mode == TEXT_SCAN ? (c->scan.a.sortedRule ? 2 : 1) : 0));
+  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, mode == TEXT_SCAN ? (c->scan.a.sortedRule ? 2 : 1) : 0, sam));
   HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
   // ... and counted where the triples are

@@ -3,8 +3,11 @@
 // CPU test suite checks the packer (line handling, tokenising, order checks, error text and line numbers,
 // thread-count independence) on machines without an MI355X.
 //
-//   gtx_packtool MODE [-t THREADS] [-s] [-a] [-l MAXLABEL] [-c CHROM,CHROM,...] [FILE]
+//   gtx_packtool MODE [-t THREADS] [-s] [-a] [-l MAXLABEL] [--sam] [-c CHROM,CHROM,...] [FILE]
 //     MODE   ou = overlaps/unsorted   os = overlaps/sorted   su = scan/unsorted   ss = scan/sorted
+//     -g / -m / -e   multi-interval regions: on their envelope (-gaps) / listed (count) / one read per interval (coverage)
+//     --sam  the file is SAM: its '@' header lines are skipped (they keep their line numbers; FILE only), the alignments read as
+//            GenomicRegionSAM does; a spliced read's intervals are printed as "# blocks class start end n s1 e1 s2 e2 ..."
 //     -s sorted by strand   -a strand-aware classes   -c known chromosomes (default: all seen in FILE order? no:
 //        the list is required for reproducible class ids)
 //   output: one line per packed read "class start end [weight]", then "# lines=N"; errors like the CLIs.
@@ -22,7 +25,7 @@ using namespace gtxhost;
 #include <algorithm>
 #include <thread>
 #include <vector>
-static int SynthBed(bool refs, long long n, unsigned long long seed, const char *out_path, long read_len)
+static int SynthBed(bool refs, long long n, unsigned long long seed, const char *out_path, long read_len, bool sam = false)
 {
   static const struct { const char *name; long len; } chr[24] = {   // strcmp order
     {"chr1", 248956422}, {"chr10", 133797422}, {"chr11", 135086622}, {"chr12", 133275309}, {"chr13", 114364328}, {"chr14", 107043718},
@@ -46,7 +49,21 @@ static int SynthBed(bool refs, long long n, unsigned long long seed, const char 
     std::sort(s.begin(), s.end());
     if (refs) for (long long i = 0; i < k; i++) ln[(size_t)i] = 50 + (unsigned)(next() % 1950);
     std::string &t = text[c];
-    t.reserve((size_t)k * (refs ? 40 : 30));
+    t.reserve((size_t)k * (refs ? 40 : sam ? (size_t)(2 * read_len + 100) : 30));
+    if (sam) {                                                    // SAM: the same reads as alignments, r<i> FLAG 0|16 ... <LEN>M
+      static const char base[4] = {'A', 'C', 'G', 'T'};
+      std::string seq((size_t)read_len, 'A'), qual((size_t)read_len, 'F');
+      char head[160];
+      for (long long i = 0; i < k; i++) {
+        for (long b = 0; b < read_len; b++) seq[(size_t)b] = base[(next() >> 7) & 3];
+        const unsigned flag = (next() & 1) ? 16u : 0u;
+        int h = snprintf(head, sizeof head, "r%lld\t%u\t%s\t%u\t60\t%ldM\t*\t0\t0\t", first[c] + i, flag, chr[c].name, s[(size_t)i] + 1, read_len);
+        t.append(head, (size_t)h); t += seq; t += '\t'; t += qual;
+        h = snprintf(head, sizeof head, "\tNM:i:0\tMD:Z:%ld\tAS:i:%ld\n", read_len, read_len);
+        t.append(head, (size_t)h);
+      }
+      return;
+    }
     char buf[96];
     const size_t nl = strlen(chr[c].name);
     for (long long i = 0; i < k; i++) {
@@ -65,6 +82,10 @@ static int SynthBed(bool refs, long long n, unsigned long long seed, const char 
   }
   FILE *o = fopen(out_path, "wb");
   if (!o) { fprintf(stderr, "Error: cannot create file '%s'!\n", out_path); return 1; }
+  if (sam) {
+    fprintf(o, "@HD\tVN:1.6\tSO:coordinate\n");
+    for (int c = 0; c < 24; c++) fprintf(o, "@SQ\tSN:%s\tLN:%ld\n", chr[c].name, chr[c].len);
+  }
   for (int c = 0; c < 24; c++) if (fwrite(text[c].data(), 1, text[c].size(), o) != text[c].size()) { fprintf(stderr, "Error: cannot write file '%s'!\n", out_path); return 1; }
   return fclose(o) == 0 ? 0 : 1;
 }
@@ -75,13 +96,14 @@ int main(int argc, char **argv)
   PackOptions opt;
   std::string m = argv[1];
   if (m == "pack") {
-    // gtx_packtool pack IN.bed[.gz] OUT.gtx : tokenise once, keep the columns (gtx_bed.h, "packed region files")
-    if (argc != 4) { fprintf(stderr, "usage: gtx_packtool pack IN.bed OUT.gtx\n"); return 2; }
+    // gtx_packtool pack [--sam] IN.bed[.gz] OUT.gtx : tokenise once, keep the columns (gtx_bed.h, "packed region files")
+    const bool sam = argc == 5 && !strcmp(argv[2], "--sam");
+    if (argc != 4 && !sam) { fprintf(stderr, "usage: gtx_packtool pack [--sam] IN.bed OUT.gtx\n"); return 2; }
     std::string err;
-    LineSource *src = LineSource::Open(argv[2], &err);
+    LineSource *src = LineSource::Open(argv[sam ? 3 : 2], &err);
     if (!src) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
     PackError e;
-    if (!WriteGtx(src, argv[3], &e)) {
+    if (!WriteGtx(src, argv[sam ? 4 : 3], &e, sam)) {
       if (e.no_prefix) fprintf(stderr, "%s\n", e.msg.c_str()); else fprintf(stderr, "\nError: Line %ld: %s\n", e.line, e.msg.c_str());
       return 1;
     }
@@ -95,6 +117,12 @@ int main(int argc, char **argv)
     // Workload files for the end-to-end timings (bench.py text_to_stdout): written by a thread per chromosome, ~1 GB/s.
     if (argc < 5) { fprintf(stderr, "usage: gtx_packtool synth|synthrefs N SEED OUT.bed [LEN]\n"); return 2; }
     return SynthBed(m == "synthrefs", atoll(argv[2]), strtoull(argv[3], NULL, 10), argv[4], argc > 5 ? atol(argv[5]) : 50);
+  }
+  if (m == "synthsam") {
+    // gtx_packtool synthsam N SEED OUT.sam [LEN]   the reads of `synth` as SAM alignments: a header, QNAME r<i>, FLAG 0 or 16, MAPQ 60,
+    //                                              CIGAR <LEN>M, SEQ and QUAL of LEN bases, three optional tags (lines of ~2.5 LEN + 80 bytes)
+    if (argc < 5) { fprintf(stderr, "usage: gtx_packtool synthsam N SEED OUT.sam [LEN]\n"); return 2; }
+    return SynthBed(false, atoll(argv[2]), strtoull(argv[3], NULL, 10), argv[4], argc > 5 ? atol(argv[5]) : 100, true);
   }
   if (m == "stats") {
     // the host-side tail probabilities of `genomic_scans peaks` (gtx_stats.h), one "b K P N" / "p K MU" / "g X" query per stdin line
@@ -121,6 +149,10 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[a], "-a")) opt.strand_aware = true;
     else if (!strcmp(argv[a], "-z")) opt.collect_zero_length = true;
     else if (!strcmp(argv[a], "-q")) quiet = true;
+    else if (!strcmp(argv[a], "--sam")) opt.sam = true;
+    else if (!strcmp(argv[a], "-g")) opt.match_gaps = true;           // -gaps: a multi-interval region on its envelope
+    else if (!strcmp(argv[a], "-m")) opt.collect_blocks = true;       // count without -gaps: multi-interval regions on their own list
+    else if (!strcmp(argv[a], "-e")) opt.explode_blocks = true;       // coverage without -gaps: every interval a read of its own
     else if (!strcmp(argv[a], "-l") && a + 1 < argc) opt.max_label_value = atol(argv[++a]);
     else if (!strcmp(argv[a], "-b") && a + 1 < argc) batch = (size_t)atol(argv[++a]);
     else if (!strcmp(argv[a], "-c") && a + 1 < argc) {
@@ -137,6 +169,13 @@ int main(int argc, char **argv)
   else { src = LineSource::Open(file, &err); if (!src) { fprintf(stderr, "%s\n", err.c_str()); return 1; } }
   BedPacker packer_text(src, opt), packer_packed(packed, opt);
   BedPacker &packer = packed ? packer_packed : packer_text;
+  if (opt.sam && src && file) {                              // the '@' header is skipped (its lines counted): a first look counts them
+    long h = 0;
+    LineSource *peek = LineSource::Open(file, &err);
+    for (char *l = peek ? peek->Next() : NULL; l && l[0] == '@'; l = peek->Next()) h++;
+    delete peek;
+    for (long k = 0; k < h; k++) src->Next();
+  }
   PackedBatch b; PackError e; int64_t lines = 0;
   for (;;) {
     bool more = packer.NextBatch(&b, batch, &e);
@@ -151,6 +190,11 @@ int main(int argc, char **argv)
       else printf("%d %d %d %d\n", b.tri[i], b.tri[i + 1], b.tri[i + 2], b.w[i / 3]);
     }
     for (size_t i = 0; i + 2 < b.zero_len.size(); i += 3) printf("# zero %d %d %d\n", b.zero_len[i], b.zero_len[i + 1], b.zero_len[i + 2]);
+    for (size_t i = 0, at = 0; i < b.m_cnt.size(); i++) {
+      printf("# blocks %d %d %d %d", b.m_tri[3 * i], b.m_tri[3 * i + 1], b.m_tri[3 * i + 2], b.m_cnt[i]);
+      for (int k = 0; k < 2 * b.m_cnt[i]; k++) printf(" %d", b.m_blocks[at++]);
+      printf("\n");
+    }
     lines += b.n_lines;
     if (!more) break;
   }

@@ -1,4 +1,4 @@
-// gtx_text.hip -- BED text to packed triples ON THE DEVICE (gtx_count_add_text / gtx_coverage_add_text of include/gtx.h).
+// gtx_text.hip -- BED or SAM text to packed triples ON THE DEVICE (gtx_count_add_text / gtx_coverage_add_text of include/gtx.h).
 //
 // What the reference does per query line (GenomicRegionBED::Read, gtools/genomic_intervals.cpp:2157-2182; tokenizer
 // core.cpp:577-625; FileBufferText::Next core.cpp:241-259): cut the line at tabs, atol() two columns, look the chromosome up,
@@ -18,6 +18,11 @@
 //                       all (every class set to -1) and reported: the host packer redoes that block and produces the reference's
 //                       result or error message with its line number.  The device path never decides an error, it only recognises
 //                       the plain case.
+// SAM (GTX_TEXT_SAM, GenomicRegionSAM::Read :2771-2812): the same passes; the parse block reads RNAME, FLAG's strand bit, POS and the
+// CIGAR's reference length of each alignment (parse_sam_line) and stages up to 72 KiB of text for its 128 lines (kLdsSam) -- a block
+// whose 128 lines are longer than that on average goes to the host packer, as do spliced reads (N), '=' in a CIGAR, a SEQ of another
+// length than the CIGAR's fragment and everything else outside parse_sam_line's plain case.  The 11th and later columns are read only
+// as far as the newline pass reads every byte.
 // The counting kernels then run on the triples where they are.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -36,6 +41,8 @@ typedef unsigned long long u64;
 static constexpr int kSeg = 1024;                  // bytes per newline-count segment (one wave: 64 lanes x 16 bytes)
 static constexpr int kLines = 128;                 // lines per parse block
 static constexpr int kLdsText = 40 * 1024;         // bytes of text a parse block stages (lines of 320 bytes on average fit)
+static constexpr int kLdsSam = 72 * 1024;          // ... of SAM text (GTX_TEXT_SAM): lines of ~570 bytes on average fit -- a 150 bp read with
+                                                   // its QUAL and a few tags is 400-500 -- and two parse blocks still share a CU's 160 KiB
 
 __device__ __forceinline__ unsigned nl_mask16(const uint4 v)
 {
@@ -168,9 +175,100 @@ __device__ __forceinline__ bool parse_line(PTR s, unsigned b, unsigned e, bool w
   return true;
 }
 
+// one SAM alignment (GenomicRegionSAM::Read, genomic_intervals.cpp:2771-2812) in the plain case: 11 or more TAB-separated tokens, the
+// first ten non-empty and without a blank, '\r' or NUL, QUAL non-empty, no '\r' at the end of the line; FLAG and POS 1-10 decimal digits;
+// CIGAR "*" or operations of 1-9 digits each from M I D S H P X - (no N: a spliced read is the host's, no '=': the reference refuses it);
+// SEQ "*" or as long as the CIGAR's fragment (M I S X).  Out: the RNAME token [nameOff, nameOff + nameLen), strand ('-' iff FLAG & 0x10),
+// start = POS, stop = POS + reference length (M D X) - 1, reference length > 0; QNAME's atol value when wantLabel.
+template <class PTR>
+__device__ __forceinline__ bool parse_sam_line(PTR s, unsigned b, unsigned e, bool wantLabel, unsigned &nameOff, unsigned &nameLen,
+                                               long long &S, long long &E, int &strand, long long &label)
+{
+  unsigned p = b;
+  auto token = [&]() -> bool {                                     // one of tokens 1-10: [p, tab); p ends on the tab
+    const unsigned q = p;
+    for (; p < e; p++) {
+      const unsigned char c = s[p];
+      if (c == '\t') break;
+      if (c == ' ' || c == '\r' || c == 0) return false;
+    }
+    return p < e && p > q;
+  };
+  auto number = [&](u64 &out) -> bool {                            // 1-10 digits, then the tab
+    const unsigned q = p; u64 v = 0;
+    while (p < e && (unsigned)(s[p] - '0') < 10u) { v = v * 10 + (unsigned)(s[p] - '0'); p++; }
+    if (p == q || p - q > 10 || p >= e || s[p] != '\t') return false;
+    out = v;
+    return true;
+  };
+  const unsigned qb = p;
+  if (!token()) return false;                                      // QNAME
+  label = 0;
+  if (wantLabel) {                                                 // atol (the BED path's column 4 rules)
+    unsigned r = qb; bool neg = false;
+    if ((unsigned char)s[r] <= ' ') return false;                  // (atol would skip it)
+    if (s[r] == '-') { neg = true; r++; } else if (s[r] == '+') r++;
+    u64 v = 0; unsigned nd = 0;
+    while (r < p && (unsigned)(s[r] - '0') < 10u) { v = v * 10 + (unsigned)(s[r] - '0'); r++; if (++nd > 18) return false; }
+    label = neg ? -(long long)v : (long long)v;
+  }
+  p++;
+  u64 flag, pos;
+  if (!number(flag)) return false;                                 // FLAG
+  strand = (flag & 0x10) ? '-' : '+';
+  p++;
+  nameOff = p;
+  if (!token()) return false;                                      // RNAME
+  nameLen = p - nameOff;
+  p++;
+  if (!number(pos)) return false;                                  // POS
+  p++;
+  if (!token()) return false;                                      // MAPQ
+  p++;
+  // CIGAR
+  bool star = false; long long ref = 0, frag = 0;
+  if (p + 1 < e && s[p] == '*' && s[p + 1] == '\t') { star = true; p++; }
+  else {
+    const unsigned q = p;
+    while (p < e && s[p] != '\t') {
+      const unsigned d = p; long long v = 0;
+      while (p < e && (unsigned)(s[p] - '0') < 10u) { v = v * 10 + (s[p] - '0'); p++; }
+      if (p == d || p - d > 9 || p >= e) return false;
+      const unsigned char op = s[p++];
+      if (op == 'M' || op == 'X') { ref += v; frag += v; }
+      else if (op == 'D') ref += v;
+      else if (op == 'I' || op == 'S') frag += v;
+      else if (op != 'H' && op != 'P' && op != '-') return false;  // N (spliced: several intervals), '=' (refused), anything else
+    }
+    if (p == q || p >= e) return false;
+  }
+  p++;
+  if (!token()) return false;                                      // RNEXT
+  p++;
+  if (!token()) return false;                                      // PNEXT
+  p++;
+  if (!token()) return false;                                      // TLEN
+  p++;
+  const unsigned sb = p;
+  if (!token()) return false;                                      // SEQ
+  const long long seqLen = p - sb;
+  const bool seqStar = seqLen == 1 && s[sb] == '*';
+  p++;
+  if (p >= e) return false;                                        // QUAL: present and non-empty, no blank in front
+  { const unsigned char c = s[p]; if (c == '\t' || c == ' ' || c == '\r') return false; }
+  if (s[e - 1] == '\r') return false;                              // CRLF
+  if (star) ref = seqLen;                                          // "*" reads as "<strlen(SEQ)>M" (1M for SEQ "*")
+  else if (!seqStar && seqLen != frag) return false;               // the reference's error
+  if (ref <= 0) return false;                                      // no interval: the host's error
+  S = (long long)pos; E = (long long)pos + ref - 1;
+  return true;
+}
+
+template <bool SAM>
 __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
 {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[kLdsText];
+  constexpr int kStage = SAM ? kLdsSam : kLdsText;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[kStage];
   __shared__ int tooLong;
   __shared__ unsigned long long sumLabels;
   if (threadIdx.x == 0) sumLabels = 0;
@@ -181,7 +279,7 @@ __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
   if (a.segTotal[0] != a.nLines) { if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.flag, 4); return; }
   // text of the block's lines: [t0, t1) (the newline of the last line included)
   const size_t t0 = j0 ? (size_t)a.nl[j0 - 1] + 1 : 0, t1 = (size_t)a.nl[j1 - 1] + 1;
-  if (threadIdx.x == 0) tooLong = (t1 - t0 > (size_t)kLdsText - 32) ? 1 : 0;
+  if (threadIdx.x == 0) tooLong = (t1 - t0 > (size_t)kStage - 32) ? 1 : 0;
   __syncthreads();
   if (tooLong) { if (threadIdx.x == 0) atomicOr(a.flag, 2); return; }
   const size_t a0 = t0 & ~(size_t)15;                             // staged from the 16-byte line below t0: lds[k] = text[a0 + k]
@@ -191,80 +289,101 @@ __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
   }
   __syncthreads();
   const unsigned j = j0 + threadIdx.x;
-  if (j >= j1) { if (a.blockSum) __syncthreads(); return; }       // (the barrier of the label sum below)
-  const unsigned b = (unsigned)((j ? (size_t)a.nl[j - 1] + 1 : 0) - a0), e = (unsigned)((size_t)a.nl[j] - a0);
-  long long v2, v3, label; int nTok, strand; unsigned tokLen;
-  bool plain = parse_line((const unsigned char *)lds, b, e, a.weighted != 0, v2, v3, nTok, tokLen, strand, label);
+  // (no early return for the threads behind the last line: a barrier inside a branch that splits a wave is passed twice by that
+  // wave, and the label sum of its live lanes was read before they had added to it)
+  const bool live = j < j1;
+  bool plain = false;
   int cls = -1, start = 0, stop = 0, wv = 1;
   long long lineLabel = 0;                                        // GetLabelValue of the line (genomic_intervals.cpp:1081-1085), whatever becomes of it
-  if (plain) {
-    lineLabel = 1;
-    if (a.weighted) { const long long lv = nTok >= 4 ? label : 0; lineLabel = lv < a.maxLabel ? lv : a.maxLabel; }
-    const long long S = v2 + 1, E = v3;                           // BED: start = atol(col2) + 1, stop = atol(col3)
-    if (S >= INT_MAX - 1 || E >= INT_MAX - 1) plain = false;
-    // the order check of the sorted merge (NextQuery :5889-5898 via IsBefore :396-401): key (chromosome, [strand,] start) against the line before
-    if (plain && a.sortedRules) {
-      bool before = false, havePrev = true;
-      const unsigned char *pn; unsigned pl; int ps; long long pstart;
-      long long q2 = 0, q3 = 0, ql = 0; int qn = 0, qs = '+'; unsigned qlen = 0;
-      if (j > j0) {
-        const unsigned pb = (unsigned)((j - 1 ? (size_t)a.nl[j - 2] + 1 : 0) - a0), pe = (unsigned)((size_t)a.nl[j - 1] - a0);
-        if (!parse_line((const unsigned char *)lds, pb, pe, false, q2, q3, qn, qlen, qs, ql)) havePrev = false;   // (that line voids the block anyway)
-        pn = lds + pb; pl = qlen; ps = qs; pstart = q2 + 1;
-      } else if (j > 0) {
-        const size_t pb = j - 1 ? (size_t)a.nl[j - 2] + 1 : 0, pe = a.nl[j - 1];
-        const unsigned char *g = (const unsigned char *)a.text + pb;
-        // (a line the parser refuses voids the block from its own thread; one that is merely too long to look at here leaves the
-        // order of this line undecided -- not a plain case: the host packer takes the block)
-        if (pe - pb > 4096) { havePrev = false; plain = false; }
-        else if (!parse_line(g, 0u, (unsigned)(pe - pb), false, q2, q3, qn, qlen, qs, ql)) havePrev = false;
-        pn = g; pl = qlen; ps = qs; pstart = q2 + 1;
-      } else {
-        havePrev = a.havePrev != 0;
-        if (a.prevLost) plain = false;                            // the seam's key is not here to compare with: the host packer's block
-        pn = (const unsigned char *)a.names + a.prevNameOff; pl = a.prevNameLen; ps = a.prevStrand; pstart = a.prevStart;
-      }
-      if (havePrev) {
-        int d = 0;
-        const unsigned n = tokLen < pl ? tokLen : pl;
-        for (unsigned k = 0; k < n && d == 0; k++) d = (int)lds[b + k] - (int)pn[k];     // strcmp
-        if (d == 0) d = (int)tokLen - (int)pl;
-        if (d != 0) before = d < 0;
-        else if (a.byStrand && strand != ps) before = strand < ps;
-        else before = S < pstart;
-      }
-      if (before) plain = false;                                  // "query regions are not sorted": the host says so, with the line number
+  if (live) {
+    const unsigned b = (unsigned)((j ? (size_t)a.nl[j - 1] + 1 : 0) - a0), e = (unsigned)((size_t)a.nl[j] - a0);
+    long long S = 0, E = 0, label = 0; int strand = '+'; unsigned nameOff = b, tokLen = 0; bool hasLabel = true;
+    plain = false;
+    if (SAM) plain = parse_sam_line((const unsigned char *)lds, b, e, a.weighted != 0, nameOff, tokLen, S, E, strand, label);
+    else {
+      long long v2 = 0, v3 = 0; int nTok = 0;
+      plain = parse_line((const unsigned char *)lds, b, e, a.weighted != 0, v2, v3, nTok, tokLen, strand, label);
+      S = v2 + 1; E = v3;                                           // BED: start = atol(col2) + 1, stop = atol(col3)
+      hasLabel = plain && nTok >= 4;
     }
     if (plain) {
-      // chromosome -> class through the hash table of the index set's names (unknown: the line is dropped, :5719-5720)
-      const unsigned h = fnv1a(lds + b, tokLen);
-      int id = -1;
-      for (unsigned q = h & a.tableMask;; q = (q + 1) & a.tableMask) {
-        const ChromEntry en = a.table[q];
-        if (en.id < 0) break;
-        if (en.hash == h && en.len == tokLen) {
-          bool same = true;
-          for (unsigned k = 0; k < tokLen && same; k++) same = (unsigned char)a.names[en.off + k] == lds[b + k];
-          if (same) { id = en.id; break; }
+      lineLabel = 1;
+      if (a.weighted) { const long long lv = hasLabel ? label : 0; lineLabel = lv < a.maxLabel ? lv : a.maxLabel; }
+      if (S >= INT_MAX - 1 || E >= INT_MAX - 1) plain = false;
+      // the order check of the sorted merge (NextQuery :5889-5898 via IsBefore :396-401): key (chromosome, [strand,] start) against the line before
+      if (plain && a.sortedRules) {
+        bool before = false, havePrev = true;
+        const unsigned char *pn; unsigned pl; int ps; long long pstart;
+        // the key of the line before: (name at q0, qlen), strand qs, start qS
+        auto key_of = [&](auto src, unsigned pb, unsigned pe, unsigned &q0, unsigned &qlen, int &qs, long long &qS) -> bool {
+          long long q2 = 0, q3 = 0, ql = 0; int qn = 0;
+          q0 = pb; qs = '+';
+          if (SAM) return parse_sam_line(src, pb, pe, false, q0, qlen, qS, q3, qs, ql);
+          const bool ok = parse_line(src, pb, pe, false, q2, q3, qn, qlen, qs, ql);
+          qS = q2 + 1;
+          return ok;
+        };
+        unsigned q0 = 0, qlen = 0; int qs = '+'; long long qS = 0;
+        if (j > j0) {
+          const unsigned pb = (unsigned)((j - 1 ? (size_t)a.nl[j - 2] + 1 : 0) - a0), pe = (unsigned)((size_t)a.nl[j - 1] - a0);
+          if (!key_of((const unsigned char *)lds, pb, pe, q0, qlen, qs, qS)) havePrev = false;   // (that line voids the block anyway)
+          pn = lds + q0; pl = qlen; ps = qs; pstart = qS;
+        } else if (j > 0) {
+          const size_t pb = j - 1 ? (size_t)a.nl[j - 2] + 1 : 0, pe = a.nl[j - 1];
+          const unsigned char *g = (const unsigned char *)a.text + pb;
+          // (a line the parser refuses voids the block from its own thread; one that is merely too long to look at here leaves the
+          // order of this line undecided -- not a plain case: the host packer takes the block)
+          if (pe - pb > 4096) { havePrev = false; plain = false; }
+          else if (!key_of(g, 0u, (unsigned)(pe - pb), q0, qlen, qs, qS)) havePrev = false;
+          pn = g + q0; pl = qlen; ps = qs; pstart = qS;
+        } else {
+          havePrev = a.havePrev != 0;
+          if (a.prevLost) plain = false;                            // the seam's key is not here to compare with: the host packer's block
+          pn = (const unsigned char *)a.names + a.prevNameOff; pl = a.prevNameLen; ps = a.prevStrand; pstart = a.prevStart;
         }
+        if (havePrev) {
+          int d = 0;
+          const unsigned n = tokLen < pl ? tokLen : pl;
+          for (unsigned k = 0; k < n && d == 0; k++) d = (int)lds[nameOff + k] - (int)pn[k];     // strcmp
+          if (d == 0) d = (int)tokLen - (int)pl;
+          if (d != 0) before = d < 0;
+          else if (a.byStrand && strand != ps) before = strand < ps;
+          else before = S < pstart;
+        }
+        if (before) plain = false;                                  // "query regions are not sorted": the host says so, with the line number
       }
-      if (a.scanRules == 1 && (S > E || E <= 0)) id = -1;         // the unsorted scanner skips such an interval before it looks at the chromosome (:5039)
-      if (id >= 0) {
-        if (!a.scanRules && !a.sortedRules && (E <= 0 || S > E)) plain = false;   // the unsorted algorithm's errors (:5740-5741): the host reports them
-        else {
-          cls = id + ((a.strandAware && strand == '-') ? a.nChrom : 0);
-          start = (int)S; stop = (int)E;
-          if (a.weighted) { const long long lv = nTok >= 4 ? label : 0; wv = (int)(lv < a.maxLabel ? lv : a.maxLabel); }
+      if (plain) {
+        // chromosome -> class through the hash table of the index set's names (unknown: the line is dropped, :5719-5720)
+        const unsigned h = fnv1a(lds + nameOff, tokLen);
+        int id = -1;
+        for (unsigned q = h & a.tableMask;; q = (q + 1) & a.tableMask) {
+          const ChromEntry en = a.table[q];
+          if (en.id < 0) break;
+          if (en.hash == h && en.len == tokLen) {
+            bool same = true;
+            for (unsigned k = 0; k < tokLen && same; k++) same = (unsigned char)a.names[en.off + k] == lds[nameOff + k];
+            if (same) { id = en.id; break; }
+          }
+        }
+        if (a.scanRules == 1 && (S > E || E <= 0)) id = -1;         // the unsorted scanner skips such an interval before it looks at the chromosome (:5039)
+        if (id >= 0) {
+          if (!a.scanRules && !a.sortedRules && (E <= 0 || S > E)) plain = false;   // the unsorted algorithm's errors (:5740-5741): the host reports them
+          else {
+            cls = id + ((a.strandAware && strand == '-') ? a.nChrom : 0);
+            start = (int)S; stop = (int)E;
+            if (a.weighted) { const long long lv = hasLabel ? label : 0; wv = (int)(lv < a.maxLabel ? lv : a.maxLabel); }
+          }
         }
       }
     }
   }
-  if (!plain) atomicOr(a.flag, 1);
+  if (live && !plain) atomicOr(a.flag, 1);
   if (a.blockSum) {
     if (plain && lineLabel != 0) atomicAdd(&sumLabels, (unsigned long long)lineLabel);
     __syncthreads();
     if (threadIdx.x == 0 && sumLabels != 0) atomicAdd(a.blockSum, sumLabels);
   }
+  if (!live) return;
   a.tri[3 * (size_t)j] = cls; a.tri[3 * (size_t)j + 1] = start; a.tri[3 * (size_t)j + 2] = stop;
   if (a.weighted) a.w[j] = wv;
   if (a.blkMinus && cls >= a.nChrom) atomicAdd(&a.blkMinus[blockIdx.x], 1u);
@@ -307,7 +426,7 @@ __global__ __launch_bounds__(256) void text_void_kernel(int *__restrict__ tri, u
   for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nLines; j += (size_t)gridDim.x * 256) tri[3 * j] = -1;
 }
 
-hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules)
+hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules, bool sam)
 {
   const unsigned nSeg = (unsigned)((bytes + kSeg - 1) / kSeg);
   nl_count_kernel<<<nSeg, 64, 0, st>>>(d.text, bytes, d.segCount);
@@ -328,7 +447,8 @@ hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_t
     hipError_t e = hipMemsetAsync(d.blkMinus, 0, sizeof(unsigned) * ((size_t)nBlocks + 1), st);
     if (e != hipSuccess) return e;
   }
-  text_parse_kernel<<<nBlocks, kLines, 0, st>>>(a);
+  if (sam) text_parse_kernel<true><<<nBlocks, kLines, 0, st>>>(a);
+  else text_parse_kernel<false><<<nBlocks, kLines, 0, st>>>(a);
   text_void_kernel<<<256, 256, 0, st>>>(d.tri, nLines, d.flag, d.labelSum ? d.blockSum : nullptr, d.labelSum);
   if (a.blkMinus) {
     nl_scan_kernel<<<1, 1024, 0, st>>>(d.blkMinus, nBlocks);

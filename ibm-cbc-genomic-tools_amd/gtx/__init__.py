@@ -21,6 +21,7 @@ JOIN_GAPS = 32
 OFFSET_SKIP_REF_GAPS = 64
 OFFSET_FROM_QUERY = 128
 SIGNAL_PER_REF = 256
+TEXT_SAM = 512            # gtx_*_add_text: the block is SAM alignments, not BED
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
@@ -315,6 +316,23 @@ class Engine:
         self._chk(self.lib.gtx_count_end(self.ctx, _ptr(hits), ctypes.byref(info)))
         return hits[:self.n_refs], info.as_dict()
 
+    def count_text(self, blocks, rules, flags=READS_SORTED, sam=False):
+        """gtx_count_begin / gtx_count_add_text per block of text (bytes of complete lines) / gtx_count_end; sam=True: SAM alignments
+        (GTX_TEXT_SAM).  Returns (hits, info, needs_host verdict per block) -- a block that comes back was not counted."""
+        self._chk(self.lib.gtx_count_begin(self.ctx))
+        verdicts = []
+        for text in blocks:
+            t = ctypes.c_int(-1)
+            self._chk(self.lib.gtx_count_add_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(rules),
+                                                  int(flags) | (TEXT_SAM if sam else 0), ctypes.byref(t)))
+            redo = ctypes.c_int(0)
+            self._chk(self.lib.gtx_text_result(self.ctx, t.value, ctypes.byref(redo)))
+            verdicts.append(redo.value)
+        hits = np.zeros(max(self.n_refs, 1), dtype=np.uint64)
+        info = CountInfo()
+        self._chk(self.lib.gtx_count_end(self.ctx, _ptr(hits), ctypes.byref(info)))
+        return hits[:self.n_refs], info.as_dict(), verdicts
+
     def count(self, reads, weights=None, flags=READS_SORTED):
         reads = _triples(reads)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32)
@@ -495,10 +513,10 @@ class Engine:
                                     preprocess.encode()[0:1], int(flags), _ptr(out), _ptr(off)))
         return out[:tot], off
 
-    def scan_stream(self, pieces, class_len, win_step, win_size, preprocess="1", weighted=False, flags=0):
+    def scan_stream(self, pieces, class_len, win_step, win_size, preprocess="1", weighted=False, flags=0, sam=False):
         """gtx_scan_begin .. gtx_scan_end over `pieces`: (reads, weights | None, flags) tuples for packed host batches, or (text bytes,
-        TextRules, flags) for blocks of BED text tokenised on the device.  Returns (windows, class offsets, label sum of the text blocks
-        the device took, tickets' needs_host verdicts)."""
+        TextRules, flags) for blocks of BED text tokenised on the device (sam=True: SAM alignments, GTX_TEXT_SAM).  Returns (windows,
+        class offsets, label sum of the text blocks the device took, tickets' needs_host verdicts)."""
         cl = np.ascontiguousarray(class_len, dtype=np.int32)
         off, tot = scan_layout(cl, win_step, win_size)
         out = np.zeros(max(tot, 1), dtype=np.uint64)
@@ -507,7 +525,7 @@ class Engine:
         for a, b, fl in pieces:
             if isinstance(a, (bytes, bytearray)):
                 t = ctypes.c_int(-1)
-                self._chk(self.lib.gtx_scan_add_text(self.ctx, a, len(a), a.count(b"\n"), ctypes.byref(b), int(fl), ctypes.byref(t)))
+                self._chk(self.lib.gtx_scan_add_text(self.ctx, a, len(a), a.count(b"\n"), ctypes.byref(b), int(fl) | (TEXT_SAM if sam else 0), ctypes.byref(t)))
                 redo = ctypes.c_int(0)
                 self._chk(self.lib.gtx_text_result(self.ctx, t.value, ctypes.byref(redo)))
                 verdicts.append(redo.value)

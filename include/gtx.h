@@ -476,8 +476,16 @@ typedef struct gtx_text_rules {
   int64_t max_label_value;
   int32_t have_prev; const char *prev_chrom; int32_t prev_strand /* '+' | '-' */; int64_t prev_start;
 } gtx_text_rules;
+/* GTX_TEXT_SAM in the flags of gtx_count_add_text, gtx_coverage_add_text, gtx_scan_add_text and gtx_group_*_add_text: the block is
+ * SAM alignments (GenomicRegionSAM::Read genomic_intervals.cpp:2771-2812) without the '@' header, not BED.  The plain case: 11 or more
+ * TAB-separated columns, the first ten non-empty and without blanks or '\r', no '\r' at the end of the line; FLAG and POS decimal;
+ * CIGAR "*" or operations of 1-9 digits from M I D S H P X - (no N, no =); SEQ "*" or as long as the CIGAR's M I S X; a reference
+ * length (M D X) > 0.  A read becomes (class of RNAME [+ n_chrom when strand_aware and FLAG & 0x10], POS, POS + reference length - 1)
+ * with QNAME's atol value as its label; order check and validity rules as for BED.  Spliced reads, '=' and every other line go back
+ * to the caller (needs_host), as do blocks whose 128-line groups average more than ~570 bytes a line.  gtx_text_rules is the same. */
+#define GTX_TEXT_SAM       512u
 /* text: host memory (page-locked memory is read by the DMA engine directly and must stay untouched until gtx_text_result of the
- * ticket has returned).  flags as gtx_count_add / gtx_coverage_add.  Up to two blocks are in flight: the call waits for the block
+ * ticket has returned).  flags as gtx_count_add / gtx_coverage_add, and GTX_TEXT_SAM.  Up to two blocks are in flight: the call waits for the block
  * before last. */
 int gtx_count_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
 int gtx_coverage_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
