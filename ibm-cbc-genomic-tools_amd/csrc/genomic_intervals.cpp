@@ -1897,10 +1897,13 @@ struct JoinIndex {
   bool multi = false;                                                   // some region has more than one interval
   std::set<std::string> valid_chrom;                                    // chromosomes the bin index has (a valid region on them)
   gtx_ctx *ctx = NULL;
+  bool strand_major = false;                                            // classes as the device-side tokenizer numbers them: rank, + chromosomes on '-' (set before BuildJoinIndex)
   int ClassOf(const GenomicInterval *i) const
   {
     std::map<std::string, int>::const_iterator it = cid.find(i->CHROMOSOME);
-    return it == cid.end() ? -1 : it->second * (ignore_strand ? 1 : 2) + (ignore_strand ? 0 : (i->STRAND == '-'));
+    if (it == cid.end()) return -1;
+    if (ignore_strand) return it->second;
+    return strand_major ? it->second + (i->STRAND == '-' ? (int)cid.size() : 0) : it->second * 2 + (i->STRAND == '-');
   }
   void Chk(int rc) const { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(ctx)); exit(1); } }
 };
@@ -2041,14 +2044,22 @@ void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char
   ix.Chk(gtx_set_ref_order(ix.ctx, ix.sorted ? NULL : key.data()));
 }
 
+// What the caller's operation does with the merge per query, and when its loop ends.  overlap, intersect, offset and the signal
+// bins walk every match and stop at Done(); subset (gtools/genomic_overlaps.cpp:794-795) calls GetOverlap once -- which erases from
+// the merge's buffer only what lies in front of the first accepted match (:5903-5918), and Done() looks at that buffer (:5934-5937)
+// -- and with -inv goes on while there is a query.
+struct LoopWalk { bool single = false, match_gaps = false, ignore_strand = false, past_done = false; };
+
 // the reference's query loop on the overlaps object: errors, the merge's buffer and Done() (its early stop) come from the class
-// layer; add(q) takes every query in order.  Returns with err set when the loop stopped at an error.
-void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &err, const std::function<void(GenomicRegion *)> &add)
+// layer, on which the caller's walk is replayed; add(q) takes every query in order.  Returns with err set when the loop stopped at
+// an error.
+void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &err, const std::function<void(GenomicRegion *)> &add,
+                  const LoopWalk &walk = LoopWalk())
 {
   tls_load_error = &err;
   try {
     bool index_checked = ix.sorted;
-    for (GenomicRegion *q = ov->GetQuery(); ov->Done() == false; q = ov->NextQuery()) {
+    for (GenomicRegion *q = ov->GetQuery(); walk.past_done ? q != NULL : ov->Done() == false; q = ov->NextQuery()) {
       if (!index_checked) {                                               // the bin index is built at the first query's match (:5603-5616)
         for (long int k = 0; k < ix.M; k++)
           if (!ix.IS->R[k]->IsCompatibleSortedAndNonoverlapping()) ix.IS->R[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
@@ -2056,7 +2067,10 @@ void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &
       }
       GenomicInterval *f = q->I.front();
       const long int s = f->START, e = q->I.back()->STOP;
-      if (ix.sorted) { for (GenomicRegion *r = ov->GetMatch(); r; r = ov->NextMatch()) {} }   // the merge's buffer as the reference's walk leaves it
+      if (ix.sorted) {                                                    // the merge's buffer as the reference's walk leaves it
+        if (walk.single) ov->GetOverlap(walk.match_gaps, walk.ignore_strand);
+        else for (GenomicRegion *r = ov->GetMatch(); r; r = ov->NextMatch()) {}
+      }
       else if (ix.valid_chrom.count(f->CHROMOSOME)) {                    // :5740-5741, on chromosomes the index knows
         if (e <= 0) q->PrintError("stop position must be positive!");
         if (s > e) q->PrintError("start position cannot be greater than stop position!");
@@ -2138,6 +2152,180 @@ void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps
   });
   flush();                                                                // the pairs before an error are printed, then the error
   ExitOnLoadError(err);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// genomic_subset: hits per query from the device (gtx_query_hits), or the file's text selected there (gtx_subset_text)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+// May the test set's text go to the device as it is?  A streamed, uncompressed BED file (32 MB or more, or GTX_TEXT_ON_DEVICE=1;
+// never with GTX_TEXT_ON_DEVICE=0) on one GPU, over an index set in which the loop could find no error of its own: every region
+// compatible, sorted and non-overlapping, and under the merge the set in order.
+bool SubsetTextUsable(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, bool by_strand)
+{
+  static const char *e = getenv("GTX_TEXT_ON_DEVICE");
+  GenomicRegionSet *QS = ov->QuerySet;
+  if ((e && atoi(e) == 0) || QS->load_in_memory || QS->format != "BED" || QS->file == NULL || QS->from_stdin) return false;
+  const long left = QS->StreamBytesLeft();
+  if (left < ((e && atoi(e) == 1) ? 1 : (32l << 20))) return false;                    // (-1: stdin, .gz)
+  if (gtx_group_size(Devices()) != 1) return false;
+  if (g_pool_future.valid()) g_pool_future.get();
+  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
+  for (long int k = 0; k < ix.M; k++) {
+    if (!ix.IS->R[k]->IsCompatibleSortedAndNonoverlapping()) return false;
+    if (ix.sorted && k > 0 && ix.IS->R[k]->IsBefore(ix.IS->R[k - 1], by_strand)) return false;
+  }
+  return true;
+}
+
+// The test set's file block by block through gtx_subset_text, the selected text to stdout in block order.  Returns 0 when the
+// whole file went that way, else the file line of the first block that came back: what the loop has to do from there on.
+long int SubsetText(GenomicRegionSet *QS, const JoinIndex &ix, bool by_strand, uint32_t flags)
+{
+  gtx_ctx *ctx = ix.ctx;
+  std::string first; long int first_no = 0;
+  LineSource *src = QS->DetachStream(&first, &first_no);
+  if (first_no <= 0) return 0;                                             // no region in the file
+  ChromTable chroms;
+  for (const auto &c : ix.cid) chroms.Add(c.first.c_str());
+  chroms.Freeze();
+  std::vector<const char *> names((size_t)chroms.size());
+  for (int i = 0; i < chroms.size(); i++) names[i] = chroms.name(i).c_str();
+  PackOptions opt;
+  opt.mode = ix.sorted ? gtxhost::PACK_OVERLAPS_SORTED : gtxhost::PACK_OVERLAPS_UNSORTED;
+  opt.chroms = &chroms; opt.strand_aware = !ix.ignore_strand; opt.sorted_by_strand = by_strand;
+  gtx_text_rules rules;
+  rules.chrom_names = names.empty() ? NULL : names.data(); rules.n_chrom = chroms.size();
+  rules.strand_aware = opt.strand_aware; rules.sorted_rules = ix.sorted; rules.sorted_by_strand = by_strand; rules.max_label_value = 1;
+  BedPacker packer(src, opt);
+  // the line the set's constructor has read for its format check: packed here for what it says to the block behind it (the seam's
+  // key; an error of its own is the loop's to report), and a block of one line for the device
+  long int takeover = 0, takeover_block = 0, on_device = 0, n_blocks = 0, block_no[2] = {1, 1};
+  auto report = [&]() {
+    if (!getenv("GTX_TEXT_TRACE")) return;
+    if (takeover) fprintf(stderr, "[gtx subset] blocks selected on the device: %ld, the loop took over at block %ld (line %ld)\n", on_device, takeover_block, takeover);
+    else fprintf(stderr, "[gtx subset] blocks selected on the device: %ld, none came back\n", on_device);
+  };
+  packer.Prime(first, first_no);
+  {
+    PackedBatch batch; PackError err;
+    packer.PackPrimedText(&batch, &err);
+    if (err.set) { takeover = first_no; takeover_block = 1; report(); return takeover; }
+  }
+  g_pool.used[0] = g_pool.used[1] = true;                                  // (the buffers hold text now)
+  packer.UseTextBuffers((char *)g_pool.buf[0], (char *)g_pool.buf[1], kPoolBytes);
+  first += '\n';
+  BedPacker::TextBlock blk[2]; int ticket[2] = {-1, -1};
+  char *out = NULL; size_t out_cap = 0;
+  auto settle = [&](int k) {                                               // the verdict on the block in blk[k]; what it selected goes out
+    if (ticket[k] < 0) return;
+    if (blk[k].bytes > out_cap) {
+      if (out) gtx_host_free(ctx, out);
+      out_cap = blk[k].bytes + (blk[k].bytes >> 3);
+      out = (char *)gtx_host_alloc(ctx, out_cap);
+      if (!out) ix.Chk(GTX_E_HIP);
+    }
+    int redo = 0; size_t got = 0;
+    ix.Chk(gtx_subset_result(ctx, ticket[k], &redo, out, &got, NULL));
+    ticket[k] = -1;
+    if (takeover) return;                                                  // (a block behind the one that came back: the loop's)
+    if (redo) { takeover = blk[k].first_line; takeover_block = block_no[k]; return; }
+    if (blk[k].text != first.data()) on_device++;
+    if (got) fwrite(out, 1, got, stdout);
+  };
+  auto add = [&](int k) {
+    const BedPacker::TextBlock &b = blk[k];
+    rules.have_prev = b.have_prev; rules.prev_chrom = b.prev_chrom.c_str(); rules.prev_strand = b.prev_strand; rules.prev_start = b.prev_start;
+    ix.Chk(gtx_subset_text(ctx, b.text, b.bytes, b.n_lines, &rules, flags, &ticket[k]));
+  };
+  blk[0].text = &first[0]; blk[0].bytes = first.size(); blk[0].first_line = first_no; blk[0].n_lines = 1; blk[0].have_prev = false;
+  add(0);
+  int cur = 1;
+  for (;; cur ^= 1) {
+    settle(cur);                                                           // (its buffer is about to be read over)
+    if (takeover) break;
+    if (!packer.NextTextBlock(&blk[cur])) break;
+    block_no[cur] = ++n_blocks;
+    if (!blk[cur].seam_ok) {                                               // a block behind a last line that could not be read: no key for the order check at the seam
+      settle(cur ^ 1);
+      if (!takeover) { takeover = blk[cur].first_line; takeover_block = n_blocks; }
+      break;
+    }
+    add(cur);
+  }
+  settle(cur); settle(cur ^ 1);                                            // (the older block first)
+  if (out) gtx_host_free(ctx, out);
+  g_pool.used[0] = g_pool.used[1] = false;
+  report();
+  return takeover;
+}
+}  // namespace
+
+void GtxPrintSubset(GenomicRegionSetOverlaps *ov, bool match_gaps, bool ignore_strand, bool inverse, const char *bin_bits)
+{
+  GenomicRegionSet *IS = ov->IndexSet, *QS = ov->QuerySet;
+  if (!IS->load_in_memory) { fprintf(stderr, "Error: [GtxPrintSubset] the index set must be loaded in memory!\n"); exit(1); }
+  if (QS->format == "GTX") { fprintf(stderr, "Error: subset prints the query lines: a packed region file has no labels, give the BED text!\n"); exit(1); }
+  JoinIndex ix;
+  ix.strand_major = true;
+  BuildJoinIndex(ov, ignore_strand, bin_bits, false, ix);
+  gtx_ctx *ctx = ix.ctx;
+  ix.Chk(gtx_set_ref_blocks(ctx, ix.multi && !match_gaps ? ix.first.data() : NULL, ix.blocks.data()));
+  const uint32_t flags = (ix.sorted ? GTX_ZERO_LENGTH_OK : 0) | (match_gaps ? GTX_JOIN_GAPS : 0);
+  const bool by_strand = ix.sorted && static_cast<SortedGenomicRegionSetOverlaps *>(ov)->sorted_by_strand;
+
+  // ---- the text path: whole blocks selected on the device; the first one that comes back hands the rest of the file to the loop,
+  // which reads the file again from its start -- silently up to that block, so that the merge's cursor, buffer and previous query
+  // are what they would have been -- on a set and an overlaps object of its own
+  long int resume = 0;                                                    // the loop prints the queries from this file line on
+  GenomicRegionSet *again = NULL; GenomicRegionSetOverlaps *again_ov = NULL;
+  if (SubsetTextUsable(ov, ix, by_strand)) {
+    resume = SubsetText(QS, ix, by_strand, flags | (inverse ? GTX_SUBSET_INVERT : 0));
+    if (resume == 0) { fflush(stdout); return; }
+    again = new GenomicRegionSet(QS->file, QS->buffer_size, QS->verbose, false, true);
+    if (ix.sorted) again_ov = new SortedGenomicRegionSetOverlaps(again, IS, by_strand);
+    else again_ov = new UnsortedGenomicRegionSetOverlaps(again, IS, bin_bits);
+    ov = again_ov; QS = again;
+  }
+
+  // ---- the loop: batches of the queries it hands out, their hits from the device, the selected ones printed in order ----
+  std::vector<PairQuery> batch; batch.reserve(4096);
+  QueryBatch qb;
+  std::vector<uint32_t> hits;
+  std::string out;
+  auto flush = [&]() {
+    const int64_t n = qb.Size();
+    if (n == 0) return;
+    hits.resize((size_t)n);
+    ix.Chk(gtx_query_hits(ctx, qb.qtri.data(), qb.First(), qb.qblk.data(), n, flags, hits.data(), NULL));
+    for (int64_t i = 0; i < n; i++) {
+      if ((hits[i] == 0) != inverse) continue;
+      const PairQuery &q = batch[i];
+      PrintBed(out, q, q.iv, q.label, q.score, q.thick_start, q.thick_end);
+      WriteOut(out, 1u << 22);
+    }
+    WriteOut(out);
+    batch.clear(); qb.Clear();
+  };
+
+  LoopWalk walk;
+  walk.single = true; walk.match_gaps = match_gaps; walk.ignore_strand = ignore_strand; walk.past_done = inverse;
+  LoadError err;
+  RunQueryLoop(ov, ix, err, [&](GenomicRegion *q) {
+    if (q->n_line < resume) return;
+    GenomicInterval *f = q->I.front();
+    PairQuery pq;
+    pq.chrom = f->CHROMOSOME; pq.strand = f->STRAND; pq.label = q->LABEL;
+    pq.n_tokens = static_cast<GenomicRegionBED *>(q)->n_tokens;
+    ParseTail(QS->CurrentLine(), pq);
+    for (GenomicInterval *i : q->I) { pq.iv.push_back(i->START); pq.iv.push_back(i->STOP); }
+    qb.Add(ix, q);
+    batch.push_back(std::move(pq));
+    if (batch.size() >= kQueryBatch) flush();
+  }, walk);
+  flush();                                                                // what was selected before an error is printed, then the error
+  ExitOnLoadError(err);
+  delete again_ov; delete again;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -347,6 +347,19 @@ class UnsortedGenomicRegionSetScanner : public GenomicRegionSetScanner
 // streamed BED text set; the index set is loaded in memory.
 void GtxPrintPairs(GenomicRegionSetOverlaps *overlaps, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits);
 
+// genomic_overlaps subset (gtools/genomic_overlaps.cpp:782-800) in bulk: the test regions that overlap some index region, with
+// `inverse` (-inv) those that overlap none, each printed once as GenomicRegionBED::Print does.  Two paths.  The loop, for every
+// input: the reference's loop on the overlaps object -- with `inverse` it runs while there is a query, otherwise until Done(); per
+// query ONE GetOverlap(match_gaps, ignore_strand) is replayed on the class layer, which is what leaves the merge's buffer, and so
+// Done(), as the reference's subset does (:794-795) -- with the hits of every batch of queries from the device (gtx_query_hits).
+// The text path, when the test set is a streamed uncompressed BED file of 32 MB or more (GTX_TEXT_ON_DEVICE=1: of any size, =0:
+// never) on one GPU and the index set is valid and in order: blocks of the file's text through gtx_subset_text, the selected
+// lines written as they come back; the first block that holds a line the device does not take (or a query outside its rank
+// difference) ends that path and the loop does the rest of the file -- it reads the file again from its start, printing nothing
+// before that block, so that the merge is exactly where the reference's would be.  GTX_TEXT_TRACE=1 reports the blocks selected on
+// the device and the block at which the loop took over.  The index set is loaded in memory; bin_bits as for GtxPrintPairs.
+void GtxPrintSubset(GenomicRegionSetOverlaps *overlaps, bool match_gaps, bool ignore_strand, bool inverse, const char *bin_bits);
+
 // genomic_overlaps offset (gtools/genomic_overlaps.cpp:545-670) in bulk, on the overlaps object the driver built: without -S the
 // index set is the reference file and every (reference region, test region) pair prints the test envelope's offsets from the
 // reference region (:595-632), with skip_ref_gaps those of every test interval inside a reference interval, less the gaps

@@ -18,6 +18,7 @@
 #include "gtx_kernels.h"
 #include "gtx_pairs.h"
 #include "gtx_join.h"
+#include "gtx_query.h"
 #include "gtx_offset.h"
 #include "gtx_signal.h"
 #include "gtx_text.h"
@@ -144,6 +145,9 @@ struct TextSlot {
   DevBuf<int> tri2; DevBuf<unsigned> blk; DevBuf<int> w2;      // ... w2 those of the strand-aware outputs
   DevBuf<int> flag; PinBuf<int> hostFlag; PinBuf<char> pin, seam; DevBuf<unsigned long long> sum;
   hipEvent_t evParsed = nullptr, evConsumed = nullptr, evCopied = nullptr; bool busy = false;
+  // gtx_subset_text: the lines' hits, the tiles' kept bytes / lines, the kept text and its
+  // totals on the host; whether the slot holds a subset block whose result has not been fetched
+  DevBuf<unsigned> hits; DevBuf<unsigned long long> tile; DevBuf<char> out; PinBuf<unsigned long long> hostTotal; bool subsetPending = false;
 };
 
 } // namespace
@@ -179,6 +183,7 @@ struct gtx_ctx {
   DevBuf<long long> joinOff, joinPart, joinCut; DevBuf<int> joinPairs, joinScratch; DevBuf<unsigned> joinBig;
   DevBuf<int> joinReads; DevBuf<int2> joinQBlk, joinQIv;
   DevBuf<gtx::JoinInfo> joinInfo;
+  DevBuf<unsigned> hitsOut;             // gtx_query_hits: a batch's hits
   int64_t joinBuffer = 1ll << 26;       // pairs per device chunk of gtx_join (gtx_set_join_buffer)
   DevBuf<long long> offInv, offOut, offCnt, offPart; DevBuf<int8_t> offQStrand;   // the pair offsets' host entry
   DevBuf<gtx::SignalInfo> sigInfo; DevBuf<unsigned long long> sigBins; DevBuf<long long> sigW;   // the signal bins' info block, the host entry's bins and weights
@@ -1388,6 +1393,77 @@ int gtx_join(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32
 } // extern "C"
 
 // ---------------------------------------------------------------------------------------------
+// per-query hits (gtx_query.hip)
+// ---------------------------------------------------------------------------------------------
+
+// d_hits[i] = the pairs of query i, *hi = what the pass observed: the join's count walk, its counts narrowed to 32 bits.  Returns
+// with the work complete.
+static int hits_pass(gtx_ctx *c, const gtx::JoinQueries &q, int mode, unsigned *d_hits, gtx::JoinInfo *hi)
+{
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->joinInfo) HIPCHK(c, c->joinInfo.alloc(1));
+  const gtx::JoinInfo init = {0, 0, INT64_MAX, INT64_MAX, 0};
+  *hi = init;
+  if (q.n == 0) return GTX_OK;
+  HIPCHK(c, hipMemcpyAsync(c->joinInfo.get(), &init, sizeof init, hipMemcpyHostToDevice, c->stream));
+  int rc = join_prepare(c); if (rc) return rc;
+  HIPCHK(c, c->joinOff.grow((size_t)q.n));
+  HIPCHK(c, gtx::launch_join_count(q, c->rx.pairAll.ix, ref_blocks(c), mode, c->joinOff.get(), c->joinInfo.get(), c->stream));
+  HIPCHK(c, gtx::launch_query_narrow(c->joinOff.get(), q.n, d_hits, c->stream));
+  HIPCHK(c, hipMemcpyAsync(hi, c->joinInfo.get(), sizeof *hi, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTX_OK;
+}
+
+extern "C" {
+
+int gtx_query_hits_device(gtx_ctx *c, const void *d_reads, int64_t n, uint32_t flags, void *d_hits, gtx_count_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_query_hits_device: gtx_set_refs has not been called");
+  if (n < 0 || (n > 0 && (!d_reads || !d_hits))) return fail(c, GTX_E_ARG, "gtx_query_hits_device: bad argument");
+  const int mode = join_mode(c, flags);
+  const gtx::JoinQueries q{(const int *)d_reads, nullptr, nullptr, n};
+  gtx::JoinInfo hi;
+  int rc = hits_pass(c, q, mode, (unsigned *)d_hits, &hi); if (rc) return rc;
+  if (info) { memset(info, 0, sizeof *info); info->first_unsorted = -1; info->first_degenerate = -1; join_info_merge(info, hi, 0); }
+  return GTX_OK;
+}
+
+int gtx_query_hits(gtx_ctx *c, const int32_t *reads, const int64_t *first, const int32_t *blocks, int64_t n, uint32_t flags,
+                   uint32_t *hits_out, gtx_count_info *info)
+{
+  const std::string w("gtx_query_hits");
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_query_hits: gtx_set_refs has not been called");
+  if ((n > 0 && !hits_out) || !queries_ok(reads, first, blocks, n)) return fail(c, GTX_E_ARG, "gtx_query_hits: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int mode = join_mode(c, flags);
+  const bool with_blocks = first && !(mode & gtx::JOIN_GAPS);   // (under -gaps the envelopes alone decide)
+  gtx_count_info acc; memset(&acc, 0, sizeof acc); acc.first_unsorted = -1; acc.first_degenerate = -1;
+  const int64_t per = std::max<int64_t>(1, c->batchReads);
+  for (int64_t b0 = 0; b0 < n; b0 += per) {
+    const int64_t b1 = std::min(n, b0 + per), m = b1 - b0;
+    gtx::JoinQueries q{};
+    std::vector<int2> qb, iv;
+    int rc = stage_queries(c, w, reads, first, blocks, b0, b1, with_blocks, qb, iv, q); if (rc) return rc;
+    HIPCHK(c, c->hitsOut.grow((size_t)m));
+    gtx::JoinInfo hi;
+    rc = hits_pass(c, q, mode, c->hitsOut.get(), &hi); if (rc) return rc;                 // (synchronises: qb / iv may go)
+    if ((flags & GTX_CHECK_SORTED) && b0 > 0 && acc.first_unsorted < 0) {                         // the seam between two batches, as in join_batches
+      const int32_t *p = reads + 3 * (b0 - 1), *r = reads + 3 * b0;
+      if (r[0] < p[0] || (r[0] == p[0] && r[1] < p[1])) acc.first_unsorted = b0;
+    }
+    join_info_merge(&acc, hi, b0);
+    HIPCHK(c, hipMemcpy(hits_out + b0, c->hitsOut.get(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+  }
+  if (info) *info = acc;
+  return GTX_OK;
+}
+
+} // extern "C"
+
+// ---------------------------------------------------------------------------------------------
 // pair offsets (gtx_offset.hip)
 // ---------------------------------------------------------------------------------------------
 
@@ -2243,20 +2319,17 @@ int gtx_scan_end(gtx_ctx *c, uint64_t *out, int64_t *labelSum)
 // region text tokenised on the device (gtx_text.hip)
 // ---------------------------------------------------------------------------------------------
 enum TextMode { TEXT_COUNT, TEXT_COVER, TEXT_SCAN };
-static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, uint32_t flags, int *ticket)
+
+// A block of text into the slot whose turn it is, and tokenised there (launch_tokenize enqueued on the context's stream): the front
+// of add_text and gtx_subset_text.  grouped: the strand-aware outputs (tri2 / w2) are made too when the rules are strand-aware.
+// *tp = the slot, *ticket its number; *empty: a block without lines -- nothing was enqueued but the slot's evParsed, its verdict is 0.
+static int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, bool grouped, int scanRules,
+                      unsigned long long *labelSum, bool sam, TextSlot **tp, int *ticket, bool *empty)
 {
-  const bool coverage = mode == TEXT_COVER;
-  const char *who = mode == TEXT_SCAN ? "gtx_scan_add_text" : coverage ? "gtx_coverage_add_text" : "gtx_count_add_text";
-  if (mode == TEXT_SCAN ? !c->scan.open : coverage ? !c->covOpen : !c->streamOpen) return fail(c, GTX_E_STATE, "gtx_*_add_text: no open count / coverage / scan call");
-  if (mode == TEXT_SCAN && r && (r->max_label_value > 1) != c->scan.weighted) return fail(c, GTX_E_ARG, "gtx_scan_add_text: the rules' label weights do not match gtx_scan_begin's");
-  if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names))
-    { c->err = std::string(who) + ": bad argument"; return GTX_E_ARG; }
-  const bool sam = (flags & GTX_TEXT_SAM) != 0;                  // (the format of the text, not a flag of the count)
-  flags &= ~GTX_TEXT_SAM;
   HIPCHK(c, hipSetDevice(c->device));
   const int slot = (int)(c->textSeq & 1);
   TextSlot &t = c->text[slot];
-  *ticket = slot;
+  *ticket = slot; *tp = &t; *empty = false;
   if (!t.evParsed) {
     HIPCHK(c, hipEventCreateWithFlags(&t.evParsed, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&t.evConsumed, hipEventDisableTiming));
     HIPCHK(c, hipEventCreateWithFlags(&t.evCopied, hipEventDisableTiming));
@@ -2265,7 +2338,7 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
   }
   if (t.busy) { HIPCHK(c, hipEventSynchronize(t.evConsumed)); t.busy = false; }          // the block before last has been counted: its buffers are free
   c->textSeq++;
-  if (nLines == 0 || bytes == 0) { *t.hostFlag.get() = 0; HIPCHK(c, hipEventRecord(t.evParsed, c->stream)); return GTX_OK; }
+  if (nLines == 0 || bytes == 0) { *t.hostFlag.get() = 0; HIPCHK(c, hipEventRecord(t.evParsed, c->stream)); *empty = true; return GTX_OK; }
   const size_t nSeg = (bytes + 1023) / 1024;
   if (bytes + 128 > t.text.cap) HIPCHK(c, t.text.alloc(bytes + (bytes >> 3) + 4096));              // (128 bytes beyond the block kept free)
   if (nSeg + 4 > t.seg.cap) HIPCHK(c, t.seg.alloc(nSeg + (nSeg >> 3) + 16));
@@ -2311,15 +2384,36 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
   HIPCHK(c, hipEventRecord(t.evCopied, c->copyStream));
   HIPCHK(c, hipStreamWaitEvent(c->stream, t.evCopied, 0));
   HIPCHK(c, hipMemsetAsync(t.flag.get(), 0, sizeof(int), c->stream));
-  if (r->strand_aware && (size_t)nLines > t.w2.cap) {
+  grouped = grouped && r->strand_aware;
+  if (grouped && (size_t)nLines > t.w2.cap) {
     t.tri2.reset(); t.blk.reset(); t.w2.reset();
     HIPCHK(c, t.tri2.alloc(3 * t.w.cap)); HIPCHK(c, t.blk.alloc(t.w.cap / 128 + 4)); HIPCHK(c, t.w2.alloc(t.w.cap));
   }
   gtxtext::TextDevice d; d.text = t.text.get(); d.segCount = t.seg.get(); d.nl = t.nl.get(); d.tri = t.tri.get(); d.w = t.w.get(); d.flag = t.flag.get();
-  d.tri2 = r->strand_aware ? t.tri2.get() : nullptr; d.w2 = r->strand_aware ? t.w2.get() : nullptr; d.blkMinus = r->strand_aware ? t.blk.get() : nullptr;
+  d.tri2 = grouped ? t.tri2.get() : nullptr; d.w2 = grouped ? t.w2.get() : nullptr; d.blkMinus = grouped ? t.blk.get() : nullptr;
+  d.labelSum = labelSum; d.blockSum = t.sum.get();
+  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, scanRules, sam));
+  return GTX_OK;
+}
+
+static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, uint32_t flags, int *ticket)
+{
+  const bool coverage = mode == TEXT_COVER;
+  const char *who = mode == TEXT_SCAN ? "gtx_scan_add_text" : coverage ? "gtx_coverage_add_text" : "gtx_count_add_text";
+  if (mode == TEXT_SCAN ? !c->scan.open : coverage ? !c->covOpen : !c->streamOpen) return fail(c, GTX_E_STATE, "gtx_*_add_text: no open count / coverage / scan call");
+  if (mode == TEXT_SCAN && r && (r->max_label_value > 1) != c->scan.weighted) return fail(c, GTX_E_ARG, "gtx_scan_add_text: the rules' label weights do not match gtx_scan_begin's");
+  if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names))
+    { c->err = std::string(who) + ": bad argument"; return GTX_E_ARG; }
+  const bool sam = (flags & GTX_TEXT_SAM) != 0;                  // (the format of the text, not a flag of the count)
+  flags &= ~GTX_TEXT_SAM;
+  TextSlot *tp = nullptr; bool empty = false;
+  {
+    int rc = text_stage(c, text, bytes, nLines, r, true, mode == TEXT_SCAN ? (c->scan.a.sortedRule ? 2 : 1) : 0,
+                        mode == TEXT_SCAN ? c->scan.labelSum.get() : nullptr, sam, &tp, ticket, &empty);
+    if (rc || empty) return rc;
+  }
+  TextSlot &t = *tp;
   const int *triOut = r->strand_aware ? t.tri2.get() : t.tri.get();
-  d.labelSum = mode == TEXT_SCAN ? c->scan.labelSum.get() : nullptr; d.blockSum = t.sum.get();
-  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, mode == TEXT_SCAN ? (c->scan.a.sortedRule ? 2 : 1) : 0, sam));
   HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
   // ... and counted where the triples are
@@ -2366,6 +2460,67 @@ int gtx_text_result(gtx_ctx *c, int ticket, int *needs_host)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(t.evParsed));
   *needs_host = *t.hostFlag.get();
+  return GTX_OK;
+}
+
+// text -> triples in line order -> hits -> verbatim check -> select, scan, gather; everything enqueued, the verdict and the totals
+// on their way to the host behind it
+int gtx_subset_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, uint32_t flags, int *ticket)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_subset_text: gtx_set_refs has not been called");
+  if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names) ||
+      (flags & GTX_TEXT_SAM) || r->max_label_value > 1)
+    return fail(c, GTX_E_ARG, "gtx_subset_text: bad argument");
+  if (c->text[c->textSeq & 1].subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_text: the result of the block before last has not been fetched (gtx_subset_result)");
+  const int mode = join_mode(c, flags);
+  { int rc = join_prepare(c); if (rc) return rc; }
+  TextSlot *tp = nullptr; bool empty = false;
+  { int rc = text_stage(c, text, bytes, nLines, r, false, 0, nullptr, false, &tp, ticket, &empty); if (rc) return rc; }
+  TextSlot &t = *tp;
+  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
+  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
+  t.subsetPending = true;
+  if (empty) return GTX_OK;
+  const size_t nTiles = gtxtext::subset_tiles((unsigned)nLines);
+  if ((size_t)nLines > t.hits.cap) HIPCHK(c, t.hits.alloc(t.w.cap));
+  if (2 * (nTiles + 1) > t.tile.cap) HIPCHK(c, t.tile.alloc(2 * (nTiles + 1) + (nTiles >> 2)));
+  if (bytes > t.out.cap) HIPCHK(c, t.out.alloc(t.text.cap));
+  const gtx::JoinQueries q{t.tri.get(), nullptr, nullptr, nLines};
+  if (!c->joinInfo) HIPCHK(c, c->joinInfo.alloc(1));
+  if ((size_t)nLines > c->joinOff.cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, c->joinOff.grow((size_t)nLines)); }   // (the block before may still be narrowing out of it)
+  HIPCHK(c, gtx::launch_join_count(q, c->rx.pairAll.ix, ref_blocks(c), mode & ~gtx::JOIN_CHECK, c->joinOff.get(), c->joinInfo.get(), c->stream));
+  HIPCHK(c, gtx::launch_query_narrow(c->joinOff.get(), nLines, t.hits.get(), c->stream));
+  HIPCHK(c, gtxtext::launch_verbatim(t.text.get(), t.nl.get(), (unsigned)nLines, t.flag.get(), c->stream));
+  const gtxtext::SubsetDevice d{t.text.get(), t.nl.get(), (unsigned)nLines, t.hits.get(), (flags & GTX_SUBSET_INVERT) ? 1 : 0, t.flag.get(), t.tile.get(), t.out.get()};
+  HIPCHK(c, gtxtext::launch_subset_gather(d, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], t.tile.get() + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], t.tile.get() + 2 * nTiles + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  return GTX_OK;
+}
+
+int gtx_subset_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t *out_bytes, int64_t *n_selected)
+{
+  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_subset_result: bad argument") : GTX_E_ARG;
+  TextSlot &t = c->text[ticket];
+  if (!t.evParsed || !t.subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_result: no such block");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(t.evParsed));
+  t.subsetPending = false;
+  *needs_host = *t.hostFlag.get();
+  *out_bytes = 0;
+  if (n_selected) *n_selected = 0;
+  if (*needs_host) return GTX_OK;
+  const size_t n = (size_t)t.hostTotal.get()[0];
+  if (n > 0 && !out) return fail(c, GTX_E_ARG, "gtx_subset_result: bad argument");
+  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
+  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->copyStream)); HIPCHK(c, hipStreamSynchronize(c->copyStream)); }
+  *out_bytes = n;
+  if (n_selected) *n_selected = (int64_t)t.hostTotal.get()[1];
   return GTX_OK;
 }
 }

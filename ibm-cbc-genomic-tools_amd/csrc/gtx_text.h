@@ -26,4 +26,18 @@ struct TextTables {               // per reference set: hash table of the chromo
 hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules = 0, bool sam = false);
 void build_tables(const gtx_text_rules &r, std::vector<int32_t> *table, unsigned *mask, std::string *blob);
 
+// ---- gtx_subset_text: the lines of a tokenised block that are kept, byte for byte ----
+// A line may be copied instead of printed only if GenomicRegionBED::Print (genomic_intervals.cpp:2188-2218) would render the line
+// itself.  On top of the tokenizer's plain case: 3 to 6 tokens, none beginning with or holding a blank, a '\r' or any other byte
+// below ' '; columns 2 and 3 canonical decimal ("0" or no leading zero); column 5 a canonical long (optional '-', no leading zero,
+// not "-0", at most 18 digits); column 6 exactly "+" or "-".  One line per thread over nl[]; a line that is not raises *flag (16).
+// Leaves at once when the tokenizer has already set *flag.
+hipError_t launch_verbatim(const char *text, const unsigned *nl, unsigned nLines, int *flag, hipStream_t st);
+// line j is kept when (hits[j] == 0) == invert.  tile: 2 * (tiles + 1) words, tiles = subset_tiles(nLines) -- the kept bytes of every
+// 256 lines, then the kept lines, each made into its exclusive prefix with the total behind the last; out receives the kept lines
+// (newline included) in order.  With *flag set nothing is written but zero totals.
+struct SubsetDevice { const char *text; const unsigned *nl; unsigned nLines; const unsigned *hits; int invert; const int *flag; unsigned long long *tile; char *out; };
+size_t subset_tiles(unsigned nLines);
+hipError_t launch_subset_gather(const SubsetDevice &d, hipStream_t st);
+
 }  // namespace gtxtext

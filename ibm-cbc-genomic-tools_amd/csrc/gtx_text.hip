@@ -457,6 +457,144 @@ hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_t
   return hipGetLastError();
 }
 
+// ---- gtx_subset_text ----
+static constexpr int kTile = 256;                  // lines per tile of the select / gather passes
+
+// does Print re-render the line [b, e) as it stands?  (see gtx_text.h)
+__device__ __forceinline__ bool verbatim_line(const unsigned char *__restrict__ s, unsigned b, unsigned e)
+{
+  int tok = 1;
+  unsigned q = b;                                                 // the token's first byte
+  for (unsigned p = b;; p++) {
+    if (p < e && s[p] != '\t') { if (s[p] <= ' ') return false; continue; }
+    const unsigned n = p - q;
+    if (n == 0 || tok > 6) return false;
+    if (tok == 2 || tok == 3) {
+      for (unsigned k = q; k < p; k++) if ((unsigned)(s[k] - '0') >= 10u) return false;
+      if (n > 1 && s[q] == '0') return false;
+    } else if (tok == 5) {
+      const bool neg = s[q] == '-';
+      const unsigned r = q + (neg ? 1 : 0), nd = p - r;
+      if (nd == 0 || nd > 18) return false;
+      for (unsigned k = r; k < p; k++) if ((unsigned)(s[k] - '0') >= 10u) return false;
+      if (s[r] == '0' && (nd > 1 || neg)) return false;
+    } else if (tok == 6) {
+      if (n != 1 || (s[q] != '+' && s[q] != '-')) return false;
+    }
+    if (p >= e) break;
+    tok++; q = p + 1;
+  }
+  return tok >= 3;
+}
+
+__global__ __launch_bounds__(kTile) void text_verbatim_kernel(const char *__restrict__ text, const unsigned *__restrict__ nl, unsigned nLines,
+                                                               int *flag)
+{
+  if (*flag & 7) return;                                          // the tokenizer's verdict: nl[] may hold nothing to go by
+  const unsigned j = blockIdx.x * kTile + threadIdx.x;
+  if (j >= nLines) return;
+  const unsigned b = j ? nl[j - 1] + 1 : 0, e = nl[j];
+  if (!verbatim_line((const unsigned char *)text, b, e)) atomicOr(flag, 16);
+}
+
+// the kept bytes of line j of the tile (0: not kept, or behind the last line) and where the line begins
+__device__ __forceinline__ unsigned subset_line(const SubsetDevice &d, unsigned j, unsigned &from)
+{
+  from = 0;
+  if (j >= d.nLines) return 0;
+  from = j ? d.nl[j - 1] + 1 : 0;
+  return ((d.hits[j] == 0) == (d.invert != 0)) ? d.nl[j] + 1 - from : 0;
+}
+
+__global__ __launch_bounds__(kTile) void subset_mark_kernel(SubsetDevice d, unsigned nTiles)
+{
+  __shared__ unsigned bytes, lines;
+  if (threadIdx.x == 0) { bytes = 0; lines = 0; }
+  __syncthreads();
+  if (*d.flag == 0) {
+    unsigned from;
+    const unsigned n = subset_line(d, blockIdx.x * kTile + threadIdx.x, from);
+    if (n) { atomicAdd(&bytes, n); atomicAdd(&lines, 1u); }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) { d.tile[blockIdx.x] = bytes; d.tile[(size_t)nTiles + 1 + blockIdx.x] = lines; }
+}
+
+// both halves of tile[] into exclusive prefixes, the totals at [nTiles] and [2 nTiles + 1]
+__global__ __launch_bounds__(1024) void subset_scan_kernel(unsigned long long *__restrict__ tile, unsigned nTiles)
+{
+  __shared__ unsigned long long sh[1024];
+  for (int half = 0; half < 2; half++) {
+    unsigned long long *v = tile + (size_t)half * ((size_t)nTiles + 1);
+    unsigned long long carry = 0;
+    for (unsigned base = 0; base < nTiles; base += 1024) {
+      const unsigned i = base + threadIdx.x;
+      const unsigned long long x = i < nTiles ? v[i] : 0;
+      sh[threadIdx.x] = x;
+      __syncthreads();
+      for (int o = 1; o < 1024; o <<= 1) {
+        const unsigned long long y = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
+        __syncthreads();
+        sh[threadIdx.x] += y;
+        __syncthreads();
+      }
+      if (i < nTiles) v[i] = carry + sh[threadIdx.x] - x;
+      carry += sh[1023];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) v[nTiles] = carry;
+  }
+}
+
+// the kept lines of a tile are one run of the output: every thread writes bytes of that run in turn (whole lines of the output
+// per wave-instruction) and finds each byte's line by a search over the tile's 256 offsets in LDS
+__global__ __launch_bounds__(kTile) void subset_gather_kernel(SubsetDevice d)
+{
+  __shared__ unsigned off[kTile], src[kTile];
+  if (*d.flag) return;
+  const int t = threadIdx.x;
+  unsigned from;
+  const unsigned n = subset_line(d, blockIdx.x * kTile + t, from);
+  off[t] = n; src[t] = from;
+  __syncthreads();
+  for (int o = 1; o < kTile; o <<= 1) {                           // inclusive prefix of the kept bytes
+    const unsigned y = t >= o ? off[t - o] : 0;
+    __syncthreads();
+    off[t] += y;
+    __syncthreads();
+  }
+  const unsigned total = off[kTile - 1];
+  const unsigned mine = off[t] - n;
+  __syncthreads();
+  off[t] = mine;                                                  // exclusive: where the line begins inside the run
+  __syncthreads();
+  char *__restrict__ out = d.out + d.tile[blockIdx.x];
+  for (unsigned i = t; i < total; i += kTile) {
+    int a = 0, b = kTile;                                         // the last line that begins at or before byte i (lines not kept share the offset of the next)
+    while (a < b) { const int m = (a + b) >> 1; if (off[m] <= i) a = m + 1; else b = m; }
+    out[i] = d.text[src[a - 1] + (i - off[a - 1])];
+  }
+}
+
+size_t subset_tiles(unsigned nLines) { return ((size_t)nLines + kTile - 1) / kTile; }
+
+hipError_t launch_verbatim(const char *text, const unsigned *nl, unsigned nLines, int *flag, hipStream_t st)
+{
+  if (nLines == 0) return hipSuccess;
+  text_verbatim_kernel<<<(unsigned)subset_tiles(nLines), kTile, 0, st>>>(text, nl, nLines, flag);
+  return hipGetLastError();
+}
+
+hipError_t launch_subset_gather(const SubsetDevice &d, hipStream_t st)
+{
+  if (d.nLines == 0) return hipSuccess;
+  const unsigned nTiles = (unsigned)subset_tiles(d.nLines);
+  subset_mark_kernel<<<nTiles, kTile, 0, st>>>(d, nTiles);
+  subset_scan_kernel<<<1, 1024, 0, st>>>(d.tile, nTiles);
+  subset_gather_kernel<<<nTiles, kTile, 0, st>>>(d);
+  return hipGetLastError();
+}
+
 // the hash table of the chromosome names and the name blob (+ room for the seam's name behind it), host side
 void build_tables(const gtx_text_rules &r, std::vector<int32_t> *table, unsigned *mask, std::string *blob)
 {

@@ -22,6 +22,7 @@ OFFSET_SKIP_REF_GAPS = 64
 OFFSET_FROM_QUERY = 128
 SIGNAL_PER_REF = 256
 TEXT_SAM = 512            # gtx_*_add_text: the block is SAM alignments, not BED
+SUBSET_INVERT = 1024      # gtx_subset_text: keep the lines without hits (-inv)
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
@@ -147,12 +148,17 @@ ABI = {
     "gtx_count_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_coverage_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_text_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gtx_subset_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "gtx_subset_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_ref_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_join_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "gtx_join": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "gtx_join_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_query_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
+                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_query_hits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_ref_strands": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_join_offsets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -333,6 +339,26 @@ class Engine:
         self._chk(self.lib.gtx_count_end(self.ctx, _ptr(hits), ctypes.byref(info)))
         return hits[:self.n_refs], info.as_dict(), verdicts
 
+    def subset_text(self, blocks, rules, flags=0):
+        """gtx_subset_text / gtx_subset_result per block of text (bytes of complete lines), two blocks in flight: per block
+        (needs_host, the selected text, the number of selected lines); a block that comes back selected nothing."""
+        tickets, results = [], []
+
+        def collect(text, t):
+            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
+            out = ctypes.create_string_buffer(max(len(text), 1))
+            self._chk(self.lib.gtx_subset_result(self.ctx, t, ctypes.byref(redo), out, ctypes.byref(nb), ctypes.byref(ns)))
+            results.append((redo.value, out.raw[:nb.value], ns.value))
+        for text in blocks:
+            if len(tickets) == 2:
+                collect(*tickets.pop(0))
+            t = ctypes.c_int(-1)
+            self._chk(self.lib.gtx_subset_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(rules), int(flags), ctypes.byref(t)))
+            tickets.append((text, t.value))
+        for x in tickets:
+            collect(*x)
+        return results
+
     def count(self, reads, weights=None, flags=READS_SORTED):
         reads = _triples(reads)
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32)
@@ -386,6 +412,27 @@ class Engine:
         self._chk(self.lib.gtx_join_device(self.ctx, _ptr(d_reads), int(n_reads), int(flags), _ptr(d_offsets), _ptr(d_pairs), int(capacity),
                                            ctypes.byref(tot), ctypes.byref(done), ctypes.byref(info)))
         return tot.value, done.value, info.as_dict()
+
+    def query_hits(self, reads, flags=0, first=None, blocks=None):
+        """gtx_query_hits: (hits [n] uint32, info); hits[i] = the reference regions query i overlaps = the length of its segment
+        in join() with the same arguments."""
+        reads = _triples(reads)
+        n = reads.shape[0]
+        if first is not None:
+            first = np.ascontiguousarray(first, dtype=np.int64)
+            blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1)
+            if first.shape[0] != n + 1 or int(first[-1]) * 2 != blocks.shape[0]:
+                raise GtxError("query_hits: first must have n + 1 entries and end at len(blocks)")
+        hits = np.zeros(n, dtype=np.uint32)
+        info = CountInfo()
+        self._chk(self.lib.gtx_query_hits(self.ctx, _ptr(reads), _ptr(first), _ptr(blocks), n, int(flags), _ptr(hits), ctypes.byref(info)))
+        return hits, info.as_dict()
+
+    def query_hits_device(self, d_reads, n_reads, d_hits, flags=0):
+        """gtx_query_hits_device on raw device addresses: info."""
+        info = CountInfo()
+        self._chk(self.lib.gtx_query_hits_device(self.ctx, _ptr(d_reads), int(n_reads), int(flags), _ptr(d_hits), ctypes.byref(info)))
+        return info.as_dict()
 
     def set_ref_strands(self, strand=None):
         """gtx_set_ref_strands: one of '+' / '-' (or 0 '+', 1 '-') per reference region; None: all '+'."""

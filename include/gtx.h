@@ -231,6 +231,31 @@ int gtx_join_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_reads, u
                     void *d_pairs, int64_t pair_capacity, int64_t *n_pairs_out, int64_t *n_done_out,
                     gtx_count_info *info /* may be NULL */);
 
+/* ---- genomic_overlaps subset: hits per query ---------------------------------------------------- */
+
+/* genomic_overlaps subset (gtools/genomic_overlaps.cpp:782-800) keeps the test regions that overlap some reference
+ * region, or with -inv those that overlap none; CountQueryOverlaps (genomic_intervals.cpp:5292-5302) is the same
+ * answer as a number: how many index regions GetOverlap / NextOverlap deliver for a query, each after the filter of
+ * :5224-5248.  Where every other count of this library is keyed by the reference region, this one is keyed by the
+ * query:
+ *     hits[i] = the number of reference regions query i overlaps
+ *             = offsets[i + 1] - offsets[i] of gtx_join with the same reference set, blocks and flags,
+ * with the same info.  A query whose class is outside [0, n_classes) has 0.  flags: GTX_ZERO_LENGTH_OK,
+ * GTX_JOIN_GAPS, GTX_CHECK_SORTED.
+ *
+ * The hits are the counts of the join's first pass (one walk of the envelope index per query), narrowed to 32 bits: no
+ * offsets are scanned and no pair is written.  Every rule of gtx_join holds as it stands: gtx_set_ref_blocks, multi-interval
+ * queries, GTX_REFS_KEEP_ZERO_LENGTH sets with inverted regions, zero-length and inverted queries under GTX_ZERO_LENGTH_OK.
+ *
+ * gtx_query_hits: queries from host memory as gtx_join takes them (first / blocks: NULL when every query has one
+ * interval), in batches; hits_out receives n_reads values.
+ * gtx_query_hits_device: single-interval triples and the hits (uint32[n_reads]) in this device's HBM.
+ * Both return with the work complete. */
+int gtx_query_hits(gtx_ctx *ctx, const int32_t *read_triples, const int64_t *first /* n + 1, or NULL */, const int32_t *blocks,
+                   int64_t n_reads, uint32_t flags, uint32_t *hits_out /* n_reads */, gtx_count_info *info /* may be NULL */);
+int gtx_query_hits_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_reads, uint32_t flags,
+                          void *d_hits /* uint32[n_reads] */, gtx_count_info *info /* may be NULL */);
+
 /* ---- genomic_overlaps offset: pair offsets on the join ----------------------------------------- */
 
 /* genomic_overlaps offset (gtools/genomic_overlaps.cpp:545-670) prints, per (test region, reference region)
@@ -491,6 +516,22 @@ int gtx_count_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_l
 int gtx_coverage_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
 /* waits for the tokenizer of that block; *needs_host != 0: nothing of the block was counted, the caller packs and adds it */
 int gtx_text_result(gtx_ctx *ctx, int ticket, int *needs_host);
+/* genomic_overlaps subset on text (gtools/genomic_overlaps.cpp:782-800): a block of complete BED lines goes to the device as for
+ * gtx_count_add_text (same buffers contract, same rules, same seam key, two blocks in flight; no count call need be open), is cut
+ * into triples there, gets its hits per line (gtx_query_hits_device, in line order; flags: GTX_ZERO_LENGTH_OK, GTX_JOIN_GAPS), and
+ * the lines with hits > 0 -- hits == 0 under GTX_SUBSET_INVERT, the reference's -inv -- are gathered, newline included, in order.
+ * The reference prints a selected region with GenomicRegionBED::Print (genomic_intervals.cpp:2188-2218), which renders the line
+ * again from its parsed fields; a line is copied only where that rendering is the line itself: on top of the tokenizer's plain
+ * case, 3 to 6 tab-separated tokens without blanks, '\r' or control bytes, columns 2 and 3 in canonical decimal ("0" or no leading
+ * zero), column 5 a canonical long (optional '-', no leading zero, not "-0", at most 18 digits), column 6 exactly "+" or "-".
+ * A block with ANY other line yields nothing: gtx_subset_result says needs_host, and the caller does that block by its own means.
+ * gtx_subset_result waits for the block of that ticket; out receives the selected text (room for the block's bytes),
+ * *out_bytes its length, *n_selected (may be NULL) the number of lines.  The result of a ticket must be fetched before the block
+ * after next is added. */
+#define GTX_SUBSET_INVERT 1024u   /* gtx_subset_text: keep the lines with hits == 0 */
+int gtx_subset_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
+int gtx_subset_result(gtx_ctx *ctx, int ticket, int *needs_host, char *out /* >= bytes of the block */, size_t *out_bytes,
+                      int64_t *n_selected /* may be NULL */);
 /* The same in a group that holds all its members (between gtx_group_count_begin / gtx_group_coverage_begin and their _end): a block goes
  * to the members in turn, whatever the classes of its lines -- the read stream split evenly over members that each hold the whole
  * reference set (SURVEY 8(e)'s second partition) -- and a count call that took text blocks ends with the ncclReduce(sum) of the
