@@ -134,6 +134,19 @@ class GenomicRegionSet
   void Reset();
   void PrintError(std::string error_msg);                         // "\nError: msg\n", exit(1)
 
+  // `genomic_regions link` (genomic_intervals.cpp:4605-4644): the position-sorted set merged into groups of regions whose START lies
+  // within max_difference of the group's running maximum STOP, one "label TAB chromosome strand START new_stop" line per group;
+  // label_func "" prints "_", min / max / sum fold atof(LABEL), anything else is a delimiter between the members' labels.  The
+  // reference's output and errors (order, multi-interval region, malformed line: the earliest line wins, with the groups closed
+  // before it on stdout).  MI355X path, for a streamed BED set (load_in_memory = false).  Without a label function the text goes to
+  // the device block by block and is tokenised there (files of 32 MB or more; GTX_TEXT_ON_DEVICE=1: of any size, =0: never); a block
+  // the tokenizer hands back is parsed here and its regions follow the others (gtx_link_text_begin .. _end, include/gtx.h).  With a
+  // label function the labels are read here, so the host packer takes every line and gtx_link gets packed triples; min / max / sum
+  // run on the device for canonical integer labels, otherwise here from the device's boundaries, group by group in input order.
+  // GTX_TEXT_TRACE=1 reports which way the text went.  Known limit: labels that atof() reads as nan or inf are folded with
+  // std::min / std::max and printed with "%g", which may differ from the reference's stream output in spelling or in which operand wins.
+  void RunGlobalLink(bool sorted_by_strand, long int max_difference, char *label_func);
+
   // MI355X path: hands the not yet consumed part of a streaming set (the current region's raw
   // line first) to the bulk packer.  After this call Get()/Next() report the end of the set.
   gtxhost::LineSource *DetachStream(std::string *current_line, long int *current_line_no);

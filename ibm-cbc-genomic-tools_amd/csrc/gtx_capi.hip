@@ -22,6 +22,7 @@
 #include "gtx_offset.h"
 #include "gtx_signal.h"
 #include "gtx_text.h"
+#include "gtx_link.h"
 #include "gtx_internal.h"
 
 typedef unsigned long long u64;
@@ -187,6 +188,15 @@ struct gtx_ctx {
   int64_t joinBuffer = 1ll << 26;       // pairs per device chunk of gtx_join (gtx_set_join_buffer)
   DevBuf<long long> offInv, offOut, offCnt, offPart; DevBuf<int8_t> offQStrand;   // the pair offsets' host entry
   DevBuf<gtx::SignalInfo> sigInfo; DevBuf<unsigned long long> sigBins; DevBuf<long long> sigW;   // the signal bins' info block, the host entry's bins and weights
+
+  // link: the scans' per-tile values and break bit map, the info block and its page-locked copy (handed to the caller's struct by
+  // gtx_sync after a device call), the host entry's inputs and group records
+  DevBuf<int2> linkAgg, linkPrefix; DevBuf<u64> linkBits; DevBuf<unsigned> linkHeads; DevBuf<long long> linkBase;
+  DevBuf<gtx::LinkInfo> linkInfo; PinBuf<gtx::LinkInfo> linkHost; gtx_link_info *linkPending = nullptr;
+  DevBuf<int> linkTri, linkStop; DevBuf<long long> linkVals, linkVal; DevBuf<unsigned> linkHead, linkCnt;
+  // gtx_link_text_begin .. _end: the input collected on the device block by block, the strands beside it, the heads' keys
+  bool linkTextOpen = false; int64_t linkTextN = 0, linkTextCap = 0; int linkTextChrom = 0, linkTextByStrand = 0;
+  DevBuf<int> linkTextTri; DevBuf<unsigned char> linkMinus; DevBuf<int2> linkHeadKey;
 
   DevBuf<gtx::DevInfo> d_info;          // 2 blocks: the finalize of one call resets the block of the next
   int infoCur = 0;
@@ -418,6 +428,11 @@ int gtx_sync(gtx_ctx *c)
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->copyStream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->linkPending) {                                              // the last gtx_link_device's info block has arrived
+    const gtx::LinkInfo &h = c->linkHost.get()[0];
+    c->linkPending->n_groups = h.nGroups; c->linkPending->first_unsorted = h.firstUnsortedOut;
+    c->linkPending = nullptr;
+  }
   return GTX_OK;
 }
 
@@ -2671,6 +2686,173 @@ int gtxi_wait_direct(gtx_ctx *c)
 hipStream_t gtxi_stream(gtx_ctx *c) { return c->stream; }
 int gtxi_device(gtx_ctx *c) { return c->device; }
 void gtxi_set_error(gtx_ctx *c, const char *msg) { c->err = msg; }
+
+// ---------------------------------------------------------------------------------------------
+// link (kernels: gtx_link.hip)
+// ---------------------------------------------------------------------------------------------
+static int link_mode(uint32_t flags, bool haveValues, int *mode)
+{
+  const uint32_t f = flags & (GTX_LINK_SUM | GTX_LINK_MIN | GTX_LINK_MAX);
+  if (flags & ~(GTX_LINK_SUM | GTX_LINK_MIN | GTX_LINK_MAX)) return GTX_E_ARG;
+  if (f & (f - 1)) return GTX_E_ARG;                                 // at most one fold
+  if (f && !haveValues) return GTX_E_ARG;
+  *mode = f == GTX_LINK_SUM ? gtx::LINK_SUM : f == GTX_LINK_MIN ? gtx::LINK_MIN : f == GTX_LINK_MAX ? gtx::LINK_MAX : gtx::LINK_NONE;
+  return GTX_OK;
+}
+
+// the info block of a gtx_link_device call that has not been synchronised yet goes to its caller's struct before the page-locked
+// block is used again
+static int link_settle(gtx_ctx *c)
+{
+  if (!c->linkPending) return GTX_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const gtx::LinkInfo &h = c->linkHost.get()[0];
+  c->linkPending->n_groups = h.nGroups; c->linkPending->first_unsorted = h.firstUnsortedOut;
+  c->linkPending = nullptr;
+  return GTX_OK;
+}
+
+// the kernels and the copy of the info block into page-locked memory, enqueued
+static int link_enqueue(gtx_ctx *c, const void *d_tri, const void *d_vals, int64_t n, int64_t d, int mode, void *d_head, void *d_cnt, void *d_stop, void *d_val)
+{
+  const size_t nt = (size_t)gtx::link_tiles(n);
+  HIPCHK(c, c->linkAgg.reserve(nt)); HIPCHK(c, c->linkPrefix.reserve(nt)); HIPCHK(c, c->linkBits.reserve(nt * (gtx::kLinkTile / 64) + 1));
+  HIPCHK(c, c->linkHeads.reserve(nt)); HIPCHK(c, c->linkBase.reserve(nt + 1));
+  if (!c->linkInfo) HIPCHK(c, c->linkInfo.alloc(1));
+  if (!c->linkHost) HIPCHK(c, c->linkHost.alloc(1));
+  gtx::LinkWork w;
+  w.tileAgg = c->linkAgg.get(); w.tilePrefix = c->linkPrefix.get(); w.bits = c->linkBits.get(); w.tileHeads = c->linkHeads.get();
+  w.tileHeadBase = c->linkBase.get(); w.info = c->linkInfo.get();
+  HIPCHK(c, gtx::launch_link((const int *)d_tri, (const long long *)d_vals, n, d, mode, w, (unsigned *)d_head, (unsigned *)d_cnt, (int *)d_stop,
+                             (long long *)d_val, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->linkHost.get(), c->linkInfo.get(), sizeof(gtx::LinkInfo), hipMemcpyDeviceToHost, c->stream));
+  return GTX_OK;
+}
+
+int gtx_link_device(gtx_ctx *c, const void *d_triples, const void *d_values, int64_t n, int64_t max_difference, uint32_t flags,
+                    void *d_head, void *d_count, void *d_stop, void *d_value, gtx_link_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  int mode = 0;
+  if (link_mode(flags, d_values != nullptr && d_value != nullptr, &mode)) return fail(c, GTX_E_ARG, "gtx_link_device: at most one of GTX_LINK_SUM / _MIN / _MAX, and values with it");
+  if (n < 0 || n >= (1ll << 32) || !info || (n > 0 && (!d_triples || !d_head || !d_count || !d_stop))) return fail(c, GTX_E_ARG, "gtx_link_device: bad argument (n < 2^32)");
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = link_settle(c); if (rc) return rc; }
+  info->n_groups = 0; info->first_unsorted = -1;
+  if (n == 0) return GTX_OK;
+  if (int rc = link_enqueue(c, d_triples, d_values, n, max_difference, mode, d_head, d_count, d_stop, d_value)) return rc;
+  c->linkPending = info;
+  return GTX_OK;
+}
+
+int gtx_link(gtx_ctx *c, const int32_t *triples, const int64_t *values, int64_t n, int64_t max_difference, uint32_t flags,
+             uint32_t *head_out, uint32_t *count_out, int32_t *stop_out, int64_t *value_out, gtx_link_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  int mode = 0;
+  if (link_mode(flags, values != nullptr && value_out != nullptr, &mode)) return fail(c, GTX_E_ARG, "gtx_link: at most one of GTX_LINK_SUM / _MIN / _MAX, and values with it");
+  if (n < 0 || n >= (1ll << 32) || !info || (n > 0 && (!triples || !head_out || !count_out || !stop_out))) return fail(c, GTX_E_ARG, "gtx_link: bad argument (n < 2^32)");
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = link_settle(c); if (rc) return rc; }
+  info->n_groups = 0; info->first_unsorted = -1;
+  if (n == 0) return GTX_OK;
+  const size_t m = (size_t)n;
+  HIPCHK(c, c->linkTri.reserve(3 * m)); HIPCHK(c, c->linkHead.reserve(m)); HIPCHK(c, c->linkCnt.reserve(m)); HIPCHK(c, c->linkStop.reserve(m));
+  if (mode) { HIPCHK(c, c->linkVals.reserve(m)); HIPCHK(c, c->linkVal.reserve(m)); }
+  HIPCHK(c, hipMemcpyAsync(c->linkTri.get(), triples, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+  if (mode) HIPCHK(c, hipMemcpyAsync(c->linkVals.get(), values, sizeof(int64_t) * m, hipMemcpyHostToDevice, c->stream));
+  if (int rc = link_enqueue(c, c->linkTri.get(), mode ? c->linkVals.get() : nullptr, n, max_difference, mode, c->linkHead.get(), c->linkCnt.get(),
+                            c->linkStop.get(), mode ? c->linkVal.get() : nullptr)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const gtx::LinkInfo &h = c->linkHost.get()[0];
+  info->n_groups = h.nGroups; info->first_unsorted = h.firstUnsortedOut;
+  const size_t g = (size_t)h.nGroups;
+  if (g) {
+    HIPCHK(c, hipMemcpyAsync(head_out, c->linkHead.get(), sizeof(uint32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(count_out, c->linkCnt.get(), sizeof(uint32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stop_out, c->linkStop.get(), sizeof(int32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    if (mode) HIPCHK(c, hipMemcpyAsync(value_out, c->linkVal.get(), sizeof(int64_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GTX_OK;
+}
+
+// link fed as a stream of text blocks (the tool's path): see include/gtx.h
+int gtx_link_text_begin(gtx_ctx *c, int32_t n_chrom, int sorted_by_strand, int64_t capacity)
+{
+  if (!c) return GTX_E_ARG;
+  if (n_chrom < 0 || capacity < 0 || capacity >= (1ll << 32)) return fail(c, GTX_E_ARG, "gtx_link_text_begin: bad argument (capacity < 2^32)");
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = link_settle(c); if (rc) return rc; }
+  HIPCHK(c, c->linkTextTri.reserve(3 * (size_t)std::max<int64_t>(capacity, 1))); HIPCHK(c, c->linkMinus.reserve((size_t)std::max<int64_t>(capacity, 1)));
+  c->linkTextOpen = true; c->linkTextN = 0; c->linkTextCap = capacity; c->linkTextChrom = n_chrom; c->linkTextByStrand = sorted_by_strand != 0;
+  return GTX_OK;
+}
+
+int gtx_link_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, int *needs_host)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->linkTextOpen) return fail(c, GTX_E_STATE, "gtx_link_add_text: gtx_link_text_begin has not been called");
+  if (!text || !r || !needs_host || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom != c->linkTextChrom || (r->n_chrom > 0 && !r->chrom_names) ||
+      !r->strand_aware || r->sorted_rules || r->max_label_value > 1 || c->linkTextN + nLines > c->linkTextCap)
+    return fail(c, GTX_E_ARG, "gtx_link_add_text: bad argument (strand-aware rules without order or label rules, the names of gtx_link_text_begin, room for the lines)");
+  *needs_host = 0;
+  TextSlot *tp = nullptr; bool empty = false; int ticket = 0;
+  // (the sorted scanner's rules: nothing about the interval is checked -- zero-length and inverted regions are link's to take)
+  { int rc = text_stage(c, text, bytes, nLines, r, false, 2, nullptr, false, &tp, &ticket, &empty); if (rc || empty) return rc; }
+  TextSlot &t = *tp;
+  HIPCHK(c, gtx::launch_link_append(t.tri.get(), nLines, c->linkTextChrom, c->linkTextByStrand, c->linkTextTri.get() + 3 * c->linkTextN,
+                                    c->linkMinus.get() + c->linkTextN, t.flag.get(), c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (*t.hostFlag.get()) { *needs_host = 1; return GTX_OK; }           // (what was appended lies behind the end and is written over)
+  c->linkTextN += nLines;
+  return GTX_OK;
+}
+
+int gtx_link_add(gtx_ctx *c, const int32_t *triples, const uint8_t *minus, int64_t n)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->linkTextOpen) return fail(c, GTX_E_STATE, "gtx_link_add: gtx_link_text_begin has not been called");
+  if (n < 0 || (n > 0 && (!triples || !minus)) || c->linkTextN + n > c->linkTextCap) return fail(c, GTX_E_ARG, "gtx_link_add: bad argument");
+  if (n == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(c->linkTextTri.get() + 3 * c->linkTextN, triples, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->linkMinus.get() + c->linkTextN, minus, (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->linkTextN += n;
+  return GTX_OK;
+}
+
+int gtx_link_text_end(gtx_ctx *c, int64_t max_difference, uint32_t *head_out, int32_t *stop_out, int32_t *head_key_out, gtx_link_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->linkTextOpen) return fail(c, GTX_E_STATE, "gtx_link_text_end: gtx_link_text_begin has not been called");
+  c->linkTextOpen = false;
+  const int64_t n = c->linkTextN;
+  if (!info || (n > 0 && (!head_out || !stop_out || !head_key_out))) return fail(c, GTX_E_ARG, "gtx_link_text_end: bad argument");
+  info->n_groups = 0; info->first_unsorted = -1;
+  if (n == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t m = (size_t)n;
+  HIPCHK(c, c->linkHead.reserve(m)); HIPCHK(c, c->linkCnt.reserve(m)); HIPCHK(c, c->linkStop.reserve(m)); HIPCHK(c, c->linkHeadKey.reserve(m));
+  if (int rc = link_enqueue(c, c->linkTextTri.get(), nullptr, n, max_difference, gtx::LINK_NONE, c->linkHead.get(), c->linkCnt.get(), c->linkStop.get(), nullptr)) return rc;
+  HIPCHK(c, gtx::launch_link_head_keys(c->linkTextTri.get(), c->linkMinus.get(), c->linkHead.get(), c->linkInfo.get(), n, c->linkTextByStrand, c->linkHeadKey.get(), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const gtx::LinkInfo &h = c->linkHost.get()[0];
+  info->n_groups = h.nGroups; info->first_unsorted = h.firstUnsortedOut;
+  const size_t g = (size_t)h.nGroups;
+  if (g) {
+    HIPCHK(c, hipMemcpyAsync(head_out, c->linkHead.get(), sizeof(uint32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stop_out, c->linkStop.get(), sizeof(int32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(head_key_out, c->linkHeadKey.get(), sizeof(int2) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GTX_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // measurement

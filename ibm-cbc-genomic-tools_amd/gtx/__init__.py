@@ -23,6 +23,10 @@ OFFSET_FROM_QUERY = 128
 SIGNAL_PER_REF = 256
 TEXT_SAM = 512            # gtx_*_add_text: the block is SAM alignments, not BED
 SUBSET_INVERT = 1024      # gtx_subset_text: keep the lines without hits (-inv)
+LINK_SUM = 1              # gtx_link: fold the values (at most one of the three)
+LINK_MIN = 2
+LINK_MAX = 4
+LINK_TILE = 2048          # GTX_LINK_TILE: regions per block of link's scans
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
@@ -45,6 +49,13 @@ class CountInfo(ctypes.Structure):
 class SignalInfo(ctypes.Structure):
     _fields_ = [("n_pairs", ctypes.c_int64), ("n_binned", ctypes.c_int64), ("n_dropped", ctypes.c_int64),
                 ("weight_abs_sum", ctypes.c_int64), ("n_no_class", ctypes.c_int64), ("n_degenerate", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class LinkInfo(ctypes.Structure):
+    _fields_ = [("n_groups", ctypes.c_int64), ("first_unsorted", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -109,6 +120,14 @@ ABI = {
     "gtx_scan_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_link": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
+                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_link_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_link_text_begin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int, ctypes.c_int64]),
+    "gtx_link_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_link_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "gtx_link_text_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_group_count_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_group_coverage_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_group_text_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -267,6 +286,7 @@ class Engine:
 
     def sync(self):
         self._chk(self.lib.gtx_sync(self.ctx))
+        self._link_infos = []
 
     def pinned_array(self, shape, dtype=np.int32):
         """numpy array over page-locked memory from gtx_host_alloc (the DMA engine reads it without a staging copy).
@@ -549,6 +569,32 @@ class Engine:
     def sort_device(self, d_reads, n_reads, n_classes, d_order, d_sorted=None):
         """raw device addresses; returns when the result is complete"""
         self._chk(self.lib.gtx_sort_device(self.ctx, _ptr(d_reads), int(n_reads), int(n_classes), _ptr(d_order), _ptr(d_sorted)))
+
+    def link(self, regions, values=None, max_difference=0, flags=0):
+        """gtx_link: (heads uint32, counts uint32, stops int32, folded values int64 or None, info) of the groups a position-sorted
+        stream of (class, start, stop) merges into; values: one int64 per region for LINK_SUM / LINK_MIN / LINK_MAX."""
+        regions = _triples(regions)
+        n = regions.shape[0]
+        v = None if values is None else np.ascontiguousarray(values, dtype=np.int64)
+        if v is not None and len(v) != n:
+            raise GtxError("link: one value per region")
+        heads, counts = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        stops = np.zeros(max(n, 1), dtype=np.int32)
+        folded = None if v is None else np.zeros(max(n, 1), dtype=np.int64)
+        info = LinkInfo()
+        self._chk(self.lib.gtx_link(self.ctx, _ptr(regions), _ptr(v), n, int(max_difference), int(flags), _ptr(heads), _ptr(counts), _ptr(stops),
+                                    _ptr(folded), ctypes.byref(info)))
+        g = int(info.n_groups)
+        return heads[:g], counts[:g], stops[:g], (None if folded is None or not flags else folded[:g]), info.as_dict()
+
+    def link_device(self, d_regions, n, d_heads, d_counts, d_stops, d_values=None, d_folded=None, max_difference=0, flags=0):
+        """gtx_link_device on raw device addresses (outputs sized n); returns the LinkInfo the library fills: read it after sync()."""
+        info = LinkInfo()
+        self._link_infos = getattr(self, "_link_infos", [])
+        self._link_infos.append(info)                       # the library writes it at the next sync: it must live until then
+        self._chk(self.lib.gtx_link_device(self.ctx, _ptr(d_regions), _ptr(d_values), int(n), int(max_difference), int(flags), _ptr(d_heads),
+                                           _ptr(d_counts), _ptr(d_stops), _ptr(d_folded), ctypes.byref(info)))
+        return info
 
     def scan(self, reads, class_len, win_step, win_size, preprocess="1", weights=None, flags=0):
         reads = _triples(reads)

@@ -551,6 +551,50 @@ int gtx_group_text_result(gtx_group *g, int ticket, int *needs_host);
 int gtx_sort(gtx_ctx *ctx, const int32_t *read_triples, int64_t n_reads, int32_t n_classes, uint32_t *order_out, int32_t *sorted_out);
 int gtx_sort_device(gtx_ctx *ctx, const void *d_reads, int64_t n_reads, int32_t n_classes, void *d_order, void *d_sorted);
 
+/* A position-sorted region stream merged into its covered territory: the reference's `genomic_regions link [-s] [-d N] [--label-func F]`
+ * (genomic_regions.cpp:437-451, 546-550, 704, 744; RunGlobalLink genomic_intervals.cpp:4605-4644 over Next :3874-3882, IsBefore :396-401,
+ * IsCompatibleWith :416-421, PrintModified :909-913) -- what `bedtools merge` does.  The loop: the first region is the head of a group
+ * and new_stop its STOP; a following region joins while it is compatible with the head (same class: the caller folds the chromosome
+ * and, under -s, the strand into the class id, as everywhere in this header; ANY int32 is a class, there is no n_classes and no
+ * reference set) and START - new_stop <= max_difference, and then new_stop = max(STOP, new_stop); otherwise the group is closed and the
+ * region heads the next one.  max_difference may be negative; 0 joins overlapping regions but not adjacent ones (coordinates are the
+ * set's: BED start + 1, stop).
+ * The parallel form the kernels compute: within a class the starts do not decrease (anything else is the order error below), so region
+ * i heads a group exactly when it is the first of its class or START[i] - P[i-1] > max_difference, P[i-1] the largest STOP of ALL
+ * regions of the class in front of it (a group closed earlier at j had START[j] - its maximum > d and START[i] >= START[j]: its
+ * maximum never decides for i).  The difference is taken in 64 bits.  A group's new_stop is the maximum over ITS members, which P is
+ * not when max_difference < 0 or an interval is inverted.
+ * Per group g, in stream order: head[g] = the ordinal of its first region, count[g] = its members, stop[g] = new_stop, and with one of
+ * the fold flags value[g] = the sum (two's complement) / minimum / maximum of the members' int64 values.  info->n_groups = the groups
+ * written.  info->first_unsorted = the first region that is before its predecessor in (class, start) -- Next's "input regions are not
+ * sorted" -- or -1; groups are reported only for the prefix in front of it, and the group open at that region is not among them (the
+ * reference prints the groups closed before the offending line and stops).  Outputs hold n entries.  n < 2^32 (else GTX_E_ARG); two
+ * fold flags, or a fold flag without values / value_out, are GTX_E_ARG.  gtx_link_device: all pointers but info in the context's HBM,
+ * enqueued on its stream; *info is valid after gtx_sync (and must live until then). */
+#define GTX_LINK_SUM 1u   /* fold the values: at most one of the three */
+#define GTX_LINK_MIN 2u
+#define GTX_LINK_MAX 4u
+#define GTX_LINK_TILE 2048   /* regions per block of the scans (what tests place their boundary cases by) */
+typedef struct gtx_link_info { int64_t n_groups, first_unsorted; } gtx_link_info;
+int gtx_link(gtx_ctx *ctx, const int32_t *triples, const int64_t *values /* may be NULL */, int64_t n, int64_t max_difference,
+             uint32_t flags, uint32_t *head_out, uint32_t *count_out, int32_t *stop_out, int64_t *value_out /* may be NULL */,
+             gtx_link_info *info);
+int gtx_link_device(gtx_ctx *ctx, const void *d_triples, const void *d_values, int64_t n, int64_t max_difference, uint32_t flags,
+                    void *d_head, void *d_count, void *d_stop, void *d_value, gtx_link_info *info);
+
+/* Link fed block by block (the path of `genomic_regions link` for BED text): gtx_link_text_begin opens a call for at most `capacity`
+ * regions over n_chrom chromosome names (the caller's table, ids in strcmp order; sorted_by_strand: the strand is folded below the id
+ * into link's class).  gtx_link_add_text tokenises a block of complete lines on the device (rules: the table, strand_aware = 1, no
+ * order and no label rules; zero-length and inverted regions are taken) and, when every line of it is plain, appends its regions in
+ * line order -- the text's triples never exist on the host; a block with anything else in it (*needs_host = 1) appends nothing and
+ * is packed by the caller, who hands its regions to gtx_link_add (link classes, one strand byte -- 0 '+', 1 '-' -- per region).
+ * gtx_link_text_end runs gtx_link over what was collected (no fold) and writes, per group, head, stop and the head's key
+ * {2 * chromosome id + strand, START} (head_key_out: 2 int32 per group), with info as for gtx_link.  The calls synchronise. */
+int gtx_link_text_begin(gtx_ctx *ctx, int32_t n_chrom, int sorted_by_strand, int64_t capacity);
+int gtx_link_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, int *needs_host);
+int gtx_link_add(gtx_ctx *ctx, const int32_t *triples, const uint8_t *minus, int64_t n);
+int gtx_link_text_end(gtx_ctx *ctx, int64_t max_difference, uint32_t *head_out, int32_t *stop_out, int32_t *head_key_out, gtx_link_info *info);
+
 /* genomic_scans counts fed as a stream (UnsortedGenomicRegionSetScanner ctor genomic_intervals.cpp:5019-5080, sorted scanner :4928-4957):
  * gtx_scan_begin fixes the geometry (arguments as gtx_scan; flags: GTX_ZERO_LENGTH_OK = the sorted scanner's rule; weighted != 0: every
  * batch brings label weights), gtx_scan_add adds packed reads from host memory (flags: GTX_READS_UNSORTED as a hint), gtx_scan_add_text a
