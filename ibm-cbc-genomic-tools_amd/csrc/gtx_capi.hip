@@ -86,8 +86,11 @@ struct BucketTables {
 struct BucketCuts { std::vector<int32_t> posHi, eLo, eHi, sLo, sHi, cls, clsStart; };
 
 // histograms, tile sums, prefix arrays of one count call and the finalize_scan_chained_kernel's flags (one per tile and histogram)
-// with the call's epoch
-struct HistSet { DevBuf<u64> histA, histB, partA, partB, prefA, prefB; DevBuf<unsigned> flags; unsigned epoch = 0; unsigned long long draws = 0; };
+// with the call's epoch; the tiles' totals of the two-launch finalize (finalize_local_kernel), two per histogram, and whose turn it is
+struct HistSet {
+  DevBuf<u64> histA, histB, partA, partB, prefA, prefB; DevBuf<unsigned> flags; unsigned epoch = 0; unsigned long long draws = 0;
+  DevBuf<u64> totals; unsigned totalsTurn = 0;
+};
 
 // What a reference set is made into, in four parts that gtx_set_refs_ex drops together (by assignment) before it makes them anew.
 // The count index: sorted boundary arrays, the search kernel's top levels, placement, the partition path's tables, the histograms
@@ -169,6 +172,7 @@ struct gtx_ctx {
   bool covTileSums = true;                           // false: a batch went through the partition path, the tile sums are rebuilt before the finalize step
   DevBuf<u64> bktReads; DevBuf<int> bktWeights; DevBuf<unsigned> bktDir, bktCnt;   // scratch of the partition path (gtx::BucketWork)
   int64_t bucketMinReads = 1 << 18;                  // below this the per-read search kernel is used (GTX_BUCKET_MIN_READS)
+  int localMaxTiles = gtx::kLocalScanMaxTiles;       // tile sums not kept: local scan + gather up to this many tiles (GTX_LOCAL_SCAN_MAX_TILES; 0: tile sums + scan + gather)
   bool histDirty = false;              // a call was abandoned between begin and end
   bool covDirty = false, covOpen = false;
   std::vector<int32_t> h_refS, h_refE, h_refC;
@@ -261,16 +265,17 @@ template <class T> static hipError_t upload(DevBuf<T> &b, const T *v, size_t n)
   return e == hipSuccess ? hipMemcpy(b.get(), v, sizeof(T) * n, hipMemcpyHostToDevice) : e;
 }
 
-// histograms, tile sums, prefix arrays and chain flags over histLen slots; histograms, tile sums and flags zero (the invariant between
-// calls: the finalize kernels leave them so)
+// histograms, tile sums, prefix arrays, chain flags and tile totals over histLen slots; histograms, tile sums, flags and totals zero
+// (the invariant between calls: the finalize kernels leave them so -- of the totals, the ones the next call writes)
 static int make_hist_set(gtx_ctx *c, HistSet &h, int64_t histLen)
 {
   const size_t parts = (size_t)gtx::scan_tiles(histLen) + 2;
   HIPCHK(c, h.histA.alloc(histLen)); HIPCHK(c, h.histB.alloc(histLen)); HIPCHK(c, h.partA.alloc(parts)); HIPCHK(c, h.partB.alloc(parts));
   HIPCHK(c, h.prefA.alloc(histLen)); HIPCHK(c, h.prefB.alloc(histLen)); HIPCHK(c, h.flags.alloc(8 * parts));
-  for (DevBuf<u64> *b : {&h.histA, &h.histB, &h.partA, &h.partB}) HIPCHK(c, hipMemset(b->get(), 0, sizeof(u64) * b->cap));
+  HIPCHK(c, h.totals.alloc(4 * parts));
+  for (DevBuf<u64> *b : {&h.histA, &h.histB, &h.partA, &h.partB, &h.totals}) HIPCHK(c, hipMemset(b->get(), 0, sizeof(u64) * b->cap));
   HIPCHK(c, hipMemset(h.flags.get(), 0, sizeof(unsigned) * h.flags.cap));
-  h.epoch = 0; h.draws = 0;
+  h.epoch = 0; h.draws = 0; h.totalsTurn = 0;
   return GTX_OK;
 }
 
@@ -400,6 +405,7 @@ gtx_ctx *gtx_create(int device_id)
   const char *br = getenv("GTX_BATCH_READS");
   if (br && atoll(br) > 0) c->batchReads = atoll(br);
   if (const char *bm = getenv("GTX_BUCKET_MIN_READS")) c->bucketMinReads = atoll(bm);   // unsorted reads: batches below this use the search kernel
+  if (const char *lt = getenv("GTX_LOCAL_SCAN_MAX_TILES")) c->localMaxTiles = std::min(std::max(atoi(lt), 0), gtx::kLocalScanMaxTiles);
   const char *pf = getenv("GTX_READS_PER_LANE");        // tuning knob (1..4), default 4
   if (pf && atoi(pf) > 0) c->prefetch = atoi(pf);
   return c;
@@ -760,7 +766,7 @@ static int count_begin(gtx_ctx *c)
 {
   if (c->histDirty) {                             // only after an abandoned call
     HistSet &h = c->ix.hist;
-    for (DevBuf<u64> *b : {&h.histA, &h.histB, &h.partA, &h.partB}) HIPCHK(c, hipMemsetAsync(b->get(), 0, sizeof(u64) * b->cap, c->stream));
+    for (DevBuf<u64> *b : {&h.histA, &h.histB, &h.partA, &h.partB, &h.totals}) HIPCHK(c, hipMemsetAsync(b->get(), 0, sizeof(u64) * b->cap, c->stream));
   }
   // the info block is shared by count and coverage calls: an abandoned call of either kind leaves counts in it
   if (c->histDirty || c->covDirty) HIPCHK(c, hipMemcpyAsync(c->d_info.get() + c->infoCur, &c->h_info.get()[1], sizeof(gtx::DevInfo), hipMemcpyHostToDevice, c->stream));
@@ -783,7 +789,7 @@ static int finalize_set(gtx_ctx *c, HistSet &h, bool sumsValid, u64 *d_hits, gtx
   if (++h.epoch == 0) { HIPCHK(c, hipMemsetAsync(h.flags.get(), 0, sizeof(unsigned) * h.flags.cap, s)); h.epoch = 1; h.draws = 0; }   // (after 2^32 calls: the flags start over)
   HIPCHK(c, gtx::launch_finalize(h.histA.get(), h.histB.get(), c->histLen, h.partA.get(), h.partB.get(), sumsValid, h.prefA.get(), h.prefB.get(),
                                  c->ix.posE.get(), c->ix.posS.get(), c->ix.classBase.get(), c->nRefs, d_hits, infoNext, s, fs, h.flags.get(), h.epoch, info,
-                                 &h.draws, hist32));
+                                 &h.draws, hist32, h.totals.get(), &h.totalsTurn, c->localMaxTiles));
   return GTX_OK;
 }
 
@@ -2644,6 +2650,24 @@ int gtxi_count_device_share_async(gtx_ctx *c, const void *d_reads, const void *d
   if (c->profThis) { if (c->profEvery <= 1) HIPCHK(c, hipEventRecord(c->ev[3], run)); c->profCalls++; }
   c->ix.lastShareInfo = info;
   *d_piece = dst; *pieceLen = c->share.nRegions;
+  return GTX_OK;
+}
+
+// For the tests of the two-launch finalize: how many words of the tile totals that the NEXT such finalize on a set will write are not
+// zero (the invariant between calls: none -- the gather of the call before zeroed them).  set < 0: the context's own set, else the
+// group's set `set`.  Waits for the device.
+int gtxi_next_totals_nonzero(gtx_ctx *c, int set, int64_t *nonzero)
+{
+  if (!c || !nonzero) return GTX_E_ARG;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());
+  const HistSet &h = set < 0 ? c->ix.hist : c->ix.alt[set % GTXI_SHARE_STREAMS];
+  *nonzero = 0;
+  if (!h.totals) return GTX_OK;
+  const size_t pair = h.totals.cap / 2;                              // one turn's totals: both histograms
+  std::vector<u64> host(pair);
+  HIPCHK(c, hipMemcpy(host.data(), h.totals.get() + (size_t)(h.totalsTurn & 1) * pair, sizeof(u64) * pair, hipMemcpyDeviceToHost));
+  for (u64 v : host) *nonzero += v != 0;
   return GTX_OK;
 }
 

@@ -22,6 +22,7 @@ int gtxi_count_device_share(gtx_ctx *c, const void *d_reads, const void *d_weigh
 int gtxi_count_device_share_async(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, uint32_t flags, int slot, int set, hipStream_t run,
                                   void *direct_out, void **d_piece, int64_t *pieceLen);   // kernel + finalize on `run` with histogram set `set` (0 | 1), into the piece of compact vector `slot`
 int gtxi_last_share_info(gtx_ctx *c, gtx_count_info *info);
+int gtxi_next_totals_nonzero(gtx_ctx *c, int set, int64_t *nonzero);   // tests: words not zero in the tile totals the next two-launch finalize on a set (< 0: the context's own) writes
 void *gtxi_out_buffer(gtx_ctx *c);                      // the context's result vector in HBM (n_refs uint64)
 int gtxi_ensure_out(gtx_ctx *c, int64_t n);             // ... with room for n uint64
 int gtxi_scratch(gtx_ctx *c, size_t bytes, void **p);   // a second device buffer of the context

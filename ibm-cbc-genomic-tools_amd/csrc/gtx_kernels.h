@@ -208,11 +208,16 @@ hipError_t launch_finalize(unsigned long long *histA, unsigned long long *histB,
                            const int *posE, const int *posS, const int *classBase, long long m,
                            unsigned long long *hits, DevInfo *nextInfo, hipStream_t st, const FinalizeShare *share = nullptr,
                            unsigned *chainFlags = nullptr, unsigned epoch = 0, DevInfo *info = nullptr, unsigned long long *chainDraws = nullptr,
-                           bool hist32 = false);
+                           bool hist32 = false, unsigned long long *totals = nullptr, unsigned *totalsTurn = nullptr, int localMaxTiles = 0);
 // chainFlags (may be null): 8 x (tiles + 2) words (two 64-bit words per tile and histogram; the word behind each histogram's is the kernel's ticket counter), zero when
 // made, never written by the caller; epoch: a value no earlier call on these flags used (and not 0); info: the call's block (DevInfo::fault); chainDraws: the host's count of
 // the tickets drawn from these flags so far (0 when they are made; the launcher advances it).  With them a call whose tile sums are not valid and whose tiles are few
 // enough takes one launch for tile sums + scan (finalize_scan_chained_kernel).
+// totals (may be null): 4 x (tiles + 2) 64-bit words, zero when made, never written by the caller -- the tiles' totals of the two histograms, twice (taken in turn);
+// totalsTurn: the host's word that says which (0 when they are made; the launcher flips it).  With them a call whose tile sums are not valid, that does not take the
+// chained kernel and whose histograms have at most localMaxTiles tiles (kLocalScanMaxTiles at the most) takes two launches: a tile-local scan, then a gather that adds
+// the tiles' offsets (finalize_local_kernel, gather_hits_local_kernel) -- instead of tile sums, scan and gather.
+constexpr int kLocalScanMaxTiles = 2048;      // 2 x 2048 offsets in the gather's LDS: 16 KB with 32-bit slots, 32 KB with 64-bit ones
 hipError_t launch_coverage(const void *reads, const void *weights, long long n, const CoverArgs &a, hipStream_t st);
 hipError_t launch_coverage_finalize(const CoverArgs &a, long long histLen, const CoverGather &g, long long m,
                                     unsigned long long *cov, DevInfo *nextInfo, hipStream_t st);

@@ -31,8 +31,8 @@
 //
 // Kernels in this file: count_walk_kernel (dominant) and its two variants, count_search_kernel (order-agnostic, small
 // batches; large unsorted batches take the bucket path of gtx_bucket.hip), coverage_walk_kernel (CalcIndexCoverage, one
-// launch per boundary array), tile_sums/finalize_scan/gather_hits/gather_coverage (prefix + gather), scan_hist_kernel +
-// scan_window_kernel (genomic_scans counts).
+// launch per boundary array), tile_sums/finalize_scan/gather_hits/gather_coverage (prefix + gather; finalize_local +
+// gather_hits_local for a large call), scan_hist_kernel + scan_window_kernel (genomic_scans counts).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -1685,6 +1685,142 @@ __global__ __launch_bounds__(256) void gather_hits_kernel(const T *__restrict__ 
   hits[outIdx] = h;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Finalize of a call whose tile sums were not kept, above kChainMaxTiles tiles (2 launches, no block waits for another and none
+// reads what another block of its launch wrote: the kernel boundary is the only synchronisation):
+//   finalize_local_kernel      one block per tile and histogram: local scan only -- writes the TILE-LOCAL inclusive prefixes
+//                              LA/LB, the tile's total (plain store, one writer), and ZEROES the histograms for the next call
+//   gather_hits_local_kernel   every block scans the 2 x nTiles totals into LDS for itself (exclusive: the tiles' offsets), then
+//                              gathers with P[i] = L[i] + off[i >> kTileShift]
+// Instead of tile_sums + finalize_scan + gather_hits: no second pass over the histograms, no per-block loop over the tile sums
+// below, one kernel boundary fewer.  The offsets take 2 x nTiles x sizeof(T) bytes of LDS: kLocalScanMaxTiles bounds them.
+// Totals: 64-bit, two buffers per histogram taken in turn -- a member of a group writes the totals of ITS tiles only and the
+// others must read 0, so the gather of a call zeroes the buffer the NEXT call on the set will write (it cannot zero the one its
+// own blocks are still reading); the launcher flips the turn.
+// ---------------------------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(256) void finalize_local_kernel(T *__restrict__ ha, T *__restrict__ hb, i64 len,
+                                                             u64 *__restrict__ totA, u64 *__restrict__ totB,
+                                                             T *__restrict__ pa, T *__restrict__ pb, const int *__restrict__ tileList)
+{
+  // grid (tiles, 2) and tile ownership as in finalize_scan_kernel; thread t owns 4 consecutive slots
+  __shared__ u64 wsum[4];
+  T *__restrict__ h = blockIdx.y ? hb : ha;
+  T *__restrict__ p = blockIdx.y ? pb : pa;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int tile = tileList ? tileList[blockIdx.x] : (int)blockIdx.x;
+  const i64 i0 = (i64)tile * kTile + (i64)threadIdx.x * 4;
+  const bool full = i0 + 4 <= len;                   // (the histograms come from hipMalloc, i0 is a multiple of 4)
+  u64 v[4];
+  if (full) load4<T>(h + i0, v);
+  else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = i0 + k < len ? (u64)h[i0 + k] : 0;
+  }
+  v[1] += v[0]; v[2] += v[1]; v[3] += v[2];
+  const u64 x = wave_scan_add64(v[3]);             // inclusive scan of the thread totals across the wave (DPP)
+  if (lane == 63) wsum[wv] = x;
+  __syncthreads();
+  u64 o = x - v[3];
+  for (int k = 0; k < wv; k++) o += wsum[k];
+  if (full) { store4<T>(p + i0, v[0] + o, v[1] + o, v[2] + o, v[3] + o); store4<T>(h + i0, 0, 0, 0, 0); }
+  else {
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (i0 + k < len) { p[i0 + k] = (T)(v[k] + o); h[i0 + k] = 0; }
+  }
+  if (threadIdx.x == 255) (blockIdx.y ? totB : totA)[tile] = o + v[3];   // the last thread's inclusive prefix: the tile's total
+}
+
+// Block shape of the gather: kGatherLocalThreads x kGatherLocalPer regions per block, so that a block pays the scan of the totals
+// once for many regions and the ~1 M regions of the headline shape are one round of resident blocks, one per CU (DESIGN.md 4.3
+// has the shapes that were measured)
+static constexpr int kGatherLocalThreads = 1024, kGatherLocalPer = 4;
+static constexpr int kGatherLocalTot = kLocalScanMaxTiles / kGatherLocalThreads;      // totals a thread loads, at the most
+static_assert(kLocalScanMaxTiles % kGatherLocalThreads == 0, "gather_hits_local_kernel: every tile's total has a thread");
+
+// (T = unsigned: offsets, prefixes and differences are taken modulo 2^32.  L[i] + off[tile] is the global prefix modulo 2^32 --
+// truncation commutes with the additions of the scan -- and a count is a difference of differences of global prefixes that is
+// itself below the number of reads, which is below 2^32 for a call with 32-bit slots: the same argument as gather_hits_kernel's.
+// T = u64, weights: modulo 2^64, negative weights included, as before.)
+template <class T>
+__global__ __launch_bounds__(kGatherLocalThreads) void gather_hits_local_kernel(const T *__restrict__ pa, const T *__restrict__ pb,
+                                                          const u64 *__restrict__ totA, const u64 *__restrict__ totB,
+                                                          u64 *__restrict__ nextTotA, u64 *__restrict__ nextTotB,
+                                                          const int *__restrict__ posE, const int *__restrict__ posS,
+                                                          const int *__restrict__ classBase, i64 m, u64 *__restrict__ hits,
+                                                          u64 *__restrict__ ta, u64 *__restrict__ tb, int nTiles, DevInfo *nextInfo,
+                                                          const int *__restrict__ regionList, int scatter)
+{
+  // regionList / scatter: as in gather_hits_kernel
+  extern __shared__ u64 ldsOff[];                    // T[2 * nTiles]: the tiles' offsets, histogram A then B
+  __shared__ u64 wtot[2][kGatherLocalThreads / 64];
+  T *off = (T *)ldsOff;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  // the block's regions: issued first, used last
+  const i64 first = (i64)blockIdx.x * (kGatherLocalThreads * kGatherLocalPer) + threadIdx.x;
+  i64 outIdx[kGatherLocalPer];
+  int pe[kGatherLocalPer], ps[kGatherLocalPer], cb[kGatherLocalPer];
+#pragma unroll
+  for (int j = 0; j < kGatherLocalPer; j++) {
+    i64 k = first + (i64)j * kGatherLocalThreads;
+    outIdx[j] = k < m ? k : -1;
+    pe[j] = -1; ps[j] = 0; cb[j] = -1;
+    if (k < m) {
+      if (regionList) { k = regionList[k]; if (scatter) outIdx[j] = k; }
+      pe[j] = posE[k]; ps[j] = posS[k]; cb[j] = classBase[k];       // cb: slot just below the class's first slot, -1 if none
+    }
+  }
+  // the tiles' totals: thread t takes `per` consecutive tiles (neighbouring threads, neighbouring words; nTiles <= kLocalScanMaxTiles:
+  // the launcher's rule)
+  const int per = (nTiles + kGatherLocalThreads - 1) / kGatherLocalThreads, t0 = (int)threadIdx.x * per;
+  u64 ra[kGatherLocalTot], rb[kGatherLocalTot];
+#pragma unroll
+  for (int q = 0; q < kGatherLocalTot; q++) {
+    const bool in = q < per && t0 + q < nTiles;
+    ra[q] = in ? totA[t0 + q] : 0; rb[q] = in ? totB[t0 + q] : 0;
+  }
+  // four look-ups per region, all of a thread's in flight together while the block scans the totals: they need the regions' slots
+  // only, the tiles' offsets are added at the end (an absent base or region: slot 0 is read and dropped)
+  T ve[kGatherLocalPer], vs[kGatherLocalPer], ba[kGatherLocalPer], bb[kGatherLocalPer];
+#pragma unroll
+  for (int j = 0; j < kGatherLocalPer; j++) {
+    const int e = pe[j] >= 0 ? pe[j] : 0, s = pe[j] >= 0 ? ps[j] : 0, c = cb[j] >= 0 ? cb[j] : 0;
+    ve[j] = pa[e]; vs[j] = pb[s]; ba[j] = pa[c]; bb[j] = pb[c];
+  }
+  // exclusive scan of each histogram's totals across the block, into LDS: the tiles' offsets
+  u64 sa = 0, sb = 0;
+#pragma unroll
+  for (int q = 0; q < kGatherLocalTot; q++) { sa += ra[q]; sb += rb[q]; }
+  const u64 xa = wave_scan_add64(sa), xb = wave_scan_add64(sb);
+  if (lane == 63) { wtot[0][wv] = xa; wtot[1][wv] = xb; }
+  __syncthreads();
+  u64 oa = xa - sa, ob = xb - sb;
+  for (int k = 0; k < wv; k++) { oa += wtot[0][k]; ob += wtot[1][k]; }
+#pragma unroll
+  for (int q = 0; q < kGatherLocalTot; q++) {
+    if (q < per && t0 + q < nTiles) { off[t0 + q] = (T)oa; off[nTiles + t0 + q] = (T)ob; }
+    oa += ra[q]; ob += rb[q];
+  }
+  __syncthreads();
+  // the tile sums (a search kernel may have left some) and the totals the NEXT call on this set writes: clean
+  const i64 gtid = (i64)blockIdx.x * kGatherLocalThreads + threadIdx.x;
+  for (i64 i = gtid; i < nTiles; i += (i64)gridDim.x * kGatherLocalThreads) { ta[i] = 0; tb[i] = 0; nextTotA[i] = 0; nextTotB[i] = 0; }
+  if (gtid == 0) { nextInfo->first_unsorted = INT64_MAX; nextInfo->n_no_class = 0; nextInfo->n_degenerate = 0; nextInfo->first_degenerate = INT64_MAX; nextInfo->n_unplaced = 0; nextInfo->fault = 0; }
+#pragma unroll
+  for (int j = 0; j < kGatherLocalPer; j++) {
+    if (outIdx[j] < 0) continue;
+    u64 h = 0;
+    if (pe[j] >= 0) {
+      const int e = pe[j], s = ps[j], c = cb[j] >= 0 ? cb[j] : 0;
+      const T fa = (T)(ve[j] + off[e >> kTileShift]), fb = (T)(vs[j] + off[nTiles + (s >> kTileShift)]);
+      const T ga = cb[j] >= 0 ? (T)(ba[j] + off[c >> kTileShift]) : (T)0, gb = cb[j] >= 0 ? (T)(bb[j] + off[nTiles + (c >> kTileShift)]) : (T)0;
+      h = (u64)(T)((T)(fa - ga) - (T)(fb - gb));
+    }
+    hits[outIdx[j]] = h;
+  }
+}
+
 __global__ __launch_bounds__(256) void gather_coverage_kernel(CoverGather g, i64 m, u64 *__restrict__ cov, int nTiles, DevInfo *nextInfo)
 {
   i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2024,7 +2160,8 @@ hipError_t launch_tile_sums(u64 *histA, u64 *histB, i64 histLen, u64 *tileA, u64
 template <class T>
 static hipError_t launch_finalize_t(T *histA, T *histB, i64 histLen, u64 *tileA, u64 *tileB, bool tileSumsValid, T *prefA, T *prefB,
                                     const int *posE, const int *posS, const int *classBase, i64 m, u64 *hits, DevInfo *nextInfo, hipStream_t st,
-                                    const FinalizeShare *share, unsigned *chainFlags, unsigned epoch, DevInfo *info, unsigned long long *chainDraws)
+                                    const FinalizeShare *share, unsigned *chainFlags, unsigned epoch, DevInfo *info, unsigned long long *chainDraws,
+                                    u64 *totals, unsigned *totalsTurn, int localMaxTiles)
 {
   const int nb = scan_tiles(histLen);
   const int nbRun = share ? share->nTiles : nb;                // a group member: the tiles of its classes, its regions (compact)
@@ -2038,6 +2175,18 @@ static hipError_t launch_finalize_t(T *histA, T *histB, i64 histLen, u64 *tileA,
       *chainDraws += (unsigned long long)nbRun;
     }
     else {
+      if (!tileSumsValid && totals && totalsTurn && nb <= localMaxTiles) {
+        // local scan + gather with the tiles' offsets: the totals of this turn (all zero on entry), the other turn's zeroed for the next call
+        const size_t parts = (size_t)nb + 2;
+        u64 *tot = totals + (size_t)(*totalsTurn & 1) * 2 * parts, *next = totals + (size_t)((*totalsTurn & 1) ^ 1) * 2 * parts;
+        finalize_local_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, tot, tot + parts, prefA, prefB, tl);
+        const i64 mm = share ? share->nRegions : m, perBlock = (i64)kGatherLocalThreads * kGatherLocalPer;
+        gather_hits_local_kernel<T><<<(unsigned)((std::max<i64>(mm, 1) + perBlock - 1) / perBlock), kGatherLocalThreads, sizeof(T) * 2 * (size_t)nb, st>>>(
+            prefA, prefB, tot, tot + parts, next, next + parts, posE, posS, classBase, mm, hits, tileA, tileB, nb, nextInfo,
+            share ? share->regionList : nullptr, share && share->scatter ? 1 : 0);
+        *totalsTurn ^= 1;
+        return hipGetLastError();
+      }
       if (!tileSumsValid) tile_sums_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, tileA, tileB, tl);
       finalize_scan_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, tileA, tileB, prefA, prefB, tl);
     }
@@ -2051,13 +2200,15 @@ static hipError_t launch_finalize_t(T *histA, T *histB, i64 histLen, u64 *tileA,
 
 hipError_t launch_finalize(u64 *histA, u64 *histB, i64 histLen, u64 *tileA, u64 *tileB, bool tileSumsValid, u64 *prefA, u64 *prefB,
                            const int *posE, const int *posS, const int *classBase, i64 m, u64 *hits, DevInfo *nextInfo, hipStream_t st,
-                           const FinalizeShare *share, unsigned *chainFlags, unsigned epoch, DevInfo *info, unsigned long long *chainDraws, bool hist32)
+                           const FinalizeShare *share, unsigned *chainFlags, unsigned epoch, DevInfo *info, unsigned long long *chainDraws, bool hist32,
+                           u64 *totals, unsigned *totalsTurn, int localMaxTiles)
 {
+  if (localMaxTiles > kLocalScanMaxTiles) localMaxTiles = kLocalScanMaxTiles;     // (the gather's LDS)
   // hist32: the call's streaming kernel counted into 32-bit slots (CountArgs::hist32): the same buffers, read as unsigned[]
   if (hist32) return launch_finalize_t<unsigned>((unsigned *)histA, (unsigned *)histB, histLen, tileA, tileB, tileSumsValid, (unsigned *)prefA, (unsigned *)prefB,
-                                                 posE, posS, classBase, m, hits, nextInfo, st, share, chainFlags, epoch, info, chainDraws);
+                                                 posE, posS, classBase, m, hits, nextInfo, st, share, chainFlags, epoch, info, chainDraws, totals, totalsTurn, localMaxTiles);
   return launch_finalize_t<u64>(histA, histB, histLen, tileA, tileB, tileSumsValid, prefA, prefB, posE, posS, classBase, m, hits, nextInfo, st, share, chainFlags, epoch,
-                                info, chainDraws);
+                                info, chainDraws, totals, totalsTurn, localMaxTiles);
 }
 
 hipError_t launch_coverage(const void *reads, const void *weights, i64 n, const CoverArgs &a, hipStream_t st)
