@@ -1389,6 +1389,8 @@ bool SortedGenomicRegionSetOverlaps::Done() { return current_qreg == NULL || (in
 // ---------------------------------------------------------------------------------------------------
 // scanners
 // ---------------------------------------------------------------------------------------------------
+static int g_keep_next = -1;                                      // KeepNextOnDevice: the slot the next scanner keeps its windows in
+
 GenomicRegionSetScanner::GenomicRegionSetScanner(GenomicRegionSet *R, StringLIntMap *bounds, long int win_step, long int win_size,
                                                  long int max_label_value, bool ignore_strand, char preprocess)
 {
@@ -1400,6 +1402,7 @@ GenomicRegionSetScanner::GenomicRegionSetScanner(GenomicRegionSet *R, StringLInt
   n_win_combine = win_size / win_step;
   cur_block = 0; cur_win = 0; computed = false; total_label_value = 0;
   halt_set = false; halt_block = 0; halt_win = 0; halt_line = 0; halt_no_prefix = false;
+  keep_slot = g_keep_next; g_keep_next = -1;
 }
 
 GenomicRegionSetScanner::~GenomicRegionSetScanner() {}
@@ -1429,7 +1432,7 @@ void GenomicRegionSetScanner::Compute(bool sorted_rules)
       total += nw;
     }
   }
-  values.assign((size_t)std::max<long long>(total, 1), 0);
+  values.assign((size_t)std::max<long long>(keep_slot >= 0 ? 1 : total, 1), 0);
   if (n_chrom == 0) return;
   if (sorted_rules && preprocess == 'p') { ComputeMappable(class_len, class_off); return; }
 
@@ -1506,10 +1509,12 @@ void GenomicRegionSetScanner::Compute(bool sorted_rules)
   if (!grp) device_side();                                         // (an in-memory input: DrainSet has not run the hand-over's first step)
   if (one) {
     int64_t text_labels = 0;                                       // the lines the device took: their label values are summed there
-    check_one(gtx_scan_end(one, (uint64_t *)values.data(), &text_labels));
+    if (keep_slot >= 0) check_one(gtx_scan_end_keep(one, keep_slot, &text_labels));
+    else check_one(gtx_scan_end(one, (uint64_t *)values.data(), &text_labels));
     total_label_value += (long int)text_labels;
     return;
   }
+  if (keep_slot >= 0) { keep_error = "windows are kept on the device on one GPU only!"; return; }
   CheckGrp(grp, gtx_group_scan(grp, tri.data(), w.empty() ? NULL : w.data(), (int64_t)(tri.size() / 3), class_len.data(), n_chrom * ns,
                                (int32_t)win_step, (int32_t)win_size, prep, rule_flags | (LooksSortedVec(tri) ? GTX_READS_SORTED : 0u),
                                (uint64_t *)values.data(), class_off.data()));
@@ -1595,6 +1600,67 @@ void GenomicRegionSetScanner::ComputeMappable(const std::vector<int32_t> &class_
                                GTX_ZERO_LENGTH_OK | (order ? 0u : GTX_READS_SORTED), (uint64_t *)values.data(), class_off.data()));
 }
 
+void GenomicRegionSetScanner::KeepNextOnDevice(int slot)
+{
+  if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) { std::cerr << "Error: [GenomicRegionSetScanner] no such device slot!\n"; exit(1); }
+  g_keep_next = slot;
+}
+
+long long GenomicRegionSetScanner::WindowCount()
+{
+  if (!computed) Compute(false);
+  return block_offset.empty() ? 0 : block_offset.back() + n_windows.back();
+}
+
+void GenomicRegionSetScanner::PrintIntervalAt(FILE *out_file, long long window)
+{
+  if (!computed) Compute(false);
+  const int ns = ignore_strand ? 1 : 2;
+  const size_t b = (size_t)(std::upper_bound(block_offset.begin(), block_offset.end(), window) - block_offset.begin()) - 1;   // (empty blocks share an offset: the last one at or below holds it)
+  const long long k = window - block_offset[b];
+  fprintf(out_file, "%s %c %lld %lld", chrom_names[b / ns].c_str(), (b % ns) ? '-' : '+', (long long)win_step * k + 1, (long long)win_step * k + win_size);
+}
+
+bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_control, const std::vector<std::vector<int> > &tables, long int win_size,
+                      std::vector<long long> &ordinals, std::vector<int> &rows, std::string *error)
+{
+  ordinals.clear(); rows.clear();
+  if (n_tested < 1 || n_tested > 4 || (n_control != 0 && n_control != n_tested) || (int)tables.size() != n_tested || win_size < 1 || win_size >= INT_MAX) {
+    *error = "[GtxSelectWindows] one to four tested inputs, a control for each or for none, a table for each!"; return false;
+  }
+  gtx_group *grp = Devices();
+  if (gtx_group_size(grp) != 1) { *error = "this operation runs on one GPU only!"; return false; }
+  gtx_ctx *one = gtx_group_ctx(grp, 0);
+  const void *d_vec[8] = {};
+  const int32_t *tab[4] = {};
+  long long n = -1;
+  for (int f = 0; f < n_tested + n_control; f++) {
+    const long long nf = scanners[f]->WindowCount();
+    if (!scanners[f]->KeepError().empty()) { *error = scanners[f]->KeepError(); return false; }
+    void *d = NULL; int64_t kept = 0;                                // (bounds without a window: nothing was scanned, nothing is selected)
+    if (nf > 0 && (scanners[f]->KeptSlot() < 0 || gtx_scan_kept(one, scanners[f]->KeptSlot(), &d, &kept) != GTX_OK || (long long)kept != nf)) {
+      *error = "[GtxSelectWindows] an input's windows are not on the device!"; return false;
+    }
+    if (n >= 0 && nf != n) { *error = "[GtxSelectWindows] the inputs differ in their number of windows!"; return false; }
+    n = nf; d_vec[f] = d;
+  }
+  for (int f = 0; f < n_tested; f++) {
+    if (tables[(size_t)f].size() != (size_t)(n_control ? win_size + 1 : 1)) { *error = "[GtxSelectWindows] a table of the wrong size!"; return false; }
+    tab[f] = tables[(size_t)f].data();
+  }
+  const size_t cols = (size_t)(n_tested + n_control);
+  int64_t cap = std::max<int64_t>(1 << 16, n / 64), kept = 0;        // a retry with the reported count when this was too small
+  for (;;) {
+    ordinals.resize((size_t)cap); rows.resize((size_t)cap * cols);
+    const int rc = gtx_window_select(one, d_vec, n_control ? d_vec + n_tested : NULL, n_tested, n, (int32_t)win_size, tab, cap, (int64_t *)ordinals.data(), rows.data(), &kept);
+    if (rc != GTX_OK) { *error = std::string("[gtx] ") + gtx_last_error(one); return false; }
+    if (kept <= cap) break;
+    cap = kept;
+  }
+  ordinals.resize((size_t)kept); rows.resize((size_t)kept * cols);
+  return true;
+}
+
 long int GenomicRegionSetScanner::TotalLabelValue()
 {
   if (!computed) Compute(false);
@@ -1641,6 +1707,7 @@ void GenomicRegionSetScanner::RaiseHalt()
 long int GenomicRegionSetScanner::Next()
 {
   if (!computed) Compute(false);
+  if (keep_slot >= 0) { std::cerr << "Error: [GenomicRegionSetScanner] the windows were kept on the device!\n"; exit(1); }
   while (cur_block < n_windows.size()) {
     if (halt_set && (cur_block > halt_block || (cur_block == halt_block && cur_win >= halt_win))) RaiseHalt();
     if (cur_win < n_windows[cur_block]) { cur_win++; return (long int)values[(size_t)(block_offset[cur_block] + cur_win - 1)]; }
@@ -1653,6 +1720,7 @@ long int GenomicRegionSetScanner::Next()
 void GenomicRegionSetScanner::PrintRemaining(FILE *out_file, long int min_value)
 {
   if (!computed) Compute(false);
+  if (keep_slot >= 0) { std::cerr << "Error: [GenomicRegionSetScanner] the windows were kept on the device!\n"; exit(1); }
   const int ns = ignore_strand ? 1 : 2;
   std::vector<char> buf; buf.reserve(8u << 20);
   auto put_num = [&](long int v) {

@@ -300,6 +300,17 @@ class GenomicRegionSetScanner
   // Next() / PrintInterval() loop prints (genomic_scans.cpp:421-428), formatted in bulk (three stdio calls per window are half a
   // second for the three million windows of a genome at -w 1000)
   void PrintRemaining(FILE *out_file, long int min_value);
+  // MI355X path: the windows of the NEXT scanner that is constructed stay in slot `slot` (0..7) of the device context instead of
+  // coming to the host (gtx_scan_end_keep) -- said before the constructor because the unsorted scanner scans in its constructor, as
+  // the reference's does.  TotalLabelValue() works as before; Next() and PrintRemaining() have no values to hand out and end the
+  // run; the windows are read through GtxSelectWindows.  One GPU only (KeepError() says so otherwise).
+  static void KeepNextOnDevice(int slot);
+  int KeptSlot() const { return keep_slot; }
+  long long WindowCount();                                        // windows of all blocks together (computes)
+  const std::string &KeepError() const { return keep_error; }
+  // "chr strand start stop" of the window with this ordinal in iteration order (0-based over all blocks): what PrintInterval()
+  // prints when Next() has just returned that window
+  void PrintIntervalAt(FILE *out_file, long long window);
 
   GenomicRegionSet *R;
   StringLIntMap *bounds;
@@ -323,6 +334,8 @@ class GenomicRegionSetScanner
   // line and notes where the walk stops: all windows of the blocks before halt_block, halt_win windows of that block, then the error.
   bool halt_set; size_t halt_block; long int halt_win; long int halt_line; bool halt_no_prefix; std::string halt_msg;
   void RaiseHalt();
+  int keep_slot;                                                  // -1: the windows come to `values`
+  std::string keep_error;
 };
 
 class SortedGenomicRegionSetScanner : public GenomicRegionSetScanner
@@ -397,6 +410,15 @@ struct GtxSignalSpec {
   long int n_bins;
 };
 unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *overlaps, const GtxSignalSpec &spec, std::vector<double> &bins);
+
+// The data pass of genomic_apps peakdiff (ScanReadFiles, gtools/genomic_apps.cpp:385-412) on the device: scanners[0 .. n_tested) are the
+// tested inputs, scanners[n_tested .. n_tested + n_control) their controls (n_control = 0 or n_tested), all made behind KeepNextOnDevice with
+// slots of their own over the same bounds and geometry; tables[f] is tested input f's critical counts (gtx_peakdiff.h: win_size + 1
+// entries with controls, one without).  Returns the kept windows' ordinals in window order and, per kept window, n_tested + n_control
+// counts clamped to win_size (gtx_window_select; the result buffers grow and the call is repeated when they were too small).  False
+// with *error set when the scanners cannot be selected over (more than one GPU, unequal window counts).
+bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_control, const std::vector<std::vector<int> > &tables, long int win_size,
+                      std::vector<long long> &ordinals, std::vector<int> &rows, std::string *error);
 
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxAcceptSAM(bool on);                                      // false: a SAM file is "unsupported input format!" (drivers that print query lines; default true)

@@ -23,6 +23,7 @@
 #include "gtx_signal.h"
 #include "gtx_text.h"
 #include "gtx_link.h"
+#include "gtx_select.h"
 #include "gtx_internal.h"
 
 typedef unsigned long long u64;
@@ -245,6 +246,10 @@ struct gtx_ctx {
   // gtx_scan_begin .. gtx_scan_end: the open scan's geometry and what its batches have added so far
   struct ScanOpen { bool open = false, weighted = false; gtx::ScanArgs a; std::vector<int32_t> classLen; int64_t extent = 0; char prep = '1'; uint32_t flags = 0;
                     DevBuf<unsigned long long> labelSum; } scan;
+  // gtx_scan_end_keep: window vectors that stay in HBM (their extents beside them); the window selection's tile counts and bases,
+  // its tables, the total on the host, the host entry's results
+  DevBuf<u64> kept[GTX_SCAN_KEEP_SLOTS]; int64_t keptLen[GTX_SCAN_KEEP_SLOTS] = {};
+  DevBuf<unsigned> selCount; DevBuf<long long> selBase, selOrd; DevBuf<int> selTab, selRows; PinBuf<long long> selTotal;
   int64_t seamUnsorted = INT64_MAX;    // first order violation found at a seam between batches (host-side check)
 
   int64_t batchReads = 8ll << 20;       // reads per device batch of the host-buffer entry points (96 MiB of triples: ~2 ms of PCIe)
@@ -2331,6 +2336,117 @@ int gtx_scan_end(gtx_ctx *c, uint64_t *out, int64_t *labelSum)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipStreamSynchronize(c->copyStream));
   if (labelSum) *labelSum = (int64_t)sum;
+  return GTX_OK;
+}
+
+// gtx_scan_end with the windows left on the device: the sliding sums are written into the slot's own vector (zero first: class_offsets
+// may leave gaps), nothing but the label sum comes to the host
+int gtx_scan_end_keep(gtx_ctx *c, int slot, int64_t *labelSum)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->scan.open) return fail(c, GTX_E_STATE, "gtx_scan_end_keep: gtx_scan_begin has not been called");
+  gtx_ctx::ScanOpen &s = c->scan;
+  s.open = false;                                                    // (a refused slot ends the scan too, like gtx_scan_end's null output)
+  if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_end_keep: slot out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((size_t)s.extent > c->kept[slot].cap || !c->kept[slot]) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));                      // a selection may still be reading what the slot held
+    HIPCHK(c, c->kept[slot].alloc((size_t)std::max<int64_t>(s.extent, 1)));
+  }
+  c->keptLen[slot] = s.extent;
+  if (s.extent > 0) HIPCHK(c, hipMemsetAsync(c->kept[slot].get(), 0, (size_t)s.extent * sizeof(u64), c->stream));
+  HIPCHK(c, gtx::launch_scan_windows(c->micro.get(), s.weighted, s.a, c->scanTotalTiles, c->kept[slot].get(), c->stream));
+  unsigned long long sum = 0;
+  HIPCHK(c, hipMemcpyAsync(&sum, s.labelSum.get(), sizeof sum, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->copyStream));
+  if (labelSum) *labelSum = (int64_t)sum;
+  return GTX_OK;
+}
+
+int gtx_scan_kept(gtx_ctx *c, int slot, void **d_ptr, int64_t *n_windows)
+{
+  if (!c) return GTX_E_ARG;
+  if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_kept: slot out of range");
+  if (!c->kept[slot]) return fail(c, GTX_E_STATE, "gtx_scan_kept: the slot is empty");
+  if (d_ptr) *d_ptr = c->kept[slot].get();
+  if (n_windows) *n_windows = c->keptLen[slot];
+  return GTX_OK;
+}
+
+int gtx_scan_drop(gtx_ctx *c, int slot)
+{
+  if (!c) return GTX_E_ARG;
+  if (slot < -1 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_drop: slot out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < GTX_SCAN_KEEP_SLOTS; k++) if (slot == -1 || slot == k) { c->kept[k].reset(); c->keptLen[k] = 0; }
+  return GTX_OK;
+}
+
+// ---- window selection (gtx_select.hip) ----
+int gtx_window_select_limits(int32_t *tile, int32_t *lds_max_w)
+{
+  if (tile) *tile = gtx::kSelectTile;
+  if (lds_max_w) *lds_max_w = gtx::kSelectLdsMaxW;
+  return GTX_OK;
+}
+
+int gtx_window_select_device(gtx_ctx *c, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows, int32_t W,
+                             const int32_t *const *kcrit, int64_t capacity, void *d_ordinals, void *d_rows, int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  if (n_tested < 1 || n_tested > gtx::kSelectMaxTested || !d_tested || !kcrit || !n_kept) return fail(c, GTX_E_ARG, "gtx_window_select: 1 to 4 tested vectors, their tables and n_kept are required");
+  if (n_windows < 0 || W < 1 || W == INT32_MAX || capacity < 0) return fail(c, GTX_E_ARG, "gtx_window_select: bad window count, window size or capacity");
+  int n_ctl = 0;
+  for (int f = 0; f < n_tested; f++) n_ctl += d_control && d_control[f] ? 1 : 0;
+  if (n_ctl != 0 && n_ctl != n_tested) return fail(c, GTX_E_ARG, "gtx_window_select: a control for every tested vector, or for none");
+  const bool ctl = n_ctl > 0;
+  gtx::SelectArgs a = {};
+  for (int f = 0; f < n_tested; f++) {
+    if (!kcrit[f]) return fail(c, GTX_E_ARG, "gtx_window_select: null table");
+    a.tested[f] = (const u64 *)d_tested[f]; a.control[f] = ctl ? (const u64 *)d_control[f] : nullptr;
+    if (n_windows > 0 && (!a.tested[f] || ((uintptr_t)a.tested[f] & 15) || ((uintptr_t)a.control[f] & 15))) return fail(c, GTX_E_ARG, "gtx_window_select: vectors must be 16-byte aligned device memory");
+  }
+  if (capacity > 0 && (!d_ordinals || !d_rows)) return fail(c, GTX_E_ARG, "gtx_window_select: null output");
+  *n_kept = 0;
+  if (n_windows == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t stride = ctl ? (size_t)W + 1 : 1;
+  const int64_t nt = gtx::select_tiles(n_windows);
+  if (!c->selTotal) HIPCHK(c, c->selTotal.alloc(1));
+  if (stride * n_tested > c->selTab.cap || (size_t)nt > c->selCount.cap || (size_t)nt + 1 > c->selBase.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->selTab.reserve(stride * n_tested)); HIPCHK(c, c->selCount.reserve((size_t)nt)); HIPCHK(c, c->selBase.reserve((size_t)nt + 1));
+  }
+  // (the tables are pageable host memory: these copies return when the source has been read)
+  for (int f = 0; f < n_tested; f++) HIPCHK(c, hipMemcpyAsync(c->selTab.get() + f * stride, kcrit[f], stride * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  a.tab = c->selTab.get(); a.nTested = n_tested; a.W = W; a.n = n_windows;
+  HIPCHK(c, gtx::launch_window_select(a, c->selCount.get(), c->selBase.get(), capacity, (long long *)d_ordinals, (int *)d_rows, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->selTotal.get(), c->selBase.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_kept = *c->selTotal.get();
+  return GTX_OK;
+}
+
+int gtx_window_select(gtx_ctx *c, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows, int32_t W,
+                      const int32_t *const *kcrit, int64_t capacity, int64_t *ordinals, int32_t *rows, int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  if (capacity < 0 || (capacity > 0 && (!ordinals || !rows))) return fail(c, GTX_E_ARG, "gtx_window_select: null output");
+  if (n_tested < 1 || n_tested > gtx::kSelectMaxTested) return fail(c, GTX_E_ARG, "gtx_window_select: 1 to 4 tested vectors, their tables and n_kept are required");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t cols = (size_t)n_tested * ((d_control && d_control[0]) ? 2 : 1);
+  if ((size_t)capacity > c->selOrd.cap || (size_t)capacity * cols > c->selRows.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->selOrd.reserve((size_t)capacity)); HIPCHK(c, c->selRows.reserve((size_t)capacity * cols));
+  }
+  int rc = gtx_window_select_device(c, d_tested, d_control, n_tested, n_windows, W, kcrit, capacity, c->selOrd.get(), c->selRows.get(), n_kept); if (rc) return rc;
+  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
+  if (got) {
+    HIPCHK(c, hipMemcpy(ordinals, c->selOrd.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rows, c->selRows.get(), got * cols * sizeof(int), hipMemcpyDeviceToHost));
+  }
   return GTX_OK;
 }
 

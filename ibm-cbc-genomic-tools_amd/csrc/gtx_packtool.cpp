@@ -18,6 +18,7 @@
 
 #include "gtx_bed.h"
 #include "gtx_stats.h"
+#include "gtx_peakdiff.h"
 
 using namespace gtxhost;
 
@@ -135,6 +136,15 @@ int main(int argc, char **argv)
       else if (n >= 2 && kind == 'g') printf("%.17g\n", gtxstats::GaussianQ(x));
       else { fprintf(stderr, "bad query: %s", line); return 2; }
     }
+    return 0;
+  }
+  if (m == "critical") {
+    // gtx_packtool critical P W CUTOFF CONTROL : peakdiff's table of critical counts (gtx_peakdiff.h), one per line -- W + 1 lines
+    // with CONTROL = 1 (one per control count), one line with CONTROL = 0
+    if (argc != 6) { fprintf(stderr, "usage: gtx_packtool critical P W CUTOFF CONTROL\n"); return 2; }
+    const long W = atol(argv[3]);
+    if (W < 1) { fprintf(stderr, "bad window size: %s\n", argv[3]); return 2; }
+    for (int k : gtxstats::CriticalCounts(atof(argv[2]), W, atof(argv[4]), atoi(argv[5]) != 0)) printf("%d\n", k);
     return 0;
   }
   if (m == "ou") opt.mode = PACK_OVERLAPS_UNSORTED; else if (m == "os") opt.mode = PACK_OVERLAPS_SORTED;

@@ -27,6 +27,7 @@ LINK_SUM = 1              # gtx_link: fold the values (at most one of the three)
 LINK_MIN = 2
 LINK_MAX = 4
 LINK_TILE = 2048          # GTX_LINK_TILE: regions per block of link's scans
+SCAN_KEEP_SLOTS = 8       # GTX_SCAN_KEEP_SLOTS: window vectors a context keeps in HBM
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
@@ -118,6 +119,14 @@ ABI = {
     "gtx_scan_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32]),
     "gtx_scan_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_scan_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_scan_end_keep": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gtx_scan_kept": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_scan_drop": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "gtx_window_select_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_window_select_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_window_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_link": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
@@ -256,6 +265,14 @@ def scan_layout(class_len, win_step, win_size):
         off.append(tot)
         tot += lib.gtx_scan_n_windows(int(ln), int(win_step), int(win_size))
     return np.asarray(off, dtype=np.int64), tot
+
+
+def window_select_limits():
+    """(tile, lds_max_w) of gtx_window_select_limits: windows per tile of the selection's passes; the largest window size whose
+    tables sit in LDS with four tested vectors and controls"""
+    t, w = ctypes.c_int32(), ctypes.c_int32()
+    load().gtx_window_select_limits(ctypes.byref(t), ctypes.byref(w))
+    return int(t.value), int(w.value)
 
 
 class Engine:
@@ -629,6 +646,67 @@ class Engine:
         labels = ctypes.c_int64(0)
         self._chk(self.lib.gtx_scan_end(self.ctx, _ptr(out), ctypes.byref(labels)))
         return out[:tot], off, int(labels.value), verdicts
+
+    def scan_keep(self, slot, reads, class_len, win_step, win_size, preprocess="1", weights=None, flags=0):
+        """gtx_scan_begin / gtx_scan_add / gtx_scan_end_keep: the windows of `reads` stay in slot `slot` of the context's HBM.
+        Returns (device address, number of windows, class offsets)."""
+        reads = _triples(reads)
+        cl = np.ascontiguousarray(class_len, dtype=np.int32)
+        off, _ = scan_layout(cl, win_step, win_size)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32)
+        self._chk(self.lib.gtx_scan_begin(self.ctx, _ptr(cl), len(cl), int(win_step), int(win_size), preprocess.encode()[0:1], int(flags), int(w is not None), _ptr(off)))
+        rc = self.lib.gtx_scan_add(self.ctx, _ptr(reads), _ptr(w), reads.shape[0], int(flags) & READS_UNSORTED)
+        if rc != 0:
+            self.lib.gtx_scan_end(self.ctx, None, None)            # close the open scan before the error is raised
+            self._chk(rc)
+        self._chk(self.lib.gtx_scan_end_keep(self.ctx, int(slot), None))
+        return self.scan_kept(slot) + (off,)
+
+    def scan_kept(self, slot):
+        """(device address, number of windows) of a kept slot"""
+        d, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._chk(self.lib.gtx_scan_kept(self.ctx, int(slot), ctypes.byref(d), ctypes.byref(n)))
+        return int(d.value or 0), int(n.value)
+
+    def scan_drop(self, slot=-1):
+        """free a kept slot (-1: all of them)"""
+        self._chk(self.lib.gtx_scan_drop(self.ctx, int(slot)))
+
+    def window_select(self, tested, tables, window_size, controls=None, n_windows=None, capacity=None, device_out=None):
+        """gtx_window_select over window vectors in HBM.  tested / controls: kept slots (small ints, n_windows taken from the slot) or
+        raw device addresses (n_windows required); tables: per tested vector its critical counts (window_size + 1 entries with
+        controls, one without).  Returns (ordinals int64, rows int32 [kept, columns], number kept); when the number kept exceeds
+        `capacity` only the first `capacity` windows are returned.  capacity=None grows and repeats the call until everything fits.
+        device_out=(d_ordinals, d_rows): gtx_window_select_device into the caller's device buffers (capacity required), returns the
+        number kept."""
+        def addr(v):
+            if isinstance(v, (int, np.integer)) and 0 <= int(v) < SCAN_KEEP_SLOTS:
+                return self.scan_kept(int(v))
+            return int(v), None
+        t = [addr(v) for v in tested]
+        c = None if controls is None else [(None, None) if v is None else addr(v) for v in controls]
+        if n_windows is None:
+            n_windows = t[0][1]
+        nt = len(t)
+        d_t = (ctypes.c_void_p * max(nt, 1))(*[a for a, _ in t])
+        d_c = None if c is None else (ctypes.c_void_p * max(len(c), 1))(*[a for a, _ in c])
+        tabs = [np.ascontiguousarray(x, dtype=np.int32) for x in tables]
+        d_k = (ctypes.c_void_p * max(len(tabs), 1))(*[x.ctypes.data for x in tabs])
+        cols = nt * (2 if c is not None and any(a for a, _ in c) else 1)
+        kept = ctypes.c_int64(0)
+        if device_out is not None:
+            self._chk(self.lib.gtx_window_select_device(self.ctx, d_t, d_c, nt, int(n_windows), int(window_size), d_k, int(capacity), _ptr(device_out[0]),
+                                                        _ptr(device_out[1]), ctypes.byref(kept)))
+            return int(kept.value)
+        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
+        while True:
+            ordinals, rows = np.full(max(cap, 1), -1, dtype=np.int64), np.full((max(cap, 1), max(cols, 1)), -1, dtype=np.int32)
+            self._chk(self.lib.gtx_window_select(self.ctx, d_t, d_c, nt, int(n_windows), int(window_size), d_k, cap, _ptr(ordinals), _ptr(rows), ctypes.byref(kept)))
+            if capacity is not None or kept.value <= cap:
+                break
+            cap = int(kept.value)
+        got = min(int(kept.value), cap)
+        return ordinals[:got], rows[:got], int(kept.value)
 
     def scan_device(self, d_reads, n_reads, class_len, win_step, win_size, d_out, preprocess="1", d_weights=None, flags=0):
         cl = np.ascontiguousarray(class_len, dtype=np.int32)

@@ -608,6 +608,34 @@ int gtx_scan_add(gtx_ctx *ctx, const int32_t *read_triples, const int32_t *weigh
 int gtx_scan_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
 int gtx_scan_end(gtx_ctx *ctx, uint64_t *windows_out, int64_t *label_sum);
 
+/* Scan results that stay on the device.  gtx_scan_end_keep is gtx_scan_end with the window sums written into one of
+ * GTX_SCAN_KEEP_SLOTS vectors the context owns (layout of gtx_scan, gaps between classes zero) instead of host memory; what the slot
+ * held is replaced.  gtx_scan_kept gives a slot's device address and its number of windows (GTX_E_STATE for an empty slot);
+ * gtx_scan_drop frees one slot, slot -1 all of them.  A slot outside [0, GTX_SCAN_KEEP_SLOTS) is GTX_E_ARG.  No other call touches
+ * a kept vector. */
+#define GTX_SCAN_KEEP_SLOTS 8
+int gtx_scan_end_keep(gtx_ctx *ctx, int slot, int64_t *label_sum);
+int gtx_scan_kept(gtx_ctx *ctx, int slot, void **d_windows, int64_t *n_windows);
+int gtx_scan_drop(gtx_ctx *ctx, int slot);
+
+/* Window selection: the data pass of `genomic_apps peakdiff` (ScanReadFiles, genomic_apps.cpp:385-412) over window vectors in HBM.
+ * d_tested: n_tested (1..4) device vectors of n_windows uint64 sums; d_control: NULL (or all entries NULL), or one control vector per
+ * tested vector -- a control for some only is GTX_E_ARG.  window_size is the clamp W >= 1.  kcrit[f] (host memory) is tested vector
+ * f's table of critical counts: int32[W + 1] with controls, int32[1] without.  With k_f = min(v_f, W) and c_f = min(ctl_f, W), a window
+ * is kept when k_f >= kcrit[f][c_f] for any f (kcrit[f][0] without controls).  The kept windows come out in window order: ordinals
+ * (int64[capacity]) and rows (int32[capacity * columns], columns = n_tested, or 2 * n_tested with controls: the clamped tested counts,
+ * then the clamped control counts).  *n_kept is the number of kept windows whatever the capacity; when it exceeds capacity only the
+ * first `capacity` windows have been written and nothing behind them: grow the buffers and call again (the policy of gtx_join).  The
+ * vectors must be 16-byte aligned (kept slots are).  gtx_window_select_device writes device buffers and returns when the result is
+ * complete; gtx_window_select brings the result to host memory.  Three launches over tiles of `tile` windows (count, prefix, emit);
+ * the tables sit in LDS while n_tested * (W + 1) * 4 bytes <= 64 KB and are read through L2 beyond that: gtx_window_select_limits
+ * reports the tile and the largest W of the LDS path for four tested vectors with controls (n tested vectors: (lds_max_w + 1) * 4 / n - 1). */
+int gtx_window_select_limits(int32_t *tile, int32_t *lds_max_w);
+int gtx_window_select_device(gtx_ctx *ctx, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows,
+                             int32_t window_size, const int32_t *const *kcrit, int64_t capacity, void *d_ordinals, void *d_rows, int64_t *n_kept);
+int gtx_window_select(gtx_ctx *ctx, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows,
+                      int32_t window_size, const int32_t *const *kcrit, int64_t capacity, int64_t *ordinals, int32_t *rows, int64_t *n_kept);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* on = 1: every *_device call brackets its dominant kernel and the whole call with HIP events on the
