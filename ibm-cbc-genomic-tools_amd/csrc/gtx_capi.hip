@@ -255,7 +255,6 @@ struct gtx_ctx {
   int64_t batchReads = 8ll << 20;       // reads per device batch of the host-buffer entry points (96 MiB of triples: ~2 ms of PCIe)
   int chunksPerWave = 0;                // 0 = choose per call from the number of reads
   int64_t waveSlots = 8192;             // resident waves of the device (CUs x 32)
-  int prefetch = 4;                     // reads per lane per step (R) of the streaming kernel (GTX_READS_PER_LANE)
 };
 
 #define HIPCHK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
@@ -411,8 +410,6 @@ gtx_ctx *gtx_create(int device_id)
   if (br && atoll(br) > 0) c->batchReads = atoll(br);
   if (const char *bm = getenv("GTX_BUCKET_MIN_READS")) c->bucketMinReads = atoll(bm);   // unsorted reads: batches below this use the search kernel
   if (const char *lt = getenv("GTX_LOCAL_SCAN_MAX_TILES")) c->localMaxTiles = std::min(std::max(atoi(lt), 0), gtx::kLocalScanMaxTiles);
-  const char *pf = getenv("GTX_READS_PER_LANE");        // tuning knob (1..4), default 4
-  if (pf && atoi(pf) > 0) c->prefetch = atoi(pf);
   return c;
 }
 
@@ -627,8 +624,8 @@ static gtx::CountArgs count_args(gtx_ctx *c, const HistSet &h, uint32_t flags, i
 {
   gtx::CountArgs a;
   a.indexBase = indexBase;
-  { static const bool off = (getenv("GTX_HIST32") && atoi(getenv("GTX_HIST32")) == 0) || (getenv("GTX_PF") && atoi(getenv("GTX_PF")));
-    a.hist32 = hist32 && !off && nReads < (1ll << 32) && c->prefetch >= 4; }
+  { static const bool off = getenv("GTX_HIST32") && atoi(getenv("GTX_HIST32")) == 0;
+    a.hist32 = hist32 && !off && nReads < (1ll << 32); }
   a.owned = who != COUNT_ANY && c->share.on ? c->share.owned.get() : nullptr;
   a.sortedE = c->ix.sortedE.get(); a.sortedS = c->ix.sortedS.get(); a.segStart = c->ix.segStart.get();
   a.histA = h.histA.get(); a.histB = h.histB.get(); a.partA = h.partA.get(); a.partB = h.partB.get(); a.info = c->d_info.get() + c->infoCur;
@@ -649,10 +646,10 @@ static gtx::CountArgs count_args(gtx_ctx *c, const HistSet &h, uint32_t flags, i
   // (launches of one to three rounds -- a group member's share of 100 M reads -- take 16 chunks per wave from a full round of
   // 16-chunk spans on: the start of a span is paid once per 16 chunks instead of 8, 0.039 -> 0.034 ms for 12.9 M reads; scripts/r04_share.sh)
   if (cpw <= 0) { int64_t nChunks = (nReads + 63) >> 6; cpw = (int)std::min<int64_t>(56, std::max<int64_t>(nChunks >= 16 * c->waveSlots ? 16 : 8, nChunks / 24576)); }
-  const int r = std::max(1, std::min(4, c->prefetch));
+  const int r = 4;                                // reads per lane per step of the streaming kernel
   a.chunksPerWave = (cpw + r - 1) / r * r;
   a.sched = gtx::span_schedule((nReads + 63) >> 6, a.chunksPerWave, r, c->waveSlots);
-  a.checkSorted = (flags & GTX_CHECK_SORTED) ? 1 : 0; a.sortClassShift = 0; a.prefetch = c->prefetch;
+  a.checkSorted = (flags & GTX_CHECK_SORTED) ? 1 : 0; a.sortClassShift = 0;
   a.zeroLenOk = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
   const bool merge = (flags & GTX_ZERO_LENGTH_OK) && c->mergeRefs && c->side.get();       // full sorted-merge semantics (see merge_prepare)
   a.side = merge ? c->side.get() : nullptr; a.sideCount = merge ? c->sideCount.get() : nullptr; a.sideCap = c->sideCap; a.coverRule = 0; a.keyCenter = 0;

@@ -43,9 +43,8 @@ struct PlaceTable {
 };
 
 // How the read stream is dealt to the waves of a launch: segment k = the waves from wave0[k] up to the next segment take cpw[k]
-// chunks each, beginning at chunk chunk0[k].  Workgroups are dispatched in grid order, so the segments are phases in time: a
-// head of spans of growing length (the first round's waves all start together; equal spans would also end together, and again
-// a round later), the main segment, and a tail of spans that shrink in step with the time the launch has left.
+// chunks each, beginning at chunk chunk0[k].  Workgroups are dispatched in grid order, so the segments are phases in time: the
+// main segment, and a tail of spans that shrink in step with the time the launch has left.
 struct SpanSchedule {
   static constexpr int kMax = 32;
   int wave0[kMax];               // INT32_MAX for the segments not in use
@@ -70,7 +69,6 @@ struct CountArgs {
   int chunksPerWave;             // 64-read chunks one wave streams
   int checkSorted;               // verify (class >> sortClassShift, start) order
   int sortClassShift;
-  int prefetch;                  // reads per lane per step of the streaming kernel (1..4)
   int zeroLenOk;                 // start == end+1 is a countable read (sorted-merge semantics)
   const int *sampE;              // every (1 << sampShift)-th element of sortedE / sortedS: the
   const int *sampS;              //   search kernel keeps them in LDS as the top level of its searches
@@ -80,7 +78,7 @@ struct CountArgs {
   PlaceTable place;
   SpanSchedule sched;
   int flip;                      // streaming kernel: meet all boundaries of a window at once (dense references)
-  int hist32;                    // streaming kernel (unweighted, R = 4): histA / histB are read and written as unsigned[] -- the caller's finalize step too
+  int hist32;                    // streaming kernel (unweighted): histA / histB are read and written as unsigned[] -- the caller's finalize step too
                                  //   (launch_finalize(..., hist32)).  For calls of fewer than 2^32 reads in ONE launch: no slot or prefix can pass that
   long long indexBase;           // position of reads[0] in the caller's stream: added to the indices reported in `info`
   // sorted-merge semantics (zeroLenOk): inverted reads (start > end + 1) are not degenerate there -- the merge matches them

@@ -430,7 +430,7 @@ __device__ __forceinline__ void walk_chunk(WaveState<WEIGHTED, H32> &st, const C
   }
 }
 
-// Fast path for R x 64 reads of the current class, all valid, unweighted, window placed and no key
+// Fast path for 4 x 64 reads of the current class, all valid, unweighted, window placed and no key
 // behind the current slot (the caller has checked all that).  k[r] are the keys.
 // The boundary-crossing loop inside one register window, hand-scheduled (gfx950 ISA): hipcc turns
 // the C++ form of this multi-exit loop into a state machine of ~50 instructions per boundary; this
@@ -479,34 +479,34 @@ __device__ __forceinline__ void walk_chunk(WaveState<WEIGHTED, H32> &st, const C
       : [k0] "v"(k[0]), [k1] "v"(k[1]), [k2] "v"(k[2]), [k3] "v"(k[3]), [km] "v"(kmax), [w] "v"(X.W) \
       : "vcc", "scc")
 
-// Fast path for R x 64 reads of the current class, all valid, unweighted, window placed and no key
+// Fast path for 4 x 64 reads of the current class, all valid, unweighted, window placed and no key
 // behind the current slot (the caller has checked all that).  k[r] are the keys, kmax their per-lane maximum.
-template <int R, class WIN>
-__device__ __forceinline__ void walk_fast(WIN &X, const Seg &sg, const int (&k)[R], int kmax, int lane, bool &valid)
+template <class WIN>
+__device__ __forceinline__ void walk_fast(WIN &X, const Seg &sg, const int (&k)[4], int kmax, int lane, bool &valid)
 {
-  if (__ballot(WIN::below(kmax, X.curW)) == ~0ull) { X.pend += 64u * R; return; }   // no boundary crossed
+  if (__ballot(WIN::below(kmax, X.curW)) == ~0ull) { X.pend += 256u; return; }   // no boundary crossed
   // (readfirstlane: these are wave-uniform, and the asm below needs them in SGPRs)
   int j = rfl(X.j), curW = rfl(X.curW);
   unsigned pend = (unsigned)rfl((int)X.pend), cprev = 0;
   int adv = 0;
   for (;;) {
     int status;
-    if constexpr (R == 4 && sizeof(X.acc) == 4) {
+    if constexpr (sizeof(X.acc) == 4) {
       unsigned c, t, t1, q = pend - cprev;
       status = 1;
       if (WIN::kStrict) GTX_CROSS_LOOP4("v_cmp_gt_i32"); else GTX_CROSS_LOOP4("v_cmp_ge_i32");
       // asm results count as divergent for the compiler; they are SGPRs: tell it so
       status = rfl(status); j = rfl(j); curW = rfl(curW); q = (unsigned)rfl((int)q);
-      if (status == 0) { pend = q + 64u * R; }
+      if (status == 0) { pend = q + 256u; }
       else { pend = 0; cprev = 0u - q; }                     // window exhausted right after a deposit: q = -c
     } else {
       status = 1;
       for (;;) {                                             // inside one register window
         unsigned c = 0;
 #pragma unroll
-        for (int r = 0; r < R; ++r) c += (unsigned)__popcll(__ballot(WIN::below(k[r], curW)));
+        for (int r = 0; r < 4; ++r) c += (unsigned)__popcll(__ballot(WIN::below(k[r], curW)));
         pend += c - cprev; cprev = c;
-        if (c == 64u * R) { status = 0; break; }
+        if (c == 256u) { status = 0; break; }
         ++j;
         X.acc += (lane == j) ? pend : 0u; pend = 0;         // the slot is complete: hand its count to the lane that owns it
         if (j == kSlots) break;
@@ -523,14 +523,14 @@ __device__ __forceinline__ void walk_fast(WIN &X, const Seg &sg, const int (&k)[
       // keys spread over many windows: every key above the boundary just passed adds itself
       const int passed = rdlane(X.W, 0);
 #pragma unroll
-      for (int r = 0; r < R; ++r) { const u64 ahead = __ballot(!WIN::below(k[r], passed)); if (ahead) X.lanes_add(sg, k[r], 1, ahead, lane); }
+      for (int r = 0; r < 4; ++r) { const u64 ahead = __ballot(!WIN::below(k[r], passed)); if (ahead) X.lanes_add(sg, k[r], 1, ahead, lane); }
       X.j = 0; X.prevW = passed; X.curW = curW; X.pend = 0;
       valid = false;                                         // acc is 0 and nothing is pending: nothing to flush
       return;
     }
-    if constexpr (R == 4 && sizeof(X.acc) == 4) {
+    if constexpr (sizeof(X.acc) == 4) {
       // the asm loop is entered only with some key above curW
-      if (__ballot(WIN::below(kmax, curW)) == ~0ull) { X.j = 0; X.prevW = rdlane(X.W, 0); X.curW = curW; X.pend = 64u * R - cprev; return; }
+      if (__ballot(WIN::below(kmax, curW)) == ~0ull) { X.j = 0; X.prevW = rdlane(X.W, 0); X.curW = curW; X.pend = 256u - cprev; return; }
     }
   }
 }
@@ -653,11 +653,6 @@ __device__ __forceinline__ int min_of(const int (&k)[R]) { int m = k[0];
 #pragma unroll
   for (int r = 1; r < R; ++r) m = k[r] < m ? k[r] : m;
   return m; }
-template <int R>
-__device__ __forceinline__ int max_of(const int (&k)[R]) { int m = k[0];
-#pragma unroll
-  for (int r = 1; r < R; ++r) m = k[r] > m ? k[r] : m;
-  return m; }
 
 // Start of a wave's span: the ranks of its first keys in both boundary arrays, found together.  What a wave pays before
 // it streams is a chain of dependent memory round trips (~2 us each under load) and the cache lines its probes touch:
@@ -727,25 +722,17 @@ __device__ __forceinline__ void rank_pair(const Seg &sg, const WA &A, const int 
   }
 }
 
-// One wave owns chunksPerWave*64 consecutive reads and takes them in steps of R x 64 (register r of
+// One wave owns chunksPerWave*64 consecutive reads and takes them in steps of R x 64, R = 4 (register r of
 // lane l holds read 64 r + l of the step: R coalesced 768-byte requests).  The scalar work per step
 // (loop control, class / validity test, two "did anything cross a boundary" tests) is amortised over
 // R x 64 reads.  The kernel is two nested loops: a tight inner loop that only knows the fast path
 // and leaves -- before touching any state -- as soon as a step needs anything else (another class,
 // a degenerate read, a key behind a window, an unplaced window, the partial last step), and the
 // outer loop that gives exactly that step to the general per-chunk code and re-enters.
-// PF (the plain kernel): the NEXT step of the fast loop travels by LDS-DMA (global_load_lds_dwordx3, no register destination)
-// into 4 KB of LDS of the wave's own while the current step is being worked on in registers.  Without it a wave has bytes in
-// flight only between issuing a step's loads and their arrival -- about 60 % of the time; a wave's rate is bytes in flight /
-// latency, and the launch is short of resident waves to cover for that (8 per SIMD is the hardware's limit, a second register
-// set would cost three of them).
-template <bool WEIGHTED, int R, bool FLIP, bool PF = false, bool H32 = false>
+template <bool WEIGHTED, bool FLIP, bool H32 = false>
 __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, const CountArgs &a)
 {
-  static_assert(!PF || (R == 4 && !WEIGHTED), "the LDS prefetch is built for steps of 4 x 64 unweighted reads");
-  // per wave: one step of triples as global_load_lds_dwordx3 lays them down -- lane l's 12 bytes at 16 l (a 16-byte pitch, the
-  // fourth dword untouched; probed on the chip, scripts/dma_probe.hip): 1 KB per 64-read chunk
-  __shared__ __attribute__((aligned(16))) int ldsT[PF ? 4 : 1][PF ? 256 * R : 4];
+  constexpr int R = 4;
   __shared__ int ldsK[FLIP ? 8 : 1][FLIP ? 256 : 1];           // per wave: the keys of a step (walk_flip4)
   __shared__ int ldsP[(FLIP && WEIGHTED) ? 8 : 1][(FLIP && WEIGHTED) ? 264 : 1];   // and the prefix sums of their weights (walk_flipw4)
   const int wid = rfl(threadIdx.x >> 6);
@@ -780,23 +767,13 @@ __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, c
   const char *base = (const char *)(reads + first);            // wave-uniform
   const int *wbase = WEIGHTED ? weights + first : nullptr;
   const unsigned loff = (unsigned)lane * 12u;
-  const bool fastOk = (!a.checkSorted || R == 4) && (!WEIGHTED || (R == 4 && FLIP));
+  const bool fastOk = !WEIGHTED || FLIP;
   const int zl = a.zeroLenOk;
 
   int s = 0;
   Tri t[R];
   int tw[WEIGHTED ? R : 1];                                    // the weights of step s (weighted fast path)
   bool have = false;                                           // t (and tw) hold step s
-  int dmaStep = -1;                                            // PF: the step whose triples are in, or on their way to, ldsT[wid]
-  auto dma_step = [&](int step) {
-    if constexpr (PF) {
-      const char *p = base + (size_t)step * (768 * R) + loff;
-#pragma unroll
-      for (int r = 0; r < R; ++r)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(p + 768 * r),
-                                         (__attribute__((address_space(3))) void *)&ldsT[wid][256 * r], 12, 0, 2);   // aux 2 = nt
-    }
-  };
   if (fastOk && nFull > 0) {
     // the common start: the first step is all of one class with reference regions -- place both windows at once.
     // The scalar load of the span's first read goes out first: when a launch begins every wave asks for its 3 KB at once, and
@@ -808,7 +785,6 @@ __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, c
     for (int r = 0; r < R; ++r) { t[r] = load_tri(base + 768 * r + loff); if constexpr (WEIGHTED) tw[r] = wbase[64 * r + lane]; }
     have = true;
     const int fc = rfl(fc0), fs = rfl(fs0);
-    if constexpr (PF) { if (nFull > 1) { dma_step(1); dmaStep = 1; } }
     // While those loads are on their way: the span's FIRST read by scalar loads (their path does not queue behind the CU's
     // streaming loads), its class record and the two ranks of the cell its start lies in (PlaceTable) -- lower bounds of the
     // ranks of every key that is not below the cell -- and both windows loaded there.  Three short scalar round trips and one
@@ -874,15 +850,13 @@ __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, c
         // dg < 0 in some lane <=> some read has start > end (+zl)
         const int kmin = min_of<R>(ks), emin = min_of<R>(ke);
         if (__ballot((odd != 0) | (dg < 0) | (kmin <= st.A.prevW) | (emin < st.B.prevW))) return false;
-        if constexpr (R == 4) {
-          if (a.checkSorted) {
-            // GTX_CHECK_SORTED: a step in (class, start) order behind the previous read is consumed here; the first
-            // violation is found -- and reported with its index -- by the general code
-            const int cc = st.sg.cls >> a.sortClassShift, k0 = rdlane(ks[0], 0);
-            if (cc < st.pc || (cc == st.pc && k0 < st.ps) || !keys_ordered4(ks, lane)) return false;
-          }
+        if (a.checkSorted) {
+          // GTX_CHECK_SORTED: a step in (class, start) order behind the previous read is consumed here; the first
+          // violation is found -- and reported with its index -- by the general code
+          const int cc = st.sg.cls >> a.sortClassShift, k0 = rdlane(ks[0], 0);
+          if (cc < st.pc || (cc == st.pc && k0 < st.ps) || !keys_ordered4(ks, lane)) return false;
         }
-        if constexpr (WEIGHTED && R == 4 && FLIP) {
+        if constexpr (WEIGHTED && FLIP) {
           // weighted step: ordered keys and small weights, else the general path takes it
           bool big = false;
 #pragma unroll
@@ -894,16 +868,14 @@ __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, c
           if (lane == 0) ldsP[wid][256] = run;
           walk_flipw4(st.A, st.sg, ks, run, lane, st.validA, ldsK[wid], ldsP[wid]);
           walk_flipw4(st.B, st.sg, ke, run, lane, st.validB, ldsK[wid], ldsP[wid]);
-        } else if constexpr (!WEIGHTED && R == 4 && FLIP) {
-          if (!walk_flip4(st.A, st.sg, ks, lane, st.validA, ldsK[wid])) walk_fast<R>(st.A, st.sg, ks, max_of<R>(ks), lane, st.validA);
-          if (!walk_flip4(st.B, st.sg, ke, lane, st.validB, ldsK[wid])) walk_fast<R>(st.B, st.sg, ke, max_of<R>(ke), lane, st.validB);
+        } else if constexpr (!WEIGHTED && FLIP) {
+          if (!walk_flip4(st.A, st.sg, ks, lane, st.validA, ldsK[wid])) walk_fast(st.A, st.sg, ks, max_of4(ks), lane, st.validA);
+          if (!walk_flip4(st.B, st.sg, ke, lane, st.validB, ldsK[wid])) walk_fast(st.B, st.sg, ke, max_of4(ke), lane, st.validB);
         } else if constexpr (!WEIGHTED) {
-          walk_fast<R>(st.A, st.sg, ks, max_of<R>(ks), lane, st.validA);
-          walk_fast<R>(st.B, st.sg, ke, max_of<R>(ke), lane, st.validB);
+          walk_fast(st.A, st.sg, ks, max_of4(ks), lane, st.validA);
+          walk_fast(st.B, st.sg, ke, max_of4(ke), lane, st.validB);
         }
-        if constexpr (R == 4) {
-          if (a.checkSorted) { st.pc = st.sg.cls >> a.sortClassShift; st.ps = rdlane(ks[3], 63); }   // the step is consumed: it is the previous read now
-        }
+        if (a.checkSorted) { st.pc = st.sg.cls >> a.sortClassShift; st.ps = rdlane(ks[3], 63); }   // the step is consumed: it is the previous read now
         return true;
       };
       auto load_step = [&](Tri (&tt)[R], int step) {
@@ -912,21 +884,7 @@ __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, c
         for (int r = 0; r < R; ++r) { tt[r] = load_tri(p + 768 * r); if constexpr (WEIGHTED) tw[r] = wbase[(size_t)step * (64 * R) + 64 * r + lane]; }
       };
       while (s < nFull) {
-        if constexpr (PF) {
-          if (!have) {
-            if (dmaStep != s) dma_step(s);                            // (only behind a step that went through the general code twice over)
-            // nothing orders a ds_read behind a pending LDS-DMA except the issuing wave's vmcnt (hipcc does not insert it)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            typedef int v3i __attribute__((ext_vector_type(3)));     // 16 bytes in memory, 3 registers: ds_read_b96
-            const v3i *L = (const v3i *)&ldsT[wid][4 * lane];
-#pragma unroll
-            for (int r = 0; r < R; ++r) { const v3i v = L[64 * r]; t[r].c = v.x; t[r].s = v.y; t[r].e = v.z; }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // the buffer is about to be overwritten
-            if (s + 1 < nFull) { dma_step(s + 1); dmaStep = s + 1; }
-          }
-        } else {
-          if (!have) load_step(t, s);
-        }
+        if (!have) load_step(t, s);
         have = true;
         if (!fast_step(t)) break;
         ++s; have = false;
@@ -980,34 +938,28 @@ __device__ __forceinline__ void count_walk_body(const Tri *__restrict__ reads, c
 // 8 blocks (8 waves per SIMD) up to 80 SGPRs, 7 up to 96, 6 above (MI355X_MICROARCH.md, "Residency").  Left alone the
 // compiler takes 96-106 for this kernel; capped, it parks a dozen rarely used scalars in the lanes of one VGPR.
 // 100 M x 1 M: 6 -> 8 waves per SIMD, 0.240 -> 0.222 ms.
-template <bool WEIGHTED, int R>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void count_walk_kernel(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, CountArgs a)
 {
-  count_walk_body<WEIGHTED, R, false>(reads, weights, n, a);
+  count_walk_body<false, false>(reads, weights, n, a);
 }
 // the same with 32-bit histogram slots (CountArgs::hist32: an unweighted call of fewer than 2^32 reads on resident reads)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void count_walk_kernel_h32(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, CountArgs a)
 {
-  count_walk_body<false, 4, false, false, true>(reads, weights, n, a);
+  count_walk_body<false, false, true>(reads, weights, n, a);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void count_walk_kernel_flip_h32(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, CountArgs a)
 {
-  count_walk_body<false, 4, true, false, true>(reads, weights, n, a);
-}
-// experiment (GTX_PF=1): the next step prefetched through LDS
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void count_walk_kernel_pf(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, CountArgs a)
-{
-  count_walk_body<false, 4, false, true>(reads, weights, n, a);
+  count_walk_body<false, true, true>(reads, weights, n, a);
 }
 // weighted reads: steps of 4 x 64 with the weights' prefix sums in LDS (walk_flipw4); the general code takes what does not qualify.
 // (93 VGPRs = 5 waves per SIMD left alone; 80 = 6 without a spill when told to: 0.272 -> 0.268 ms on one box; 7 waves spill: 0.39)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(6, 6))) void count_walk_kernel_weighted(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, CountArgs a)
 {
-  count_walk_body<true, 4, true>(reads, weights, n, a);
+  count_walk_body<true, true>(reads, weights, n, a);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void count_walk_kernel_flip(const Tri *__restrict__ reads, const int *__restrict__ weights, i64 n, CountArgs a)
 {
-  count_walk_body<false, 4, true>(reads, weights, n, a);
+  count_walk_body<false, true>(reads, weights, n, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2052,56 +2004,26 @@ int scan_tiles(i64 len) { return (int)((len + kTile - 1) / kTile); }
 // Schedule of a launch over nChunks 64-read chunks, `cpw` chunks per wave in the main segment (all spans multiples of `r`),
 // `slots` = resident waves of the chip.  A wave lives p + c * tau (placement + c chunks at the chip's rate shared by all
 // slots; p / tau ~ 8 chunks measured), and a slot frees once per life.
-//  * tail (default for launches of three rounds or more): a wave dispatched when the launch has time T left should take T's
-//    worth -- levels cpw-r, cpw-2r, ... down to 8 chunks, each dealt to about as many waves as free up while the level is
-//    current, slots * r / (cpw + 8), times 5/4 (measured: 100 M reads, 512 / 640 / 800 waves per level within 1 % of each
-//    other, all 3-4 % ahead of equal spans; same-box A/B, scripts/ab_count.py).
-//  * head (off by default): levels 12, 12+r, ... below cpw spread the ends of the first round, whose waves all start together,
-//    over a wave's life.  The dips in the wave time line (scripts/wave_trace.py) go, and so does the first round's burst at
-//    full occupancy: no net gain measured.
-// GTX_SCHED: "none" | "lin:<waves per head level>:<waves per tail level>[:<shortest span>]" | "h=<c>x<w>,...;t=<c>x<w>,..."
-// (chunks x waves, in launch order) for experiments.
+// Launches of three rounds or more end in a tail: a wave dispatched when the launch has time T left should take T's
+// worth -- levels cpw-r, cpw-2r, ... down to 8 chunks, each dealt to about as many waves as free up while the level is
+// current, slots * r / (cpw + 8), times 5/4 (measured: 100 M reads, 512 / 640 / 800 waves per level within 1 % of each
+// other, all 3-4 % ahead of equal spans; same-box A/B, scripts/ab_count.py).
 SpanSchedule span_schedule(i64 nChunks, int cpw, int r, i64 slots)
 {
   SpanSchedule s;
   for (int i = 0; i < SpanSchedule::kMax; ++i) { s.wave0[i] = INT32_MAX; s.chunk0[i] = 0; s.cpw[i] = cpw; }
   struct SegSpec { int cpw; i64 waves; };
-  std::vector<SegSpec> head, tail;
-  auto up = [&](i64 c) { return (int)((c + r - 1) / r * r); };
-  auto linear = [&](i64 perHead, i64 perTail, int minSpan = 8) {
-    if (perHead > 0) for (int c = up(12); c < cpw; c += r) head.push_back({c, (perHead + 3) / 4 * 4});
-    if (perTail > 0) for (int c = cpw - r; c >= minSpan; c -= r) tail.push_back({c, (perTail + 3) / 4 * 4});
-  };
-  auto parse = [&](const char *p, std::vector<SegSpec> &out) {
-    while (*p && *p != ';') {
-      char *q; const long c = strtol(p, &q, 10); if (q == p || *q != 'x') break;
-      p = q + 1; const long long w = strtoll(p, &q, 10); if (q == p) break;
-      if (c > 0 && w > 0) out.push_back({up(c), (i64)(w + 3) / 4 * 4});
-      p = *q == ',' ? q + 1 : q;
-    }
-    return p;
-  };
-  const char *spec = getenv("GTX_SCHED");
-  if (spec && !strncmp(spec, "lin:", 4)) { long long a = 0, b = 0; int ms = 8; sscanf(spec + 4, "%lld:%lld:%d", &a, &b, &ms); linear(a, b, ms > 0 ? ms : 8); }
-  else if (spec && !strcmp(spec, "none")) {}
-  else if (spec) {
-    const char *p = spec;
-    while (*p) {
-      if (!strncmp(p, "h=", 2)) p = parse(p + 2, head); else if (!strncmp(p, "t=", 2)) p = parse(p + 2, tail); else break;
-      if (*p == ';') ++p;
-    }
-  } else if (nChunks >= 3 * slots * (i64)cpw) {
-    linear(0, slots * r * 5 / (4 * (cpw + 8)));
+  std::vector<SegSpec> tail;
+  if (nChunks >= 3 * slots * (i64)cpw) {
+    const i64 perTail = slots * r * 5 / (4 * (cpw + 8));
+    if (perTail > 0) for (int c = cpw - r; c >= 8; c -= r) tail.push_back({c, (perTail + 3) / 4 * 4});
   }
   auto chunksOf = [](const std::vector<SegSpec> &v) { i64 t = 0; for (auto &g : v) t += g.cpw * g.waves; return t; };
-  while ((int)(head.size() + tail.size()) > SpanSchedule::kMax - 1) { if (!head.empty()) head.erase(head.begin()); else tail.pop_back(); }
-  if ((chunksOf(head) + chunksOf(tail)) * 3 > nChunks * 2) head.clear();
+  while ((int)tail.size() > SpanSchedule::kMax - 1) tail.pop_back();
   if (chunksOf(tail) * 3 > nChunks * 2) tail.clear();
-  int k = 0; i64 wave = 0, chunk = 0;
-  for (auto &g : head) { s.wave0[k] = (int)wave; s.chunk0[k] = (int)chunk; s.cpw[k] = g.cpw; wave += g.waves; chunk += g.waves * g.cpw; ++k; }
-  const i64 tailChunks = chunksOf(tail);
-  const i64 mainWaves = tail.empty() ? (nChunks - chunk + cpw - 1) / cpw : (nChunks - chunk - tailChunks) / cpw;
-  s.wave0[k] = (int)wave; s.chunk0[k] = (int)chunk; s.cpw[k] = cpw; wave += mainWaves; chunk += mainWaves * cpw; ++k;
+  const i64 mainWaves = tail.empty() ? (nChunks + cpw - 1) / cpw : (nChunks - chunksOf(tail)) / cpw;
+  s.wave0[0] = 0; s.chunk0[0] = 0; s.cpw[0] = cpw;
+  int k = 1; i64 wave = mainWaves, chunk = mainWaves * cpw;
   for (size_t i = 0; i < tail.size(); ++i) {
     i64 w = tail[i].waves;
     if (i + 1 == tail.size()) w = (nChunks - chunk + tail[i].cpw - 1) / tail[i].cpw;   // the last level takes what is left
@@ -2116,21 +2038,12 @@ hipError_t launch_count(const void *reads, const void *weights, i64 n, const Cou
   if (n <= 0) return hipSuccess;
   if (sortedHint) {
     const i64 waves = a.sched.nWaves;
-    static const int wpb = getenv("GTX_WAVES_PER_BLOCK") ? std::min(4, std::max(1, atoi(getenv("GTX_WAVES_PER_BLOCK")))) : 4;   // (the kernels size their LDS for 4)
-    const unsigned grid = (unsigned)((waves + wpb - 1) / wpb);
-    const unsigned bs = 64u * wpb;
-    // a.prefetch = reads per lane per step (R)
-    static const bool wfast = !(getenv("GTX_WEIGHTED_FAST") && atoi(getenv("GTX_WEIGHTED_FAST")) == 0);
-    if (weights && wfast) count_walk_kernel_weighted<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
-    else if (weights) count_walk_kernel<true, 2><<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
-    else if (a.prefetch <= 1) count_walk_kernel<false, 1><<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
-    else if (a.prefetch == 2) count_walk_kernel<false, 2><<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
-    else if (a.prefetch == 3) count_walk_kernel<false, 3><<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
+    const unsigned grid = (unsigned)((waves + 3) / 4), bs = 256;     // (the kernels size their LDS for 4 waves)
+    if (weights) count_walk_kernel_weighted<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
     else if (a.flip && a.hist32) count_walk_kernel_flip_h32<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
     else if (a.flip) count_walk_kernel_flip<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
     else if (a.hist32) count_walk_kernel_h32<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
-    else if (getenv("GTX_PF") && atoi(getenv("GTX_PF"))) count_walk_kernel_pf<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
-    else count_walk_kernel<false, 4><<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
+    else count_walk_kernel<<<grid, bs, 0, st>>>((const Tri *)reads, (const int *)weights, n, a);
   } else {
     // one 1024-thread block per CU (the LDS top level fills most of the CU's 160 KB)
     static PerDevice attr;

@@ -71,7 +71,7 @@ def pmc_json(path, kernel, match, fetch, write, extra, alg, note):
     print(os.path.basename(path), "traffic %.4g B = %.2fx algorithmic" % (fb + wb, (fb + wb) / alg), "L2 hit %.3f" % d["l2_hit_rate"] if "l2_hit_rate" in d else "")
 
 
-pmc_json(R + "profiles/%s_pmc_count_walk.json" % rnd, "count_walk_kernel<false,4>", "count_walk_kernel", "count_fetch", "count_write", (), 1.2e9,
+pmc_json(R + "profiles/%s_pmc_count_walk.json" % rnd, "count_walk_kernel", "count_walk_kernel", "count_fetch", "count_write", (), 1.2e9,
          "100 M reads x 1 M regions, bench.py default workload")
 pmc_json(R + "profiles/%s_pmc_coverage_walk.json" % rnd, "coverage_walk_kernel<false>", "coverage_walk_kernel", "cov_fetch", "cov_write", (), 1.2e9,
          "100 M reads x 1 M regions, tests/tools/bench_coverage.py")

@@ -30,7 +30,6 @@ def main():
     ap.add_argument("--reads", type=int, default=100_000_000)
     ap.add_argument("--refs", type=int, default=1_000_000)
     ap.add_argument("--cpw", default="56")
-    ap.add_argument("--sched", default="", help="';'-separated GTX_SCHED values tried for every --cpw ('-' = the default tail, 'none' = no tail)")
     ap.add_argument("--slice-us", type=float, default=4.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "wave_trace.json"))
     args = ap.parse_args()
@@ -41,14 +40,8 @@ def main():
     n = reads.shape[0]
     hits = torch.zeros(len(refs), dtype=torch.int64, device=dev)
     res = []
-    combos = [(int(x), sc) for x in args.cpw.split(",") for sc in (args.sched.split(";") if args.sched else ["-"])]
-    for cpw, sc in combos:
+    for cpw in (int(x) for x in args.cpw.split(",")):
         os.environ["GTX_CHUNKS_PER_WAVE"] = str(cpw)
-        os.environ.pop("GTX_SCHED", None)
-        if sc == "none":
-            os.environ["GTX_SCHED"] = "0x0"
-        elif sc != "-":
-            os.environ["GTX_SCHED"] = sc
         eng = gtx.Engine(0)
         eng.set_refs(refs, synth.n_classes())
         eng.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -79,7 +72,7 @@ def main():
             lo, hi = edges[k], edges[k + 1]
             alive[k] = np.sum(np.clip(np.minimum(s2, hi) - np.maximum(s0, lo), 0, None)) / args.slice_us
             streaming[k] = np.sum(np.clip(np.minimum(s2, hi) - np.maximum(s1, lo), 0, None)) / args.slice_us
-        r = {"cpw": cpw_eff, "sched": sc, "waves": int(waves), "kernel_ms_events": [round(float(x), 4) for x in kms],
+        r = {"cpw": cpw_eff, "waves": int(waves), "kernel_ms_events": [round(float(x), 4) for x in kms],
              "span_us_first_start_to_last_end": total,
              "place_us": {"p10": float(np.percentile(s1 - s0, 10)), "p50": float(np.percentile(s1 - s0, 50)), "p90": float(np.percentile(s1 - s0, 90)), "max": float((s1 - s0).max())},
              "stream_us": {"p10": float(np.percentile(s2 - s1, 10)), "p50": float(np.percentile(s2 - s1, 50)), "p90": float(np.percentile(s2 - s1, 90)), "max": float((s2 - s1).max())},
