@@ -2588,12 +2588,16 @@ unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *ov, const GtxSignalSpe
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-// the regions of a set, column by column, up to the first line the loop cannot take: `stop` says why it ends there
+// the regions of a set, column by column, up to the first line the loop cannot take: `stop` says why it ends there.  want_score: the
+// score column beside them (NULL for a line with fewer than 5 tokens).  front_of_multi: a multi-interval line that
+// IsCompatibleSortedAndNonoverlapping (:1153-1161) is taken with its front interval -- what RunGlobalTest compares -- and one that is
+// not ends the columns (UNSORTED_MULTI).
 struct LinkColumns {
-  std::vector<const char *> chrom, label;
+  bool want_score = false, front_of_multi = false;
+  std::vector<const char *> chrom, label, score;
   std::vector<char> strand;
   std::vector<long> start, stop, line;
-  enum Stop { NONE, MALFORMED, MULTI } why = NONE;
+  enum Stop { NONE, MALFORMED, MULTI, UNSORTED_MULTI } why = NONE;
   long stop_line = 0; std::string stop_msg; bool stop_prefix = true;            // MALFORMED: the reader's message
   const char *stop_chrom = NULL; char stop_strand = '+'; long stop_start = 0;   // MULTI: the front interval (Next's order check comes first)
   std::vector<char> text;                                                        // what the pointers of a streamed set point into
@@ -2603,6 +2607,7 @@ struct LinkColumns {
     chrom.insert(chrom.end(), o.chrom.begin(), o.chrom.end()); label.insert(label.end(), o.label.begin(), o.label.end());
     strand.insert(strand.end(), o.strand.begin(), o.strand.end()); start.insert(start.end(), o.start.begin(), o.start.end());
     stop.insert(stop.end(), o.stop.begin(), o.stop.end()); line.insert(line.end(), o.line.begin(), o.line.end());
+    score.insert(score.end(), o.score.begin(), o.score.end());
   }
 };
 
@@ -2627,7 +2632,9 @@ void LinkParsePiece(char *b, char *e, long first, LinkColumns *out)
     if (f.n_tokens == 12) {
       std::vector<long> iv; gtxhost::BedBlocks(f, &iv);
       if (iv.size() < 2) { out->why = LinkColumns::MALFORMED; out->stop_line = no; out->stop_msg = "BED12 line without blocks!"; return; }
-      if (iv.size() > 2) { out->why = LinkColumns::MULTI; out->stop_line = no; out->stop_chrom = f.chrom; out->stop_strand = f.strand; out->stop_start = iv[0]; return; }
+      if (iv.size() > 2 && !out->front_of_multi) { out->why = LinkColumns::MULTI; out->stop_line = no; out->stop_chrom = f.chrom; out->stop_strand = f.strand; out->stop_start = iv[0]; return; }
+      for (size_t k = 2; k < iv.size(); k += 2)
+        if (iv[k] < iv[k - 2] || iv[k] <= iv[k - 1]) { out->why = LinkColumns::UNSORTED_MULTI; out->stop_line = no; return; }
       s = iv[0]; t = iv[1];
     }
     if (s < -(long)INT_MAX || s > (long)INT_MAX || t < -(long)INT_MAX || t > (long)INT_MAX) {
@@ -2635,6 +2642,7 @@ void LinkParsePiece(char *b, char *e, long first, LinkColumns *out)
     }
     out->chrom.push_back(f.chrom); out->label.push_back(f.label ? f.label : "_"); out->strand.push_back(f.strand);
     out->start.push_back(s); out->stop.push_back(t); out->line.push_back(no);
+    if (out->want_score) out->score.push_back(f.score);
   }
 }
 
@@ -2686,7 +2694,7 @@ static void LinkParseText(char *b, char *e, long first, LinkColumns *col)
   }
   gtxhost::ParallelFor(T, [&](int t) { pc[t].lines = gtxhost::CountNewlines(pc[t].b, pc[t].e); });
   long at = first;
-  for (auto &p : pc) { p.first = at; at += p.lines; }
+  for (auto &p : pc) { p.first = at; at += p.lines; p.out.want_score = col->want_score; p.out.front_of_multi = col->front_of_multi; }
   gtxhost::ParallelFor(T, [&](int t) { LinkParsePiece(pc[t].b, pc[t].e, pc[t].first, &pc[t].out); });
   for (auto &p : pc) {
     col->append(p.out);
@@ -2696,6 +2704,63 @@ static void LinkParseText(char *b, char *e, long first, LinkColumns *col)
       break;
     }
   }
+}
+
+// items [0, n) formatted side by side in chunks and written to stdout in order
+static void PrintInChunks(size_t n, const std::function<void(std::string &, size_t)> &put)
+{
+  StdoutIsOurs();
+  const size_t per = 1u << 16, n_chunks = (n + per - 1) / per;
+  const size_t wave = (size_t)std::max(1, gtxhost::WorkerThreads());
+  std::vector<std::string> bufs(wave);
+  for (size_t c0 = 0; c0 < n_chunks; c0 += wave) {
+    const int m = (int)std::min(wave, n_chunks - c0);
+    gtxhost::ParallelFor(m, [&](int t) {
+      std::string &buf = bufs[(size_t)t];
+      buf.clear();
+      const size_t k0 = (c0 + (size_t)t) * per, k1 = std::min(n, k0 + per);
+      for (size_t k = k0; k < k1; k++) put(buf, k);
+    });
+    for (int t = 0; t < m; t++) fwrite(bufs[(size_t)t].data(), 1, bufs[(size_t)t].size(), stdout);
+  }
+}
+
+// the current region's line, then the rest of the stream, as one text of complete lines in col->text; returns the first line's number
+static long int LinkReadStream(GenomicRegionSet *set, LinkColumns *col)
+{
+  std::string first; long int first_no = 0;
+  LineSource *ls = set->DetachStream(&first, &first_no);
+  col->text.assign(first.begin(), first.end()); col->text.push_back('\n');
+  std::vector<char> block; long bl = 0; size_t got;
+  while ((got = ls->NextBlock(block, (size_t)64 << 20, &bl)) > 0) {
+    ls->AdvanceLines(gtxhost::CountNewlines(block.data(), block.data() + got));
+    col->text.insert(col->text.end(), block.begin(), block.begin() + got);
+  }
+  return first_no;
+}
+
+// the packed triples of the columns: class = the chromosome's strcmp rank among `names` (filled here, sorted), with the strand below it
+// when the set is sorted by strand
+static void LinkPack(const LinkColumns &col, bool sorted_by_strand, std::vector<int32_t> *tri_out, std::vector<const char *> *names_out)
+{
+  const size_t n = col.size();
+  std::vector<int32_t> &tri = *tri_out;
+  std::vector<const char *> &names = *names_out;
+  tri.resize(3 * n); names.clear();
+  for (size_t k = 0; k < n; k++) if (k == 0 || (col.chrom[k] != col.chrom[k - 1] && strcmp(col.chrom[k], col.chrom[k - 1]) != 0)) names.push_back(col.chrom[k]);
+  std::sort(names.begin(), names.end(), [](const char *a, const char *b) { return strcmp(a, b) < 0; });
+  names.erase(std::unique(names.begin(), names.end(), [](const char *a, const char *b) { return strcmp(a, b) == 0; }), names.end());
+  auto rank_of = [&](const char *c) { return (int32_t)(std::lower_bound(names.begin(), names.end(), c, [](const char *a, const char *b) { return strcmp(a, b) < 0; }) - names.begin()); };
+  const int P = std::max(1, std::min<int>(gtxhost::WorkerThreads(), (int)(n >> 18) + 1));
+  gtxhost::ParallelFor(P, [&](int t) {
+    const size_t b = n * (size_t)t / (size_t)P, e = n * (size_t)(t + 1) / (size_t)P;
+    const char *last = NULL; int32_t last_rank = 0;
+    for (size_t k = b; k < e; k++) {
+      if (!last || (col.chrom[k] != last && strcmp(col.chrom[k], last) != 0)) { last = col.chrom[k]; last_rank = rank_of(last); }
+      tri[3 * k] = sorted_by_strand ? 2 * last_rank + (col.strand[k] == '-' ? 1 : 0) : last_rank;
+      tri[3 * k + 1] = (int32_t)col.start[k]; tri[3 * k + 2] = (int32_t)col.stop[k];
+    }
+  });
 }
 
 // The text path of link (no label function: the labels are not needed): the file's text goes to the device block by block and is
@@ -2839,16 +2904,7 @@ void GenomicRegionSet::RunGlobalLink(bool sorted_by_strand, long int max_differe
 
   // ---- the input: the current region's line, then the rest of the stream ----
   LinkColumns col;
-  std::string first; long int first_no = 0;
-  LineSource *ls = DetachStream(&first, &first_no);
-  col.text.assign(first.begin(), first.end()); col.text.push_back('\n');
-  {
-    std::vector<char> block; long bl = 0; size_t got;
-    while ((got = ls->NextBlock(block, (size_t)64 << 20, &bl)) > 0) {
-      ls->AdvanceLines(gtxhost::CountNewlines(block.data(), block.data() + got));
-      col.text.insert(col.text.end(), block.begin(), block.begin() + got);
-    }
-  }
+  const long int first_no = LinkReadStream(this, &col);
   Mark("link: input read");
   char *tb = col.text.data(), *te = tb + col.text.size();
   // Without a label function the labels are not needed: the text is tokenised on the device (files of 32 MB or more;
@@ -2865,24 +2921,9 @@ void GenomicRegionSet::RunGlobalLink(bool sorted_by_strand, long int max_differe
   const size_t n = col.size();
 
   // ---- classes: the chromosome's strcmp rank, with the strand below it when the set is sorted by strand ----
-  std::vector<int32_t> tri(3 * n);
-  {
-    std::vector<const char *> names;
-    for (size_t k = 0; k < n; k++) if (k == 0 || (col.chrom[k] != col.chrom[k - 1] && strcmp(col.chrom[k], col.chrom[k - 1]) != 0)) names.push_back(col.chrom[k]);
-    std::sort(names.begin(), names.end(), [](const char *a, const char *b) { return strcmp(a, b) < 0; });
-    names.erase(std::unique(names.begin(), names.end(), [](const char *a, const char *b) { return strcmp(a, b) == 0; }), names.end());
-    auto rank_of = [&](const char *c) { return (int32_t)(std::lower_bound(names.begin(), names.end(), c, [](const char *a, const char *b) { return strcmp(a, b) < 0; }) - names.begin()); };
-    const int P = std::max(1, std::min<int>(gtxhost::WorkerThreads(), (int)(n >> 18) + 1));
-    gtxhost::ParallelFor(P, [&](int t) {
-      const size_t b = n * (size_t)t / (size_t)P, e = n * (size_t)(t + 1) / (size_t)P;
-      const char *last = NULL; int32_t last_rank = 0;
-      for (size_t k = b; k < e; k++) {
-        if (!last || (col.chrom[k] != last && strcmp(col.chrom[k], last) != 0)) { last = col.chrom[k]; last_rank = rank_of(last); }
-        tri[3 * k] = sorted_by_strand ? 2 * last_rank + (col.strand[k] == '-' ? 1 : 0) : last_rank;
-        tri[3 * k + 1] = (int32_t)col.start[k]; tri[3 * k + 2] = (int32_t)col.stop[k];
-      }
-    });
-  }
+  std::vector<int32_t> tri;
+  std::vector<const char *> names;
+  LinkPack(col, sorted_by_strand, &tri, &names);
 
   // ---- a fold the device's int64 arithmetic reproduces bit for bit: canonical integers whose sums stay below 2^53 ----
   std::vector<int64_t> vals;
@@ -2936,41 +2977,192 @@ void GenomicRegionSet::RunGlobalLink(bool sorted_by_strand, long int max_differe
   }
 
   // ---- print: chunks of groups formatted side by side, written in order ----
-  StdoutIsOurs();
-  const size_t per = 1u << 16, n_chunks = (n_print + per - 1) / per;
-  const size_t wave = (size_t)std::max(1, gtxhost::WorkerThreads());
-  std::vector<std::string> bufs(wave);
-  for (size_t c0 = 0; c0 < n_chunks; c0 += wave) {
-    const int m = (int)std::min(wave, n_chunks - c0);
-    gtxhost::ParallelFor(m, [&](int t) {
-      std::string &buf = bufs[(size_t)t];
-      buf.clear();
-      const size_t g0 = (c0 + (size_t)t) * per, g1 = std::min(n_print, g0 + per);
-      char num[64];
-      for (size_t g = g0; g < g1; g++) {
-        const size_t h = head[g], cnt = count[g];
-        if (!label_func[0]) buf.push_back('_');
-        else if (concat) {
-          buf += col.label[h];
-          for (size_t k = h + 1; k < h + cnt; k++) { buf += label_func; buf += col.label[k]; }
-        } else {
-          double v;
-          if (device_fold) v = (double)gval[g];
-          else {
-            v = atof(col.label[h]);
-            for (size_t k = h + 1; k < h + cnt; k++) { const double x = atof(col.label[k]); v = mode == 1 ? v + x : mode == 2 ? std::min(v, x) : std::max(v, x); }
-          }
-          buf.append(num, (size_t)snprintf(num, sizeof num, "%g", v));
-        }
-        buf.push_back('\t'); buf += col.chrom[h]; buf.push_back(' '); buf.push_back(col.strand[h]); buf.push_back(' ');
-        LinkPutNum(buf, col.start[h]); buf.push_back(' '); LinkPutNum(buf, (long)gstop[g]); buf.push_back('\n');
+  PrintInChunks(n_print, [&](std::string &buf, size_t g) {
+    char num[64];
+    const size_t h = head[g], cnt = count[g];
+    if (!label_func[0]) buf.push_back('_');
+    else if (concat) {
+      buf += col.label[h];
+      for (size_t k = h + 1; k < h + cnt; k++) { buf += label_func; buf += col.label[k]; }
+    } else {
+      double v;
+      if (device_fold) v = (double)gval[g];
+      else {
+        v = atof(col.label[h]);
+        for (size_t k = h + 1; k < h + cnt; k++) { const double x = atof(col.label[k]); v = mode == 1 ? v + x : mode == 2 ? std::min(v, x) : std::max(v, x); }
       }
-    });
-    for (int t = 0; t < m; t++) fwrite(bufs[(size_t)t].data(), 1, bufs[(size_t)t].size(), stdout);
-  }
+      buf.append(num, (size_t)snprintf(num, sizeof num, "%g", v));
+    }
+    buf.push_back('\t'); buf += col.chrom[h]; buf.push_back(' '); buf.push_back(col.strand[h]); buf.push_back(' ');
+    LinkPutNum(buf, col.start[h]); buf.push_back(' '); LinkPutNum(buf, (long)gstop[g]); buf.push_back('\n');
+  });
   Mark("link: output written");
   if (err_line) {
     if (err_prefix) DieLine(err_line, err_msg);
     fflush(stdout); fprintf(stderr, "%s\n", err_msg.c_str()); exit(1);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// GenomicRegionSet::RunGlobalTest / RunGlobalCalcDistances / RunGlobalInvert (genomic_intervals.cpp:4755-4778, :4523-4542, :4576-4600)
+// on the device: the neighbour passes gtx_adjacent / gtx_gaps over the set's packed triples
+// ---------------------------------------------------------------------------------------------------
+namespace {
+
+// the set as columns and packed triples; total_lines = the number of the file's last complete line
+struct AdjacentInput {
+  LinkColumns col;
+  std::vector<int32_t> tri;
+  std::vector<const char *> names;
+  long total_lines = 0;
+  size_t size() const { return col.size(); }
+};
+
+void AdjacentRead(GenomicRegionSet *set, const char *what, bool by_strand, AdjacentInput *in)
+{
+  if (set->format != "BED") set->PrintError(std::string(what) + " takes BED regions on the MI355X path!");
+  if (set->load_in_memory) set->PrintError(std::string(what) + " streams its input on the MI355X path: open the set with load_in_memory = false!");
+  const long first_no = LinkReadStream(set, &in->col);
+  char *tb = in->col.text.data(), *te = tb + in->col.text.size();
+  in->total_lines = first_no - 1 + gtxhost::CountNewlines(tb, te);
+  LinkParseText(tb, te, first_no, &in->col);
+  LinkPack(in->col, by_strand, &in->tri, &in->names);
+  Mark("adjacent: input parsed");
+}
+
+gtx_ctx *AdjacentContext() { return gtx_group_ctx(Devices(), 0); }
+
+void AdjacentDie(gtx_ctx *ctx, int rc)
+{
+  fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(ctx)); exit(1);
+}
+
+// the error of the line the parser stopped at, after everything in front of it has been written
+void AdjacentParserError(const LinkColumns &col, const char *multi_msg)
+{
+  if (col.why == LinkColumns::NONE) return;
+  if (col.why == LinkColumns::MULTI) DieLine(col.stop_line, multi_msg);
+  if (col.why == LinkColumns::UNSORTED_MULTI) DieLine(col.stop_line, "input regions must be compatible, sorted and non-overlapping!");
+  if (col.stop_prefix) DieLine(col.stop_line, col.stop_msg);
+  fflush(stdout); fprintf(stderr, "%s\n", col.stop_msg.c_str()); exit(1);
+}
+
+std::string AdjacentOrderMessage(bool sorted_by_strand)
+{
+  return std::string("input regions are not sorted (sorted-by-strand = ") + (sorted_by_strand ? "true" : "false") + ")!";
+}
+
+int AdjacentPoint(const char *op)
+{
+  return strcmp(op, "1") == 0 ? GTX_POINT_START : strcmp(op, "2") == 0 ? GTX_POINT_STOP : strcmp(op, "5p") == 0 ? GTX_POINT_5P : strcmp(op, "3p") == 0 ? GTX_POINT_3P : -1;
+}
+
+}  // namespace
+
+void GenomicRegionSet::RunGlobalTest(bool sorted_by_strand)
+{
+  if (n_regions == 0) return;
+  AdjacentInput in;
+  in.col.front_of_multi = true;
+  AdjacentRead(this, "test", sorted_by_strand, &in);
+  gtx_adjacent_info info = {-1, 0, 0};
+  gtx_ctx *ctx = AdjacentContext();
+  const int rc = gtx_adjacent(ctx, in.tri.data(), NULL, (int64_t)in.size(), GTX_POINT_START, GTX_POINT_START, NULL, &info);
+  if (rc != GTX_OK) AdjacentDie(ctx, rc);
+  Mark("adjacent: pairs computed");
+  if (info.first_unsorted >= 0) DieLine(in.col.line[(size_t)info.first_unsorted], AdjacentOrderMessage(sorted_by_strand));
+  AdjacentParserError(in.col, "");
+  fflush(stdout);
+  fprintf(stderr, "* The file is sorted! Found %ld inclusions and %ld overlaps.\n", (long)info.n_inclusions, (long)info.n_overlaps);
+}
+
+void GenomicRegionSet::RunGlobalCalcDistances(char *op1, char *op2)
+{
+  if (n_regions == 0) return;
+  AdjacentInput in;
+  AdjacentRead(this, "gdist", true, &in);
+  const LinkColumns &col = in.col;
+  const size_t n = in.size();
+  const int p1 = AdjacentPoint(op1), p2 = AdjacentPoint(op2);
+  const bool known = p1 >= 0 && p2 >= 0;
+  std::vector<uint8_t> minus(n);
+  for (size_t k = 0; k < n; k++) minus[k] = col.strand[k] == '-';
+  std::vector<int64_t> dist(std::max<size_t>(n, 1));
+  gtx_adjacent_info info = {-1, 0, 0};
+  gtx_ctx *ctx = AdjacentContext();
+  const int rc = gtx_adjacent(ctx, in.tri.data(), minus.data(), (int64_t)n, known ? p1 : GTX_POINT_START, known ? p2 : GTX_POINT_START, dist.data(), &info);
+  if (rc != GTX_OK) AdjacentDie(ctx, rc);
+  Mark("adjacent: distances computed");
+  // one line per pair (k - 1, k) in front of the first error; an unknown operation word is met at the first compatible pair (:471)
+  size_t n_print = info.first_unsorted >= 0 ? (size_t)info.first_unsorted : n;
+  bool unknown_met = false;
+  if (!known)
+    for (size_t k = 1; k < n_print; k++) if (dist[k] != INT64_MIN) { n_print = k; unknown_met = true; break; }
+  PrintInChunks(n_print > 0 ? n_print - 1 : 0, [&](std::string &buf, size_t j) {
+    const size_t k = j + 1;
+    buf += col.label[k - 1]; buf.push_back('\t'); buf += col.label[k]; buf.push_back('\t');
+    if (dist[k] == INT64_MIN) buf += "NaN"; else LinkPutNum(buf, (long)dist[k]);
+    buf.push_back('\n');
+  });
+  Mark("adjacent: output written");
+  if (unknown_met) {
+    printf("%s\t%s\t", col.label[n_print - 1], col.label[n_print]);
+    fflush(stdout); fprintf(stderr, "Error: unknown offset reference point operation!\n"); exit(1);
+  }
+  if (info.first_unsorted >= 0) DieLine(col.line[(size_t)info.first_unsorted], AdjacentOrderMessage(true));
+  AdjacentParserError(col, "this operation requires single-interval regions!");
+}
+
+void GenomicRegionSet::RunGlobalInvert(StringLIntMap *bounds)
+{
+  if (n_regions == 0) return;
+  AdjacentInput in;
+  in.col.want_score = true;
+  AdjacentRead(this, "inv", true, &in);
+  const LinkColumns &col = in.col;
+  const size_t n = in.size();
+  // a bound per class: 2 * the chromosome's rank + strand
+  std::vector<int64_t> size(2 * in.names.size(), -1);
+  for (size_t r = 0; r < in.names.size(); r++) {
+    StringLIntMap::iterator it = bounds->find(in.names[r]);
+    if (it != bounds->end()) size[2 * r] = size[2 * r + 1] = it->second;
+  }
+  gtx_gaps_info info = {0, -1, 0};
+  std::vector<uint32_t> owner; std::vector<int32_t> gstart, gstop;
+  gtx_ctx *ctx = AdjacentContext();
+  for (int64_t cap = (int64_t)(n / 2 + 1024); n > 0; cap = info.n_gaps) {       // (the policy of gtx_window_select: at most one repeat)
+    owner.resize((size_t)cap); gstart.resize((size_t)cap); gstop.resize((size_t)cap);
+    const int rc = gtx_gaps(ctx, in.tri.data(), (int64_t)n, size.data(), (int32_t)size.size(), cap, owner.data(), gstart.data(), gstop.data(), &info);
+    if (rc != GTX_OK) AdjacentDie(ctx, rc);
+    if (info.n_gaps <= cap) break;
+  }
+  Mark("adjacent: gaps computed");
+  size_t n_print = (size_t)info.n_gaps;
+  // The parser's stop line ended the run of the last region only if the reference got as far as looking at it: a malformed line dies
+  // in Next() (:4588), and a multi-interval line that continues the run dies at :4589 -- in both cases before the trailing gap (:4596).
+  if (info.first_bad < 0 && col.why != LinkColumns::NONE && n > 0) {
+    const bool continues = col.why == LinkColumns::MULTI && strcmp(col.stop_chrom, col.chrom[n - 1]) == 0 && col.stop_strand == col.strand[n - 1];
+    if (col.why != LinkColumns::MULTI || continues) {
+      const bool head = n == 1 || in.tri[3 * (n - 1)] != in.tri[3 * (n - 2)];
+      const size_t own_front = head ? col.start[n - 1] > 1 : col.start[n - 1] > col.stop[n - 2] + 1;
+      size_t owned = 0;
+      while (owned < n_print && owner[n_print - 1 - owned] == (uint32_t)(n - 1)) owned++;
+      if (owned > own_front) n_print--;
+    }
+  }
+  PrintInChunks(n_print, [&](std::string &buf, size_t g) {
+    const size_t o = owner[g];
+    buf += col.chrom[o]; buf.push_back('\t'); LinkPutNum(buf, (long)gstart[g] - 1); buf.push_back('\t'); LinkPutNum(buf, (long)gstop[g]);
+    buf += "\t_\t"; LinkPutNum(buf, col.score[o] ? atol(col.score[o]) : 0); buf.push_back('\t'); buf.push_back(col.strand[o]); buf.push_back('\n');
+  });
+  Mark("adjacent: output written");
+  if (info.first_bad >= 0) {
+    const size_t b = (size_t)info.first_bad;
+    if (info.bad_kind == 1) DieLine(col.line[b], AdjacentOrderMessage(true));
+    // (:4585 prints the buffer's line counter: the line behind the head's, or 0 when the head is the file's last line)
+    fflush(stdout);
+    fprintf(stderr, "Line %ld: chromosome %s not found!\n", col.line[b] < in.total_lines ? col.line[b] + 1 : 0L, col.chrom[b]);
+    exit(1);
+  }
+  AdjacentParserError(col, "not a single-interval region!");
 }

@@ -146,6 +146,17 @@ class GenomicRegionSet
   // GTX_TEXT_TRACE=1 reports which way the text went.  Known limit: labels that atof() reads as nan or inf are folded with
   // std::min / std::max and printed with "%g", which may differ from the reference's stream output in spelling or in which operand wins.
   void RunGlobalLink(bool sorted_by_strand, long int max_difference, char *label_func);
+  // The reference's three other operations over a position-sorted stream that compare a region with the one directly in front of it
+  // (genomic_intervals.cpp:4576-4600, :4523-4542, :4755-4778): `inv` (the complement inside the chromosome bounds), `gdist` (the
+  // distance between successive regions) and `test` (is the file sorted; its inclusions and overlaps).  Same signatures, output and
+  // errors.  MI355X path, for a streamed BED set: the lines are read by link's host parser, packed with chromosome = strcmp rank and
+  // the strand folded below it (always for inv / gdist, under sorted_by_strand for test) and handed to gtx_gaps / gtx_adjacent
+  // (include/gtx.h); the printing is done here in bulk.  The earliest of {malformed line, multi-interval line, the device's first
+  // bad region} ends the run, with the output in front of it on stdout.  A gap prints through the BED form of PrintModified (:2310-2314)
+  // with the score of the region it is printed through -- 0 for a line with fewer than 5 tokens, where the reference's is unset.
+  void RunGlobalInvert(StringLIntMap *bounds);
+  void RunGlobalCalcDistances(char *op1, char *op2);
+  void RunGlobalTest(bool sorted_by_strand);
 
   // MI355X path: hands the not yet consumed part of a streaming set (the current region's raw
   // line first) to the bulk packer.  After this call Get()/Next() report the end of the set.

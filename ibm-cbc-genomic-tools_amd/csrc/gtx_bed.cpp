@@ -379,7 +379,7 @@ BedStatus ParseBedLine(char *line, BedFields *o, char **bad)
   o->stop = FastAtol(TakeToken(&cur, sep));
   o->strand = '+';
   o->label = o->n_tokens == 3 ? nullptr : TakeToken(&cur, sep);
-  if (o->n_tokens >= 5) (void)TakeToken(&cur, sep);     // score
+  o->score = o->n_tokens >= 5 ? TakeToken(&cur, sep) : nullptr;
   if (o->n_tokens >= 6) {
     char *t = TakeToken(&cur, sep);
     if (!strcmp(t, "1") || !strcmp(t, "+") || !strcmp(t, ".")) o->strand = '+';

@@ -70,6 +70,7 @@ void ParallelFor(int n, const std::function<void(int)> &fn);
 // ---- one BED line ---------------------------------------------------------------------------------
 struct BedFields {
   char *chrom; char *label;          // label == NULL means "_" (3-column line)
+  char *score = nullptr;             // the 5th token as it stands (NULL with fewer than 5: the reference leaves its score unset, :2167)
   long start, stop;                  // 1-based inclusive
   char strand;
   int n_tokens;

@@ -23,6 +23,7 @@
 #include "gtx_signal.h"
 #include "gtx_text.h"
 #include "gtx_link.h"
+#include "gtx_adjacent.h"
 #include "gtx_select.h"
 #include "gtx_internal.h"
 
@@ -202,6 +203,12 @@ struct gtx_ctx {
   // gtx_link_text_begin .. _end: the input collected on the device block by block, the strands beside it, the heads' keys
   bool linkTextOpen = false; int64_t linkTextN = 0, linkTextCap = 0; int linkTextChrom = 0, linkTextByStrand = 0;
   DevBuf<int> linkTextTri; DevBuf<unsigned char> linkMinus; DevBuf<int2> linkHeadKey;
+  // the neighbour passes (gtx_adjacent / gtx_gaps): per-tile sums, per-span gap counts and bases, the class bounds, the info blocks
+  // and their page-locked copies (handed over like link's), the host entries' inputs and outputs
+  DevBuf<uint2> adjSums; DevBuf<unsigned> gapCount; DevBuf<long long> gapBase, gapBounds;
+  DevBuf<gtx::AdjInfo> adjInfo; PinBuf<gtx::AdjInfo> adjHost; gtx_adjacent_info *adjPending = nullptr;
+  DevBuf<gtx::GapInfo> gapInfo; PinBuf<gtx::GapInfo> gapHost; gtx_gaps_info *gapPending = nullptr;
+  DevBuf<int> adjTri, gapStart, gapStop; DevBuf<unsigned char> adjMinus; DevBuf<long long> adjDist; DevBuf<unsigned> gapOwner;
 
   DevBuf<gtx::DevInfo> d_info;          // 2 blocks: the finalize of one call resets the block of the next
   int infoCur = 0;
@@ -430,6 +437,8 @@ const char *gtx_last_error(const gtx_ctx *c) { return c ? c->err.c_str() : g_cre
 
 int gtx_set_stream(gtx_ctx *c, void *s) { if (!c) return GTX_E_ARG; c->stream = (hipStream_t)s; return GTX_OK; }
 
+static void adjacent_hand_over(gtx_ctx *c);
+
 int gtx_sync(gtx_ctx *c)
 {
   if (!c) return GTX_E_ARG;
@@ -441,6 +450,7 @@ int gtx_sync(gtx_ctx *c)
     c->linkPending->n_groups = h.nGroups; c->linkPending->first_unsorted = h.firstUnsortedOut;
     c->linkPending = nullptr;
   }
+  adjacent_hand_over(c);
   return GTX_OK;
 }
 
@@ -2986,6 +2996,147 @@ int gtx_link_text_end(gtx_ctx *c, int64_t max_difference, uint32_t *head_out, in
     HIPCHK(c, hipMemcpyAsync(head_out, c->linkHead.get(), sizeof(uint32_t) * g, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(stop_out, c->linkStop.get(), sizeof(int32_t) * g, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(head_key_out, c->linkHeadKey.get(), sizeof(int2) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return GTX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the neighbour passes (kernels: gtx_adjacent.hip)
+// ---------------------------------------------------------------------------------------------
+// the info blocks of device calls that have completed go to their callers' structs
+static void adjacent_hand_over(gtx_ctx *c)
+{
+  if (c->adjPending) {
+    const gtx::AdjInfo &h = c->adjHost.get()[0];
+    c->adjPending->first_unsorted = h.firstUnsortedOut; c->adjPending->n_inclusions = h.nInclusions; c->adjPending->n_overlaps = h.nOverlaps;
+    c->adjPending = nullptr;
+  }
+  if (c->gapPending) {
+    const gtx::GapInfo &h = c->gapHost.get()[0];
+    c->gapPending->n_gaps = h.nGaps; c->gapPending->first_bad = h.firstBadOut; c->gapPending->bad_kind = h.badKind;
+    c->gapPending = nullptr;
+  }
+}
+
+// ... before a page-locked block is used again
+static int adjacent_settle(gtx_ctx *c)
+{
+  if (!c->adjPending && !c->gapPending) return GTX_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  adjacent_hand_over(c);
+  return GTX_OK;
+}
+
+static int adjacent_enqueue(gtx_ctx *c, const void *d_tri, const void *d_minus, int64_t n, int op1, int op2, void *d_dist)
+{
+  HIPCHK(c, c->adjSums.reserve((size_t)gtx::adjacent_tiles(n)));
+  if (!c->adjInfo) HIPCHK(c, c->adjInfo.alloc(1));
+  if (!c->adjHost) HIPCHK(c, c->adjHost.alloc(1));
+  HIPCHK(c, gtx::launch_adjacent((const int *)d_tri, (const unsigned char *)d_minus, n, op1, op2, (long long *)d_dist, c->adjSums.get(), c->adjInfo.get(), c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->adjHost.get(), c->adjInfo.get(), sizeof(gtx::AdjInfo), hipMemcpyDeviceToHost, c->stream));
+  return GTX_OK;
+}
+
+static bool adjacent_args_ok(int64_t n, int op1, int op2, const void *tri, const void *info)
+{
+  return n >= 0 && n < (1ll << 32) && op1 >= GTX_POINT_START && op1 <= GTX_POINT_3P && op2 >= GTX_POINT_START && op2 <= GTX_POINT_3P && info && (n == 0 || tri);
+}
+
+int gtx_adjacent_device(gtx_ctx *c, const void *d_triples, const void *d_minus, int64_t n, int op1, int op2, void *d_dist, gtx_adjacent_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (!adjacent_args_ok(n, op1, op2, d_triples, info)) return fail(c, GTX_E_ARG, "gtx_adjacent_device: bad argument (n < 2^32, points 0..3)");
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = adjacent_settle(c); if (rc) return rc; }
+  info->first_unsorted = -1; info->n_inclusions = 0; info->n_overlaps = 0;
+  if (n == 0) return GTX_OK;
+  if (int rc = adjacent_enqueue(c, d_triples, d_minus, n, op1, op2, d_dist)) return rc;
+  c->adjPending = info;
+  return GTX_OK;
+}
+
+int gtx_adjacent(gtx_ctx *c, const int32_t *triples, const uint8_t *minus, int64_t n, int op1, int op2, int64_t *dist_out, gtx_adjacent_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (!adjacent_args_ok(n, op1, op2, triples, info)) return fail(c, GTX_E_ARG, "gtx_adjacent: bad argument (n < 2^32, points 0..3)");
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = adjacent_settle(c); if (rc) return rc; }
+  info->first_unsorted = -1; info->n_inclusions = 0; info->n_overlaps = 0;
+  if (n == 0) return GTX_OK;
+  const size_t m = (size_t)n;
+  const bool strands = minus != nullptr && dist_out != nullptr;
+  HIPCHK(c, c->adjTri.reserve(3 * m));
+  if (strands) HIPCHK(c, c->adjMinus.reserve(m));
+  if (dist_out) HIPCHK(c, c->adjDist.reserve(m));
+  HIPCHK(c, hipMemcpyAsync(c->adjTri.get(), triples, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+  if (strands) HIPCHK(c, hipMemcpyAsync(c->adjMinus.get(), minus, m, hipMemcpyHostToDevice, c->stream));
+  if (int rc = adjacent_enqueue(c, c->adjTri.get(), strands ? c->adjMinus.get() : nullptr, n, op1, op2, dist_out ? c->adjDist.get() : nullptr)) return rc;
+  if (dist_out) HIPCHK(c, hipMemcpyAsync(dist_out, c->adjDist.get(), sizeof(int64_t) * m, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const gtx::AdjInfo &h = c->adjHost.get()[0];
+  info->first_unsorted = h.firstUnsortedOut; info->n_inclusions = h.nInclusions; info->n_overlaps = h.nOverlaps;
+  return GTX_OK;
+}
+
+// the arguments of both gap entries; the bounds go to the device here (they are host memory in both)
+static int gaps_prepare(gtx_ctx *c, const char *who, const void *tri, int64_t n, const int64_t *bounds, int32_t n_bounds, int64_t capacity, const void *owner,
+                        const void *start, const void *stop, gtx_gaps_info *info)
+{
+  if (n < 0 || n >= (1ll << 32) || n_bounds < 0 || (n_bounds > 0 && !bounds) || capacity < 0 || !info || (n > 0 && !tri) || (capacity > 0 && (!owner || !start || !stop)))
+    return fail(c, GTX_E_ARG, (std::string(who) + ": bad argument (n < 2^32)").c_str());
+  for (int32_t k = 0; k < n_bounds; k++)
+    if (bounds[k] > (int64_t)INT32_MAX - 2) return fail(c, GTX_E_RANGE, (std::string(who) + ": a bound above 2^31 - 3").c_str());
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = adjacent_settle(c); if (rc) return rc; }
+  info->n_gaps = 0; info->first_bad = -1; info->bad_kind = 0;
+  if (n == 0) return GTX_OK;
+  HIPCHK(c, c->gapBounds.reserve((size_t)std::max<int32_t>(n_bounds, 1)));
+  if (n_bounds > 0) HIPCHK(c, hipMemcpyAsync(c->gapBounds.get(), bounds, sizeof(int64_t) * (size_t)n_bounds, hipMemcpyHostToDevice, c->stream));
+  const size_t ns = (size_t)gtx::adjacent_spans(n);
+  HIPCHK(c, c->gapCount.reserve(ns)); HIPCHK(c, c->gapBase.reserve(ns + 1));
+  if (!c->gapInfo) HIPCHK(c, c->gapInfo.alloc(1));
+  if (!c->gapHost) HIPCHK(c, c->gapHost.alloc(1));
+  return GTX_OK;
+}
+
+static int gaps_enqueue(gtx_ctx *c, const void *d_tri, int64_t n, int32_t n_bounds, int64_t capacity, void *d_owner, void *d_start, void *d_stop)
+{
+  HIPCHK(c, gtx::launch_gaps((const int *)d_tri, n, c->gapBounds.get(), n_bounds, capacity, c->gapCount.get(), c->gapBase.get(), c->gapInfo.get(), (unsigned *)d_owner,
+                             (int *)d_start, (int *)d_stop, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->gapHost.get(), c->gapInfo.get(), sizeof(gtx::GapInfo), hipMemcpyDeviceToHost, c->stream));
+  return GTX_OK;
+}
+
+int gtx_gaps_device(gtx_ctx *c, const void *d_triples, int64_t n, const int64_t *bounds, int32_t n_bounds, int64_t capacity, void *d_owner, void *d_start, void *d_stop,
+                    gtx_gaps_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (int rc = gaps_prepare(c, "gtx_gaps_device", d_triples, n, bounds, n_bounds, capacity, d_owner, d_start, d_stop, info)) return rc;
+  if (n == 0) return GTX_OK;
+  if (int rc = gaps_enqueue(c, d_triples, n, n_bounds, capacity, d_owner, d_start, d_stop)) return rc;
+  c->gapPending = info;
+  return GTX_OK;
+}
+
+int gtx_gaps(gtx_ctx *c, const int32_t *triples, int64_t n, const int64_t *bounds, int32_t n_bounds, int64_t capacity, uint32_t *owner_out, int32_t *start_out,
+             int32_t *stop_out, gtx_gaps_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (int rc = gaps_prepare(c, "gtx_gaps", triples, n, bounds, n_bounds, capacity, owner_out, start_out, stop_out, info)) return rc;
+  if (n == 0) return GTX_OK;
+  const size_t m = (size_t)n, cap = (size_t)std::max<int64_t>(capacity, 1);
+  HIPCHK(c, c->adjTri.reserve(3 * m)); HIPCHK(c, c->gapOwner.reserve(cap)); HIPCHK(c, c->gapStart.reserve(cap)); HIPCHK(c, c->gapStop.reserve(cap));
+  HIPCHK(c, hipMemcpyAsync(c->adjTri.get(), triples, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice, c->stream));
+  if (int rc = gaps_enqueue(c, c->adjTri.get(), n, n_bounds, capacity, c->gapOwner.get(), c->gapStart.get(), c->gapStop.get())) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const gtx::GapInfo &h = c->gapHost.get()[0];
+  info->n_gaps = h.nGaps; info->first_bad = h.firstBadOut; info->bad_kind = h.badKind;
+  const size_t g = (size_t)std::min<int64_t>(h.nGaps, capacity);
+  if (g) {
+    HIPCHK(c, hipMemcpyAsync(owner_out, c->gapOwner.get(), sizeof(uint32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(start_out, c->gapStart.get(), sizeof(int32_t) * g, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(stop_out, c->gapStop.get(), sizeof(int32_t) * g, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return GTX_OK;

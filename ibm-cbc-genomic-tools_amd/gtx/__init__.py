@@ -27,6 +27,8 @@ LINK_SUM = 1              # gtx_link: fold the values (at most one of the three)
 LINK_MIN = 2
 LINK_MAX = 4
 LINK_TILE = 2048          # GTX_LINK_TILE: regions per block of link's scans
+ADJACENT_TILE = 2048      # GTX_ADJACENT_TILE: regions per block of the neighbour passes
+POINTS = {"1": 0, "2": 1, "5p": 2, "3p": 3}   # GTX_POINT_*: gdist's reference points
 SCAN_KEEP_SLOTS = 8       # GTX_SCAN_KEEP_SLOTS: window vectors a context keeps in HBM
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 REFS_KEEP_ZERO_LENGTH = 1
@@ -57,6 +59,20 @@ class SignalInfo(ctypes.Structure):
 
 class LinkInfo(ctypes.Structure):
     _fields_ = [("n_groups", ctypes.c_int64), ("first_unsorted", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class AdjacentInfo(ctypes.Structure):
+    _fields_ = [("first_unsorted", ctypes.c_int64), ("n_inclusions", ctypes.c_int64), ("n_overlaps", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class GapsInfo(ctypes.Structure):
+    _fields_ = [("n_gaps", ctypes.c_int64), ("first_bad", ctypes.c_int64), ("bad_kind", ctypes.c_int32)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -137,6 +153,13 @@ ABI = {
     "gtx_link_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_link_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     "gtx_link_text_end": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_adjacent": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_adjacent_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "gtx_gaps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_gaps_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_group_count_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_group_coverage_add_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_group_text_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -611,6 +634,57 @@ class Engine:
         self._link_infos.append(info)                       # the library writes it at the next sync: it must live until then
         self._chk(self.lib.gtx_link_device(self.ctx, _ptr(d_regions), _ptr(d_values), int(n), int(max_difference), int(flags), _ptr(d_heads),
                                            _ptr(d_counts), _ptr(d_stops), _ptr(d_folded), ctypes.byref(info)))
+        return info
+
+    def adjacent(self, regions, minus=None, op1=0, op2=0, want_dist=False):
+        """gtx_adjacent: (distances int64 or None, info) of a position-sorted stream of (class, start, stop): the first region before
+        its predecessor, the inclusions and overlaps among same-class neighbours, and with want_dist per region the distance from
+        its predecessor's point op1 to its own point op2 (POINTS; INT64_MIN where there is none).  minus: one strand byte per region."""
+        regions = _triples(regions)
+        n = regions.shape[0]
+        m = None if minus is None else np.ascontiguousarray(minus, dtype=np.uint8)
+        if m is not None and len(m) != n:
+            raise GtxError("adjacent: one strand byte per region")
+        dist = np.zeros(n, dtype=np.int64) if want_dist else None
+        info = AdjacentInfo()
+        self._chk(self.lib.gtx_adjacent(self.ctx, _ptr(regions), _ptr(m), n, int(op1), int(op2), _ptr(dist), ctypes.byref(info)))
+        return dist, info.as_dict()
+
+    def adjacent_device(self, d_regions, n, d_minus=None, op1=0, op2=0, d_dist=None):
+        """gtx_adjacent_device on raw device addresses; returns the AdjacentInfo the library fills: read it after sync()."""
+        info = AdjacentInfo()
+        self._link_infos = getattr(self, "_link_infos", [])
+        self._link_infos.append(info)                       # the library writes it at the next sync: it must live until then
+        self._chk(self.lib.gtx_adjacent_device(self.ctx, _ptr(d_regions), _ptr(d_minus), int(n), int(op1), int(op2), _ptr(d_dist), ctypes.byref(info)))
+        return info
+
+    def gaps(self, regions, bounds, capacity=None):
+        """gtx_gaps: (owners uint32, starts int32, stops int32, info) of the gaps between the regions of a position-sorted stream inside
+        their classes' bounds (int64 per class id, < 0: missing).  When info's n_gaps exceeds `capacity` only the first `capacity`
+        gaps are returned; capacity=None grows and repeats the call until everything fits."""
+        regions = _triples(regions)
+        n = regions.shape[0]
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        info = GapsInfo()
+        cap = int(capacity) if capacity is not None else max(1024, n // 4)
+        while True:
+            owners, starts, stops = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.int32), np.zeros(max(cap, 1), dtype=np.int32)
+            self._chk(self.lib.gtx_gaps(self.ctx, _ptr(regions), n, _ptr(b), len(b), cap, _ptr(owners), _ptr(starts), _ptr(stops), ctypes.byref(info)))
+            if capacity is not None or info.n_gaps <= cap:
+                break
+            cap = int(info.n_gaps)
+        got = min(int(info.n_gaps), cap)
+        return owners[:got], starts[:got], stops[:got], info.as_dict()
+
+    def gaps_device(self, d_regions, n, bounds, capacity, d_owners, d_starts, d_stops):
+        """gtx_gaps_device on raw device addresses (bounds: host array; outputs sized capacity); returns the GapsInfo the library
+        fills: read it after sync()."""
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        info = GapsInfo()
+        self._link_infos = getattr(self, "_link_infos", [])
+        self._link_infos.append(info)
+        self._chk(self.lib.gtx_gaps_device(self.ctx, _ptr(d_regions), int(n), _ptr(b), len(b), int(capacity), _ptr(d_owners), _ptr(d_starts), _ptr(d_stops),
+                                           ctypes.byref(info)))
         return info
 
     def scan(self, reads, class_len, win_step, win_size, preprocess="1", weights=None, flags=0):

@@ -595,6 +595,49 @@ int gtx_link_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_li
 int gtx_link_add(gtx_ctx *ctx, const int32_t *triples, const uint8_t *minus, int64_t n);
 int gtx_link_text_end(gtx_ctx *ctx, int64_t max_difference, uint32_t *head_out, int32_t *stop_out, int32_t *head_key_out, gtx_link_info *info);
 
+/* The neighbour passes over a position-sorted region stream: the reference's `genomic_regions test [-s]`, `gdist [-op1 X] [-op2 Y]`
+ * and `inv -g GENOME` (genomic_regions.cpp:413-419, 429-435, 445-451, 525-528, 536-538, 627-629, 741-745).  All three compare a
+ * region with the one directly in front of it; nothing is carried along the stream.  Classes as for gtx_link: the caller folds the
+ * chromosome's strcmp rank and, sorting by strand, the strand below it into the class id; for gtx_adjacent any int32 is a class.
+ * n < 2^32 (else GTX_E_ARG); n = 0 is legal and writes nothing.
+ *
+ * gtx_adjacent (RunGlobalTest genomic_intervals.cpp:4755-4778, RunGlobalCalcDistances :4523-4542): info->first_unsorted = the first
+ * region that is before its predecessor in (class, start) (IsBefore :396-401), or -1.  n_inclusions / n_overlaps, over ALL pairs
+ * (i - 1, i) of one class (IsCompatibleWith :416-421) whatever first_unsorted says: with START[i] <= STOP[i - 1] the pair is an
+ * inclusion when STOP[i] <= STOP[i - 1] and an overlap otherwise (:4765-4769; the predecessor, not a running maximum).  dist_out (may
+ * be NULL): one int64 per region -- for i >= 1 in its predecessor's class coord(i, op2) - coord(i - 1, op1) (CalcDistanceFrom
+ * :438-441), coord by GetCoordinate (:465-472): GTX_POINT_START, GTX_POINT_STOP, or the 5' / 3' end by the region's own strand
+ * (minus[i] != 0: '-'; minus = NULL: all '+'); INT64_MIN for region 0 and after a class change (the reference's NaN).  An op outside
+ * 0..3 is GTX_E_ARG.  gtx_adjacent_device: the pointers but info in the context's HBM, enqueued on its stream; *info is valid after
+ * gtx_sync (and must live until then).
+ *
+ * gtx_gaps (RunGlobalInvert :4576-4600): a run is a maximal stretch of consecutive regions of one class.  bounds[c] is class c's size
+ * (< 0: missing), a bound above 2^31 - 3 is GTX_E_RANGE.  The head of a run owns the gap [1, START - 1] when START > 1 (:4587); every
+ * other region the gap [pSTOP + 1, START - 1] when START > pSTOP + 1, pSTOP the STOP of the region directly in front of it (:4592;
+ * taken in 64 bits); the last region of a run then owns [STOP + 1, size] when STOP + 1 < size (:4596).  A region is bad when it is
+ * inside a run and START < its predecessor's START (bad_kind 1: the order error, :4591) or heads a run whose class is outside
+ * [0, n_bounds) or has no bound (bad_kind 2: "chromosome not found", :4585).  info->first_bad = the first bad region or -1, and exactly
+ * the gaps owned by the regions in front of it are reported, in stream order: owner (the region's ordinal), start, stop.
+ * info->n_gaps is their number whatever the capacity; when it exceeds capacity only the first `capacity` gaps have been written and
+ * nothing behind them: grow the buffers and call again (the policy of gtx_window_select).  bounds is host memory in both entries.
+ * gtx_gaps_device: triples and outputs in the context's HBM, enqueued; *info is valid after gtx_sync.
+ * Tiles of GTX_ADJACENT_TILE regions; the bounds sit in LDS up to 4096 classes and are read through L2 beyond that. */
+#define GTX_ADJACENT_TILE 2048   /* regions per block of the passes (what tests place their boundary cases by) */
+#define GTX_POINT_START 0        /* "1"  */
+#define GTX_POINT_STOP  1        /* "2"  */
+#define GTX_POINT_5P    2        /* "5p" */
+#define GTX_POINT_3P    3        /* "3p" */
+typedef struct gtx_adjacent_info { int64_t first_unsorted /* -1: none */, n_inclusions, n_overlaps; } gtx_adjacent_info;
+int gtx_adjacent(gtx_ctx *ctx, const int32_t *triples, const uint8_t *minus /* NULL: all '+' */, int64_t n, int op1, int op2,
+                 int64_t *dist_out /* may be NULL */, gtx_adjacent_info *info);
+int gtx_adjacent_device(gtx_ctx *ctx, const void *d_triples, const void *d_minus, int64_t n, int op1, int op2, void *d_dist,
+                        gtx_adjacent_info *info);
+typedef struct gtx_gaps_info { int64_t n_gaps /* needed, may exceed capacity */, first_bad /* -1: none */; int32_t bad_kind /* 0 none, 1 order, 2 no bound */; } gtx_gaps_info;
+int gtx_gaps(gtx_ctx *ctx, const int32_t *triples, int64_t n, const int64_t *bounds, int32_t n_bounds, int64_t capacity,
+             uint32_t *owner_out, int32_t *start_out, int32_t *stop_out, gtx_gaps_info *info);
+int gtx_gaps_device(gtx_ctx *ctx, const void *d_triples, int64_t n, const int64_t *bounds, int32_t n_bounds, int64_t capacity,
+                    void *d_owner, void *d_start, void *d_stop, gtx_gaps_info *info);
+
 /* genomic_scans counts fed as a stream (UnsortedGenomicRegionSetScanner ctor genomic_intervals.cpp:5019-5080, sorted scanner :4928-4957):
  * gtx_scan_begin fixes the geometry (arguments as gtx_scan; flags: GTX_ZERO_LENGTH_OK = the sorted scanner's rule; weighted != 0: every
  * batch brings label weights), gtx_scan_add adds packed reads from host memory (flags: GTX_READS_UNSORTED as a hint), gtx_scan_add_text a

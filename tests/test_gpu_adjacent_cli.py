@@ -1,0 +1,162 @@
+"""genomic_adjacent (csrc/genomic_adjacent.cpp; GenomicRegionSet::RunGlobalInvert / RunGlobalCalcDistances / RunGlobalTest in
+csrc/genomic_intervals.cpp) against the restatement's rendering (tests/adjacent_restate.py), byte for byte: stdout, stderr and the exit
+code -- on the hand-derived vectors, on a random 50 000-line file per operation, and on files with an error in their middle."""
+import gzip
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import adjacent_restate as ar
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOOL = os.path.join(ROOT, "ibm-cbc-genomic-tools_amd", "csrc", "genomic_adjacent")
+CASES = json.load(open(os.path.join(ROOT, "tests", "golden", "adjacent_manifest.json")))
+NAMES = ("chr1", "chr10", "chr2", "chrX")
+SIZES = {"chr1": 5_000_000, "chr10": 4_000_100, "chr2": 4_000_050, "chrX": 6_000_000}
+
+
+def tool(args, cwd, stdin=None):
+    r = subprocess.run([TOOL] + args, capture_output=True, cwd=cwd, input=stdin)
+    return r.stdout.decode(), r.stderr.decode(), r.returncode
+
+
+def genome(tmp_path, bounds):
+    (tmp_path / "genome.bed").write_text("".join("%s\t0\t%d\n" % (c, n) for c, n in bounds.items()))
+    return ["-g", "genome.bed"]
+
+
+def args_of(tmp_path, op, s=False, op1="1", op2="1", bounds=None):
+    if op == "inv":
+        return ["inv"] + genome(tmp_path, bounds)
+    if op == "gdist":
+        return ["gdist"] + (["-op1", op1] if op1 != "1" else []) + (["-op2", op2] if op2 != "1" else [])
+    return ["test"] + (["-s"] if s else [])
+
+
+def want(text, op, s=False, op1="1", op2="1", bounds=None):
+    """the restatement on a file's text: a last line without its newline is not a line (gtools/core.cpp:241-259)"""
+    lines = text.split("\n")[:-1]
+    return ar.inv_lines(lines, bounds) if op == "inv" else ar.gdist_lines(lines, op1, op2) if op == "gdist" else ar.test_lines(lines, s)
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_hand_derived_vectors(tmp_path, case):
+    (tmp_path / "in.bed").write_text("".join(x + "\n" for x in case["lines"]))
+    got = tool(args_of(tmp_path, case["op"], case["s"], case["op1"], case["op2"], case["bounds"]) + ["in.bed"], tmp_path)
+    assert got == (case["stdout"], case["stderr"], case["code"])
+
+
+def bed_lines(seed, n, by_strand=True, span=4_000_000):
+    rng = np.random.default_rng(seed)
+    chrom, strand = rng.integers(0, len(NAMES), size=n), rng.integers(0, 2, size=n)
+    start = rng.integers(0, span, size=n)
+    stop = start + rng.integers(1, 200, size=n)
+    score = rng.integers(0, 1000, size=n)
+    order = sorted(range(n), key=(lambda k: (NAMES[chrom[k]].encode(), strand[k], start[k])) if by_strand else (lambda k: (NAMES[chrom[k]].encode(), start[k])))
+    return ["%s\t%d\t%d\tr%d\t%d\t%s" % (NAMES[chrom[k]], start[k], stop[k], k, score[k], "+-"[strand[k]]) for k in order]
+
+
+def text_of(lines):
+    return "".join(x + "\n" for x in lines)
+
+
+@pytest.mark.parametrize("op,s,op1,op2", [("inv", False, "1", "1"), ("gdist", False, "2", "1"), ("gdist", False, "5p", "3p"), ("test", False, "1", "1"),
+                                          ("test", True, "1", "1")], ids=["inv", "gdist-2-1", "gdist-5p-3p", "test", "test-s"])
+def test_a_random_50k_line_file(tmp_path, op, s, op1, op2):
+    text = "track name=reads\n" + text_of(bed_lines(1, 50_000, by_strand=(op != "test" or s), span=1_500_000))
+    (tmp_path / "in.bed").write_text(text)
+    exp = want(text, op, s, op1, op2, SIZES)
+    assert exp[2] == 0 and exp[0].startswith("track name=reads\n")
+    if op == "inv":
+        assert exp[0].count("\n") > 25_000
+    elif op == "gdist":
+        assert exp[0].count("\n") == 50_000 and exp[0].count("NaN") == 7
+    else:
+        assert "Found 0 inclusions" not in exp[1] and " 0 overlaps" not in exp[1]
+    assert tool(args_of(tmp_path, op, s, op1, op2, SIZES) + ["in.bed"], tmp_path) == exp
+
+
+@pytest.mark.parametrize("op", ["inv", "gdist", "test"])
+def test_stdin_gz_and_a_last_line_without_newline(tmp_path, op):
+    text = text_of(bed_lines(3, 3000))
+    (tmp_path / "in.bed.gz").write_bytes(gzip.compress(text.encode()))
+    a = args_of(tmp_path, op, True, "3p", "2", SIZES)
+    exp = want(text, op, True, "3p", "2", SIZES)
+    assert exp[2] == 0
+    assert tool(a + ["in.bed.gz"], tmp_path) == exp
+    assert tool(a, tmp_path, stdin=text.encode()) == exp
+    cut = text[:-1]                                                              # the last line is not a line
+    assert tool(a, tmp_path, stdin=cut.encode()) == want(cut, op, True, "3p", "2", SIZES)
+
+
+def test_an_order_error_at_a_late_line(tmp_path):
+    lines = bed_lines(4, 9000)
+    k = next(j for j in range(7000, 8999) if lines[j].split("\t")[0::5] == lines[j + 1].split("\t")[0::5] and lines[j].split("\t")[1] != lines[j + 1].split("\t")[1])
+    lines[k], lines[k + 1] = lines[k + 1], lines[k]                              # line k + 2 is before line k + 1
+    text = text_of(lines)
+    (tmp_path / "in.bed").write_text(text)
+    for op in ("inv", "gdist", "test"):
+        exp = want(text, op, True, "1", "2", SIZES)
+        assert exp[2] == 1 and "Line %d: input regions are not sorted (sorted-by-strand = true)!" % (k + 2) in exp[1]
+        assert exp[0].count("\n") > (3000 if op != "test" else -1)
+        assert tool(args_of(tmp_path, op, True, "1", "2", SIZES) + ["in.bed"], tmp_path) == exp
+
+
+def test_a_missing_chromosome_in_the_middle(tmp_path):
+    lines = bed_lines(5, 6000)
+    text = text_of(lines)
+    (tmp_path / "in.bed").write_text(text)
+    part = {c: n for c, n in SIZES.items() if c != "chr2"}
+    exp = want(text, "inv", bounds=part)
+    head = next(j for j in range(len(lines)) if lines[j].startswith("chr2\t"))
+    assert exp[1:] == ("Line %d: chromosome chr2 not found!\n" % (head + 2), 1) and exp[0].count("\n") > 1000
+    assert tool(["inv"] + genome(tmp_path, part) + ["in.bed"], tmp_path) == exp
+
+
+@pytest.mark.parametrize("where", ["inside_a_run", "heading_a_run"])
+def test_a_multi_interval_line_in_the_middle(tmp_path, where):
+    lines = bed_lines(5, 6000)
+    k = 3000 if where == "inside_a_run" else next(j for j in range(len(lines)) if lines[j].startswith("chr2\t"))
+    f = lines[k].split("\t")
+    assert (lines[k - 1].split("\t")[0::5] == f[0::5]) == (where == "inside_a_run")
+    lines[k] = "%s\t%s\t%s\tm\t9\t%s\t0\t0\t0\t2\t10,10,\t0,90," % (f[0], f[1], int(f[1]) + 100, f[5])
+    text = text_of(lines)
+    (tmp_path / "in.bed").write_text(text)
+    for op in ("inv", "gdist"):
+        exp = want(text, op, False, "2", "1", SIZES)
+        assert exp[2] == 1 and ("Line %d: " % (k + 1)) in exp[1] and "single-interval" in exp[1]
+        assert tool(args_of(tmp_path, op, False, "2", "1", SIZES) + ["in.bed"], tmp_path) == exp
+    if where == "inside_a_run":
+        exp = want(text, "test", True)
+        assert exp[2] == 0                                                       # `test` takes the line: its blocks are sorted and disjoint
+        assert tool(["test", "-s", "in.bed"], tmp_path) == exp
+
+
+def test_a_malformed_line_in_the_middle(tmp_path):
+    lines = bed_lines(5, 6000)
+    (tmp_path / "in.bed").write_text(text_of(lines[:3000] + ["chr1\t70"] + lines[3001:]))
+    ok = text_of(lines[:3000])
+    for op in ("inv", "gdist", "test"):
+        out, err, code = want(ok, op, True, "1", "1", SIZES)
+        if op == "inv":                                                          # the reader dies before the loop closes the run: no trailing gap
+            f = lines[2999].split("\t")
+            assert out.endswith("%s\t%s\t%d\t_\t%s\t%s\n" % (f[0], f[2], SIZES[f[0]], f[4], f[5]))
+            out = out[:out.rindex("\n", 0, len(out) - 1) + 1]
+        got = tool(args_of(tmp_path, op, True, "1", "1", SIZES) + ["in.bed"], tmp_path)
+        assert got == (out if op != "test" else "", "\nError: Line 3001: number of tokens should be at least 3 for BED format!\n", 1)
+
+
+def test_unknown_operation_word_late_in_a_file(tmp_path):
+    """3000 chromosomes of one region each: no compatible pair, so the word is not looked at until two regions share the last one"""
+    lines = ["c%04d\t%d\t%d\tr%d\t0\t+" % (k, 10 * k, 10 * k + 5, k) for k in range(3000)] + ["c2999\t40000\t40010\tlast\t0\t+", "c2999\t40020\t40030\tnever\t0\t+"]
+    text = text_of(lines)
+    (tmp_path / "in.bed").write_text(text)
+    exp = want(text, "gdist", op1="1", op2="middle")
+    assert exp == ("".join("r%d\tr%d\tNaN\n" % (k, k + 1) for k in range(2999)) + "r2999\tlast\t", "Error: unknown offset reference point operation!\n", 1)
+    assert tool(["gdist", "-op2", "middle", "in.bed"], tmp_path) == exp
+    assert tool(["gdist", "-op1", "0", "in.bed"], tmp_path) == exp
