@@ -785,6 +785,7 @@ static inline bool HandleRecord(Piece *p, const PackOptions &o, const BedFields 
         break;
     }
     if (p->err.set) return false;
+    if (weighted && (wv > INT_MAX || wv < INT_MIN)) { SetErr(&p->err, line_no, "label value does not fit the packed 32-bit representation of the MI355X path!"); return false; }
     const bool minus = o.strand_aware && f.strand == '-';
     const int32_t cls = (int32_t)(id + (minus ? n_chrom : 0));
     if (!p->cur_blocks.empty() && o.collect_blocks) {

@@ -367,11 +367,13 @@ __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
         }
         if (a.scanRules == 1 && (S > E || E <= 0)) id = -1;         // the unsorted scanner skips such an interval before it looks at the chromosome (:5039)
         if (id >= 0) {
+          const long long lv = hasLabel ? label : 0, capped = lv < a.maxLabel ? lv : a.maxLabel;
           if (!a.scanRules && !a.sortedRules && (E <= 0 || S > E)) plain = false;   // the unsorted algorithm's errors (:5740-5741): the host reports them
+          else if (a.weighted && (capped > INT_MAX || capped < INT_MIN)) plain = false;   // no int32 weight holds it: the host reports that too
           else {
             cls = id + ((a.strandAware && strand == '-') ? a.nChrom : 0);
             start = (int)S; stop = (int)E;
-            if (a.weighted) { const long long lv = hasLabel ? label : 0; wv = (int)(lv < a.maxLabel ? lv : a.maxLabel); }
+            if (a.weighted) wv = (int)capped;
           }
         }
       }

@@ -382,22 +382,34 @@ class Engine:
         self._chk(self.lib.gtx_count_end(self.ctx, _ptr(hits), ctypes.byref(info)))
         return hits[:self.n_refs], info.as_dict()
 
-    def count_text(self, blocks, rules, flags=READS_SORTED, sam=False):
-        """gtx_count_begin / gtx_count_add_text per block of text (bytes of complete lines) / gtx_count_end; sam=True: SAM alignments
-        (GTX_TEXT_SAM).  Returns (hits, info, needs_host verdict per block) -- a block that comes back was not counted."""
-        self._chk(self.lib.gtx_count_begin(self.ctx))
+    def _reduce_text(self, which, blocks, rules, flags, sam):
+        begin, add, end = (getattr(self.lib, "gtx_%s_%s" % (which, f)) for f in ("begin", "add_text", "end"))
+        blocks = list(blocks)
+        per_block = rules if isinstance(rules, (list, tuple)) else [rules] * len(blocks)
+        if len(per_block) != len(blocks):
+            raise GtxError("%s_text: one TextRules per block" % which)
+        self._chk(begin(self.ctx))
         verdicts = []
-        for text in blocks:
+        for text, r in zip(blocks, per_block):
             t = ctypes.c_int(-1)
-            self._chk(self.lib.gtx_count_add_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(rules),
-                                                  int(flags) | (TEXT_SAM if sam else 0), ctypes.byref(t)))
+            self._chk(add(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(r), int(flags) | (TEXT_SAM if sam else 0), ctypes.byref(t)))
             redo = ctypes.c_int(0)
             self._chk(self.lib.gtx_text_result(self.ctx, t.value, ctypes.byref(redo)))
             verdicts.append(redo.value)
-        hits = np.zeros(max(self.n_refs, 1), dtype=np.uint64)
+        out = np.zeros(max(self.n_refs, 1), dtype=np.uint64)
         info = CountInfo()
-        self._chk(self.lib.gtx_count_end(self.ctx, _ptr(hits), ctypes.byref(info)))
-        return hits[:self.n_refs], info.as_dict(), verdicts
+        self._chk(end(self.ctx, _ptr(out), ctypes.byref(info)))
+        return out[:self.n_refs], info.as_dict(), verdicts
+
+    def count_text(self, blocks, rules, flags=READS_SORTED, sam=False):
+        """gtx_count_begin / gtx_count_add_text per block of text (bytes of complete lines) / gtx_count_end; sam=True: SAM alignments
+        (GTX_TEXT_SAM).  rules: one TextRules for every block, or a list with one per block (each block's own seam key).
+        Returns (hits, info, needs_host verdict per block) -- a block that comes back was not counted."""
+        return self._reduce_text("count", blocks, rules, flags, sam)
+
+    def coverage_text(self, blocks, rules, flags=READS_SORTED, sam=False):
+        """the same through gtx_coverage_begin / gtx_coverage_add_text / gtx_coverage_end: (coverage, info, verdicts)"""
+        return self._reduce_text("coverage", blocks, rules, flags, sam)
 
     def subset_text(self, blocks, rules, flags=0):
         """gtx_subset_text / gtx_subset_result per block of text (bytes of complete lines), two blocks in flight: per block

@@ -942,6 +942,23 @@ def _run_text(tool, args, cwd, stdin=None, block_mb=1, extra_env=None):
     return r.returncode, r.stdout.decode(), "\n".join(l for l in lines if not l.startswith("[gtx text]")), nums
 
 
+@pytest.mark.parametrize("mode", [["count", "-i"], ["count", "-S", "-i"], ["coverage", "-i"]], ids=lambda m: " ".join(m))
+def test_label_value_outside_int32_is_an_ingest_error_on_both_paths(tmp_path, mode):
+    """min(--max-label-value, atol(column 4)) that no packed int32 weight holds: the oracle's CLI adds the 64-bit value, the packed path
+    used to add its low 32 bits; now the line is reported, by the host packer and -- the tokenizer hands the block back, which
+    tests/test_gpu_text_seams.py holds -- from the device path.  A label inside int32 keeps matching the oracle's CLI."""
+    (tmp_path / "refs.bed").write_text("chr1\t0\t1000\tA\t0\t+\n")
+    (tmp_path / "reads.bed").write_text("chr1\t10\t20\t3\t0\t+\nchr1\t30\t40\t-5000000000\t0\t+\n")
+    (tmp_path / "fits.bed").write_text("chr1\t10\t20\t3\t0\t+\nchr1\t30\t40\t-2147483648\t0\t+\nchr1\t50\t60\t5000000000\t0\t+\n")
+    args = mode + ["--max-label-value", "5", "refs.bed"]
+    for run in (lambda a: product("overlaps", a, cwd=tmp_path), lambda a: _run_text("overlaps", a, tmp_path)[:3]):
+        rc, out, err = run(args + ["reads.bed"])
+        assert rc == 1 and out == "", (out, err)
+        assert "Line 2: label value does not fit the packed 32-bit representation" in err
+        want = oracle(args + ["fits.bed"], cwd=tmp_path)
+        assert want[0] == 0 and run(args + ["fits.bed"])[:2] == want[:2]
+
+
 @pytest.mark.parametrize("mode", [["count", "-S", "-i"], ["count", "-i", "--max-label-value", "5"], ["coverage", "-S", "-i"], ["density", "-i"]],
                          ids=lambda m: " ".join(m))
 def test_text_on_device_from_a_pipe_and_from_gz(text_beds, mode):

@@ -46,6 +46,21 @@ def test_labels_become_clamped_weights():
     assert rc == 0 and [r[3] for r in rows] == [3, 2, 0]
 
 
+@pytest.mark.parametrize("mode", ["ou", "os", "su", "ss"])
+def test_label_weight_outside_int32_is_reported_not_truncated(mode):
+    """min(max, atol(column 4)) outside int32 used to be packed as its low 32 bits (-5000000000 as -705032704)"""
+    msg = "label value does not fit the packed 32-bit representation"
+    rc, rows, _, err = pack([mode, "-l", "5", "-c", "chr1"], stdin=b"chr1\t1\t9\t3\nchr1\t2\t9\t-5000000000\n")
+    assert rc == 1 and "Error: Line 2: " + msg in err
+    rc, rows, _, err = pack([mode, "-l", "9000000000", "-c", "chr1"], stdin=b"chr1\t1\t9\t5000000000\n")
+    assert rc == 1 and "Error: Line 1: " + msg in err
+    # inside int32, at both ends; a line that is dropped, or a run without label weights, is not looked at
+    rc, rows, _, err = pack([mode, "-l", "9000000000", "-c", "chr1"], stdin=b"chr1\t1\t9\t2147483647\nchr1\t2\t9\t-2147483648\nchrQ\t3\t9\t-5000000000\n")
+    assert rc == 0 and rows == [(0, 2, 9, 2147483647), (0, 3, 9, -2147483648)], err
+    rc, rows, _, err = pack([mode, "-c", "chr1"], stdin=b"chr1\t1\t9\t-5000000000\n")
+    assert rc == 0 and rows == [(0, 2, 9)], err
+
+
 @pytest.mark.parametrize("mode,file,frag", [
     ("ou", "g4_reads_zero_length.bed", "Error: Line 2: start position cannot be greater than stop position!"),
     ("os", "g4_reads_zero_length.bed", None),                       # the sorted merge has no such check
