@@ -311,6 +311,16 @@ GenomicRegionSet::GenomicRegionSet(FILE *file_ptr, unsigned long int buffer_size
   Init();
 }
 
+GenomicRegionSet::GenomicRegionSet(const std::vector<GenomicRegion *> &regions)
+{
+  file = NULL; file_ptr = NULL; buffer_size = 0; verbose = false; from_stdin = false; load_in_memory = true; hide_header = true;
+  src = NULL; packed = NULL; r_index = 0;
+  n_regions = (long int)regions.size();
+  R = n_regions > 0 ? new GenomicRegion *[n_regions] : NULL;
+  for (long int k = 0; k < n_regions; k++) R[k] = regions[k];
+  format = n_regions > 0 ? "REG" : "EMPTY";
+}
+
 GenomicRegionSet::~GenomicRegionSet()
 {
   GtxRegionFree(file);
@@ -1964,6 +1974,8 @@ struct JoinIndex {
   std::vector<int32_t> tri, blocks; std::vector<int64_t> first;
   bool multi = false;                                                   // some region has more than one interval
   std::set<std::string> valid_chrom;                                    // chromosomes the bin index has (a valid region on them)
+  std::vector<GenomicRegion *> regs;                                    // the regions by ordinal: the index set's, then (annotate) the upstream set's
+  long int n_primary = 0;                                               // ordinals below it are the index set's
   gtx_ctx *ctx = NULL;
   bool strand_major = false;                                            // classes as the device-side tokenizer numbers them: rank, + chromosomes on '-' (set before BuildJoinIndex)
   int ClassOf(const GenomicInterval *i) const
@@ -2036,7 +2048,7 @@ int64_t JoinOffsets(const JoinIndex &ix, const QueryBatch &qb, const int8_t *str
 void SetRefStrands(const JoinIndex &ix)
 {
   std::vector<int8_t> strand((size_t)std::max<long int>(ix.M, 1), '+');
-  for (long int k = 0; k < ix.M; k++) strand[k] = ix.IS->R[k]->I.front()->STRAND == '-' ? '-' : '+';
+  for (long int k = 0; k < ix.M; k++) strand[k] = ix.regs[k]->I.front()->STRAND == '-' ? '-' : '+';
   ix.Chk(gtx_set_ref_strands(ix.ctx, strand.data()));
 }
 
@@ -2050,16 +2062,25 @@ void WriteOut(std::string &out, size_t above = 0)
 // single_if_invalid a region that is not compatible, sorted and non-overlapping is given its envelope alone: no pair of it can be
 // printed (the bin index raises its error at the first query, the merge treats it as below), and its intervals may not be what
 // gtx_set_ref_blocks accepts.
-void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char *bin_bits, bool single_if_invalid, JoinIndex &ix)
+//
+// `second` (annotate's upstream set, NULL otherwise) follows the index set as ordinals n_primary ..: one reference set on the device,
+// in which the bin index's order key is the rank of (set, level, bin, -ordinal within its own set) -- each set's own iteration
+// order (every region of the index set first), so one join returns a query's pairs as the reference's two walks hand them out.
+void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char *bin_bits, bool single_if_invalid, JoinIndex &ix,
+                    GenomicRegionSet *second = NULL)
 {
   // the per-pair operations print query lines as BED text (and read their BED columns back): a SAM set of the class API's is refused
   // here, with the message the CLIs give for it (GtxAcceptSAM)
   if (ov->QuerySet->format == "SAM" || ov->IndexSet->format == "SAM") ov->QuerySet->PrintError("unsupported input format!\n");
   GenomicRegionSet *IS = ov->IndexSet;
-  const long int M = IS->n_regions;
+  ix.n_primary = IS->n_regions;
+  ix.regs.assign(IS->R, IS->R + IS->n_regions);
+  if (second) ix.regs.insert(ix.regs.end(), second->R, second->R + second->n_regions);
+  const std::vector<GenomicRegion *> &R = ix.regs;
+  const long int M = (long int)R.size();
   ix.IS = IS; ix.M = M; ix.ignore_strand = ignore_strand;
   ix.sorted = dynamic_cast<SortedGenomicRegionSetOverlaps *>(ov) != NULL;
-  for (long int k = 0; k < M; k++) ix.cid[IS->R[k]->I.front()->CHROMOSOME] = 0;
+  for (long int k = 0; k < M; k++) ix.cid[R[k]->I.front()->CHROMOSOME] = 0;
   { int n = 0; for (auto &c : ix.cid) c.second = n++; }
   ix.n_classes = std::max<int>(1, (int)ix.cid.size() * (ignore_strand ? 1 : 2));
   // under the merge an index region out of order or with overlapping blocks is the reference's error when the merge pulls it
@@ -2068,11 +2089,11 @@ void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char
   if (ix.sorted) {
     const bool by_strand = static_cast<SortedGenomicRegionSetOverlaps *>(ov)->sorted_by_strand;
     for (long int k = 0; k < M && v == M; k++)
-      if (!IS->R[k]->IsCompatibleSortedAndNonoverlapping() || (k > 0 && IS->R[k]->IsBefore(IS->R[k - 1], by_strand))) v = k;
+      if (!R[k]->IsCompatibleSortedAndNonoverlapping() || (k > 0 && R[k]->IsBefore(R[k - 1], by_strand))) v = k;
   }
   ix.tri.assign((size_t)3 * std::max<long int>(M, 1), 0); ix.first.assign((size_t)M + 1, 0);
   for (long int k = 0; k < M; k++) {
-    GenomicRegion *r = IS->R[k];
+    GenomicRegion *r = R[k];
     const long int s = r->I.front()->START, e = r->I.back()->STOP;
     if (k >= v) { ix.tri[3 * k] = -1; ix.tri[3 * k + 1] = 1; ix.tri[3 * k + 2] = 0; ix.blocks.push_back(1); ix.blocks.push_back(0); ix.first[k + 1] = (int64_t)ix.blocks.size() / 2; continue; }
     if (!FitsPacked(s) || !FitsPacked(e)) r->PrintError("coordinate does not fit the packed 32-bit representation of the MI355X path!");
@@ -2095,15 +2116,17 @@ void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char
       for (;;) { size_t q = bb.find(',', p); bits.push_back(atoi(bb.substr(p, q == std::string::npos ? q : q - p).c_str())); if (q == std::string::npos) break; p = q + 1; }
       bits.push_back(60);
     }
-    struct LB { long int level, bin, k; };
+    struct LB { long int set, level, bin, k; };
     std::vector<LB> lb((size_t)M);
     for (long int k = 0; k < M; k++) {
-      long int s = IS->R[k]->I.front()->START; const long int e = IS->R[k]->I.back()->STOP;
+      long int s = R[k]->I.front()->START; const long int e = R[k]->I.back()->STOP;
       if (s <= 0) s = 1;
-      lb[k] = {(long int)bits.size(), 0, k};
-      for (size_t l = 0; l < bits.size(); l++) if ((s >> bits[l]) == (e >> bits[l])) { lb[k] = {(long int)l, s >> bits[l], k}; break; }
+      lb[k] = {k >= ix.n_primary, (long int)bits.size(), 0, k};
+      for (size_t l = 0; l < bits.size(); l++) if ((s >> bits[l]) == (e >> bits[l])) { lb[k] = {k >= ix.n_primary, (long int)l, s >> bits[l], k}; break; }
     }
-    std::sort(lb.begin(), lb.end(), [](const LB &a, const LB &b) { return a.level != b.level ? a.level < b.level : (a.bin != b.bin ? a.bin < b.bin : a.k > b.k); });
+    std::sort(lb.begin(), lb.end(), [](const LB &a, const LB &b) {
+      return a.set != b.set ? a.set < b.set : (a.level != b.level ? a.level < b.level : (a.bin != b.bin ? a.bin < b.bin : a.k > b.k));
+    });
     key.resize((size_t)std::max<long int>(M, 1));
     for (long int j = 0; j < M; j++) key[lb[j].k] = j;
   }
@@ -2116,7 +2139,10 @@ void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char
 // bins walk every match and stop at Done(); subset (gtools/genomic_overlaps.cpp:794-795) calls GetOverlap once -- which erases from
 // the merge's buffer only what lies in front of the first accepted match (:5903-5918), and Done() looks at that buffer (:5934-5937)
 // -- and with -inv goes on while there is a query.
-struct LoopWalk { bool single = false, match_gaps = false, ignore_strand = false, past_done = false; };
+// annotate has no overlaps object: its loop reads the test set itself (gtools/genomic_overlaps.cpp:332) and asks a
+// GenomicRegionSetIndex, whose constructor has checked the index regions before the loop and which answers a query with
+// stop <= 0 or start > stop with no match instead of an error (:5500-5501) -- `index_rules`.
+struct LoopWalk { bool single = false, match_gaps = false, ignore_strand = false, past_done = false, index_rules = false; };
 
 // the reference's query loop on the overlaps object: errors, the merge's buffer and Done() (its early stop) come from the class
 // layer, on which the caller's walk is replayed; add(q) takes every query in order.  Returns with err set when the loop stopped at
@@ -2126,11 +2152,12 @@ void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &
 {
   tls_load_error = &err;
   try {
-    bool index_checked = ix.sorted;
-    for (GenomicRegion *q = ov->GetQuery(); walk.past_done ? q != NULL : ov->Done() == false; q = ov->NextQuery()) {
+    bool index_checked = ix.sorted || walk.index_rules;
+    for (GenomicRegion *q = walk.index_rules ? ov->QuerySet->Get() : ov->GetQuery(); walk.index_rules || walk.past_done ? q != NULL : ov->Done() == false;
+         q = walk.index_rules ? ov->QuerySet->Next() : ov->NextQuery()) {
       if (!index_checked) {                                               // the bin index is built at the first query's match (:5603-5616)
         for (long int k = 0; k < ix.M; k++)
-          if (!ix.IS->R[k]->IsCompatibleSortedAndNonoverlapping()) ix.IS->R[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
+          if (!ix.regs[k]->IsCompatibleSortedAndNonoverlapping()) ix.regs[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
         index_checked = true;
       }
       GenomicInterval *f = q->I.front();
@@ -2139,7 +2166,7 @@ void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &
         if (walk.single) ov->GetOverlap(walk.match_gaps, walk.ignore_strand);
         else for (GenomicRegion *r = ov->GetMatch(); r; r = ov->NextMatch()) {}
       }
-      else if (ix.valid_chrom.count(f->CHROMOSOME)) {                    // :5740-5741, on chromosomes the index knows
+      else if (!walk.index_rules && ix.valid_chrom.count(f->CHROMOSOME)) { // :5740-5741, on chromosomes the index knows
         if (e <= 0) q->PrintError("stop position must be positive!");
         if (s > e) q->PrintError("start position cannot be greater than stop position!");
       }
@@ -2488,6 +2515,202 @@ void GtxPrintOffsets(GenomicRegionSetOverlaps *ov, const char *op, bool skip_ref
     qb.Add(ix, q);
     if (batch.size() >= kQueryBatch) flush();
   });
+  flush();
+  ExitOnLoadError(err);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// genomic_overlaps annotate: the upstream builder (host), and the device join with its annotate pass under the reference's loop
+// ---------------------------------------------------------------------------------------------------
+GenomicRegionSet *CreateGenomicRegionSetAnnotator(GenomicRegionSet *RefRegSet, StringLIntMap *bounds, bool ignore_strand, long int upstream_max_distance,
+                                                  long int upstream_min_distance, char *bin_bits)
+{
+  auto make = [](const std::string &label, GenomicInterval *of, long int start, long int stop, long int n_line) {
+    GenomicRegion *u = new GenomicRegion();
+    u->n_line = n_line;
+    u->LABEL = CopyString(label.c_str());
+    u->I.push_back(new GenomicInterval(of->CHROMOSOME, of->STRAND, start, stop, n_line));
+    return u;
+  };
+  const char *range_msg = "upstream region does not fit the packed 32-bit representation of the MI355X path!";
+  // one upstream region per reference region (:6231-6241)
+  std::vector<GenomicRegion *> up;
+  std::vector<GenomicRegion *> gene;                                      // the region each one was made from (error lines)
+  for (GenomicRegion *ireg = RefRegSet->Get(); ireg != NULL; ireg = RefRegSet->Next()) {
+    if (ireg->I.size() != 1) ireg->PrintError("single-interval reference regions are required for this operation!");
+    GenomicInterval *i = ireg->I[0];
+    const bool plus = i->STRAND == '+';
+    const long int new_start = plus ? std::max(i->START - upstream_max_distance, 1L) : i->STOP + 1;
+    long int new_stop = plus ? std::max(i->START - 1, 1L) : i->STOP + upstream_max_distance;
+    if (bounds) new_stop = std::min(new_stop, (*bounds)[i->CHROMOSOME]);  // (operator[]: an unnamed chromosome is inserted with 0)
+    if (!FitsPacked(new_start) || !FitsPacked(new_stop)) ireg->PrintError(range_msg);
+    up.push_back(make(std::string("upstream:") + ireg->LABEL, i, new_start, new_stop, (long int)up.size() + 1));
+    gene.push_back(ireg);
+  }
+  RefRegSet->Reset();
+  GenomicRegionSet *U = new GenomicRegionSet(up);
+  if (!(upstream_min_distance < upstream_max_distance)) return U;
+
+  // a non-overlapping set (:6250-6294): every region against the untrimmed set, through that set's bin index
+  std::vector<GenomicRegion *> kept;
+  {
+    UnsortedGenomicRegionSetOverlaps self(U, U, bin_bits);
+    long int k = 0;
+    for (GenomicRegion *ureg = self.GetQuery(); ureg != NULL; ureg = self.NextQuery(), k++) {
+      GenomicInterval *u = ureg->I[0];
+      long int start = u->START, stop = u->STOP;
+      const bool asks = !(stop <= 0 || start > stop);                     // GenomicRegionSetIndex::NextMatch (:5500-5501): no match, no error
+      for (GenomicRegion *r = asks ? self.GetOverlap(true, ignore_strand) : NULL; r != NULL; r = self.NextOverlap(true, ignore_strand)) {
+        GenomicInterval *o = r->I[0];
+        if (o == u) continue;
+        if (u->STRAND != o->STRAND) continue;
+        if (u->STRAND == '+') {
+          if (u->STOP > o->STOP) {
+            start = std::max(start, o->STOP + 1);
+            if (upstream_min_distance > 0 && stop - start + 1 < upstream_min_distance) start = std::max(1L, stop - upstream_min_distance + 1);
+          }
+        } else if (o->START > u->START) {
+          stop = std::min(stop, o->START - 1);
+          if (upstream_min_distance > 0 && stop - start + 1 < upstream_min_distance) {
+            stop = start + upstream_min_distance - 1;
+            if (bounds) stop = std::min(stop, (*bounds)[o->CHROMOSOME]);
+          }
+        }
+        if (start > stop) break;
+      }
+      if (start <= stop) {
+        if (!FitsPacked(start) || !FitsPacked(stop)) gene[(size_t)k]->PrintError(range_msg);
+        kept.push_back(make(ureg->LABEL, u, start, stop, (long int)kept.size() + 1));
+      }
+    }
+  }
+  delete U;
+  return new GenomicRegionSet(kept);
+}
+
+namespace {
+// what a line needs of a test region, kept until its batch is joined
+struct AnnotateQuery { std::string label, chrom; char strand; long int start, stop, n_line; };
+
+// "%s %c %ld %ld" of PrintInterval and "%lu" of the interval's size
+void AppendLocus(std::string &out, const char *chrom, char strand, long int start, long int stop)
+{
+  out += chrom; out += ' '; out += strand; out += ' '; AppendNum(out, start); out += ' '; AppendNum(out, stop);
+  char b[32]; const int n = snprintf(b, sizeof b, "\t%lu\t", (unsigned long int)(stop - start + 1)); out.append(b, (size_t)n);
+}
+
+// PrintAnnotations (gtools/genomic_overlaps.cpp:277-289) of one printed pair; offset as the reference's double
+void AppendAnnotation(std::string &out, const AnnotateQuery &q, GenomicRegion *ireg, bool three_prime, double offset, bool flag, long int proximal_dist)
+{
+  out += q.label; out += '\t';
+  AppendLocus(out, q.chrom.c_str(), q.strand, q.start, q.stop);
+  if (flag) {
+    if (three_prime) { out += offset >= proximal_dist ? "distal" : "proximal"; out += ':'; }
+    else { out += offset > proximal_dist ? "distal" : "proximal"; out += ":downstream:"; }
+  }
+  GenomicInterval *i = ireg->I[0];
+  out += ireg->LABEL; out += '\t';
+  AppendLocus(out, i->CHROMOSOME, i->STRAND, i->START, i->STOP);
+  char b[400]; const int n = snprintf(b, sizeof b, "%ld\t%f\n", (long int)offset, offset / ireg->GetSize(false));
+  out.append(b, (size_t)std::min<int>(n, (int)sizeof b - 1));
+}
+
+// GenomicInterval::GetOffsetFrom(GenomicRegion *) (:646-667) on the host, for the walk over plain pairs
+void HostOffsetFrom(GenomicRegion *ref, bool three_prime, long int s, long int e, long int *so, long int *eo)
+{
+  const bool minus = ref->I.front()->STRAND == '-';
+  const bool back = minus != three_prime;                                 // -5p and +3p: the back interval, its stop
+  GenomicInterval *iv = back ? ref->I.back() : ref->I.front();
+  const long int point = back ? iv->STOP : iv->START;
+  if (back) { *so = point - e; *eo = point - s; } else { *so = s - point; *eo = e - point; }
+}
+}  // namespace
+
+void GtxPrintAnnotations(GenomicRegionSet *TestRegSet, GenomicRegionSet *RefRegSet, GenomicRegionSet *UpstreamRefRegSet, const char *query_op,
+                         bool ignore_strand, bool distance_flag, long int proximal_dist, bool print_header, const char *bin_bits)
+{
+  if (!RefRegSet->load_in_memory || (UpstreamRefRegSet && !UpstreamRefRegSet->load_in_memory)) {
+    fprintf(stderr, "Error: [GtxPrintAnnotations] the reference sets must be loaded in memory!\n"); exit(1);
+  }
+  // the constructor of the reference's index (:5365), before anything is printed
+  for (GenomicRegionSet *set : {RefRegSet, UpstreamRefRegSet})
+    for (long int k = 0; set && k < set->n_regions; k++)
+      if (!set->R[k]->IsCompatibleSortedAndNonoverlapping()) set->R[k]->PrintError("index regions should be compatible, sorted and non-overlapping!");
+  UnsortedGenomicRegionSetOverlaps ov(TestRegSet, RefRegSet, bin_bits);
+  JoinIndex ix;
+  BuildJoinIndex(&ov, ignore_strand, bin_bits, true, ix, UpstreamRefRegSet);
+  gtx_ctx *ctx = ix.ctx;
+  ix.Chk(gtx_set_ref_blocks(ctx, NULL, NULL));                            // (match_gaps = true, :318: envelopes)
+  SetRefStrands(ix);
+  const std::string op = query_op;
+  const bool center = op == "center", known = center || op == "overlap";
+  bool multi_ref = false;                                                 // a pair may reach a multi-interval reference region: plain pairs, walked here
+  for (GenomicRegion *r : ix.regs) if (r->I.size() != 1) multi_ref = true;
+  const uint32_t flags = GTX_JOIN_GAPS;
+  const int32_t mode = center ? GTX_ANNOTATE_CENTER : GTX_ANNOTATE_START;   // (an unknown word ends the run at the first pair: every pair is kept)
+
+  if (print_header) { StdoutIsOurs(); printf("TEST-LABEL\tTEST-LOCUS\tTEST-LOCUS-SIZE\tREF-LABEL\tREF-LOCUS\tREF-LOCUS-SIZE\tOFFSET\tNORMALIZED-OFFSET\n"); }
+
+  std::vector<AnnotateQuery> batch; batch.reserve(4096);
+  QueryBatch qb;
+  std::vector<int64_t> koff, kval, off; std::vector<int32_t> kref, pairs;
+  std::string out;
+  auto die = [&](const char *msg) { WriteOut(out); fflush(stdout); fprintf(stderr, "%s", msg); exit(1); };
+  auto flush = [&]() {
+    const int64_t n = qb.Size();
+    if (n == 0) return;
+    if (multi_ref) {
+      JoinPairs(ix, qb, flags, off, pairs);
+      for (int64_t i = 0; i < n; i++) {
+        const AnnotateQuery &q = batch[i];
+        for (int64_t p = off[i]; p < off[i + 1]; p++) {
+          GenomicRegion *r = ix.regs[pairs[p]];
+          if (r->I.size() != 1) { WriteOut(out); fflush(stdout); fprintf(stderr, "\nError: Line %ld: %s\n", r->n_line, "single-interval reference regions are required for this operation!"); exit(1); }
+          const bool three_prime = pairs[p] >= ix.n_primary;
+          long int so, eo;
+          HostOffsetFrom(r, three_prime, q.start, q.stop, &so, &eo);
+          double offset = 0;
+          if (center) { offset = (double)(so + eo) / 2; if (offset < 0) continue; }
+          else if (known) offset = (double)so;
+          else die("Error [PrintAnnotations]: invalid value for query operation!\n");
+          AppendAnnotation(out, q, r, three_prime, offset, distance_flag, proximal_dist);
+          WriteOut(out, 1u << 22);
+        }
+      }
+    } else {
+      koff.assign((size_t)n + 1, 0);
+      if (kref.empty()) { kref.resize(1 << 16); kval.resize(kref.size()); }
+      auto join = [&]() {
+        ix.Chk(gtx_join_annotate(ctx, qb.qtri.data(), n, flags, ix.n_primary, GTX_OFFSET_5P, GTX_OFFSET_3P, mode, koff.data(), kref.data(), kval.data(),
+                                 (int64_t)kref.size(), NULL, NULL));
+      };
+      join();
+      if (koff[n] > (int64_t)kref.size()) { kref.resize((size_t)koff[n]); kval.resize(kref.size()); join(); }
+      for (int64_t i = 0; i < n; i++) {
+        const AnnotateQuery &q = batch[i];
+        for (int64_t p = koff[i]; p < koff[i + 1]; p++) {
+          if (!known) die("Error [PrintAnnotations]: invalid value for query operation!\n");
+          const double offset = center ? (double)kval[p] / 2 : (double)kval[p];
+          AppendAnnotation(out, q, ix.regs[kref[p]], kref[p] >= ix.n_primary, offset, distance_flag, proximal_dist);
+          WriteOut(out, 1u << 22);
+        }
+      }
+    }
+    WriteOut(out);
+    batch.clear(); qb.Clear();
+  };
+
+  LoopWalk walk;
+  walk.index_rules = true;
+  LoadError err;
+  RunQueryLoop(&ov, ix, err, [&](GenomicRegion *q) {
+    if (q->I.size() != 1) q->PrintError("single-interval test regions are required for this operation!");
+    GenomicInterval *f = q->I[0];
+    batch.push_back(AnnotateQuery{q->LABEL, f->CHROMOSOME, f->STRAND, f->START, f->STOP, q->n_line});
+    qb.Add(ix, q);
+    if (f->STOP <= 0 || f->START > f->STOP) qb.qtri[qb.qtri.size() - 3] = -1;   // the index answers such a query with no match (:5500-5501)
+    if (batch.size() >= kQueryBatch) flush();
+  }, walk);
   flush();
   ExitOnLoadError(err);
 }

@@ -164,6 +164,10 @@ class GenomicRegionSet
   // the same for a packed region file (format "GTX"): the view and the index of the current record
   const gtxhost::GtxView *DetachPacked(long int *current_record);
 
+  // an in-memory set of regions made by the library itself (format "REG": it has no text behind it); the set owns them
+  friend GenomicRegionSet *CreateGenomicRegionSetAnnotator(GenomicRegionSet *RefRegSet, StringLIntMap *bounds, bool ignore_strand, long int upstream_max_distance,
+                                                           long int upstream_min_distance, char *bin_bits);
+
   char *file;
   FILE *file_ptr;                                                  // the FILE* constructor's stream (NULL otherwise)
   unsigned long int buffer_size;
@@ -175,6 +179,7 @@ class GenomicRegionSet
   GenomicRegion **R;
 
  private:
+  explicit GenomicRegionSet(const std::vector<GenomicRegion *> &regions);
   void Init();
   void DetectFormat(const char *first_line);
   gtxhost::LineSource *src;
@@ -430,6 +435,30 @@ unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *overlaps, const GtxSig
 // with *error set when the scanners cannot be selected over (more than one GPU, unequal window counts).
 bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_control, const std::vector<std::vector<int> > &tables, long int win_size,
                       std::vector<long long> &ordinals, std::vector<int> &rows, std::string *error);
+
+// genomic_intervals.h:2815, .cpp:6218-6297: the upstream regions of a gene set, one per region of RefRegSet (single-interval regions
+// only: anything else is that region's error), labelled "upstream:LABEL" on the gene's chromosome and strand -- on '+'
+// [max(start - max, 1), max(start - 1, 1)], otherwise [stop + 1, stop + max], the stop clamped to (*bounds)[chromosome] when bounds
+// are given (a chromosome the map does not name is inserted with 0, as operator[] does there).  With upstream_min_distance <
+// upstream_max_distance every region is then trimmed on its 5' side against the untrimmed set, same strand only, in the order the
+// set's own bin index (bin_bits) hands its overlaps out under match_gaps = true and `ignore_strand`, widened back to the minimum
+// when too short, and dropped when nothing is left (:6250-6294).  The result is a new in-memory set the caller deletes; RefRegSet
+// is left reset.  Host work at reference-set scale: the trimming walks the class layer's bin index, no GPU is involved.  MI355X
+// path: a coordinate of the result outside the packed 32-bit range is an input error at the gene's line.
+GenomicRegionSet *CreateGenomicRegionSetAnnotator(GenomicRegionSet *RefRegSet, StringLIntMap *bounds, bool ignore_strand, long int upstream_max_distance,
+                                                  long int upstream_min_distance, char *bin_bits);
+
+// genomic_overlaps annotate (gtools/genomic_overlaps.cpp:310-353, PrintAnnotations :268-290) in bulk: for every test region its
+// overlaps with RefRegSet in that set's bin-index order, offset with 5p, then its overlaps with UpstreamRefRegSet (NULL: none)
+// in that set's, offset with 3p; under query_op "center" a pair whose centre offset is negative is skipped, under "overlap" the
+// start offset is reported, any other word is the reference's error at the first pair.  Both sets go to the device as one
+// reference set whose order key ranks RefRegSet's regions first, so one join (gtx_join_annotate) returns a test region's pairs in
+// print order and the annotate pass leaves only the printed pairs for the host, which formats them here.  A multi-interval test
+// region is an error at its line; a multi-interval region of RefRegSet (possible only without an upstream set, whose builder
+// refuses it) is an error when a pair reaches it: that case takes gtx_join's pairs and walks them on the host.  Both reference
+// sets are loaded in memory; the test set is streamed.
+void GtxPrintAnnotations(GenomicRegionSet *TestRegSet, GenomicRegionSet *RefRegSet, GenomicRegionSet *UpstreamRefRegSet, const char *query_op,
+                         bool ignore_strand, bool distance_flag, long int proximal_dist, bool print_header, const char *bin_bits);
 
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxAcceptSAM(bool on);                                      // false: a SAM file is "unsupported input format!" (drivers that print query lines; default true)

@@ -20,6 +20,7 @@
 #include "gtx_join.h"
 #include "gtx_query.h"
 #include "gtx_offset.h"
+#include "gtx_annotate.h"
 #include "gtx_signal.h"
 #include "gtx_text.h"
 #include "gtx_link.h"
@@ -193,6 +194,7 @@ struct gtx_ctx {
   DevBuf<unsigned> hitsOut;             // gtx_query_hits: a batch's hits
   int64_t joinBuffer = 1ll << 26;       // pairs per device chunk of gtx_join (gtx_set_join_buffer)
   DevBuf<long long> offInv, offOut, offCnt, offPart; DevBuf<int8_t> offQStrand;   // the pair offsets' host entry
+  DevBuf<long long> annCnt, annVal; DevBuf<int> annRef;   // the annotate pass' host entry: a chunk's kept offsets, values and ordinals
   DevBuf<gtx::SignalInfo> sigInfo; DevBuf<unsigned long long> sigBins; DevBuf<long long> sigW;   // the signal bins' info block, the host entry's bins and weights
 
   // link: the scans' per-tile values and break bit map, the info block and its page-locked copy (handed to the caller's struct by
@@ -1628,6 +1630,104 @@ int gtx_pair_offsets_device(gtx_ctx *c, const void *d_reads, int64_t n, const vo
   long long inv;
   rc = pair_offsets(c, a, 0, n, (const long long *)d_offsets, (const int *)d_pairs, n_pairs, (long long *)d_out, &inv); if (rc) return rc;
   if (first_inverted_out) *first_inverted_out = inv == INT64_MAX ? -1 : inv;
+  return GTX_OK;
+}
+
+// ---- the annotate pass (gtx_annotate.hip) ----
+
+} // extern "C"
+
+static bool annotate_args(gtx_ctx *c, int64_t n_primary, int32_t op_primary, int32_t op_rest, int32_t mode, const int *d_tri, gtx::AnnotateArgs *a)
+{
+  if (!offset_op(op_primary) || !offset_op(op_rest) || n_primary < 0 || n_primary > c->nRefs || (mode != GTX_ANNOTATE_CENTER && mode != GTX_ANNOTATE_START)) return false;
+  *a = gtx::AnnotateArgs{d_tri, c->rx.offRef.get(), c->rx.refStrand.get(), c->nRefs, n_primary, op_primary, op_rest,
+                         mode == GTX_ANNOTATE_CENTER ? gtx::ANN_CENTER : gtx::ANN_START};
+  return true;
+}
+
+// count, scan and emit over the pairs of queries [q0, q1): d_cnt (q1 - q0 + 1) becomes the kept offsets from 0, *kept their total;
+// the kept pairs below cap go to d_ref / d_val.  Waits for the stream.
+static int annotate_pass(gtx_ctx *c, const gtx::AnnotateArgs &a, int64_t q0, int64_t q1, const long long *d_off, const int *d_pairs, int64_t n_pairs,
+                         long long *d_cnt, int *d_ref, long long *d_val, int64_t cap, int64_t *kept)
+{
+  const int64_t m = q1 - q0;
+  HIPCHK(c, c->joinBig.grow((size_t)(m + 1)));
+  HIPCHK(c, c->offPart.grow((size_t)gtx::join_scan_partials(m + 1)));
+  HIPCHK(c, gtx::launch_annotate_count(a, q0, q1, d_off, d_pairs, n_pairs, d_cnt, c->joinBig.get(), c->stream));
+  HIPCHK(c, hipMemsetAsync(d_cnt + m, 0, sizeof(long long), c->stream));
+  HIPCHK(c, gtx::launch_join_scan(d_cnt, m + 1, c->offPart.get(), c->stream));
+  HIPCHK(c, gtx::launch_annotate_emit(a, q0, q1, d_off, d_pairs, n_pairs, d_cnt, d_ref, d_val, cap, c->joinBig.get(), c->stream));
+  long long t = 0;
+  HIPCHK(c, hipMemcpyAsync(&t, d_cnt + m, sizeof t, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *kept = t;
+  return GTX_OK;
+}
+
+extern "C" {
+
+int gtx_pair_annotate_device(gtx_ctx *c, const void *d_reads, int64_t n, const void *d_offsets, const void *d_pairs, int64_t n_pairs, int64_t n_primary,
+                             int32_t op_primary, int32_t op_rest, int32_t mode, void *d_kept_offsets, void *d_kept_ref, void *d_kept_value,
+                             int64_t cap, int64_t *n_kept_out)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_pair_annotate_device: gtx_set_refs has not been called");
+  gtx::AnnotateArgs a;
+  if (n < 0 || !d_kept_offsets || (n > 0 && (!d_reads || !d_offsets)) || n_pairs < 0 || (n_pairs > 0 && !d_pairs) || cap < 0 ||
+      (cap > 0 && (!d_kept_ref || !d_kept_value)) || !annotate_args(c, n_primary, op_primary, op_rest, mode, (const int *)d_reads, &a))
+    return fail(c, GTX_E_ARG, "gtx_pair_annotate_device: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = offset_prepare(c); if (rc) return rc;
+  a.refEnds = c->rx.offRef.get();
+  int64_t kept = 0;
+  if (n == 0) HIPCHK(c, hipMemsetAsync(d_kept_offsets, 0, sizeof(long long), c->stream));
+  rc = annotate_pass(c, a, 0, n, (const long long *)d_offsets, (const int *)d_pairs, n_pairs, (long long *)d_kept_offsets, (int *)d_kept_ref,
+                     (long long *)d_kept_value, cap, &kept); if (rc) return rc;
+  if (n_kept_out) *n_kept_out = kept;
+  return GTX_OK;
+}
+
+int gtx_join_annotate(gtx_ctx *c, const int32_t *reads, int64_t n, uint32_t flags, int64_t n_primary, int32_t op_primary, int32_t op_rest, int32_t mode,
+                      int64_t *kept_offsets_out, int32_t *kept_ref_out, int64_t *kept_value_out, int64_t cap, int64_t *n_pairs_out, gtx_count_info *info)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_join_annotate: gtx_set_refs has not been called");
+  gtx::AnnotateArgs a;
+  if (!kept_offsets_out || cap < 0 || (cap > 0 && (!kept_ref_out || !kept_value_out)) || !annotate_args(c, n_primary, op_primary, op_rest, mode, nullptr, &a))
+    return fail(c, GTX_E_ARG, "gtx_join_annotate: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = offset_prepare(c); if (rc) return rc;
+  a.refEnds = c->rx.offRef.get();
+  std::vector<int64_t> off((size_t)std::max<int64_t>(n, 0) + 1, 0), koff;
+  int64_t kbase = 0, done = 0;                                 // kept pairs before the chunk; queries whose kept offsets are written
+  kept_offsets_out[0] = 0;
+  rc = join_batches(c, "gtx_join_annotate", reads, nullptr, nullptr, n, flags, false, off.data(), INT64_MAX, info,
+    [&](const gtx::JoinQueries &q, int64_t b0, int64_t q0, int64_t q1, int64_t, int64_t len) -> int {
+      const int64_t m = q1 - q0;
+      for (; done < b0 + q0; done++) kept_offsets_out[done + 1] = kbase;      // (queries in front of the chunk that had no pair)
+      a.tri = q.tri;
+      const int64_t room = std::max<int64_t>(0, std::min(len, cap - kbase));
+      HIPCHK(c, c->annCnt.grow((size_t)(m + 1)));
+      HIPCHK(c, c->annRef.grow((size_t)std::max<int64_t>(room, 1)));
+      HIPCHK(c, c->annVal.grow((size_t)std::max<int64_t>(room, 1)));
+      int64_t kept = 0;
+      int r = annotate_pass(c, a, q0, q1, c->joinOff.get(), c->joinPairs.get(), len, c->annCnt.get(), c->annRef.get(), c->annVal.get(), room, &kept);
+      if (r) return r;
+      koff.resize((size_t)m + 1);
+      HIPCHK(c, hipMemcpy(koff.data(), c->annCnt.get(), sizeof(int64_t) * (m + 1), hipMemcpyDeviceToHost));
+      for (int64_t i = 1; i <= m; i++) kept_offsets_out[b0 + q0 + i] = kbase + koff[i];
+      done = b0 + q1;
+      const int64_t take = std::min(kept, room);
+      if (take > 0) {
+        HIPCHK(c, hipMemcpy(kept_ref_out + kbase, c->annRef.get(), sizeof(int32_t) * take, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(kept_value_out + kbase, c->annVal.get(), sizeof(int64_t) * take, hipMemcpyDeviceToHost));
+      }
+      kbase += kept;
+      return GTX_OK;
+    });
+  if (rc) return rc;
+  for (; done < n; done++) kept_offsets_out[done + 1] = kbase;
+  if (n_pairs_out) *n_pairs_out = off[(size_t)std::max<int64_t>(n, 0)];
   return GTX_OK;
 }
 

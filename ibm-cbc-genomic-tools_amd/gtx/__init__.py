@@ -31,6 +31,8 @@ ADJACENT_TILE = 2048      # GTX_ADJACENT_TILE: regions per block of the neighbou
 POINTS = {"1": 0, "2": 1, "5p": 2, "3p": 3}   # GTX_POINT_*: gdist's reference points
 SCAN_KEEP_SLOTS = 8       # GTX_SCAN_KEEP_SLOTS: window vectors a context keeps in HBM
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
+ANNOTATE_CENTER = 1
+ANNOTATE_START = 2
 REFS_KEEP_ZERO_LENGTH = 1
 GROUP_ID_BYTES = 128
 
@@ -216,6 +218,12 @@ ABI = {
                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_pair_offsets_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                                ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_pair_annotate_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "gtx_join_annotate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_signal_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p]),
     "gtx_signal_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -553,6 +561,37 @@ class Engine:
         self._chk(self.lib.gtx_pair_offsets_device(self.ctx, _ptr(d_reads), int(n_reads), _ptr(d_offsets), _ptr(d_pairs), int(n_pairs), code,
                                                    _ptr(d_out), ctypes.byref(inv)))
         return inv.value
+
+    def pair_annotate_device(self, d_reads, n_reads, d_offsets, d_pairs, n_pairs, n_primary, d_kept_offsets, d_kept_ref, d_kept_value, capacity,
+                             mode=ANNOTATE_CENTER, op_primary="5p", op_rest="3p"):
+        """gtx_pair_annotate_device on raw device addresses (the pairs gtx_join_device left): the number of kept pairs, whatever
+        the capacity."""
+        kept = ctypes.c_int64(0)
+        self._chk(self.lib.gtx_pair_annotate_device(self.ctx, _ptr(d_reads), int(n_reads), _ptr(d_offsets), _ptr(d_pairs), int(n_pairs),
+                                                    int(n_primary), OFFSET_OPS[op_primary], OFFSET_OPS[op_rest], int(mode), _ptr(d_kept_offsets),
+                                                    _ptr(d_kept_ref), _ptr(d_kept_value), int(capacity), ctypes.byref(kept)))
+        return kept.value
+
+    def join_annotate(self, reads, n_primary, mode=ANNOTATE_CENTER, flags=0, op_primary="5p", op_rest="3p", capacity=None):
+        """gtx_join_annotate: (kept offsets [n+1] int64, kept ordinals int32, kept values int64, pairs of the join, info).  capacity:
+        room for kept pairs (None: all of them, found by a first call with no room)."""
+        reads = _triples(reads)
+        n = reads.shape[0]
+        koff = np.zeros(n + 1, dtype=np.int64)
+        npairs = ctypes.c_int64(0)
+        info = CountInfo()
+
+        def call(ref, val, cap):
+            self._chk(self.lib.gtx_join_annotate(self.ctx, _ptr(reads), n, int(flags), int(n_primary), OFFSET_OPS[op_primary], OFFSET_OPS[op_rest],
+                                                 int(mode), _ptr(koff), _ptr(ref), _ptr(val), int(cap), ctypes.byref(npairs), ctypes.byref(info)))
+        if capacity is None:
+            call(None, None, 0)
+            capacity = int(koff[-1])
+        ref = np.zeros(max(int(capacity), 1), dtype=np.int32)
+        val = np.zeros(max(int(capacity), 1), dtype=np.int64)
+        call(ref, val, capacity)
+        k = min(int(capacity), int(koff[-1]))
+        return koff, ref[:k], val[:k], npairs.value, info.as_dict()
 
     def set_signal_bins(self, bin_min, bin_max, n_bins, ref_len=None):
         """gtx_set_signal_bins: the bin geometry; ref_len: one length per reference region (None: 1)."""

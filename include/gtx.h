@@ -302,6 +302,41 @@ int gtx_pair_offsets_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_
                             int64_t n_pairs, int32_t op, void *d_out /* int64[2 * n_pairs] */,
                             int64_t *first_inverted_out /* may be NULL */);
 
+/* ---- genomic_overlaps annotate: gene and upstream hits kept on the device ---------------------- */
+
+/* genomic_overlaps annotate (gtools/genomic_overlaps.cpp:310-353) reports, for every test region, the genes it
+ * overlaps and then the upstream regions it overlaps (CreateGenomicRegionSetAnnotator,
+ * genomic_intervals.cpp:6218-6297), each pair through PrintAnnotations (:268-290): the 5' offsets of the test
+ * region for a gene, the 3' offsets for an upstream region, and under --query-op center only the pairs whose
+ * centre offset (start + stop offset) / 2 is not negative.  Genes and upstream regions are ONE reference set
+ * here: ordinals below n_primary are the genes, the others the upstream regions, and an order key
+ * (gtx_set_ref_order) that ranks every gene before every upstream region makes one join hand out a query's
+ * pairs in the order the reference prints them.  Strands come from gtx_set_ref_strands.
+ *
+ * gtx_pair_annotate_device: over the pairs gtx_join_device left in HBM (d_read_triples, n_reads, d_offsets,
+ * d_pairs, n_pairs as for gtx_pair_offsets_device) the offsets with op_primary for ordinals < n_primary and
+ * op_rest for the rest (GTX_OFFSET_*).  mode GTX_ANNOTATE_CENTER keeps the pairs with start + stop offset >= 0
+ * and gives that sum as their value (the caller halves: the .5 stays exact); GTX_ANNOTATE_START keeps every pair
+ * and gives its start offset.  d_kept_offsets (int64[n_reads + 1], from 0) are the positions of each query's
+ * kept pairs, in pair order; d_kept_ref (int32) / d_kept_value (int64) receive the first `capacity` kept pairs;
+ * *n_kept_out is the number kept whatever the capacity: when it exceeds the capacity, grow and call again.
+ * Returns with the work complete.
+ *
+ * gtx_join_annotate: single-interval queries from host memory, joined in gtx_join's batches and chunks (a query
+ * with more pairs than the join buffer alone in a buffer of its size), each chunk's pairs annotated where they
+ * lie; the host receives the kept CSR alone -- kept_offsets_out (n_reads + 1) always complete, the first
+ * `capacity` kept pairs, *n_pairs_out = the pairs of the join.  flags, info: as gtx_join. */
+#define GTX_ANNOTATE_CENTER 1    /* --query-op center  */
+#define GTX_ANNOTATE_START  2    /* --query-op overlap */
+int gtx_pair_annotate_device(gtx_ctx *ctx, const void *d_read_triples, int64_t n_reads, const void *d_offsets, const void *d_pairs,
+                             int64_t n_pairs, int64_t n_primary, int32_t op_primary, int32_t op_rest, int32_t mode,
+                             void *d_kept_offsets /* int64[n_reads + 1] */, void *d_kept_ref /* int32[capacity] */,
+                             void *d_kept_value /* int64[capacity] */, int64_t capacity, int64_t *n_kept_out /* may be NULL */);
+int gtx_join_annotate(gtx_ctx *ctx, const int32_t *read_triples, int64_t n_reads, uint32_t flags, int64_t n_primary,
+                      int32_t op_primary, int32_t op_rest, int32_t mode, int64_t *kept_offsets_out /* n_reads + 1 */,
+                      int32_t *kept_ref_out, int64_t *kept_value_out, int64_t capacity, int64_t *n_pairs_out /* may be NULL */,
+                      gtx_count_info *info /* may be NULL */);
+
 /* ---- genomic_apps profile / heatmap: signal binned around reference points ---------------------- */
 
 /* genomic_apps profile and heatmap (gtools/genomic_apps.cpp:560-605, :826-880) sum, for every (read, reference

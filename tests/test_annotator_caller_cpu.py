@@ -1,0 +1,72 @@
+"""CPU suite: CreateGenomicRegionSetAnnotator of the class layer (csrc/genomic_intervals.cpp), called by tests/tools/annotator_caller.cpp
+the way `genomic_regions annotator` calls it, against the restatement (tests/annotate_restate.py): the manifest's builder cases, and a
+few hundred seeded genes with min < max, with and without a genome file, with and without -i.  No GPU is involved: the trimming
+walks the class layer's own bin index on the host."""
+import copy
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import annotate_restate as ar
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CALLER = os.path.join(ROOT, "ibm-cbc-genomic-tools_amd", "csrc", "annotator_caller")
+BUILDER = json.load(open(os.path.join(HERE, "golden", "annotate_manifest.json")))["builder"]
+ENV = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
+
+
+def caller(tmp, genes, bounds, ignore_strand, upstream_max, upstream_min):
+    (tmp / "genes.bed").write_text("".join(l + "\n" for l in genes))
+    args = []
+    if bounds is not None:
+        (tmp / "genome.bed").write_text("".join("%s\t0\t%d\n" % (c, n) for c, n in bounds.items()))
+        args += ["-g", "genome.bed"]
+    args += (["-i"] if ignore_strand else []) + ["--upstream-max", str(upstream_max), "--upstream-min", str(upstream_min), "genes.bed"]
+    r = subprocess.run([CALLER] + args, capture_output=True, cwd=tmp, env=ENV)
+    return r.stdout.decode(), r.stderr.decode(), r.returncode
+
+
+def restated(genes, bounds, ignore_strand, upstream_max, upstream_min):
+    try:
+        up = ar.upstream_set(ar.regions_of(genes), copy.deepcopy(bounds), ignore_strand, upstream_max, upstream_min)
+    except ar.InputError as err:
+        return "", err.stderr(), 1
+    return ar.reg_lines(up), "", 0
+
+
+@pytest.mark.parametrize("case", BUILDER, ids=[c["name"] for c in BUILDER])
+def test_caller_gives_the_manifest_set(tmp_path, case):
+    got = caller(tmp_path, case["genes"], case["bounds"], case["ignore_strand"], case["upstream_max"], case["upstream_min"])
+    assert got == (case["stdout"], case["stderr"], case["code"])
+
+
+def seeded_genes(seed, n=300, span=400_000):
+    """genes dense enough that upstream regions of 20 kb overlap several others, on three chromosomes and both strands; chr3 is
+    absent from the genome file below"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        s = int(rng.integers(0, span)); ln = int(rng.integers(50, 5000))
+        out.append("\t".join(["chr%d" % rng.integers(1, 4), str(s), str(s + ln), "g%d" % k, "0", "+-"[int(rng.integers(0, 2))]]))
+    return out
+
+
+@pytest.mark.parametrize("ignore_strand", [False, True], ids=["strand", "i"])
+@pytest.mark.parametrize("with_genome", [False, True], ids=["nobounds", "g"])
+@pytest.mark.parametrize("upstream_max,upstream_min", [(20_000, 3000), (50_000, 0), (5000, 4999), (10_000, 10_000)])
+def test_caller_equals_the_restatement_on_seeded_genes(tmp_path, upstream_max, upstream_min, with_genome, ignore_strand):
+    genes = seeded_genes(upstream_max + 7 * upstream_min)
+    bounds = {"chr1": 404_000, "chr2": 380_000} if with_genome else None       # chr2's bound cuts into its genes; chr3 reads as 0
+    want = restated(genes, bounds, ignore_strand, upstream_max, upstream_min)
+    got = caller(tmp_path, genes, bounds, ignore_strand, upstream_max, upstream_min)
+    assert got == want
+    lines = want[0].splitlines()
+    assert want[2] == 0 and len(lines) > 150
+    if upstream_min < upstream_max:
+        assert len(lines) < 300 or not with_genome                             # regions emptied by a clamp are dropped
+        full = restated(genes, bounds, ignore_strand, upstream_max, upstream_max)[0].splitlines()
+        assert sum(l not in full for l in lines) > 50                           # the trimming changed many of them

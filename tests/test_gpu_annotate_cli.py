@@ -1,0 +1,137 @@
+"""genomic_annotate (csrc/genomic_annotate.cpp; GtxPrintAnnotations and CreateGenomicRegionSetAnnotator in csrc/genomic_intervals.cpp,
+kept pairs from the device: gtx_join_annotate): stdout and stderr byte-equal to the restated lines (tests/annotate_restate.py) on the
+golden genes (tests/golden/genes.bed.gz) against a few thousand seeded test regions.  The pairs the restatement renders come from
+the oracle's `pairs` rows (oracle/gtx_oracle.c) for the genes and for the restated upstream set written out as BED; the manifest's
+hand-derived cases run through the tool as well."""
+import gzip
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import annotate_restate as ar
+from oracle import orc
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+TOOL = os.path.join(ROOT, "ibm-cbc-genomic-tools_amd", "csrc", "genomic_annotate")
+GENES = os.path.join(HERE, "golden", "genes.bed.gz")
+CASES = json.load(open(os.path.join(HERE, "golden", "annotate_manifest.json")))["annotate"]
+
+
+def tool(args, cwd, stdin=None):
+    r = subprocess.run([TOOL] + args, capture_output=True, cwd=cwd, input=stdin)
+    return r.returncode, r.stdout.decode(), r.stderr.decode()
+
+
+def write(path, lines):
+    path.write_text("".join(l + "\n" for l in lines))
+
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    """genes.bed (the golden genes), tests.bed: 4000 regions of 1 to 3000 bases within 15 kb of a random gene's start, on either
+    strand, in file order (annotate reads them unsorted)"""
+    d = tmp_path_factory.mktemp("annotatecli")
+    genes = gzip.open(GENES, "rt").read().splitlines()
+    write(d / "genes.bed", genes)
+    rng = np.random.default_rng(9091)
+    g = ar.regions_of(genes)
+    tests = []
+    for k in range(4000):
+        of = g[int(rng.integers(0, len(g)))]
+        s = max(0, of["s"] + int(rng.integers(-15_000, 15_000)))
+        tests.append("\t".join([of["chrom"], str(s), str(s + int(rng.integers(1, 3000))), "t%d" % k, "0", "+-"[int(rng.integers(0, 2))]]))
+    write(d / "tests.bed", tests)
+    return d
+
+
+def oracle_pairs(cwd, ignore_strand, n_tests):
+    """per set its regions as BED with the ordinal as label, then the oracle's pairs in the bin index's order"""
+    def pairs(n, regs):
+        name = "set%d_%d.bed" % (n, ignore_strand)
+        write(cwd / name, ["\t".join([r["chrom"], str(r["s"] - 1), str(r["e"]), "x%d" % k, "0", r["strand"]]) for k, r in enumerate(regs)])
+        o = subprocess.run([orc.CLI, "pairs"] + (["-i"] if ignore_strand else []) + [name, "tests.bed"], capture_output=True, cwd=cwd)
+        assert o.returncode == 0, o.stderr.decode()
+        rows = [[] for _ in range(n_tests)]
+        for a, b in (x.split("\t") for x in o.stdout.decode().splitlines()):
+            rows[int(a) - 1].append(int(b[1:]))
+        return rows
+    return pairs
+
+
+RUNS = [
+    ([], {}),
+    (["--query-op", "overlap"], dict(query_op="overlap")),
+    (["--distance-flag", "--proximal-dist", "500", "--print-header"], dict(flag=True, proximal=500, header=True)),
+    (["--upstream-max", "0"], dict(upstream_max=0)),
+    (["--upstream-min", "2000", "--upstream-max", "50000"], dict(upstream_min=2000, upstream_max=50000)),
+    (["-i"], dict(ignore_strand=True)),
+    (["-S", "-B", "10,14,18", "--distance-flag"], dict(bits="10,14,18", flag=True)),
+]
+
+
+@pytest.mark.parametrize("opts,kw", RUNS, ids=[" ".join(r[0]) or "defaults" for r in RUNS])
+def test_cli_equals_the_restated_lines(files, opts, kw):
+    genes, tests = (files / "genes.bed").read_text().splitlines(), (files / "tests.bed").read_text().splitlines()
+    want = ar.annotate(genes, tests, pairs=oracle_pairs(files, kw.get("ignore_strand", False), len(tests)) if "bits" not in kw else None, **kw)
+    assert want[1:] == ("", 0) and want[0].count("\n") > 2000
+    assert tool(opts + ["genes.bed", "tests.bed"], files) == (want[2], want[0], want[1])
+
+
+def test_the_pairs_come_in_both_kinds_and_some_are_dropped(files):
+    genes, tests = (files / "genes.bed").read_text().splitlines(), (files / "tests.bed").read_text().splitlines()
+    pairs = oracle_pairs(files, False, len(tests))
+    kept = ar.annotate(genes, tests, pairs=pairs)[0].splitlines()
+    every = ar.annotate(genes, tests, pairs=pairs, query_op="overlap")[0].splitlines()
+    up = sum("\tupstream:" in l for l in kept)
+    assert 500 < up < len(kept) - 500 and len(every) > len(kept) + 500
+    assert {l.split("\t")[1].split(" ")[1] for l in kept} == {"+", "-"}
+
+
+def test_stdin_and_gz(files):
+    plain = tool(["genes.bed", "tests.bed"], files)
+    assert plain[0] == 0 and plain[1].count("\n") > 2000
+    assert tool(["genes.bed"], files, stdin=(files / "tests.bed").read_bytes()) == plain
+    assert tool([GENES, "tests.bed"], files) == plain
+
+
+def test_bad_query_op_is_the_error_at_the_first_pair(files):
+    genes, tests = (files / "genes.bed").read_text().splitlines(), (files / "tests.bed").read_text().splitlines()
+    assert ar.annotate(genes, tests, query_op="centre", header=True) == (ar.HEADER, ar.BAD_OP, 1)
+    assert tool(["--query-op", "centre", "--print-header", "genes.bed", "tests.bed"], files) == (1, ar.HEADER, ar.BAD_OP)
+
+
+def test_bed12_test_line_in_mid_file_leaves_the_output_in_front_of_it(files):
+    tests = (files / "tests.bed").read_text().splitlines()
+    f = tests[2500].split("\t")
+    tests[2500] = "\t".join(f + [f[1], f[2], "0", "2", "1,1,", "0,%d," % (int(f[2]) - int(f[1]) + 5)])
+    write(files / "tests12.bed", tests)
+    genes = (files / "genes.bed").read_text().splitlines()
+    want = ar.annotate(genes, tests)
+    assert want[1:] == ("\nError: Line 2501: single-interval test regions are required for this operation!\n", 1) and want[0].count("\n") > 1000
+    assert tool(["genes.bed", "tests12.bed"], files) == (want[2], want[0], want[1])
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_manifest_cases_through_the_tool(tmp_path, case):
+    write(tmp_path / "g.bed", case["genes"])
+    write(tmp_path / "t.bed", case["tests"])
+    o = dict(case["opts"])
+    args = ["--upstream-max", str(o.pop("upstream_max")), "--upstream-min", str(o.pop("upstream_min"))]
+    if "query_op" in o:
+        args += ["--query-op", o.pop("query_op")]
+    if o.pop("flag", False):
+        args += ["--distance-flag"]
+    if "proximal" in o:
+        args += ["--proximal-dist", str(o.pop("proximal"))]
+    if o.pop("header", False):
+        args += ["--print-header"]
+    if o.pop("ignore_strand", False):
+        args += ["-i"]
+    assert not o
+    assert tool(args + ["g.bed", "t.bed"], tmp_path) == (case["code"], case["stdout"], case["stderr"])
