@@ -176,7 +176,8 @@ __device__ __forceinline__ bool parse_line(PTR s, unsigned b, unsigned e, bool w
 }
 
 // one SAM alignment (GenomicRegionSAM::Read, genomic_intervals.cpp:2771-2812) in the plain case: 11 or more TAB-separated tokens, the
-// first ten non-empty and without a blank, '\r' or NUL, QUAL non-empty, no '\r' at the end of the line; FLAG and POS 1-10 decimal digits;
+// first ten non-empty and without a blank, '\r' or NUL, QUAL non-empty and not beginning with a blank, '\r' or NUL (a NUL further on, in QUAL
+// or a tag, only ends what the host reads of columns it does not look at), no '\r' at the end of the line; FLAG and POS 1-10 decimal digits;
 // CIGAR "*" or operations of 1-9 digits each from M I D S H P X - (no N: a spliced read is the host's, no '=': the reference refuses it);
 // SEQ "*" or as long as the CIGAR's fragment (M I S X).  Out: the RNAME token [nameOff, nameOff + nameLen), strand ('-' iff FLAG & 0x10),
 // start = POS, stop = POS + reference length (M D X) - 1, reference length > 0; QNAME's atol value when wantLabel.
@@ -255,7 +256,8 @@ __device__ __forceinline__ bool parse_sam_line(PTR s, unsigned b, unsigned e, bo
   const bool seqStar = seqLen == 1 && s[sb] == '*';
   p++;
   if (p >= e) return false;                                        // QUAL: present and non-empty, no blank in front
-  { const unsigned char c = s[p]; if (c == '\t' || c == ' ' || c == '\r') return false; }
+  // (a NUL as its first byte ends the host's C string behind 10 tokens: "number of tokens should be at least 11")
+  { const unsigned char c = s[p]; if (c == '\t' || c == ' ' || c == '\r' || c == 0) return false; }
   if (s[e - 1] == '\r') return false;                              // CRLF
   if (star) ref = seqLen;                                          // "*" reads as "<strlen(SEQ)>M" (1M for SEQ "*")
   else if (!seqStar && seqLen != frag) return false;               // the reference's error

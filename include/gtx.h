@@ -538,11 +538,13 @@ typedef struct gtx_text_rules {
 } gtx_text_rules;
 /* GTX_TEXT_SAM in the flags of gtx_count_add_text, gtx_coverage_add_text, gtx_scan_add_text and gtx_group_*_add_text: the block is
  * SAM alignments (GenomicRegionSAM::Read genomic_intervals.cpp:2771-2812) without the '@' header, not BED.  The plain case: 11 or more
- * TAB-separated columns, the first ten non-empty and without blanks or '\r', no '\r' at the end of the line; FLAG and POS decimal;
- * CIGAR "*" or operations of 1-9 digits from M I D S H P X - (no N, no =); SEQ "*" or as long as the CIGAR's M I S X; a reference
- * length (M D X) > 0.  A read becomes (class of RNAME [+ n_chrom when strand_aware and FLAG & 0x10], POS, POS + reference length - 1)
- * with QNAME's atol value as its label; order check and validity rules as for BED.  Spliced reads, '=' and every other line go back
- * to the caller (needs_host), as do blocks whose 128-line groups average more than ~570 bytes a line.  gtx_text_rules is the same. */
+ * TAB-separated columns, the first ten non-empty and without blanks, '\r' or NUL, QUAL non-empty and not beginning with a blank, '\r'
+ * or NUL (a NUL there ends the C string behind 10 tokens: the reference's error), no '\r' at the end of the line; FLAG and POS 1-10
+ * decimal digits; CIGAR "*" or operations of 1-9 digits from M I D S H P X - (no N, no =); SEQ "*" or as long as the CIGAR's M I S X;
+ * a reference length (M D X) > 0; with max_label_value > 1, a QNAME that begins with a byte above ' ' and has at most 18 digits.
+ * A read becomes (class of RNAME [+ n_chrom when strand_aware and FLAG & 0x10], POS, POS + reference length - 1) with QNAME's atol
+ * value as its label; order check and validity rules as for BED.  Spliced reads, '=' and every other line go back to the caller
+ * (needs_host), as do blocks whose 128-line groups average more than ~570 bytes a line.  gtx_text_rules is the same. */
 #define GTX_TEXT_SAM       512u
 /* text: host memory (page-locked memory is read by the DMA engine directly and must stay untouched until gtx_text_result of the
  * ticket has returned).  flags as gtx_count_add / gtx_coverage_add, and GTX_TEXT_SAM.  Up to two blocks are in flight: the call waits for the block

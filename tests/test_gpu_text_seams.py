@@ -34,8 +34,11 @@ class Unit:
 
 
 class Rules:
-    def __init__(self, mode, aware=False, by_strand=False, max_label=1, names=tc.NAMES):
+    """the rules of one count call; sam: the blocks are SAM alignments (GTX_TEXT_SAM); cases: the module that restates what a block
+    becomes (tests/text_cases.py for BED, tests/sam_cases.py for SAM)"""
+    def __init__(self, mode, aware=False, by_strand=False, max_label=1, names=tc.NAMES, sam=False, cases=tc):
         self.mode, self.aware, self.by_strand, self.max_label, self.names = mode, aware, by_strand, max_label, list(names)
+        self.sam, self.cases = sam, cases
         self.sorted = mode in ("os", "ss")
         self.n_classes = len(self.names) * (2 if aware else 1)
 
@@ -48,7 +51,7 @@ class Rules:
         return r
 
     def expected(self, unit):
-        (res,), (s,) = tc.expected_blocks([unit.block], self.mode, self.names, self.aware, self.by_strand, self.max_label, prev=unit.prev)
+        (res,), (s,) = self.cases.expected_blocks([unit.block], self.mode, self.names, self.aware, self.by_strand, self.max_label, prev=unit.prev)
         return res, s
 
     def flags(self):
@@ -97,12 +100,12 @@ def check(engine, units, rules, lo=1, length=tc.L, call="count_text"):
             return getattr(engine, call)(*a)
         except gtx.GtxError as e:                                # a device error: nothing more is started on that GPU in this session
             pytest.exit("%s failed: %s" % (call, e), returncode=3)
-    hits, _, verdicts = run([u.block for u in units], [rules.text_rules(u.prev, u.garbage_prev) for u in units], rules.flags())
+    hits, _, verdicts = run([u.block for u in units], [rules.text_rules(u.prev, u.garbage_prev) for u in units], rules.flags(), rules.sam)
     kept = claims(units, rules, verdicts)
     want = np.array(tc.depth(kept, rules.n_classes, length, lo), dtype=np.uint64)
     if not np.array_equal(hits, want):                           # (b), (c): name the first block that is counted wrongly
         for u in units:
-            h1, _, v1 = run([u.block], [rules.text_rules(u.prev, u.garbage_prev)], rules.flags())
+            h1, _, v1 = run([u.block], [rules.text_rules(u.prev, u.garbage_prev)], rules.flags(), rules.sam)
             k1 = claims([u], rules, v1)
             assert np.array_equal(h1, np.array(tc.depth(k1, rules.n_classes, length, lo), dtype=np.uint64)), ("(b)/(c) wrong depth", u.what, v1)
         raise AssertionError("(b)/(c): the blocks are right one by one and wrong together")

@@ -157,15 +157,19 @@ def lines_of(block):
     return block[:-1].split(b"\n")
 
 
-def seam_key(block):
+count_tokens, Cursor, checked = _count_tokens, _Cursor, _checked     # (tests/sam_cases.py restates the SAM reader with them)
+
+
+def seam_key(block, read_line=read_line):
     """(name, strand, start) of the block's last line as the host reads it -- what prev_* of the next block holds -- or None"""
     r = read_line(lines_of(block)[-1])
     return None if r == ERROR else (r[0], r[3], r[1])
 
 
-def expected_blocks(blocks, mode, names, strand_aware=False, sorted_by_strand=False, max_label=1, prev=None):
+def expected_blocks(blocks, mode, names, strand_aware=False, sorted_by_strand=False, max_label=1, prev=None, read_line=read_line):
     """Per block: ERROR, or the list of (class, start, stop, weight) of the lines that are kept, in line order.  Also per block the
-    label sum of its lines (None for an ERROR block).  prev: the key (name, strand, start) in front of the first block."""
+    label sum of its lines (None for an ERROR block).  prev: the key (name, strand, start) in front of the first block.
+    read_line: the reader of one line (tests/sam_cases.py passes its own; everything behind the reader is the same for SAM)."""
     assert mode in MODES
     names = sorted(n.encode() if isinstance(n, str) else n for n in names)
     sorted_mode = mode in ("os", "ss")
@@ -210,7 +214,7 @@ def expected_blocks(blocks, mode, names, strand_aware=False, sorted_by_strand=Fa
             out.append(ERROR)
             sums.append(None)
             if sorted_mode:                                       # the next block's seam key is its last line's, as the caller fills it
-                k = seam_key(block)
+                k = seam_key(block, read_line)
                 prev = k if k is not None else prev
         else:
             out.append(kept)
@@ -395,11 +399,12 @@ def _pad(line, k):
 
 
 def place(probe, j, n_lines, first_byte=None, total_bytes_mod=None, newline_at=None, cols=7, first=0, total=None, strands=None,
-          extra=None, stretch=None):
+          extra=None, stretch=None, filler_line=filler_line, _pad=_pad):
     """A block of n_lines clean ascending filler lines with the probe (a Probe, bytes, or None for none) at line j ("last": the last
     line).  first_byte: the probe's first byte lands on that offset of the block; newline_at: its newline does;
     total_bytes_mod = (m, r): len(block) % m == r.  The lines in front of the probe (and the last line) grow to make it so.
-    extra: {line: Probe or bytes} more lines replaced; stretch: {line: length} filler lines grown to that many bytes."""
+    extra: {line: Probe or bytes} more lines replaced; stretch: {line: length} filler lines grown to that many bytes.
+    filler_line, _pad: how a filler line is written and grown (tests/sam_cases.py passes its own)."""
     if j == "last":
         j = n_lines - 1
     assert 0 <= j < n_lines
@@ -437,7 +442,7 @@ def place(probe, j, n_lines, first_byte=None, total_bytes_mod=None, newline_at=N
     return block
 
 
-def stretched(lines, total_bytes):
+def stretched(lines, total_bytes, _pad=_pad):
     """the filler lines grown evenly until they and their newlines are total_bytes long"""
     need = total_bytes - sum(len(l) + 1 for l in lines)
     assert need >= 0
