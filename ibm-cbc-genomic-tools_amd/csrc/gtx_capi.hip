@@ -93,6 +93,15 @@ struct BucketCuts { std::vector<int32_t> posHi, eLo, eHi, sLo, sHi, cls, clsStar
 struct HistSet {
   DevBuf<u64> histA, histB, partA, partB, prefA, prefB; DevBuf<unsigned> flags; unsigned epoch = 0; unsigned long long draws = 0;
   DevBuf<u64> totals; unsigned totalsTurn = 0;
+  gtx::FinalizeArgs view(int64_t histLen) const
+  {
+    gtx::FinalizeArgs a = {};
+    const size_t turn = 2 * ((size_t)gtx::scan_tiles(histLen) + 2);      // words of one turn's totals
+    a.histA = histA.get(); a.histB = histB.get(); a.tileA = partA.get(); a.tileB = partB.get(); a.prefA = prefA.get(); a.prefB = prefB.get(); a.histLen = histLen;
+    a.chainFlags = flags.get(); a.epoch = epoch; a.draws = draws;
+    a.totals = totals.get() + (totalsTurn & 1) * turn; a.nextTotals = totals.get() + ((totalsTurn & 1) ^ 1) * turn;
+    return a;
+  }
 };
 
 // What a reference set is made into, in four parts that gtx_set_refs_ex drops together (by assignment) before it makes them anew.
@@ -174,7 +183,7 @@ struct gtx_ctx {
   Share share;
   bool covTileSums = true;                           // false: a batch went through the partition path, the tile sums are rebuilt before the finalize step
   DevBuf<u64> bktReads; DevBuf<int> bktWeights; DevBuf<unsigned> bktDir, bktCnt;   // scratch of the partition path (gtx::BucketWork)
-  int64_t bucketMinReads = 1 << 18;                  // below this the per-read search kernel is used (GTX_BUCKET_MIN_READS)
+  int64_t bucketMinReads = gtx::kBucketMinReads;    // below this the per-read search kernel is used (GTX_BUCKET_MIN_READS)
   int localMaxTiles = gtx::kLocalScanMaxTiles;       // tile sums not kept: local scan + gather up to this many tiles (GTX_LOCAL_SCAN_MAX_TILES; 0: tile sums + scan + gather)
   bool histDirty = false;              // a call was abandoned between begin and end
   bool covDirty = false, covOpen = false;
@@ -636,30 +645,15 @@ static gtx::CountArgs count_args(gtx_ctx *c, const HistSet &h, uint32_t flags, i
 {
   gtx::CountArgs a;
   a.indexBase = indexBase;
-  { static const bool off = getenv("GTX_HIST32") && atoi(getenv("GTX_HIST32")) == 0;
-    a.hist32 = hist32 && !off && nReads < (1ll << 32); }
+  const gtx::RouteKnobs &knobs = gtx::route_knobs();
+  a.hist32 = gtx::hist32_slots(hist32, nReads, knobs);
   a.owned = who != COUNT_ANY && c->share.on ? c->share.owned.get() : nullptr;
   a.sortedE = c->ix.sortedE.get(); a.sortedS = c->ix.sortedS.get(); a.segStart = c->ix.segStart.get();
   a.histA = h.histA.get(); a.histB = h.histB.get(); a.partA = h.partA.get(); a.partB = h.partB.get(); a.info = c->d_info.get() + c->infoCur;
   a.nClasses = c->nClasses;
-  // Large batches: the streaming kernel leaves the per-tile sums alone and the finalize step rebuilds them from the
-  // histograms (tile_sums_kernel, one pass over 16 B per region: 6 us at 1 M regions).  Keeping them up to date costs two
-  // more atomics and a wave scan per window flush -- 100 M reads x 1 M regions: kernel 0.218 -> 0.207 ms, step 0.253 ->
-  // 0.248 ms; with few regions every wave hits the same handful of counters and the same-address atomics serialise
-  // (10 k regions: 0.28 -> 0.19 ms; a group member's 1/8 of 100 M reads over its 3 chromosomes: 0.041 -> 0.103 ms).  Small batches
-  // keep the sums (no extra launch).  GTX_PART_MAX_HIST=0 restores them.
-  { static const char *mx = getenv("GTX_PART_MAX_HIST"); const int64_t lim = mx ? atoll(mx) : INT64_MAX;
-    if (c->histLen <= lim && nReads >= (1 << 20)) { a.partA = nullptr; a.partB = nullptr; c->tileSumsValid = false; } }
-  // span of one wave: long enough to amortise the window placement at its start, short enough that the grid has >= 3
-  // rounds of the 8192 wave slots of the chip (256 CUs x 32 waves) and that the waves resident at one time read a
-  // compact piece of the stream (100 M reads: flat from 48 to 64 chunks, +3 % at 96, +12 % at 192 = one round;
-  // 1 G reads: 1.74 ms at 48, 1.76 at 64-96, 1.82 at 128; the bare load pattern behaves the same, scripts/membench.hip)
-  int cpw = c->chunksPerWave;
-  // (launches of one to three rounds -- a group member's share of 100 M reads -- take 16 chunks per wave from a full round of
-  // 16-chunk spans on: the start of a span is paid once per 16 chunks instead of 8, 0.039 -> 0.034 ms for 12.9 M reads; scripts/r04_share.sh)
-  if (cpw <= 0) { int64_t nChunks = (nReads + 63) >> 6; cpw = (int)std::min<int64_t>(56, std::max<int64_t>(nChunks >= 16 * c->waveSlots ? 16 : 8, nChunks / 24576)); }
+  if (!gtx::keeps_tile_sums(c->histLen, nReads, knobs)) { a.partA = nullptr; a.partB = nullptr; c->tileSumsValid = false; }
   const int r = 4;                                // reads per lane per step of the streaming kernel
-  a.chunksPerWave = (cpw + r - 1) / r * r;
+  a.chunksPerWave = gtx::count_chunks_per_wave(nReads, c->waveSlots, c->chunksPerWave);
   a.sched = gtx::span_schedule((nReads + 63) >> 6, a.chunksPerWave, r, c->waveSlots);
   a.checkSorted = (flags & GTX_CHECK_SORTED) ? 1 : 0; a.sortClassShift = 0;
   a.zeroLenOk = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
@@ -668,11 +662,8 @@ static gtx::CountArgs count_args(gtx_ctx *c, const HistSet &h, uint32_t flags, i
   a.sampE = c->ix.sampE.get(); a.sampS = c->ix.sampS.get(); a.sampShift = c->ix.sampShift; a.nSamp = c->ix.nSamp;
   a.topE = c->ix.topE.get(); a.topS = c->ix.topS.get();
   a.place = c->ix.place.view();
-  // dense references (>= 4 boundaries per 256 reads and array): all boundaries of a window at once instead of the
-  // per-boundary loop (100 M reads x 4 M regions: 0.41 -> 0.28 ms; at 1 M regions the loop is 3 % faster).  GTX_FLIP=0|1 forces.
   // (a group member's async call streams the reads of ITS classes only: their density is against its own regions, not the whole set's)
-  { static const char *fl = getenv("GTX_FLIP"); const int64_t regions = who == COUNT_SHARE_ASYNC && c->share.on ? std::min<int64_t>(c->nValid, c->share.nRegions) : c->nValid;
-    a.flip = fl ? atoi(fl) : (regions * 256 >= 4 * std::max<int64_t>(nReads, 1)); }
+  a.flip = gtx::flip_walk(who == COUNT_SHARE_ASYNC && c->share.on ? std::min<int64_t>(c->nValid, c->share.nRegions) : c->nValid, nReads, knobs);
 #ifdef GTX_WAVE_TRACE
   a.trace = gtx_debug_trace_buffer();
 #endif
@@ -694,19 +685,25 @@ static int bucket_scratch(gtx_ctx *c, const gtx::BucketPlan &p, int nB, gtx::Buc
   return GTX_OK;
 }
 
+// THE decision for the partition path, made once per batch of reads in no particular order: tables t are there, the batch is worth
+// partitioning and its plan fits 32-bit pair indices.  On yes the scratch is ready (*p, *w).
+static int partition_plan(gtx_ctx *c, const BucketTables &t, int64_t n, int nClasses, bool weighted, gtx::BucketPlan *p, gtx::BucketWork *w, bool *yes)
+{
+  *yes = false;
+  if (t.nB == 0 || !gtx::partition_worth(n, c->bucketMinReads)) return GTX_OK;
+  *p = gtx::bucket_plan(n, nClasses, t.nB, t.nCells, weighted);
+  if (!(p->pairs < (1ull << 32))) return GTX_OK;
+  *yes = true;
+  return bucket_scratch(c, *p, t.nB, w);
+}
+
 // reads in no particular order: bucket partition + LDS counting for large batches, per-read search kernel otherwise
 static int launch_unsorted(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, const gtx::CountArgs &a)
 {
-  const BucketTables &t = c->ix.bkt;
-  if (t.nB == 0 || n < c->bucketMinReads || n >= (1ll << 31)) {
-    HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, false, c->stream));
-    return GTX_OK;
-  }
-  const gtx::BucketPlan p = gtx::bucket_plan(n, a.nClasses, t.nB, t.nCells, d_weights != nullptr);
-  if (p.pairs >= (1ull << 32)) { HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, false, c->stream)); return GTX_OK; }
-  gtx::BucketWork w;
-  { int rc = bucket_scratch(c, p, t.nB, &w); if (rc) return rc; }
-  HIPCHK(c, gtx::launch_count_bucketed(d_reads, d_weights, n, a, t.view(), w, p, c->stream));
+  gtx::BucketPlan p; gtx::BucketWork w; bool part;
+  { int rc = partition_plan(c, c->ix.bkt, n, a.nClasses, d_weights != nullptr, &p, &w, &part); if (rc) return rc; }
+  if (part) HIPCHK(c, gtx::launch_count_bucketed(d_reads, d_weights, n, a, c->ix.bkt.view(), w, p, c->stream));
+  else HIPCHK(c, gtx::launch_count(d_reads, d_weights, n, a, false, c->stream));
   return GTX_OK;
 }
 
@@ -801,9 +798,14 @@ static int finalize_set(gtx_ctx *c, HistSet &h, bool sumsValid, u64 *d_hits, gtx
                         const gtx::FinalizeShare *fs, bool hist32)
 {
   if (++h.epoch == 0) { HIPCHK(c, hipMemsetAsync(h.flags.get(), 0, sizeof(unsigned) * h.flags.cap, s)); h.epoch = 1; h.draws = 0; }   // (after 2^32 calls: the flags start over)
-  HIPCHK(c, gtx::launch_finalize(h.histA.get(), h.histB.get(), c->histLen, h.partA.get(), h.partB.get(), sumsValid, h.prefA.get(), h.prefB.get(),
-                                 c->ix.posE.get(), c->ix.posS.get(), c->ix.classBase.get(), c->nRefs, d_hits, infoNext, s, fs, h.flags.get(), h.epoch, info,
-                                 &h.draws, hist32, h.totals.get(), &h.totalsTurn, c->localMaxTiles));
+  gtx::FinalizeArgs a = h.view(c->histLen);
+  a.tileSumsValid = sumsValid; a.localMaxTiles = c->localMaxTiles; a.posE = c->ix.posE.get(); a.posS = c->ix.posS.get(); a.classBase = c->ix.classBase.get();
+  a.m = c->nRefs; a.hits = d_hits; a.info = info; a.nextInfo = infoNext; a.share = fs; a.hist32 = hist32;
+  gtx::FinalizeRoute took;
+  HIPCHK(c, gtx::launch_finalize(a, s, &took));
+  // the launch is in the stream: the chained kernel has drawn a ticket per tile it ran, the local gather has zeroed the other turn's totals
+  if (took == gtx::FIN_CHAINED) h.draws += (unsigned long long)(fs ? fs->nTiles : gtx::scan_tiles(c->histLen));
+  if (took == gtx::FIN_LOCAL) h.totalsTurn ^= 1;
   return GTX_OK;
 }
 
@@ -1941,13 +1943,9 @@ static gtx::CoverArgs cover_args(gtx_ctx *c, int64_t nReads, int64_t indexBase =
   a.info = c->d_info.get() + c->infoCur; a.nClasses = c->nClasses;
   const bool merge = (flags & GTX_ZERO_LENGTH_OK) && (flags & GTX_GAPS_FORMULA) && c->mergeRefs && c->side.get();
   a.side = merge ? c->side.get() : nullptr; a.sideCount = merge ? c->sideCount.get() : nullptr; a.sideCap = c->sideCap;
-  { static const bool wf = !(getenv("GTX_WEIGHTED_FAST") && atoi(getenv("GTX_WEIGHTED_FAST")) == 0); a.wfast = wf ? 1 : 0; }
-  int64_t nChunks = (nReads + 63) >> 6;
-  // span per wave: as count_args, a little longer (the start of a span costs more here: 100 M reads: 0.55 ms at 16 chunks, 0.44 at 32,
-  // 0.382 at 56, 0.374 at 64, 0.383 at 96)
-  a.chunksPerWave = c->chunksPerWave > 0 ? c->chunksPerWave : (int)std::min<int64_t>(64, std::max<int64_t>(8, nChunks / 24576));
-  a.chunksPerWave = (a.chunksPerWave + 3) / 4 * 4;
-  a.sched = gtx::span_schedule(nChunks, a.chunksPerWave, 4, c->waveSlots);
+  a.wfast = gtx::route_knobs().weightedFast ? 1 : 0;
+  a.chunksPerWave = gtx::cover_chunks_per_wave(nReads, c->chunksPerWave);
+  a.sched = gtx::span_schedule((nReads + 63) >> 6, a.chunksPerWave, 4, c->waveSlots);
   a.place = c->cv.place.view();
   return a;
 }
@@ -1979,19 +1977,15 @@ static int cover_begin(gtx_ctx *c)
 static int cover_launch(gtx_ctx *c, const void *dR, const int *dW, int64_t n, int64_t indexBase, uint32_t flags, bool unsorted)
 {
   const gtx::CoverArgs cv = cover_args(c, n, indexBase, flags);
-  const BucketTables &t = c->cv.bkt;
-  if (unsorted && t.nB > 0 && n >= c->bucketMinReads && n < (1ll << 31)) {
-    const gtx::BucketPlan p = gtx::bucket_plan(n, c->nClasses, t.nB, t.nCells, dW != nullptr);
-    if (p.pairs < (1ull << 32)) {
-      gtx::BucketWork w;
-      { int rc = bucket_scratch(c, p, t.nB, &w); if (rc) return rc; }
-      gtx::CountArgs a = {};                                        // what the partition pass reads of it
-      a.nClasses = c->nClasses; a.zeroLenOk = 0; a.coverRule = 1; a.info = cv.info; a.indexBase = indexBase;
-      a.side = cv.side; a.sideCount = cv.sideCount; a.sideCap = cv.sideCap;
-      HIPCHK(c, gtx::launch_cover_bucketed(dR, dW, n, a, cv, t.view(), w, p, c->stream));
-      c->covTileSums = false;
-      return GTX_OK;
-    }
+  gtx::BucketPlan p; gtx::BucketWork w; bool part = false;
+  if (unsorted) { int rc = partition_plan(c, c->cv.bkt, n, c->nClasses, dW != nullptr, &p, &w, &part); if (rc) return rc; }
+  if (part) {
+    gtx::CountArgs a = {};                                        // what the partition pass reads of it
+    a.nClasses = c->nClasses; a.zeroLenOk = 0; a.coverRule = 1; a.info = cv.info; a.indexBase = indexBase;
+    a.side = cv.side; a.sideCount = cv.sideCount; a.sideCap = cv.sideCap;
+    HIPCHK(c, gtx::launch_cover_bucketed(dR, dW, n, a, cv, c->cv.bkt.view(), w, p, c->stream));
+    c->covTileSums = false;
+    return GTX_OK;
   }
   HIPCHK(c, gtx::launch_coverage(dR, dW, n, cv, c->stream));
   return GTX_OK;
@@ -2168,13 +2162,11 @@ static int scan_bucket_tables(gtx_ctx *c, const int32_t *classLen, int nClasses,
   if (!c->scanInfo) HIPCHK(c, c->scanInfo.alloc(1));
   long long total = 0;
   for (int i = 0; i < nClasses; i++) total += classLen[i] < 0 ? 0 : classLen[i] / step;
-  static const long long want = getenv("GTX_SCAN_BUCKETS") && atoll(getenv("GTX_SCAN_BUCKETS")) > 0 ? atoll(getenv("GTX_SCAN_BUCKETS")) : 2000;     // (100 M shuffled reads, -d 25: 500 -> 2.77 ms, 1000 -> 2.30, 2000 -> 2.15, 3000 -> 2.10)
-  long long per = std::max<long long>(16384, (total + want - 1) / want);           // micro-windows per bucket
   BucketCuts k;
   k.clsStart.assign(nClasses + 1, 0);
   std::vector<gtx::ScanPart> parts;
   const int bins = gtx::scan_part_bins(weighted);
-  if (per > bins) per = per / bins * bins;          // whole parts: every part of a bucket reads all of the bucket's chunks, a short last one as well
+  const long long per = gtx::scan_bucket_per(total, bins, gtx::route_knobs());      // micro-windows per bucket
   for (int cl = 0; cl < nClasses; cl++) {
     k.clsStart[cl] = (int32_t)k.posHi.size();
     const long long nm = classLen[cl] < 0 ? 0 : classLen[cl] / step;
@@ -2187,7 +2179,7 @@ static int scan_bucket_tables(gtx_ctx *c, const int32_t *classLen, int nClasses,
   }
   k.clsStart[nClasses] = (int32_t)k.posHi.size();
   const int nB = (int)k.posHi.size();
-  if (nB == 0 || nB > 4096 || nClasses > 2048 || total >= (1ll << 31)) { c->scanBktKey = key; return GTX_OK; }   // (bktS.nB == 0: the general kernels serve)
+  if (!gtx::scan_bucket_tables_ok(nB, nClasses, total)) { c->scanBktKey = key; return GTX_OK; }   // (bktS.nB == 0: the general kernels serve)
   int rc = build_bucket_tables(c, c->bktS, k, nClasses, true); if (rc) return rc;
   if (c->bktS.nB > 0) {
     HIPCHK(c, upload(c->scanParts, parts.data(), parts.size()));
@@ -2197,37 +2189,33 @@ static int scan_bucket_tables(gtx_ctx *c, const int32_t *classLen, int nClasses,
   return GTX_OK;
 }
 
-// one batch of reads into the micro-window histogram (zeroed by the caller): the partition path for a batch in no particular order
-// under the unsorted scanner's rule, the general kernel otherwise
-// the partition path serves this call (reads in no order, the bin index's rules, a batch worth partitioning, tables that fit)
-static int scan_takes_buckets(gtx_ctx *c, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted, bool *yes)
+// whether the partition path serves a batch of a scan: reads in no order under the unsorted scanner's rule (the bin index's), tables
+// for the geometry, and partition_plan's word
+static int scan_partition_plan(gtx_ctx *c, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted,
+                               gtx::BucketPlan *p, gtx::BucketWork *w, bool *yes)
 {
   *yes = false;
-  if (!(unsorted && !a.sortedRule && n >= c->bucketMinReads && n < (1ll << 31))) return GTX_OK;
+  if (!unsorted || a.sortedRule || !gtx::partition_worth(n, c->bucketMinReads)) return GTX_OK;
   int rc = scan_bucket_tables(c, classLen, a.nClasses, a.winStep, dW != nullptr); if (rc) return rc;
-  *yes = c->bktS.nB > 0 && gtx::bucket_plan(n, a.nClasses, c->bktS.nB, c->bktS.nCells, dW != nullptr).pairs < (1ull << 32);
+  return partition_plan(c, c->bktS, n, a.nClasses, dW != nullptr, p, w, yes);
+}
+
+// one batch of reads by the partition path: into the micro-window histogram (zeroed by the caller), or -- d_windows not null -- the
+// parts write the windows themselves (gtx::launch_scan_bucketed)
+static int scan_hist_bucketed(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const gtx::BucketPlan &p, const gtx::BucketWork &w, u64 *d_windows)
+{
+  gtx::CountArgs ca = {};                                      // what the partition pass reads of it; its counts of dropped reads go nowhere
+  ca.nClasses = a.nClasses; ca.zeroLenOk = 0; ca.coverRule = 1; ca.keyCenter = a.center; ca.info = c->scanInfo.get(); ca.indexBase = 0;
+  HIPCHK(c, gtx::launch_scan_bucketed(dR, dW, n, ca, a, c->bktS.view(), w, p, c->scanParts.get(), c->nScanParts, c->stream, d_windows));
   return GTX_OK;
 }
 
-// d_windows (may be null): the partition path writes the windows itself (gtx::launch_scan_bucketed)
-static int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted, u64 *d_windows = nullptr)
+// one batch of reads into the micro-window histogram (zeroed by the caller): the partition path or the general kernel
+static int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted)
 {
-  if (unsorted && !a.sortedRule && n >= c->bucketMinReads && n < (1ll << 31)) {
-    int rc = scan_bucket_tables(c, classLen, a.nClasses, a.winStep, dW != nullptr); if (rc) return rc;
-    const BucketTables &t = c->bktS;
-    if (t.nB > 0) {
-      const gtx::BucketPlan p = gtx::bucket_plan(n, a.nClasses, t.nB, t.nCells, dW != nullptr);
-      if (p.pairs < (1ull << 32)) {
-        gtx::BucketWork w;
-        rc = bucket_scratch(c, p, t.nB, &w); if (rc) return rc;
-        gtx::CountArgs ca = {};                                      // what the partition pass reads of it; its counts of dropped reads go nowhere
-        ca.nClasses = a.nClasses; ca.zeroLenOk = 0; ca.coverRule = 1; ca.keyCenter = a.center; ca.info = c->scanInfo.get(); ca.indexBase = 0;
-        HIPCHK(c, gtx::launch_scan_bucketed(dR, dW, n, ca, a, t.view(), w, p, c->scanParts.get(), c->nScanParts, c->stream, d_windows));
-        return GTX_OK;
-      }
-    }
-  }
-  if (d_windows) return fail(c, GTX_E_STATE, "gtx_scan: internal: the partition path was announced and not taken");
+  gtx::BucketPlan p; gtx::BucketWork w; bool part;
+  int rc = scan_partition_plan(c, dW, n, a, classLen, unsorted, &p, &w, &part); if (rc) return rc;
+  if (part) return scan_hist_bucketed(c, dR, dW, n, a, p, w, nullptr);
   HIPCHK(c, gtx::launch_scan_hist(dR, dW, n, a, c->stream));
   return GTX_OK;
 }
@@ -2237,10 +2225,10 @@ static int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, c
 static int scan_launch(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, const int32_t *classLen, int32_t nClasses, int32_t step,
                        int32_t size, char prep, uint32_t flags, const int64_t *classOff, void *d_out, bool profile)
 {
-  static const bool ownOff = getenv("GTX_SCAN_OWN") && atoi(getenv("GTX_SCAN_OWN")) == 0;
+  const gtx::RouteKnobs &knobs = gtx::route_knobs();
   int64_t totalMicro = 0;
   for (int i = 0; i < nClasses; i++) totalMicro += classLen[i] < 0 ? 0 : classLen[i] / step;
-  const int tile = ((flags & GTX_READS_SORTED) && prep == '1' && !ownOff && n > 0) ? gtx::scan_own_tile(n, totalMicro, size / step) : 0;
+  const int tile = gtx::scan_own_wanted((flags & GTX_READS_SORTED) != 0, prep == '1', n, knobs) ? gtx::scan_own_tile(n, totalMicro, size / step) : 0;
   gtx::ScanArgs a; gtx::ScanOwn own;
   int rc = scan_prepare(c, classLen, nClasses, step, size, classOff, &a, tile, &own); if (rc) return rc;
   a.center = prep == 'c'; a.sortedRule = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
@@ -2258,21 +2246,15 @@ static int scan_launch(gtx_ctx *c, const void *d_reads, const void *d_weights, i
     HIPCHK(c, gtx::launch_scan_hist(d_reads, d_weights, n, a, c->stream, runIf));
   } else {
     // reads in no order through the partition path: its parts write the windows themselves (no micro-window array, no window pass)
-    static const bool fuseOff = getenv("GTX_SCAN_FUSED") && atoi(getenv("GTX_SCAN_FUSED")) == 0;
-    bool buckets = false;
-    if (!fuseOff && a.comb <= gtx::scan_fused_max_comb() && c->scanTotalWindows > 0) {
-      rc = scan_takes_buckets(c, (const int *)d_weights, n, a, classLen, (flags & GTX_READS_UNSORTED) != 0, &buckets); if (rc) return rc;
-    }
-    if (buckets) {
-      if (profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-      rc = scan_hist_any(c, d_reads, (const int *)d_weights, n, a, classLen, true, (u64 *)d_out); if (rc) return rc;
-      if (profile) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-      return GTX_OK;
-    }
-    if (microBytes) HIPCHK(c, hipMemsetAsync(c->micro.get(), 0, microBytes, c->stream));
+    gtx::BucketPlan p; gtx::BucketWork w; bool part;
+    rc = scan_partition_plan(c, (const int *)d_weights, n, a, classLen, (flags & GTX_READS_UNSORTED) != 0, &p, &w, &part); if (rc) return rc;
+    const bool fused = part && gtx::scan_fused_ok(a.comb, gtx::scan_fused_max_comb(), c->scanTotalWindows, knobs);
+    if (!fused && microBytes) HIPCHK(c, hipMemsetAsync(c->micro.get(), 0, microBytes, c->stream));
     if (profile) HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    rc = scan_hist_any(c, d_reads, (const int *)d_weights, n, a, classLen, (flags & GTX_READS_UNSORTED) != 0); if (rc) return rc;
+    if (part) { rc = scan_hist_bucketed(c, d_reads, (const int *)d_weights, n, a, p, w, fused ? (u64 *)d_out : nullptr); if (rc) return rc; }
+    else HIPCHK(c, gtx::launch_scan_hist(d_reads, d_weights, n, a, c->stream));
     if (profile) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    if (fused) return GTX_OK;
   }
   HIPCHK(c, gtx::launch_scan_windows(c->micro.get(), micro64, a, c->scanTotalTiles, (u64 *)d_out, c->stream, runIf));
   return GTX_OK;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
+#include "gtx_routes.h"
 
 namespace gtx {
 
@@ -79,7 +80,7 @@ struct CountArgs {
   SpanSchedule sched;
   int flip;                      // streaming kernel: meet all boundaries of a window at once (dense references)
   int hist32;                    // streaming kernel (unweighted): histA / histB are read and written as unsigned[] -- the caller's finalize step too
-                                 //   (launch_finalize(..., hist32)).  For calls of fewer than 2^32 reads in ONE launch: no slot or prefix can pass that
+                                 //   (FinalizeArgs::hist32).  For calls of fewer than 2^32 reads in ONE launch: no slot or prefix can pass that
   long long indexBase;           // position of reads[0] in the caller's stream: added to the indices reported in `info`
   // sorted-merge semantics (zeroLenOk): inverted reads (start > end + 1) are not degenerate there -- the merge matches them
   // by its two comparisons like any other read (genomic_intervals.cpp:1225-1236).  The rank difference does not hold for
@@ -192,30 +193,30 @@ hipError_t launch_special_scatter(const int *specialIdx, unsigned long long *spe
 
 SpanSchedule span_schedule(long long nChunks, int cpw, int r, long long slots);
 int search_sample_shift(long long nValid);   // stride of the sample arrays such that both fit the LDS budget
-int scan_tiles(long long len);
 
 hipError_t launch_count(const void *reads, const void *weights, long long n, const CountArgs &a, bool sortedHint, hipStream_t st);
-// tileSumsValid: the streaming kernel kept tileA/tileB up to date (the search kernel does not).
+// The finalize step of a count call: which launches it takes is finalize_route's business (gtx_routes.h); *took reports the route, and the
+// launcher writes no host state -- the caller advances its ticket count and flips its totals' turn by it, once the launch has succeeded.
 // Leaves histA/histB and the tile sums zeroed for the next call.
 // share (may be null): the finalize step of a group member -- only the histogram tiles that cover the classes it owns (a class
 // has slots seg+cls-1 .. segEnd+cls; other tiles hold no counts) and only its regions, written in the group's compact order
 struct FinalizeShare { const int *tileList; int nTiles; const int *regionList; long long nRegions; bool scatter; };   // scatter: hits[region] instead of hits[place in the list]
-hipError_t launch_finalize(unsigned long long *histA, unsigned long long *histB, long long histLen,
-                           unsigned long long *tileA, unsigned long long *tileB, bool tileSumsValid,
-                           unsigned long long *prefA, unsigned long long *prefB,
-                           const int *posE, const int *posS, const int *classBase, long long m,
-                           unsigned long long *hits, DevInfo *nextInfo, hipStream_t st, const FinalizeShare *share = nullptr,
-                           unsigned *chainFlags = nullptr, unsigned epoch = 0, DevInfo *info = nullptr, unsigned long long *chainDraws = nullptr,
-                           bool hist32 = false, unsigned long long *totals = nullptr, unsigned *totalsTurn = nullptr, int localMaxTiles = 0);
-// chainFlags (may be null): 8 x (tiles + 2) words (two 64-bit words per tile and histogram; the word behind each histogram's is the kernel's ticket counter), zero when
-// made, never written by the caller; epoch: a value no earlier call on these flags used (and not 0); info: the call's block (DevInfo::fault); chainDraws: the host's count of
-// the tickets drawn from these flags so far (0 when they are made; the launcher advances it).  With them a call whose tile sums are not valid and whose tiles are few
-// enough takes one launch for tile sums + scan (finalize_scan_chained_kernel).
-// totals (may be null): 4 x (tiles + 2) 64-bit words, zero when made, never written by the caller -- the tiles' totals of the two histograms, twice (taken in turn);
-// totalsTurn: the host's word that says which (0 when they are made; the launcher flips it).  With them a call whose tile sums are not valid, that does not take the
-// chained kernel and whose histograms have at most localMaxTiles tiles (kLocalScanMaxTiles at the most) takes two launches: a tile-local scan, then a gather that adds
-// the tiles' offsets (finalize_local_kernel, gather_hits_local_kernel) -- instead of tile sums, scan and gather.
-constexpr int kLocalScanMaxTiles = 2048;      // 2 x 2048 offsets in the gather's LDS: 16 KB with 32-bit slots, 32 KB with 64-bit ones
+struct FinalizeArgs {
+  unsigned long long *histA, *histB, *tileA, *tileB, *prefA, *prefB;   // histograms, tile sums, prefixes over histLen slots
+  // chainFlags (may be null): 8 x (tiles + 2) words (two 64-bit words per tile and histogram; the word behind each histogram's is the kernel's ticket counter), zero
+  // when made, never written by the caller; epoch: a value no earlier call on these flags used (and not 0); draws: the tickets drawn from these flags so far (FIN_CHAINED
+  // draws one per tile it runs)
+  unsigned *chainFlags; unsigned epoch; unsigned long long draws;
+  // totals / nextTotals (may be null): 2 x (tiles + 2) 64-bit words each, zero when made, never written by the caller -- the tiles' totals of the two histograms for
+  // this call, and the pair the next call takes (FIN_LOCAL zeroes it: the caller swaps the two after that route)
+  unsigned long long *totals, *nextTotals;
+  long long histLen; bool tileSumsValid;   // tileSumsValid: the streaming kernel kept tileA/tileB up to date (the search kernel does not)
+  int localMaxTiles;                       // FIN_LOCAL up to this many tiles (kLocalScanMaxTiles at the most)
+  const int *posE, *posS, *classBase; long long m; unsigned long long *hits;
+  DevInfo *info, *nextInfo;                // the call's block (DevInfo::fault), the block the gather resets for the call after
+  const FinalizeShare *share; bool hist32;
+};
+hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st, FinalizeRoute *took);
 hipError_t launch_coverage(const void *reads, const void *weights, long long n, const CoverArgs &a, hipStream_t st);
 hipError_t launch_coverage_finalize(const CoverArgs &a, long long histLen, const CoverGather &g, long long m,
                                     unsigned long long *cov, DevInfo *nextInfo, hipStream_t st);

@@ -51,8 +51,6 @@ typedef long long i64;
 static constexpr int kHi = 0x7fffffff;          // +inf sentinel (coordinates are < 2^31-1)
 static constexpr int kLo = (int)0x80000000;     // -inf sentinel
 static constexpr int kSlots = 63;               // slots per register window (lane 0 holds the boundary below slot 0)
-static constexpr int kTileShift = 10;           // finalize scan tile = 1024 histogram slots
-static constexpr int kTile = 1 << kTileShift;
 static constexpr int kSearchLdsBytes = 128 * 1024;  // LDS top level of the search kernel (both arrays)
 
 __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -1554,7 +1552,6 @@ __global__ __launch_bounds__(256) void finalize_scan_kernel(T *__restrict__ ha, 
 // launcher takes this kernel for at most kChainMaxTiles tiles.  The wait is bounded all the same: a block that has polled
 // kChainSpinMax times gives up, raises DevInfo::fault (the call's result is then refused by gtx_last_info) and finishes with what it has.
 static constexpr unsigned kChainSpinMax = 1u << 22;           // polls of one word (~1 us each under load): seconds
-static constexpr int kChainMaxTiles = 512;
 template <class T>
 __global__ __launch_bounds__(256) void finalize_scan_chained_kernel(T *__restrict__ ha, T *__restrict__ hb, i64 len,
                                                                     u64 *fa, u64 *fb, u64 *ctlA, u64 *ctlB, u64 base, unsigned epoch, int nRun,
@@ -1999,7 +1996,6 @@ int search_sample_shift(i64 nValid)
   return sh;
 }
 
-int scan_tiles(i64 len) { return (int)((len + kTile - 1) / kTile); }
 
 // Schedule of a launch over nChunks 64-read chunks, `cpw` chunks per wave in the main segment (all spans multiples of `r`),
 // `slots` = resident waves of the chip.  A wave lives p + c * tau (placement + c chunks at the chip's rate shared by all
@@ -2070,58 +2066,50 @@ hipError_t launch_tile_sums(u64 *histA, u64 *histB, i64 histLen, u64 *tileA, u64
   return hipGetLastError();
 }
 
+// the route of gtx_routes.h's finalize_route, reported in *took; the caller's bookkeeping of a.draws and of the totals' turn follows it
 template <class T>
-static hipError_t launch_finalize_t(T *histA, T *histB, i64 histLen, u64 *tileA, u64 *tileB, bool tileSumsValid, T *prefA, T *prefB,
-                                    const int *posE, const int *posS, const int *classBase, i64 m, u64 *hits, DevInfo *nextInfo, hipStream_t st,
-                                    const FinalizeShare *share, unsigned *chainFlags, unsigned epoch, DevInfo *info, unsigned long long *chainDraws,
-                                    u64 *totals, unsigned *totalsTurn, int localMaxTiles)
+static hipError_t launch_finalize_t(const FinalizeArgs &a, hipStream_t st, FinalizeRoute *took)
 {
-  const int nb = scan_tiles(histLen);
-  const int nbRun = share ? share->nTiles : nb;                // a group member: the tiles of its classes, its regions (compact)
-  const int *tl = share ? share->tileList : nullptr;
-  static const bool chained = !(getenv("GTX_CHAINED_SCAN") && atoi(getenv("GTX_CHAINED_SCAN")) == 0);
-  if (nbRun > 0) {
-    static const int chainMax = getenv("GTX_CHAIN_MAX_TILES") ? atoi(getenv("GTX_CHAIN_MAX_TILES")) : kChainMaxTiles;
-    if (!tileSumsValid && chainFlags && chained && info && chainDraws && nbRun <= chainMax) {
-      finalize_scan_chained_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, (u64 *)chainFlags, (u64 *)chainFlags + 2 * (nb + 2), (u64 *)chainFlags + 2 * nb,
-                                                                      (u64 *)chainFlags + 2 * (nb + 2) + 2 * nb, *chainDraws, epoch, nbRun, prefA, prefB, tl, info);
-      *chainDraws += (unsigned long long)nbRun;
-    }
-    else {
-      if (!tileSumsValid && totals && totalsTurn && nb <= localMaxTiles) {
-        // local scan + gather with the tiles' offsets: the totals of this turn (all zero on entry), the other turn's zeroed for the next call
-        const size_t parts = (size_t)nb + 2;
-        u64 *tot = totals + (size_t)(*totalsTurn & 1) * 2 * parts, *next = totals + (size_t)((*totalsTurn & 1) ^ 1) * 2 * parts;
-        finalize_local_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, tot, tot + parts, prefA, prefB, tl);
-        const i64 mm = share ? share->nRegions : m, perBlock = (i64)kGatherLocalThreads * kGatherLocalPer;
-        gather_hits_local_kernel<T><<<(unsigned)((std::max<i64>(mm, 1) + perBlock - 1) / perBlock), kGatherLocalThreads, sizeof(T) * 2 * (size_t)nb, st>>>(
-            prefA, prefB, tot, tot + parts, next, next + parts, posE, posS, classBase, mm, hits, tileA, tileB, nb, nextInfo,
-            share ? share->regionList : nullptr, share && share->scatter ? 1 : 0);
-        *totalsTurn ^= 1;
-        return hipGetLastError();
-      }
-      if (!tileSumsValid) tile_sums_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, tileA, tileB, tl);
-      finalize_scan_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, histLen, tileA, tileB, prefA, prefB, tl);
-    }
+  T *histA = (T *)a.histA, *histB = (T *)a.histB, *prefA = (T *)a.prefA, *prefB = (T *)a.prefB;
+  const int nb = scan_tiles(a.histLen);
+  const int nbRun = a.share ? a.share->nTiles : nb;            // a group member: the tiles of its classes, its regions (compact)
+  const int *tl = a.share ? a.share->tileList : nullptr, *regions = a.share ? a.share->regionList : nullptr;
+  const i64 mm = a.share ? a.share->nRegions : a.m;
+  const int scatter = a.share && a.share->scatter ? 1 : 0;
+  *took = finalize_route(nb, nbRun, a.tileSumsValid, a.chainFlags && a.info, a.totals && a.nextTotals, a.localMaxTiles, route_knobs());
+  switch (*took) {
+  case FIN_GATHER_ONLY: break;
+  case FIN_CHAINED: {
+    u64 *f = (u64 *)a.chainFlags;
+    finalize_scan_chained_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, a.histLen, f, f + 2 * (nb + 2), f + 2 * nb, f + 2 * (nb + 2) + 2 * nb, a.draws, a.epoch,
+                                                                    nbRun, prefA, prefB, tl, a.info);
+    break;
   }
-  const i64 mm = share ? share->nRegions : m;
-  const i64 work = (mm > nb ? mm : nb) > 0 ? (mm > nb ? mm : nb) : 1;
-  gather_hits_kernel<T><<<(unsigned)((work + 255) / 256), 256, 0, st>>>(prefA, prefB, posE, posS, classBase, mm, hits, tileA, tileB, nb, nextInfo,
-                                                                        share ? share->regionList : nullptr, share && share->scatter ? 1 : 0);
+  case FIN_LOCAL: {
+    // local scan + gather with the tiles' offsets: the totals of this turn (all zero on entry), the other turn's zeroed for the next call
+    const size_t parts = (size_t)nb + 2;
+    const i64 perBlock = (i64)kGatherLocalThreads * kGatherLocalPer;
+    finalize_local_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, a.histLen, a.totals, a.totals + parts, prefA, prefB, tl);
+    gather_hits_local_kernel<T><<<(unsigned)((std::max<i64>(mm, 1) + perBlock - 1) / perBlock), kGatherLocalThreads, sizeof(T) * 2 * (size_t)nb, st>>>(
+        prefA, prefB, a.totals, a.totals + parts, a.nextTotals, a.nextTotals + parts, a.posE, a.posS, a.classBase, mm, a.hits, a.tileA, a.tileB, nb, a.nextInfo, regions, scatter);
+    return hipGetLastError();
+  }
+  case FIN_SUMS_SCAN:
+    tile_sums_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, a.histLen, a.tileA, a.tileB, tl);
+    [[fallthrough]];
+  case FIN_SUMS_KEPT:
+    finalize_scan_kernel<T><<<dim3(nbRun, 2), 256, 0, st>>>(histA, histB, a.histLen, a.tileA, a.tileB, prefA, prefB, tl);
+    break;
+  }
+  const i64 work = std::max<i64>(std::max<i64>(mm, nb), 1);
+  gather_hits_kernel<T><<<(unsigned)((work + 255) / 256), 256, 0, st>>>(prefA, prefB, a.posE, a.posS, a.classBase, mm, a.hits, a.tileA, a.tileB, nb, a.nextInfo, regions, scatter);
   return hipGetLastError();
 }
 
-hipError_t launch_finalize(u64 *histA, u64 *histB, i64 histLen, u64 *tileA, u64 *tileB, bool tileSumsValid, u64 *prefA, u64 *prefB,
-                           const int *posE, const int *posS, const int *classBase, i64 m, u64 *hits, DevInfo *nextInfo, hipStream_t st,
-                           const FinalizeShare *share, unsigned *chainFlags, unsigned epoch, DevInfo *info, unsigned long long *chainDraws, bool hist32,
-                           u64 *totals, unsigned *totalsTurn, int localMaxTiles)
+// hist32: the call's streaming kernel counted into 32-bit slots (CountArgs::hist32): the same buffers, read as unsigned[]
+hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st, FinalizeRoute *took)
 {
-  if (localMaxTiles > kLocalScanMaxTiles) localMaxTiles = kLocalScanMaxTiles;     // (the gather's LDS)
-  // hist32: the call's streaming kernel counted into 32-bit slots (CountArgs::hist32): the same buffers, read as unsigned[]
-  if (hist32) return launch_finalize_t<unsigned>((unsigned *)histA, (unsigned *)histB, histLen, tileA, tileB, tileSumsValid, (unsigned *)prefA, (unsigned *)prefB,
-                                                 posE, posS, classBase, m, hits, nextInfo, st, share, chainFlags, epoch, info, chainDraws, totals, totalsTurn, localMaxTiles);
-  return launch_finalize_t<u64>(histA, histB, histLen, tileA, tileB, tileSumsValid, prefA, prefB, posE, posS, classBase, m, hits, nextInfo, st, share, chainFlags, epoch,
-                                info, chainDraws, totals, totalsTurn, localMaxTiles);
+  return a.hist32 ? launch_finalize_t<unsigned>(a, st, took) : launch_finalize_t<u64>(a, st, took);
 }
 
 hipError_t launch_coverage(const void *reads, const void *weights, i64 n, const CoverArgs &a, hipStream_t st)

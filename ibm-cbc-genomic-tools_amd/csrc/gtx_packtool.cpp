@@ -11,6 +11,8 @@
 //     -s sorted by strand   -a strand-aware classes   -c known chromosomes (default: all seen in FILE order? no:
 //        the list is required for reproducible class ids)
 //   output: one line per packed read "class start end [weight]", then "# lines=N"; errors like the CLIs.
+//
+//   gtx_packtool route [RULE ARG...]   the library's kernel-route rules (gtx_routes.h), see RouteQuery below
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -19,6 +21,7 @@
 #include "gtx_bed.h"
 #include "gtx_stats.h"
 #include "gtx_peakdiff.h"
+#include "gtx_routes.h"
 
 using namespace gtxhost;
 
@@ -91,6 +94,35 @@ static int SynthBed(bool refs, long long n, unsigned long long seed, const char 
   return fclose(o) == 0 ? 0 : 1;
 }
 
+// One query of `gtx_packtool route`: a rule of gtx_routes.h by name with its arguments in the rule's own order, the knobs from the
+// environment as the library reads them (RouteKnobs::from_env).  Prints the result on one line; false: not a query.
+//   finalize NB NBRUN SUMSVALID HAVECHAIN HAVETOTALS LOCALMAXTILES -> gather_only | sums_kept | chained | local | sums_scan
+//   keeps_tile_sums HISTLEN NREADS      flip REGIONS NREADS      hist32 SINGLEUNWEIGHTEDLAUNCH NREADS      partition_worth N BUCKETMINREADS
+//   count_cpw NREADS WAVESLOTS FORCED   cover_cpw NREADS FORCED  scan_per TOTALMICRO PARTBINS              scan_tables_ok NB NCLASSES TOTALMICRO
+//   scan_own READSSORTED PREPONE NREADS scan_fused COMB MAXCOMB TOTALWINDOWS                               scan_tiles LEN
+static bool RouteQuery(const char *line)
+{
+  static const char *const fin[] = {"gather_only", "sums_kept", "chained", "local", "sums_scan"};
+  const gtx::RouteKnobs k = gtx::RouteKnobs::from_env();
+  char rule[32]; long long a[6] = {0, 0, 0, 0, 0, 0};
+  const int n = sscanf(line, " %31s %lld %lld %lld %lld %lld %lld", rule, &a[0], &a[1], &a[2], &a[3], &a[4], &a[5]) - 1;
+  const std::string r = n >= 0 ? rule : "";
+  if (r == "finalize" && n == 6) printf("%s\n", fin[gtx::finalize_route((int)a[0], (int)a[1], a[2] != 0, a[3] != 0, a[4] != 0, (int)a[5], k)]);
+  else if (r == "keeps_tile_sums" && n == 2) printf("%d\n", (int)gtx::keeps_tile_sums(a[0], a[1], k));
+  else if (r == "flip" && n == 2) printf("%d\n", (int)gtx::flip_walk(a[0], a[1], k));
+  else if (r == "hist32" && n == 2) printf("%d\n", (int)gtx::hist32_slots(a[0] != 0, a[1], k));
+  else if (r == "partition_worth" && n == 2) printf("%d\n", (int)gtx::partition_worth(a[0], a[1]));
+  else if (r == "count_cpw" && n == 3) printf("%d\n", gtx::count_chunks_per_wave(a[0], a[1], (int)a[2]));
+  else if (r == "cover_cpw" && n == 2) printf("%d\n", gtx::cover_chunks_per_wave(a[0], (int)a[1]));
+  else if (r == "scan_per" && n == 2) printf("%lld\n", gtx::scan_bucket_per(a[0], (int)a[1], k));
+  else if (r == "scan_tables_ok" && n == 3) printf("%d\n", (int)gtx::scan_bucket_tables_ok(a[0], (int)a[1], a[2]));
+  else if (r == "scan_own" && n == 3) printf("%d\n", (int)gtx::scan_own_wanted(a[0] != 0, a[1] != 0, a[2], k));
+  else if (r == "scan_fused" && n == 3) printf("%d\n", (int)gtx::scan_fused_ok((int)a[0], (int)a[1], a[2], k));
+  else if (r == "scan_tiles" && n == 1) printf("%d\n", gtx::scan_tiles(a[0]));
+  else return false;
+  return true;
+}
+
 int main(int argc, char **argv)
 {
   if (argc < 2) { fprintf(stderr, "usage: gtx_packtool ou|os|su|ss [-t N] [-s] [-a] [-l MAX] -c chr1,chr2,... [FILE]\n"); return 2; }
@@ -136,6 +168,15 @@ int main(int argc, char **argv)
       else if (n >= 2 && kind == 'g') printf("%.17g\n", gtxstats::GaussianQ(x));
       else { fprintf(stderr, "bad query: %s", line); return 2; }
     }
+    return 0;
+  }
+  if (m == "route") {
+    // gtx_packtool route RULE ARG... : one query from the command line; gtx_packtool route : one query per stdin line
+    std::string q;
+    for (int a = 2; a < argc; a++) { q += argv[a]; q += ' '; }
+    char line[256];
+    if (argc > 2) { if (!RouteQuery(q.c_str())) { fprintf(stderr, "bad query: %s\n", q.c_str()); return 2; } return 0; }
+    while (fgets(line, sizeof line, stdin)) if (!RouteQuery(line)) { fprintf(stderr, "bad query: %s", line); return 2; }
     return 0;
   }
   if (m == "critical") {

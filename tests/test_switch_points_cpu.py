@@ -1,7 +1,10 @@
-"""The thresholds of tests/switch_points.py read back out of the sources (no GPU): when one moves, this fails and names the GPU
-test of tests/test_gpu_switch_points.py whose cases must be re-aimed.  And the property that keeps the signal bins' n_dropped at 0."""
+"""The thresholds of tests/switch_points.py: the constants read back out of the sources, the rules asked of the library's own route
+functions (csrc/gtx_routes.h, through the host-only `gtx_packtool route`) on both sides of each threshold (no GPU): when one moves,
+this fails and names the GPU test of tests/test_gpu_switch_points.py whose cases must be re-aimed.  And the property that keeps the
+signal bins' n_dropped at 0."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -31,8 +34,28 @@ def test_threshold_matches_the_source(name):
     assert tuple(int(x) for x in got) == tuple(want), hint
 
 
+@pytest.mark.parametrize("name", sorted(sp.ROUTES))
+def test_route_rule_at_its_thresholds(name):
+    hint = "%s moved in gtx_routes.h: re-aim tests/test_gpu_switch_points.py::%s, then update tests/switch_points.py" % (name, sp.AIMED_BY[name])
+    for env in sorted({tuple(e.items()) for e, _, _ in sp.ROUTES[name]}):
+        asked = [(q, want) for e, q, want in sp.ROUTES[name] if tuple(e.items()) == env]
+        got = sp.route_answers([q for q, _ in asked], dict(env))
+        assert got == [want for _, want in asked], hint + " (%s: %s)" % (dict(env), [(q, w, g) for (q, w), g in zip(asked, got) if w != g])
+
+
+def test_route_knobs_are_read_from_the_environment_only():
+    """a knob of the caller's own environment does not leak into a query that names none, and a bad query is refused"""
+    os.environ["GTX_CHAIN_MAX_TILES"] = "10"
+    try:
+        assert sp.route_answers([sp.fin(sp.C, sp.C)], {}) == ["chained"]
+    finally:
+        del os.environ["GTX_CHAIN_MAX_TILES"]
+    assert subprocess.run([sp.PACKTOOL, "route", "finalize", "1"], capture_output=True).returncode == 2
+    assert subprocess.run([sp.PACKTOOL, "route", "finalize", "512", "512", "0", "1", "1", "2048"], capture_output=True, text=True).stdout == "chained\n"
+
+
 def test_every_entry_names_its_gpu_test():
-    assert set(sp.AIMED_BY) == set(sp.SRC)
+    assert set(sp.AIMED_BY) == set(sp.SRC) | set(sp.ROUTES) and not set(sp.SRC) & set(sp.ROUTES)
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_switch_points.py")) as f:
         text = f.read()
     for t in set(sp.AIMED_BY.values()):
