@@ -1,0 +1,462 @@
+// gtx_api_scan.hip -- the C ABI's scans: gtx_scan* over reads on the device, in host buffers or fed as a stream, the window vectors
+// kept in HBM, and the window selection over them.  Host code only (the kernels: gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip,
+// gtx_select.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <stdio.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+#include "gtx.h"
+#include "gtx_kernels.h"
+#include "gtx_select.h"
+#include "gtx_internal.h"
+#include "gtx_ctx.h"
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------
+// scan
+// ---------------------------------------------------------------------------------------------
+int64_t gtx_scan_n_windows(int64_t len, int64_t step, int64_t size)
+{
+  if (step <= 0 || size <= 0 || len < 0) return 0;
+  int64_t n = len / step, comb = size / step;
+  return n < comb ? 0 : n - comb + 1;
+}
+
+// ownTile > 0: also lay out the blocks of the owner-computes pass (ownTile windows each); *own receives its table
+static int scan_prepare(gtx_ctx *c, const int32_t *classLen, int nClasses, int step, int size, const int64_t *classOff, gtx::ScanArgs *out,
+                        int ownTile = 0, gtx::ScanOwn *own = nullptr)
+{
+  if (nClasses < 1 || !classLen || !classOff) return fail(c, GTX_E_ARG, "gtx_scan: bad class table");
+  if (step <= 0 || size <= 0 || size % step) return fail(c, GTX_E_ARG, "gtx_scan: window size must be a positive multiple of window step");
+  std::vector<long long> key;
+  key.push_back(nClasses); key.push_back(step); key.push_back(size); key.push_back(ownTile);
+  for (int i = 0; i < nClasses; i++) { key.push_back(classLen[i]); key.push_back(classOff[i]); }
+  const size_t tabLen = (size_t)6 * nClasses + 3;
+  if (key != c->scan.key) {
+    std::vector<long long> tab(tabLen);
+    long long *microOff = tab.data(), *nMicro = microOff + nClasses, *winOff = nMicro + nClasses, *outOff = winOff + nClasses + 1,
+              *tileOff = outOff + nClasses, *blkOff = tileOff + nClasses + 1;
+    long long mo = 0, wo = 0, to = 0, bo = 0;
+    const long long tile = gtx::scan_window_tile();
+    for (int i = 0; i < nClasses; i++) {
+      long long nm = classLen[i] < 0 ? 0 : classLen[i] / step;
+      long long nw = gtx_scan_n_windows(classLen[i] < 0 ? 0 : classLen[i], step, size);
+      microOff[i] = mo; nMicro[i] = nm; winOff[i] = wo; outOff[i] = classOff[i]; tileOff[i] = to; blkOff[i] = bo;
+      mo += nm; wo += nw; to += (nw + tile - 1) / tile;
+      if (ownTile > 0) bo += (nw + ownTile - 1) / ownTile;
+    }
+    winOff[nClasses] = wo; tileOff[nClasses] = to; blkOff[nClasses] = bo;
+    c->scan.totalTiles = to; c->scan.ownBlocks = bo;
+    HIPCHK(c, c->scan.tab.reserve(tabLen));
+    HIPCHK(c, c->scan.micro.reserve((size_t)mo + 1, (size_t)mo + 3));
+    HIPCHK(c, c->scan.bounds.reserve((size_t)(2 * bo + 2)));
+    if (!c->scan.flag) HIPCHK(c, c->scan.flag.alloc(1));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(c->scan.tab.get(), tab.data(), tabLen * sizeof(long long), hipMemcpyHostToDevice));
+    c->scan.key = key; c->scan.totalMicro = mo; c->scan.totalWindows = wo;
+  }
+  out->micro = c->scan.micro.get(); out->microOff = c->scan.tab.get(); out->nMicro = c->scan.tab.get() + nClasses;
+  out->winOff = c->scan.tab.get() + 2 * nClasses; out->outOff = c->scan.tab.get() + 3 * nClasses + 1; out->tileOff = c->scan.tab.get() + 4 * nClasses + 1;
+  out->nClasses = nClasses; out->winStep = step; out->comb = size / step;
+  out->winStepInv = step > 1 ? (unsigned)((1ull << 32) / (unsigned)step) : 0;
+  if (own) { own->blkOff = c->scan.tab.get() + 5 * nClasses + 2; own->tile = ownTile; own->totalBlocks = c->scan.ownBlocks; own->bounds = c->scan.bounds.get(); own->flag = c->scan.flag.get(); }
+  return GTX_OK;
+}
+
+// Bucket tables over the POSITIONS of a scan geometry, for reads in no particular order (gtx_bucket.hip: bucket_scanhist_kernel):
+// a bucket is a run of consecutive micro-windows of one class -- at most ~2000 buckets in all, at least 16 k micro-windows each --
+// and is counted in parts of scan_part_bins() micro-windows.  Built when the geometry (or weighted / not) changes.
+static int scan_bucket_tables(gtx_ctx *c, const int32_t *classLen, int nClasses, int step, bool weighted)
+{
+  std::vector<long long> key = c->scan.key; key.push_back(weighted ? 1 : 0);
+  if (key == c->scan.bktKey) return GTX_OK;
+  c->scan.bktKey.clear(); c->scan.nParts = 0;
+  c->scan.bkt = {}; c->scan.parts.reset();
+  if (!c->scan.info) HIPCHK(c, c->scan.info.alloc(1));
+  long long total = 0;
+  for (int i = 0; i < nClasses; i++) total += classLen[i] < 0 ? 0 : classLen[i] / step;
+  BucketCuts k;
+  k.clsStart.assign(nClasses + 1, 0);
+  std::vector<gtx::ScanPart> parts;
+  const int bins = gtx::scan_part_bins(weighted);
+  const long long per = gtx::scan_bucket_per(total, bins, gtx::route_knobs());      // micro-windows per bucket
+  for (int cl = 0; cl < nClasses; cl++) {
+    k.clsStart[cl] = (int32_t)k.posHi.size();
+    const long long nm = classLen[cl] < 0 ? 0 : classLen[cl] / step;
+    for (long long f = 0; f < nm; f += per) {
+      const long long g = std::min(f + per, nm);
+      k.posHi.push_back(g == nm ? INT32_MAX : (int32_t)(g * step));                // positions <= g * step lie in micro-windows < g
+      k.eLo.push_back((int32_t)f); k.eHi.push_back((int32_t)g); k.sLo.push_back(0); k.sHi.push_back(0); k.cls.push_back(cl);
+      for (long long m = f; m < g; m += bins) parts.push_back({(int)k.posHi.size() - 1, (int)m, (int)std::min<long long>(bins, g - m), 0});
+    }
+  }
+  k.clsStart[nClasses] = (int32_t)k.posHi.size();
+  const int nB = (int)k.posHi.size();
+  if (!gtx::scan_bucket_tables_ok(nB, nClasses, total)) { c->scan.bktKey = key; return GTX_OK; }   // (bktS.nB == 0: the general kernels serve)
+  int rc = build_bucket_tables(c, c->scan.bkt, k, nClasses, true); if (rc) return rc;
+  if (c->scan.bkt.nB > 0) {
+    HIPCHK(c, upload(c->scan.parts, parts.data(), parts.size()));
+    c->scan.nParts = (int)parts.size();
+  }
+  c->scan.bktKey = key;
+  return GTX_OK;
+}
+
+// whether the partition path serves a batch of a scan: reads in no order under the unsorted scanner's rule (the bin index's), tables
+// for the geometry, and partition_plan's word
+static int scan_partition_plan(gtx_ctx *c, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted,
+                               gtx::BucketPlan *p, gtx::BucketWork *w, bool *yes)
+{
+  *yes = false;
+  if (!unsorted || a.sortedRule || !gtx::partition_worth(n, c->bucketMinReads)) return GTX_OK;
+  int rc = scan_bucket_tables(c, classLen, a.nClasses, a.winStep, dW != nullptr); if (rc) return rc;
+  return partition_plan(c, c->scan.bkt, n, a.nClasses, dW != nullptr, p, w, yes);
+}
+
+// one batch of reads by the partition path: into the micro-window histogram (zeroed by the caller), or -- d_windows not null -- the
+// parts write the windows themselves (gtx::launch_scan_bucketed)
+static int scan_hist_bucketed(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const gtx::BucketPlan &p, const gtx::BucketWork &w, u64 *d_windows)
+{
+  gtx::CountArgs ca = {};                                      // what the partition pass reads of it; its counts of dropped reads go nowhere
+  ca.nClasses = a.nClasses; ca.zeroLenOk = 0; ca.coverRule = 1; ca.keyCenter = a.center; ca.info = c->scan.info.get(); ca.indexBase = 0;
+  HIPCHK(c, gtx::launch_scan_bucketed(dR, dW, n, ca, a, c->scan.bkt.view(), w, p, c->scan.parts.get(), c->scan.nParts, c->stream, d_windows));
+  return GTX_OK;
+}
+
+} // extern "C"
+
+// one batch of reads into the micro-window histogram (zeroed by the caller): the partition path or the general kernel
+int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted)
+{
+  gtx::BucketPlan p; gtx::BucketWork w; bool part;
+  int rc = scan_partition_plan(c, dW, n, a, classLen, unsorted, &p, &w, &part); if (rc) return rc;
+  if (part) return scan_hist_bucketed(c, dR, dW, n, a, p, w, nullptr);
+  HIPCHK(c, gtx::launch_scan_hist(dR, dW, n, a, c->stream));
+  return GTX_OK;
+}
+
+extern "C" {
+
+// the scan of reads resident in HBM, enqueued: owner-computes when the caller says the reads are sorted (checked on the device; the
+// general kernels follow as conditional launches and run only if the check fails), the general kernels otherwise
+static int scan_launch(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, const int32_t *classLen, int32_t nClasses, int32_t step,
+                       int32_t size, char prep, uint32_t flags, const int64_t *classOff, void *d_out, bool profile)
+{
+  const gtx::RouteKnobs &knobs = gtx::route_knobs();
+  int64_t totalMicro = 0;
+  for (int i = 0; i < nClasses; i++) totalMicro += classLen[i] < 0 ? 0 : classLen[i] / step;
+  const int tile = gtx::scan_own_wanted((flags & GTX_READS_SORTED) != 0, prep == '1', n, knobs) ? gtx::scan_own_tile(n, totalMicro, size / step) : 0;
+  gtx::ScanArgs a; gtx::ScanOwn own;
+  int rc = scan_prepare(c, classLen, nClasses, step, size, classOff, &a, tile, &own); if (rc) return rc;
+  a.center = prep == 'c'; a.sortedRule = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
+  if (c->scan.totalWindows > 0 && !d_out) return fail(c, GTX_E_ARG, "gtx_scan: null output");
+  const bool micro64 = d_weights != nullptr;
+  const size_t microBytes = (size_t)c->scan.totalMicro * (micro64 ? 8 : 4);
+  const int *runIf = nullptr;
+  if (tile > 0 && own.totalBlocks > 0) {
+    HIPCHK(c, hipMemsetAsync(c->scan.flag.get(), 0, sizeof(int), c->stream));
+    if (profile) HIPCHK(c, prof_mark(c, 1, c->stream));
+    HIPCHK(c, gtx::launch_scan_own(d_reads, d_weights, n, a, own, (u64 *)d_out, c->stream));
+    if (profile) HIPCHK(c, prof_mark(c, 2, c->stream));
+    runIf = c->scan.flag.get();
+    if (microBytes) HIPCHK(c, gtx::launch_scan_zero(c->scan.micro.get(), (long long)microBytes, runIf, c->stream));
+    HIPCHK(c, gtx::launch_scan_hist(d_reads, d_weights, n, a, c->stream, runIf));
+  } else {
+    // reads in no order through the partition path: its parts write the windows themselves (no micro-window array, no window pass)
+    gtx::BucketPlan p; gtx::BucketWork w; bool part;
+    rc = scan_partition_plan(c, (const int *)d_weights, n, a, classLen, (flags & GTX_READS_UNSORTED) != 0, &p, &w, &part); if (rc) return rc;
+    const bool fused = part && gtx::scan_fused_ok(a.comb, gtx::scan_fused_max_comb(), c->scan.totalWindows, knobs);
+    if (!fused && microBytes) HIPCHK(c, hipMemsetAsync(c->scan.micro.get(), 0, microBytes, c->stream));
+    if (profile) HIPCHK(c, prof_mark(c, 1, c->stream));
+    if (part) { rc = scan_hist_bucketed(c, d_reads, (const int *)d_weights, n, a, p, w, fused ? (u64 *)d_out : nullptr); if (rc) return rc; }
+    else HIPCHK(c, gtx::launch_scan_hist(d_reads, d_weights, n, a, c->stream));
+    if (profile) HIPCHK(c, prof_mark(c, 2, c->stream));
+    if (fused) return GTX_OK;
+  }
+  HIPCHK(c, gtx::launch_scan_windows(c->scan.micro.get(), micro64, a, c->scan.totalTiles, (u64 *)d_out, c->stream, runIf));
+  return GTX_OK;
+}
+
+// a host-buffer call's reads brought into ONE device buffer (pageable memory through the page-locked slots), so that the
+// owner-computes scan can be a single launch over all of them
+static int stage_resident(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t n, void **dR, int **dW)
+{
+  if (c->stage.directPending) { HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); c->stage.directPending = false; }
+  const size_t bytes = (size_t)n * 12, nW = weights ? (size_t)n : 0;
+  if (bytes > c->scan.resReads.cap || nW > c->scan.resWeights.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+    HIPCHK(c, c->scan.resReads.reserve(bytes));
+    HIPCHK(c, c->scan.resWeights.reserve(nW));
+  }
+  const bool direct = is_pinned(reads) && (!weights || is_pinned(weights));
+  const int64_t batch = c->batchReads;
+  const size_t slotBytes = (size_t)std::min<int64_t>(n, batch) * 16;
+  if (!direct && (slotBytes > c->stage.pin[0].cap || slotBytes > c->stage.pin[1].cap)) {
+    HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+    for (int k = 0; k < 2; k++) HIPCHK(c, c->stage.pin[k].reserve(slotBytes));
+    c->stage.slotBusy[0] = c->stage.slotBusy[1] = false;
+  }
+  // the kernels of the previous call (the context's stream) may still be reading the resident buffer
+  HIPCHK(c, hipEventRecord(c->scan.evRes[0], c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->stage.copyStream, c->scan.evRes[0], 0));
+  for (int64_t off = 0; off < n; off += batch) {
+    const int64_t cnt = std::min(batch, n - off);
+    const char *srcR = (const char *)(reads + 3 * off), *srcW = (const char *)(weights ? weights + off : nullptr);
+    int slot = -1;
+    if (!direct) {
+      slot = (int)(c->stage.seq++ & 1);
+      if (c->stage.slotBusy[slot]) HIPCHK(c, hipEventSynchronize(c->stage.evCopied[slot]));      // the DMA out of this page-locked slot is done
+      parallel_copy(c->stage.pin[slot].get(), srcR, (size_t)cnt * 12, c->stage.copyThreads);
+      if (weights) parallel_copy(c->stage.pin[slot].get() + (size_t)cnt * 12, srcW, (size_t)cnt * 4, c->stage.copyThreads);
+      srcR = c->stage.pin[slot].get(); srcW = c->stage.pin[slot].get() + (size_t)cnt * 12;
+    }
+    HIPCHK(c, hipMemcpyAsync((char *)c->scan.resReads.get() + (size_t)off * 12, srcR, (size_t)cnt * 12, hipMemcpyHostToDevice, c->stage.copyStream));
+    if (weights) HIPCHK(c, hipMemcpyAsync(c->scan.resWeights.get() + off, srcW, (size_t)cnt * 4, hipMemcpyHostToDevice, c->stage.copyStream));
+    if (slot >= 0) { HIPCHK(c, hipEventRecord(c->stage.evCopied[slot], c->stage.copyStream)); c->stage.slotBusy[slot] = true; }
+  }
+  c->stage.directPending = direct;
+  HIPCHK(c, hipEventRecord(c->scan.evRes[1], c->stage.copyStream));                              // everything has arrived before the scan starts
+  HIPCHK(c, hipStreamWaitEvent(c->stream, c->scan.evRes[1], 0));
+  *dR = c->scan.resReads.get(); *dW = weights ? c->scan.resWeights.get() : nullptr;
+  return GTX_OK;
+}
+
+int gtx_scan_device(gtx_ctx *c, const void *d_reads, const void *d_weights, int64_t n, const int32_t *classLen, int32_t nClasses,
+                    int32_t step, int32_t size, char prep, uint32_t flags, void *d_out, const int64_t *classOff)
+{
+  if (!c) return GTX_E_ARG;
+  if (n < 0 || (n > 0 && !d_reads)) return fail(c, GTX_E_ARG, "gtx_scan_device: bad argument");
+  if (prep != '1' && prep != 'c') return fail(c, GTX_E_ARG, "gtx_scan_device: preprocess operator must be '1' or 'c'");
+  if (!d_weights && n >= (1ll << 32)) return fail(c, GTX_E_ARG, "gtx_scan_device: unweighted scans count in 32 bits per micro-window: at most 2^32-1 reads per call");
+  HIPCHK(c, hipSetDevice(c->device));
+  prof_begin(c);
+  int rc = scan_launch(c, d_reads, d_weights, n, classLen, nClasses, step, size, prep, flags, classOff, d_out, c->prof.profThis); if (rc) return rc;
+  HIPCHK(c, prof_end(c, c->stream));
+  return GTX_OK;
+}
+
+// the whole scan of host reads enqueued, result left in the context's own output vector in HBM
+int gtxi_scan_enqueue(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t n, const int32_t *classLen, int32_t nClasses,
+                      int32_t step, int32_t size, char prep, uint32_t flags, const int64_t *classOff, void **d_out, int64_t *extent_out)
+{
+  if (n < 0 || (n > 0 && !reads)) return fail(c, GTX_E_ARG, "gtx_scan: bad argument");
+  if (prep != '1' && prep != 'c') return fail(c, GTX_E_ARG, "gtx_scan: preprocess operator must be '1' or 'c'");
+  if (!weights && n >= (1ll << 32)) return fail(c, GTX_E_ARG, "gtx_scan: unweighted scans count in 32 bits per micro-window: at most 2^32-1 reads per call");
+  if (nClasses < 1 || !classLen || !classOff) return fail(c, GTX_E_ARG, "gtx_scan: bad class table");
+  if (step <= 0 || size <= 0 || size % step) return fail(c, GTX_E_ARG, "gtx_scan: window size must be a positive multiple of window step");
+  HIPCHK(c, hipSetDevice(c->device));
+  // output layout in the caller's buffer is given by class_offsets: find its extent
+  int64_t extent = 0;
+  for (int i = 0; i < nClasses; i++) extent = std::max<int64_t>(extent, classOff[i] + gtx_scan_n_windows(classLen[i] < 0 ? 0 : classLen[i], step, size));
+  int rc = ensure_out(c, (size_t)extent); if (rc) return rc;
+  if (extent > 0) HIPCHK(c, hipMemsetAsync(c->out.get(), 0, (size_t)extent * sizeof(u64), c->stream));
+  if ((flags & GTX_READS_SORTED) && prep == '1' && n > 0) {
+    // sorted reads: all of them resident, one owner-computes launch (gtx_scanown.hip)
+    void *dR = nullptr; int *dW = nullptr;
+    rc = stage_resident(c, reads, weights, n, &dR, &dW); if (rc) return rc;
+    rc = scan_launch(c, dR, dW, n, classLen, nClasses, step, size, prep, flags, classOff, c->out.get(), false); if (rc) return rc;
+  } else {
+    gtx::ScanArgs a;
+    rc = scan_prepare(c, classLen, nClasses, step, size, classOff, &a); if (rc) return rc;
+    a.center = prep == 'c'; a.sortedRule = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
+    const bool micro64 = weights != nullptr;
+    if (c->scan.totalMicro > 0) HIPCHK(c, hipMemsetAsync(c->scan.micro.get(), 0, (size_t)c->scan.totalMicro * (micro64 ? 8 : 4), c->stream));
+    rc = stage_batches(c, reads, weights, n, [&](const void *dR, const int *dW, int64_t cnt, int64_t off) -> int {
+      const bool unsorted = (flags & GTX_READS_UNSORTED) || host_reads_look_unsorted(reads + 3 * off, cnt);
+      return scan_hist_any(c, dR, dW, cnt, a, classLen, unsorted);
+    });
+    if (rc) return rc;
+    HIPCHK(c, gtx::launch_scan_windows(c->scan.micro.get(), micro64, a, c->scan.totalTiles, c->out.get(), c->stream));
+  }
+  *d_out = c->out.get(); *extent_out = extent;
+  return GTX_OK;
+}
+
+int gtx_scan(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t n, const int32_t *classLen, int32_t nClasses,
+             int32_t step, int32_t size, char prep, uint32_t flags, uint64_t *out, const int64_t *classOff)
+{
+  if (!c) return GTX_E_ARG;
+  void *d = nullptr; int64_t extent = 0;
+  int rc = gtxi_scan_enqueue(c, reads, weights, n, classLen, nClasses, step, size, prep, flags, classOff, &d, &extent); if (rc) return rc;
+  if (extent > 0 && !out) return fail(c, GTX_E_ARG, "gtx_scan: null output");
+  if (extent > 0) HIPCHK(c, hipMemcpyAsync(out, d, (size_t)extent * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+  return GTX_OK;
+}
+
+// ---- the same scan fed as a stream (genomic_scans on an input of any size: host batches, or text tokenised on the device) ----
+// The micro-window histogram accumulates over the batches (general kernels; batches in no order through the partition path), the
+// sliding sums follow at the end.  The all-at-once calls above stay what a caller with every read in hand uses: they can take the
+// owner-computes pass.
+int gtx_scan_begin(gtx_ctx *c, const int32_t *classLen, int32_t nClasses, int32_t step, int32_t size, char prep, uint32_t flags, int weighted,
+                   const int64_t *classOff)
+{
+  if (!c) return GTX_E_ARG;
+  if (prep != '1' && prep != 'c') return fail(c, GTX_E_ARG, "gtx_scan_begin: preprocess operator must be '1' or 'c'");
+  if (nClasses < 1 || !classLen || !classOff) return fail(c, GTX_E_ARG, "gtx_scan_begin: bad class table");
+  if (step <= 0 || size <= 0 || size % step) return fail(c, GTX_E_ARG, "gtx_scan_begin: window size must be a positive multiple of window step");
+  if (c->scan.cur.open || c->streamOpen || c->covOpen) return fail(c, GTX_E_STATE, "gtx_scan_begin: a call is open");
+  HIPCHK(c, hipSetDevice(c->device));
+  int64_t extent = 0;
+  for (int i = 0; i < nClasses; i++) extent = std::max<int64_t>(extent, classOff[i] + gtx_scan_n_windows(classLen[i] < 0 ? 0 : classLen[i], step, size));
+  int rc = ensure_out(c, (size_t)extent); if (rc) return rc;
+  if (extent > 0) HIPCHK(c, hipMemsetAsync(c->out.get(), 0, (size_t)extent * sizeof(u64), c->stream));
+  ScanOpen &s = c->scan.cur;
+  rc = scan_prepare(c, classLen, nClasses, step, size, classOff, &s.a); if (rc) return rc;
+  s.a.center = prep == 'c'; s.a.sortedRule = (flags & GTX_ZERO_LENGTH_OK) ? 1 : 0;
+  s.weighted = weighted != 0; s.classLen.assign(classLen, classLen + nClasses); s.extent = extent; s.prep = prep; s.flags = flags;
+  if (c->scan.totalMicro > 0) HIPCHK(c, hipMemsetAsync(c->scan.micro.get(), 0, (size_t)c->scan.totalMicro * (s.weighted ? 8 : 4), c->stream));
+  if (!s.labelSum) HIPCHK(c, s.labelSum.alloc(1));
+  HIPCHK(c, hipMemsetAsync(s.labelSum.get(), 0, sizeof(unsigned long long), c->stream));
+  s.open = true;
+  return GTX_OK;
+}
+
+int gtx_scan_add(gtx_ctx *c, const int32_t *reads, const int32_t *weights, int64_t n, uint32_t flags)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->scan.cur.open) return fail(c, GTX_E_STATE, "gtx_scan_add: gtx_scan_begin has not been called");
+  if (n < 0 || (n > 0 && !reads) || (c->scan.cur.weighted && n > 0 && !weights) || (!c->scan.cur.weighted && weights)) return fail(c, GTX_E_ARG, "gtx_scan_add: bad argument (weights as announced to gtx_scan_begin)");
+  HIPCHK(c, hipSetDevice(c->device));
+  ScanOpen &s = c->scan.cur;
+  return stage_batches(c, reads, weights, n, [&](const void *dR, const int *dW, int64_t cnt, int64_t off) -> int {
+    const bool unsorted = (flags & GTX_READS_UNSORTED) || host_reads_look_unsorted(reads + 3 * off, cnt);
+    return scan_hist_any(c, dR, dW, cnt, s.a, s.classLen.data(), unsorted);
+  });
+}
+
+int gtx_scan_end(gtx_ctx *c, uint64_t *out, int64_t *labelSum)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->scan.cur.open) return fail(c, GTX_E_STATE, "gtx_scan_end: gtx_scan_begin has not been called");
+  ScanOpen &s = c->scan.cur;
+  s.open = false;
+  if (s.extent > 0 && !out) return fail(c, GTX_E_ARG, "gtx_scan_end: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, gtx::launch_scan_windows(c->scan.micro.get(), s.weighted, s.a, c->scan.totalTiles, c->out.get(), c->stream));
+  if (s.extent > 0) HIPCHK(c, hipMemcpyAsync(out, c->out.get(), (size_t)s.extent * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  unsigned long long sum = 0;
+  HIPCHK(c, hipMemcpyAsync(&sum, s.labelSum.get(), sizeof sum, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+  if (labelSum) *labelSum = (int64_t)sum;
+  return GTX_OK;
+}
+
+// gtx_scan_end with the windows left on the device: the sliding sums are written into the slot's own vector (zero first: class_offsets
+// may leave gaps), nothing but the label sum comes to the host
+int gtx_scan_end_keep(gtx_ctx *c, int slot, int64_t *labelSum)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->scan.cur.open) return fail(c, GTX_E_STATE, "gtx_scan_end_keep: gtx_scan_begin has not been called");
+  ScanOpen &s = c->scan.cur;
+  s.open = false;                                                    // (a refused slot ends the scan too, like gtx_scan_end's null output)
+  if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_end_keep: slot out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((size_t)s.extent > c->scan.kept[slot].cap || !c->scan.kept[slot]) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));                      // a selection may still be reading what the slot held
+    HIPCHK(c, c->scan.kept[slot].alloc((size_t)std::max<int64_t>(s.extent, 1)));
+  }
+  c->scan.keptLen[slot] = s.extent;
+  if (s.extent > 0) HIPCHK(c, hipMemsetAsync(c->scan.kept[slot].get(), 0, (size_t)s.extent * sizeof(u64), c->stream));
+  HIPCHK(c, gtx::launch_scan_windows(c->scan.micro.get(), s.weighted, s.a, c->scan.totalTiles, c->scan.kept[slot].get(), c->stream));
+  unsigned long long sum = 0;
+  HIPCHK(c, hipMemcpyAsync(&sum, s.labelSum.get(), sizeof sum, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+  if (labelSum) *labelSum = (int64_t)sum;
+  return GTX_OK;
+}
+
+int gtx_scan_kept(gtx_ctx *c, int slot, void **d_ptr, int64_t *n_windows)
+{
+  if (!c) return GTX_E_ARG;
+  if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_kept: slot out of range");
+  if (!c->scan.kept[slot]) return fail(c, GTX_E_STATE, "gtx_scan_kept: the slot is empty");
+  if (d_ptr) *d_ptr = c->scan.kept[slot].get();
+  if (n_windows) *n_windows = c->scan.keptLen[slot];
+  return GTX_OK;
+}
+
+int gtx_scan_drop(gtx_ctx *c, int slot)
+{
+  if (!c) return GTX_E_ARG;
+  if (slot < -1 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_drop: slot out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < GTX_SCAN_KEEP_SLOTS; k++) if (slot == -1 || slot == k) { c->scan.kept[k].reset(); c->scan.keptLen[k] = 0; }
+  return GTX_OK;
+}
+
+// ---- window selection (gtx_select.hip) ----
+int gtx_window_select_limits(int32_t *tile, int32_t *lds_max_w)
+{
+  if (tile) *tile = gtx::kSelectTile;
+  if (lds_max_w) *lds_max_w = gtx::kSelectLdsMaxW;
+  return GTX_OK;
+}
+
+int gtx_window_select_device(gtx_ctx *c, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows, int32_t W,
+                             const int32_t *const *kcrit, int64_t capacity, void *d_ordinals, void *d_rows, int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  if (n_tested < 1 || n_tested > gtx::kSelectMaxTested || !d_tested || !kcrit || !n_kept) return fail(c, GTX_E_ARG, "gtx_window_select: 1 to 4 tested vectors, their tables and n_kept are required");
+  if (n_windows < 0 || W < 1 || W == INT32_MAX || capacity < 0) return fail(c, GTX_E_ARG, "gtx_window_select: bad window count, window size or capacity");
+  int n_ctl = 0;
+  for (int f = 0; f < n_tested; f++) n_ctl += d_control && d_control[f] ? 1 : 0;
+  if (n_ctl != 0 && n_ctl != n_tested) return fail(c, GTX_E_ARG, "gtx_window_select: a control for every tested vector, or for none");
+  const bool ctl = n_ctl > 0;
+  gtx::SelectArgs a = {};
+  for (int f = 0; f < n_tested; f++) {
+    if (!kcrit[f]) return fail(c, GTX_E_ARG, "gtx_window_select: null table");
+    a.tested[f] = (const u64 *)d_tested[f]; a.control[f] = ctl ? (const u64 *)d_control[f] : nullptr;
+    if (n_windows > 0 && (!a.tested[f] || ((uintptr_t)a.tested[f] & 15) || ((uintptr_t)a.control[f] & 15))) return fail(c, GTX_E_ARG, "gtx_window_select: vectors must be 16-byte aligned device memory");
+  }
+  if (capacity > 0 && (!d_ordinals || !d_rows)) return fail(c, GTX_E_ARG, "gtx_window_select: null output");
+  *n_kept = 0;
+  if (n_windows == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t stride = ctl ? (size_t)W + 1 : 1;
+  const int64_t nt = gtx::select_tiles(n_windows);
+  if (!c->sel.total) HIPCHK(c, c->sel.total.alloc(1));
+  if (stride * n_tested > c->sel.tab.cap || (size_t)nt > c->sel.count.cap || (size_t)nt + 1 > c->sel.base.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->sel.tab.reserve(stride * n_tested)); HIPCHK(c, c->sel.count.reserve((size_t)nt)); HIPCHK(c, c->sel.base.reserve((size_t)nt + 1));
+  }
+  // (the tables are pageable host memory: these copies return when the source has been read)
+  for (int f = 0; f < n_tested; f++) HIPCHK(c, hipMemcpyAsync(c->sel.tab.get() + f * stride, kcrit[f], stride * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  a.tab = c->sel.tab.get(); a.nTested = n_tested; a.W = W; a.n = n_windows;
+  HIPCHK(c, gtx::launch_window_select(a, c->sel.count.get(), c->sel.base.get(), capacity, (long long *)d_ordinals, (int *)d_rows, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->sel.total.get(), c->sel.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_kept = *c->sel.total.get();
+  return GTX_OK;
+}
+
+int gtx_window_select(gtx_ctx *c, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows, int32_t W,
+                      const int32_t *const *kcrit, int64_t capacity, int64_t *ordinals, int32_t *rows, int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  if (capacity < 0 || (capacity > 0 && (!ordinals || !rows))) return fail(c, GTX_E_ARG, "gtx_window_select: null output");
+  if (n_tested < 1 || n_tested > gtx::kSelectMaxTested) return fail(c, GTX_E_ARG, "gtx_window_select: 1 to 4 tested vectors, their tables and n_kept are required");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t cols = (size_t)n_tested * ((d_control && d_control[0]) ? 2 : 1);
+  if ((size_t)capacity > c->sel.ord.cap || (size_t)capacity * cols > c->sel.rows.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->sel.ord.reserve((size_t)capacity)); HIPCHK(c, c->sel.rows.reserve((size_t)capacity * cols));
+  }
+  int rc = gtx_window_select_device(c, d_tested, d_control, n_tested, n_windows, W, kcrit, capacity, c->sel.ord.get(), c->sel.rows.get(), n_kept); if (rc) return rc;
+  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
+  if (got) {
+    HIPCHK(c, hipMemcpy(ordinals, c->sel.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rows, c->sel.rows.get(), got * cols * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return GTX_OK;
+}
+
+}  // extern "C"

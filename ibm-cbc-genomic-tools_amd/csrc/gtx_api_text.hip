@@ -1,0 +1,226 @@
+// gtx_api_text.hip -- the C ABI's text feed: blocks of region text (BED, SAM) tokenised on the device and counted, covered or scanned
+// where the triples are (gtx_*_add_text), and the subset of a block's lines by their hits (gtx_subset_*).  Host code only (the
+// kernels: gtx_text.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+#include <stdio.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+#include "gtx.h"
+#include "gtx_kernels.h"
+#include "gtx_join.h"
+#include "gtx_query.h"
+#include "gtx_text.h"
+#include "gtx_ctx.h"
+
+// ---------------------------------------------------------------------------------------------
+// region text tokenised on the device (gtx_text.hip)
+// ---------------------------------------------------------------------------------------------
+enum TextMode { TEXT_COUNT, TEXT_COVER, TEXT_SCAN };
+
+// A block of text into the slot whose turn it is, and tokenised there (launch_tokenize enqueued on the context's stream): the front
+// of add_text and gtx_subset_text.  grouped: the strand-aware outputs (tri2 / w2) are made too when the rules are strand-aware.
+// *tp = the slot, *ticket its number; *empty: a block without lines -- nothing was enqueued but the slot's evParsed, its verdict is 0.
+int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, bool grouped, int scanRules,
+               unsigned long long *labelSum, bool sam, TextSlot **tp, int *ticket, bool *empty)
+{
+  HIPCHK(c, hipSetDevice(c->device));
+  const int slot = (int)(c->text.seq & 1);
+  TextSlot &t = c->text.slot[slot];
+  *ticket = slot; *tp = &t; *empty = false;
+  if (!t.evParsed) {
+    HIPCHK(c, hipEventCreateWithFlags(&t.evParsed, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&t.evConsumed, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&t.evCopied, hipEventDisableTiming));
+    HIPCHK(c, t.flag.alloc(1)); HIPCHK(c, t.hostFlag.alloc(1)); HIPCHK(c, t.seam.alloc(4096));
+    HIPCHK(c, t.sum.alloc(1)); HIPCHK(c, hipMemset(t.sum.get(), 0, sizeof(unsigned long long)));
+  }
+  if (t.busy) { HIPCHK(c, hipEventSynchronize(t.evConsumed)); t.busy = false; }          // the block before last has been counted: its buffers are free
+  c->text.seq++;
+  if (nLines == 0 || bytes == 0) { *t.hostFlag.get() = 0; HIPCHK(c, hipEventRecord(t.evParsed, c->stream)); *empty = true; return GTX_OK; }
+  const size_t nSeg = (bytes + 1023) / 1024;
+  if (bytes + 128 > t.text.cap) HIPCHK(c, t.text.alloc(bytes + (bytes >> 3) + 4096));              // (128 bytes beyond the block kept free)
+  if (nSeg + 4 > t.seg.cap) HIPCHK(c, t.seg.alloc(nSeg + (nSeg >> 3) + 16));
+  if ((size_t)nLines > t.w.cap) {
+    t.nl.reset(); t.tri.reset(); t.w.reset();
+    const size_t cap = (size_t)nLines + ((size_t)nLines >> 3) + 1024;
+    HIPCHK(c, t.nl.alloc(cap)); HIPCHK(c, t.tri.alloc(3 * cap)); HIPCHK(c, t.w.alloc(cap));
+  }
+  // the names' tables: per set of names (rebuilt when they change)
+  {
+    std::string blob; std::vector<int32_t> table; unsigned mask = 0;
+    size_t total = 0; for (int i = 0; i < r->n_chrom; i++) total += strlen(r->chrom_names[i]) + 1;
+    std::string key; key.reserve(total);
+    for (int i = 0; i < r->n_chrom; i++) { key += r->chrom_names[i]; key += '\n'; }
+    if (key != c->text.blob || !c->text.names) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      gtxtext::build_tables(*r, &table, &mask, &blob);
+      c->text.table.reset(); c->text.names.reset();
+      HIPCHK(c, c->text.table.alloc(table.size()));
+      HIPCHK(c, c->text.names.alloc(blob.size() + 4096 * 2 + 16));
+      HIPCHK(c, hipMemcpy(c->text.table.get(), table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice));
+      if (!blob.empty()) HIPCHK(c, hipMemcpy(c->text.names.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
+      c->text.mask = mask; c->text.blobLen = (unsigned)blob.size(); c->text.blob = key;
+    }
+  }
+  gtxtext::TextTables tabs; tabs.table = c->text.table.get(); tabs.tableMask = c->text.mask; tabs.names = c->text.names.get(); tabs.prevOff = 0; tabs.prevLen = 0;
+  if (r->have_prev && r->prev_chrom) {
+    const size_t len = strlen(r->prev_chrom);
+    if (len > 0 && len < 4096) {                                       // the seam's name behind the names, one place per slot
+      memcpy(t.seam.get(), r->prev_chrom, len);
+      tabs.prevOff = c->text.blobLen + (unsigned)slot * 4096; tabs.prevLen = (unsigned)len;
+      HIPCHK(c, hipMemcpyAsync(c->text.names.get() + tabs.prevOff, t.seam.get(), len, hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  // the text: page-locked memory is read where it is, anything else goes through a page-locked slot of the context
+  const char *src = text;
+  if (!is_pinned(text)) {
+    if (bytes > t.pin.cap) HIPCHK(c, t.pin.alloc(bytes + (bytes >> 3)));
+    parallel_copy(t.pin.get(), text, bytes, c->stage.copyThreads);
+    src = t.pin.get();
+  }
+  HIPCHK(c, hipMemcpyAsync(t.text.get(), src, bytes, hipMemcpyHostToDevice, c->stage.copyStream));
+  HIPCHK(c, hipEventRecord(t.evCopied, c->stage.copyStream));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, t.evCopied, 0));
+  HIPCHK(c, hipMemsetAsync(t.flag.get(), 0, sizeof(int), c->stream));
+  grouped = grouped && r->strand_aware;
+  if (grouped && (size_t)nLines > t.w2.cap) {
+    t.tri2.reset(); t.blk.reset(); t.w2.reset();
+    HIPCHK(c, t.tri2.alloc(3 * t.w.cap)); HIPCHK(c, t.blk.alloc(t.w.cap / 128 + 4)); HIPCHK(c, t.w2.alloc(t.w.cap));
+  }
+  gtxtext::TextDevice d; d.text = t.text.get(); d.segCount = t.seg.get(); d.nl = t.nl.get(); d.tri = t.tri.get(); d.w = t.w.get(); d.flag = t.flag.get();
+  d.tri2 = grouped ? t.tri2.get() : nullptr; d.w2 = grouped ? t.w2.get() : nullptr; d.blkMinus = grouped ? t.blk.get() : nullptr;
+  d.labelSum = labelSum; d.blockSum = t.sum.get();
+  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, scanRules, sam));
+  return GTX_OK;
+}
+
+static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, uint32_t flags, int *ticket)
+{
+  const bool coverage = mode == TEXT_COVER;
+  const char *who = mode == TEXT_SCAN ? "gtx_scan_add_text" : coverage ? "gtx_coverage_add_text" : "gtx_count_add_text";
+  if (mode == TEXT_SCAN ? !c->scan.cur.open : coverage ? !c->covOpen : !c->streamOpen) return fail(c, GTX_E_STATE, "gtx_*_add_text: no open count / coverage / scan call");
+  if (mode == TEXT_SCAN && r && (r->max_label_value > 1) != c->scan.cur.weighted) return fail(c, GTX_E_ARG, "gtx_scan_add_text: the rules' label weights do not match gtx_scan_begin's");
+  if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names))
+    { c->err = std::string(who) + ": bad argument"; return GTX_E_ARG; }
+  const bool sam = (flags & GTX_TEXT_SAM) != 0;                  // (the format of the text, not a flag of the count)
+  flags &= ~GTX_TEXT_SAM;
+  TextSlot *tp = nullptr; bool empty = false;
+  {
+    int rc = text_stage(c, text, bytes, nLines, r, true, mode == TEXT_SCAN ? (c->scan.cur.a.sortedRule ? 2 : 1) : 0,
+                        mode == TEXT_SCAN ? c->scan.cur.labelSum.get() : nullptr, sam, &tp, ticket, &empty);
+    if (rc || empty) return rc;
+  }
+  TextSlot &t = *tp;
+  const int *triOut = r->strand_aware ? t.tri2.get() : t.tri.get();
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  // ... and counted where the triples are
+  const int *dW = r->max_label_value > 1 ? (r->strand_aware ? t.w2.get() : t.w.get()) : nullptr;
+  const int64_t seen = c->streamSeen;
+  int rc = GTX_OK;
+  if (mode == TEXT_SCAN) {
+    // (a block of a sorted stream is in order: the general kernels aggregate runs of equal micro-windows; any other block: the partition path)
+    rc = scan_hist_any(c, triOut, dW, nLines, c->scan.cur.a, c->scan.cur.classLen.data(), (flags & GTX_READS_UNSORTED) != 0); if (rc) return rc;
+    HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+    t.busy = true;
+    return GTX_OK;
+  }
+  if (coverage) {
+    if (flags & GTX_GAPS_FORMULA) { rc = merge_prepare(c, flags, 2); if (rc) return rc; }
+    rc = cover_launch(c, triOut, dW, nLines, seen, flags, (flags & GTX_READS_UNSORTED) != 0 || !(flags & GTX_READS_SORTED)); if (rc) return rc;
+  } else {
+    rc = merge_prepare(c, flags, 0); if (rc) return rc;
+    const bool streaming = (flags & (GTX_READS_SORTED | GTX_CHECK_SORTED)) != 0;
+    if (!streaming) c->tileSumsValid = false;
+    if (streaming) HIPCHK(c, gtx::launch_count(triOut, dW, nLines, count_args(c, c->ix.hist, flags & ~GTX_CHECK_SORTED, nLines, seen), true, c->stream));
+    else { rc = launch_unsorted(c, triOut, dW, nLines, count_args(c, c->ix.hist, flags, nLines, seen)); if (rc) return rc; }
+    rc = pairs_batch(c, triOut, dW, nLines); if (rc) return rc;
+  }
+  rc = merge_batch(c, triOut, dW, nLines); if (rc) return rc;
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  c->streamSeen += nLines;
+  return GTX_OK;
+}
+
+extern "C" {
+int gtx_count_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket)
+{ return c ? add_text(c, TEXT_COUNT, text, bytes, n_lines, rules, flags, ticket) : GTX_E_ARG; }
+int gtx_coverage_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket)
+{ return c ? add_text(c, TEXT_COVER, text, bytes, n_lines, rules, flags, ticket) : GTX_E_ARG; }
+int gtx_scan_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket)
+{ return c ? add_text(c, TEXT_SCAN, text, bytes, n_lines, rules, flags, ticket) : GTX_E_ARG; }
+int gtx_text_result(gtx_ctx *c, int ticket, int *needs_host)
+{
+  if (!c || !needs_host || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_text_result: bad argument") : GTX_E_ARG;
+  TextSlot &t = c->text.slot[ticket];
+  if (!t.evParsed) return fail(c, GTX_E_STATE, "gtx_text_result: no such block");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(t.evParsed));
+  *needs_host = *t.hostFlag.get();
+  return GTX_OK;
+}
+
+// text -> triples in line order -> hits -> verbatim check -> select, scan, gather; everything enqueued, the verdict and the totals
+// on their way to the host behind it
+int gtx_subset_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, uint32_t flags, int *ticket)
+{
+  if (!c) return GTX_E_ARG;
+  if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_subset_text: gtx_set_refs has not been called");
+  if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names) ||
+      (flags & GTX_TEXT_SAM) || r->max_label_value > 1)
+    return fail(c, GTX_E_ARG, "gtx_subset_text: bad argument");
+  if (c->text.slot[c->text.seq & 1].subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_text: the result of the block before last has not been fetched (gtx_subset_result)");
+  const int mode = join_mode(c, flags);
+  { int rc = join_prepare(c); if (rc) return rc; }
+  TextSlot *tp = nullptr; bool empty = false;
+  { int rc = text_stage(c, text, bytes, nLines, r, false, 0, nullptr, false, &tp, ticket, &empty); if (rc) return rc; }
+  TextSlot &t = *tp;
+  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
+  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
+  t.subsetPending = true;
+  if (empty) return GTX_OK;
+  const size_t nTiles = gtxtext::subset_tiles((unsigned)nLines);
+  if ((size_t)nLines > t.hits.cap) HIPCHK(c, t.hits.alloc(t.w.cap));
+  if (2 * (nTiles + 1) > t.tile.cap) HIPCHK(c, t.tile.alloc(2 * (nTiles + 1) + (nTiles >> 2)));
+  if (bytes > t.out.cap) HIPCHK(c, t.out.alloc(t.text.cap));
+  const gtx::JoinQueries q{t.tri.get(), nullptr, nullptr, nLines};
+  if (!c->join.info) HIPCHK(c, c->join.info.alloc(1));
+  if ((size_t)nLines > c->join.off.cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, c->join.off.grow((size_t)nLines)); }   // (the block before may still be narrowing out of it)
+  HIPCHK(c, gtx::launch_join_count(q, c->rx.pairAll.ix, ref_blocks(c), mode & ~gtx::JOIN_CHECK, c->join.off.get(), c->join.info.get(), c->stream));
+  HIPCHK(c, gtx::launch_query_narrow(c->join.off.get(), nLines, t.hits.get(), c->stream));
+  HIPCHK(c, gtxtext::launch_verbatim(t.text.get(), t.nl.get(), (unsigned)nLines, t.flag.get(), c->stream));
+  const gtxtext::SubsetDevice d{t.text.get(), t.nl.get(), (unsigned)nLines, t.hits.get(), (flags & GTX_SUBSET_INVERT) ? 1 : 0, t.flag.get(), t.tile.get(), t.out.get()};
+  HIPCHK(c, gtxtext::launch_subset_gather(d, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], t.tile.get() + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], t.tile.get() + 2 * nTiles + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  return GTX_OK;
+}
+
+int gtx_subset_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t *out_bytes, int64_t *n_selected)
+{
+  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_subset_result: bad argument") : GTX_E_ARG;
+  TextSlot &t = c->text.slot[ticket];
+  if (!t.evParsed || !t.subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_result: no such block");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(t.evParsed));
+  t.subsetPending = false;
+  *needs_host = *t.hostFlag.get();
+  *out_bytes = 0;
+  if (n_selected) *n_selected = 0;
+  if (*needs_host) return GTX_OK;
+  const size_t n = (size_t)t.hostTotal.get()[0];
+  if (n > 0 && !out) return fail(c, GTX_E_ARG, "gtx_subset_result: bad argument");
+  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
+  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
+  *out_bytes = n;
+  if (n_selected) *n_selected = (int64_t)t.hostTotal.get()[1];
+  return GTX_OK;
+}
+}

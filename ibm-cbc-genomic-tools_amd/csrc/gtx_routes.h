@@ -1,5 +1,5 @@
 // gtx_routes.h -- which kernels a call takes: every shape rule of the count, coverage and scan paths as a pure function of the
-// shape and the knobs, with the constants they turn on.  Host only, no HIP: the library calls these (gtx_capi.hip, launch_finalize),
+// shape and the knobs, with the constants they turn on.  Host only, no HIP: the library calls these (gtx_capi.hip, gtx_api_scan.hip, launch_finalize),
 // and the CPU suite calls them at their thresholds through `gtx_packtool route`.
 #pragma once
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// gtx_text.h -- launch interface of the device-side BED / SAM tokenizer (gtx_text.hip), used by gtx_capi.hip
+// gtx_text.h -- launch interface of the device-side BED / SAM tokenizer (gtx_text.hip), used by gtx_api_text.hip and gtx_api_link.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -43,7 +43,7 @@ SRC = {
     "JOIN_LDS_SEG": ("gtx_join.h", r"constexpr int kJoinLdsSeg = (\d+);", (JOIN_LDS_SEG,)),
     "JOIN_SCAN_TILE": ("gtx_join.hip", r"constexpr int kScanThreads = (\d+), kScanItems = (\d+), kScanTile = kScanThreads \* kScanItems;",
                        (JOIN_SCAN_THREADS, JOIN_SCAN_TILE // JOIN_SCAN_THREADS)),
-    "JOIN_SCAN_N1": ("gtx_capi.hip", r"gtx::launch_join_scan\(d_off, q\.n \+ 1, ", ()),
+    "JOIN_SCAN_N1": ("gtx_api_join.hip", r"gtx::launch_join_scan\(d_off, q\.n \+ 1, ", ()),
     "OFF_SMALL_SEG": ("gtx_offset.h", r"constexpr int kOffSmallSeg = (\d+);", (OFF_SMALL_SEG,)),
     "SIGNAL_LDS_BINS": ("gtx_signal.h", r"constexpr int kSignalLdsBins = (\d+);", (SIGNAL_LDS_BINS,)),
     "SIGNAL_LDS_RULE": ("gtx_signal.hip", r"const bool lds = !a\.perRef && a\.nBins <= kSignalLdsBins;", ()),

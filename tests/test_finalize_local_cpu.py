@@ -22,7 +22,7 @@ LOCAL_SCAN_MAX_TILES = sp.LOCAL_SCAN_MAX_TILES     # local scan + gather up to t
 
 SRC = {
     "LOCAL_SCAN_MAX_TILES": ("gtx_routes.h", r"constexpr int kLocalScanMaxTiles = (\d+);", (LOCAL_SCAN_MAX_TILES,)),
-    "LOCAL_DEFAULT": ("gtx_capi.hip", r"int localMaxTiles = gtx::kLocalScanMaxTiles;", ()),
+    "LOCAL_DEFAULT": ("gtx_ctx.h", r"int localMaxTiles = gtx::kLocalScanMaxTiles;", ()),
     "LOCAL_KNOB": ("gtx_capi.hip", r'getenv\("GTX_LOCAL_SCAN_MAX_TILES"\)\) c->localMaxTiles = std::min\(std::max\(atoi\(lt\), 0\), gtx::kLocalScanMaxTiles\);', ()),
     "LOCAL_LDS": ("gtx_kernels.hip", r"kGatherLocalThreads, sizeof\(T\) \* 2 \* \(size_t\)nb, st>>>", ()),
 }

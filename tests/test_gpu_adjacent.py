@@ -268,6 +268,41 @@ def test_device_entries_on_torch_tensors_two_calls_and_one_sync(eng):
     eng.sync()
 
 
+def test_link_adjacent_and_gaps_infos_pending_under_one_sync(eng):
+    """one device call of each family enqueued, then one sync: every info reaches its own struct and every output is the packed loop's"""
+    import torch
+    import link_restate
+    a = sorted_regions(21, 2 * T + 5, 3, 30 * T)
+    ma = (a[:, 0] & 1).astype(np.uint8)
+    bounds = [30 * T + 100] * 3
+    want_l, want_a, want_g = link_restate.link_packed(a, 0), ar.adjacent_packed(a, ma, 2, 1), ar.gaps_packed(a, bounds)
+    n, ng = len(a), len(want_g[0])
+    da, dma = torch.from_numpy(a).cuda(), torch.from_numpy(ma).cuda()
+    ol = [torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(3)]
+    od = torch.zeros(n, dtype=torch.int64, device="cuda")
+    og = [torch.zeros(max(ng, 1), dtype=torch.int32, device="cuda") for _ in range(3)]
+    torch.cuda.synchronize()
+    il = eng.link_device(da.data_ptr(), n, ol[0].data_ptr(), ol[1].data_ptr(), ol[2].data_ptr(), None, None, 0, 0)
+    ia = eng.adjacent_device(da.data_ptr(), n, dma.data_ptr(), 2, 1, od.data_ptr())
+    ig = eng.gaps_device(da.data_ptr(), n, bounds, ng, *[t.data_ptr() for t in og])
+    eng.sync()
+    groups = len(want_l[0])
+    assert il.as_dict() == {"n_groups": groups, "first_unsorted": want_l[4]} and groups > 1 and want_l[4] == -1
+    assert ia.as_dict() == {"first_unsorted": want_a[1], "n_inclusions": want_a[2], "n_overlaps": want_a[3]}
+    assert ig.as_dict() == {"n_gaps": ng, "first_bad": want_g[3], "bad_kind": want_g[4]} and ng > T
+    np.testing.assert_array_equal(ol[0].cpu().numpy().view(np.uint32)[:groups], want_l[0])
+    np.testing.assert_array_equal(ol[1].cpu().numpy().view(np.uint32)[:groups], want_l[1])
+    np.testing.assert_array_equal(ol[2].cpu().numpy()[:groups], want_l[2])
+    np.testing.assert_array_equal(od.cpu().numpy(), want_a[0])
+    np.testing.assert_array_equal(og[0].cpu().numpy().view(np.uint32), want_g[0])
+    np.testing.assert_array_equal(og[1].cpu().numpy(), want_g[1])
+    np.testing.assert_array_equal(og[2].cpu().numpy(), want_g[2])
+    del il, ia, ig                                                               # dropped before the next sync: the binding keeps them alive
+    eng.link_device(da.data_ptr(), n, ol[0].data_ptr(), ol[1].data_ptr(), ol[2].data_ptr(), None, None, 0, 0)
+    eng.adjacent_device(da.data_ptr(), n)
+    eng.sync()
+
+
 def test_bad_arguments(eng):
     tri = sorted_regions(1, 10, 1, 100)
     for op1, op2 in ((4, 0), (0, 4), (-1, 0), (0, -1)):
