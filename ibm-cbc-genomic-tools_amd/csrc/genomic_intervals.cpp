@@ -590,6 +590,15 @@ static int g_ngpu = 0;                                   // 0 = not set: GTX_NGP
 
 void GtxSetDevices(int n) { g_ngpu = n; }
 
+bool GtxScanFilterOnDevice()
+{
+  const char *e = getenv("GTX_SCAN_FILTER_ON_DEVICE");      // 0: the per-window loop on the host
+  if (e && atoi(e) == 0) return false;
+  int n = g_ngpu;
+  if (n <= 0) { const char *g = getenv("GTX_NGPU"); n = g ? atoi(g) : 1; }
+  return n <= 1;
+}
+
 // Page-locked batch buffers for the bulk packer (gtxhost::BatchArena): two of them, filled in turn by DrainSet -- the packer
 // threads write the packed triples where the DMA engine reads them (gtx_host_alloc memory skips the library's staging copy, and
 // the call returns with the copy in flight: the contract of include/gtx.h is "untouched until the NEXT call has returned", which
@@ -1759,6 +1768,78 @@ done:
   if (halt_set && (cur_block >= n_windows.size() || cur_block > halt_block || (cur_block == halt_block && cur_win >= halt_win))) { fflush(out_file); RaiseHalt(); }
 }
 
+void GenomicRegionSetScanner::PrintFiltered(FILE *out_file, GenomicRegionSetIndex *index, long int min_value)
+{
+  if (!computed) Compute(false);
+  if (keep_slot < 0) { std::cerr << "Error: [GenomicRegionSetScanner] the windows were not kept on the device!\n"; exit(1); }
+  if (!keep_error.empty()) { std::cerr << "Error: " << keep_error << "\n"; exit(1); }
+  const int n_chrom = (int)chrom_names.size(), ns = ignore_strand ? 1 : 2;
+  const long long total = WindowCount();
+  // a sorted scanner's input error: the windows in front of where the walk meets it, then the error
+  const long long limit = halt_set ? std::min<long long>(total, block_offset[halt_block] + halt_win) : total;
+  const unsigned long long floor_value = min_value < 0 ? 0ull : (unsigned long long)min_value;
+  bool ended = false;                                              // at a value of -1 (PrintRemaining: a caller's loop takes it for the end)
+  if (total > 0 && limit > 0) {
+    gtx_ctx *one = gtx_group_ctx(Devices(), 0);
+    auto check = [&](int rc) { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(one)); exit(1); } };
+    void *d_windows = NULL; int64_t n_kept_windows = 0;
+    check(gtx_scan_kept(one, keep_slot, &d_windows, &n_kept_windows));
+    // the scan's classes (Compute: strand-major) over the blocks' offsets, and the index's regions in that numbering
+    std::vector<int32_t> class_len((size_t)(n_chrom * ns));
+    std::vector<int64_t> class_off((size_t)(n_chrom * ns));
+    for (int r = 0; r < n_chrom; r++)
+      for (int s = 0; s < ns; s++) {
+        class_len[(size_t)(s * n_chrom + r)] = (int32_t)std::max<long int>(0, (*bounds)[chrom_names[(size_t)r]]);
+        class_off[(size_t)(s * n_chrom + r)] = block_offset[(size_t)(r * ns + s)];
+      }
+    std::vector<int32_t> tri;
+    GenomicRegionSet *set = index->regSet;
+    for (long k = 0; k < set->n_regions; k++) {
+      GenomicInterval *i = set->R[k]->I.front();
+      if (i->STOP <= 0 || i->START > i->STOP || i->START >= INT_MAX) continue;   // never found (:5659), or behind every window
+      const size_t ci = (size_t)(std::lower_bound(chrom_names.begin(), chrom_names.end(), std::string(i->CHROMOSOME)) - chrom_names.begin());
+      if (ci >= chrom_names.size() || chrom_names[ci] != i->CHROMOSOME) continue;
+      tri.push_back((int32_t)(((!ignore_strand && i->STRAND == '-') ? n_chrom : 0) + (int)ci));
+      tri.push_back((int32_t)std::max<long int>(i->START, 1)); tri.push_back((int32_t)std::min<long int>(i->STOP, INT_MAX - 1));
+    }
+    check(gtx_window_refs(one, tri.data(), (int64_t)(tri.size() / 3), class_len.data(), class_off.data(), n_chrom * ns, (int32_t)win_step, (int32_t)win_size));
+    std::vector<long long> ordinals;
+    std::vector<unsigned long long> kept_values;
+    int64_t cap = std::max<int64_t>(1 << 16, total / 64), kept = 0;    // a retry with the reported count when this was too small
+    for (;;) {
+      ordinals.resize((size_t)cap); kept_values.resize((size_t)cap);
+      check(gtx_window_filter(one, d_windows, (int64_t)total, floor_value, cap, (int64_t *)ordinals.data(), (uint64_t *)kept_values.data(), &kept));
+      if (kept <= cap) break;
+      cap = kept;
+    }
+    std::vector<char> buf; buf.reserve(8u << 20);
+    auto put_num = [&](long long v) {
+      char tmp[24]; int n = 0;
+      unsigned long long u = (unsigned long long)v;
+      do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
+      while (n) buf.push_back(tmp[--n]);
+    };
+    size_t b = 0;
+    for (int64_t j = 0; j < kept; j++) {
+      const long long at = ordinals[(size_t)j];
+      if (at >= limit) break;
+      const unsigned long long v = kept_values[(size_t)j];
+      if (v == ~0ull) { ended = true; break; }
+      if ((long long)v < 0) continue;                                // (a caller's loop compares as long int)
+      while (b + 1 < block_offset.size() && block_offset[b + 1] <= at) b++;   // (empty blocks share an offset: the last one at or below holds it)
+      const long long k = at - block_offset[b];
+      const std::string &chrom = chrom_names[b / (size_t)ns];
+      put_num((long long)v); buf.push_back('\t');
+      buf.insert(buf.end(), chrom.begin(), chrom.end()); buf.push_back(' '); buf.push_back((b % (size_t)ns) ? '-' : '+'); buf.push_back(' ');
+      put_num(win_step * k + 1); buf.push_back(' '); put_num(win_step * k + win_size); buf.push_back('\n');
+      if (buf.size() > (7u << 20)) { fwrite(buf.data(), 1, buf.size(), out_file); buf.clear(); }
+    }
+    if (!buf.empty()) fwrite(buf.data(), 1, buf.size(), out_file);
+  }
+  cur_block = n_windows.size(); cur_win = 0;
+  if (halt_set && !ended) { fflush(out_file); RaiseHalt(); }
+}
+
 void GenomicRegionSetScanner::PrintInterval(FILE *out_file)
 {
   const int ns = ignore_strand ? 1 : 2;
@@ -1773,8 +1854,9 @@ GenomicInterval *GenomicRegionSetScanner::GetInterval()
                              win_step * (cur_win - 1) + win_size);
 }
 
-// reference filter of `genomic_scans counts -r`: windows are produced by the GPU scan as always; which of them
-// are reported is a host-side question per window (at most one rank query or one merge step each)
+// reference filter of `genomic_scans counts -r` through the reference's own iteration: windows are produced by the GPU scan as
+// always; which of them are reported is a host-side question per window (at most one rank query or one merge step each).
+// PrintFiltered answers the indexed form for all windows at once on the device.
 long int GenomicRegionSetScanner::Next(GenomicRegionSet *Ref)
 {
   if (Ref == NULL) return Next();

@@ -316,6 +316,12 @@ class GenomicRegionSetScanner
   // Next() / PrintInterval() loop prints (genomic_scans.cpp:421-428), formatted in bulk (three stdio calls per window are half a
   // second for the three million windows of a genome at -w 1000)
   void PrintRemaining(FILE *out_file, long int min_value);
+  // MI355X path: the same lines for the windows that overlap a region of `index` -- what a caller's Next(index) / PrintInterval()
+  // loop prints (genomic_scans.cpp:411-428) -- with the filter on the device (gtx_window_refs / gtx_window_filter): the scanner was
+  // made behind KeepNextOnDevice, its windows never come to the host, only the kept ones do.  The index's regions go to the device in
+  // the scan's class numbering (those on chromosomes the bounds do not name take no part).  A negative min_value counts as 0; a sorted
+  // scanner's input error is met where Next() meets it; a value of -1 ends the output as it ends a caller's loop.  One GPU only.
+  void PrintFiltered(FILE *out_file, GenomicRegionSetIndex *index, long int min_value);
   // MI355X path: the windows of the NEXT scanner that is constructed stay in slot `slot` (0..7) of the device context instead of
   // coming to the host (gtx_scan_end_keep) -- said before the constructor because the unsorted scanner scans in its constructor, as
   // the reference's does.  TotalLabelValue() works as before; Next() and PrintRemaining() have no values to hand out and end the
@@ -460,6 +466,7 @@ GenomicRegionSet *CreateGenomicRegionSetAnnotator(GenomicRegionSet *RefRegSet, S
 void GtxPrintAnnotations(GenomicRegionSet *TestRegSet, GenomicRegionSet *RefRegSet, GenomicRegionSet *UpstreamRefRegSet, const char *query_op,
                          bool ignore_strand, bool distance_flag, long int proximal_dist, bool print_header, const char *bin_bits);
 
+bool GtxScanFilterOnDevice();                                  // MI355X path: may `genomic_scans counts -r` filter on the device?  One GPU, and GTX_SCAN_FILTER_ON_DEVICE is not 0
 void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxAcceptSAM(bool on);                                      // false: a SAM file is "unsupported input format!" (drivers that print query lines; default true)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)

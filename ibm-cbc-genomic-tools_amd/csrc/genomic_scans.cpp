@@ -3,8 +3,9 @@
 // Sliding-window read counts over the chromosomes of a genome file; the histogram + window sums
 // run on the GPU behind the reference's GenomicRegionSetScanner classes.  `peaks` scans a signal and a control
 // read set the same way -- and, when given, a mappability track with the sorted scanner's operator 'p' -- and tests every
-// window on the host (tail probabilities: gtx_stats.h, GSL is not linked); the -r reference filter of `counts` is a
-// host-side test per reported window.
+// window on the host (tail probabilities: gtx_stats.h, GSL is not linked); the -r reference filter of `counts` runs on the
+// device over the kept window vector (one GPU; GTX_SCAN_FILTER_ON_DEVICE=0: the per-window loop on the host), with -Sref it is the
+// reference's merge with the sorted stream, one window at a time on the host.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -224,6 +225,9 @@ int main(int argc, char *argv[])
   char *INPUT_REG_FILE = next_arg == argc ? NULL : argv[next_arg];
   StringLIntMap *bounds = ReadBounds((char *)GENOME_REG_FILE, false);
   GenomicRegionSet InputRegSet(INPUT_REG_FILE, BUFFER_SIZE, VERBOSE, false, true);
+  // -r without -Sref: the windows stay in HBM and the filter runs there (PrintFiltered)
+  const bool device_filter = strlen(REF_REG_FILE) > 0 && !REF_SORTED && PREPROCESS != 'p' && GtxScanFilterOnDevice();
+  if (device_filter) GenomicRegionSetScanner::KeepNextOnDevice(0);
   GenomicRegionSetScanner *scanner;
   if (SORTED) scanner = new SortedGenomicRegionSetScanner(&InputRegSet, bounds, WIN_DIST, WIN_SIZE, MAX_LABEL_VALUE, IGNORE_STRAND, PREPROCESS);
   else scanner = new UnsortedGenomicRegionSetScanner(&InputRegSet, bounds, WIN_DIST, WIN_SIZE, MAX_LABEL_VALUE, IGNORE_STRAND, PREPROCESS);
@@ -238,6 +242,7 @@ int main(int argc, char *argv[])
     }
   }
   if (RefRegSet == NULL) scanner->PrintRemaining(stdout, (long int)MIN_READS);   // (no -r filter: the same lines, formatted in bulk)
+  else if (device_filter) scanner->PrintFiltered(stdout, RefIndex, (long int)MIN_READS);
   else
   for (long int v = REF_SORTED ? scanner->Next(RefRegSet) : scanner->Next(RefIndex); v != -1; v = REF_SORTED ? scanner->Next(RefRegSet) : scanner->Next(RefIndex)) {
     if (v >= MIN_READS) {

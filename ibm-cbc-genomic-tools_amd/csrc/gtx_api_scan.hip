@@ -1,6 +1,6 @@
 // gtx_api_scan.hip -- the C ABI's scans: gtx_scan* over reads on the device, in host buffers or fed as a stream, the window vectors
-// kept in HBM, and the window selection over them.  Host code only (the kernels: gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip,
-// gtx_select.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
+// kept in HBM, and the window selection and the window filter over them.  Host code only (the kernels: gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip,
+// gtx_select.hip, gtx_filter.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -11,6 +11,7 @@
 #include "gtx.h"
 #include "gtx_kernels.h"
 #include "gtx_select.h"
+#include "gtx_filter.h"
 #include "gtx_internal.h"
 #include "gtx_ctx.h"
 
@@ -455,6 +456,107 @@ int gtx_window_select(gtx_ctx *c, const void *const *d_tested, const void *const
   if (got) {
     HIPCHK(c, hipMemcpy(ordinals, c->sel.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(rows, c->sel.rows.get(), got * cols * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return GTX_OK;
+}
+
+// ---- window filter (gtx_filter.hip) ----
+static_assert(GTX_FILTER_TILE == gtx::kFilterTile, "include/gtx.h names the filter's tile");
+
+int gtx_window_refs(gtx_ctx *c, const int32_t *refs, int64_t n_refs, const int32_t *classLen, const int64_t *classOff, int32_t nClasses, int32_t step,
+                    int32_t size)
+{
+  if (!c) return GTX_E_ARG;
+  FilterState &f = c->flt;
+  f.set = false;
+  if (n_refs < 0 || n_refs >= (int64_t)INT32_MAX - 64 || (n_refs > 0 && !refs)) return fail(c, GTX_E_ARG, "gtx_window_refs: bad argument (n_refs < 2^31 - 64)");
+  if (nClasses < 1 || nClasses >= INT32_MAX - 1 || !classLen || !classOff) return fail(c, GTX_E_ARG, "gtx_window_refs: bad class table");
+  if (step <= 0 || size <= 0 || size % step) return fail(c, GTX_E_ARG, "gtx_window_refs: window size must be a positive multiple of window step");
+  // the classes that have windows, in the order of their offsets
+  struct Blk { int64_t off, end; int cls; };
+  std::vector<Blk> blk;
+  for (int i = 0; i < nClasses; i++) {
+    const int64_t nw = gtx_scan_n_windows(classLen[i] < 0 ? 0 : classLen[i], step, size);
+    if (nw == 0) continue;
+    if (classOff[i] < 0 || classOff[i] > INT64_MAX - nw) return fail(c, GTX_E_ARG, "gtx_window_refs: bad class offset");
+    blk.push_back({classOff[i], classOff[i] + nw, i});
+  }
+  std::sort(blk.begin(), blk.end(), [](const Blk &a, const Blk &b) { return a.off < b.off; });
+  for (size_t k = 1; k < blk.size(); k++) if (blk[k].off < blk[k - 1].end) return fail(c, GTX_E_ARG, "gtx_window_refs: two classes share window ordinals");
+  std::vector<long long> off(blk.size() + 1, 0), end(blk.size() + 1, 0);
+  std::vector<int> cls(blk.size() + 1, 0);
+  for (size_t k = 0; k < blk.size(); k++) { off[k] = blk[k].off; end[k] = blk[k].end; cls[k] = blk[k].cls; }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));                          // a pass may still be reading what the buffers held
+  HIPCHK(c, upload(f.blkOff, off.data(), off.size())); HIPCHK(c, upload(f.blkEnd, end.data(), end.size())); HIPCHK(c, upload(f.blkCls, cls.data(), cls.size()));
+  HIPCHK(c, f.first.reserve((size_t)nClasses + 2));
+  HIPCHK(c, f.start.grow((size_t)n_refs)); HIPCHK(c, f.runmax.grow((size_t)n_refs));
+  if (n_refs == 0) HIPCHK(c, hipMemsetAsync(f.first.get(), 0, ((size_t)nClasses + 2) * sizeof(int), c->stream));
+  else {
+    const size_t n3 = 3 * (size_t)n_refs;
+    HIPCHK(c, f.tri.reserve(n3)); HIPCHK(c, f.keyed.reserve(n3)); HIPCHK(c, f.sorted.reserve(n3)); HIPCHK(c, f.order.reserve((size_t)n_refs));
+    if (!f.bad) HIPCHK(c, f.bad.alloc(1));
+    // (the triples are pageable host memory: the copy returns when the source has been read)
+    HIPCHK(c, hipMemcpyAsync(f.tri.get(), refs, n3 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(f.bad.get(), 0, sizeof(unsigned), c->stream));
+    HIPCHK(c, gtx::launch_filter_prepare(f.tri.get(), n_refs, nClasses, f.keyed.get(), f.bad.get(), c->stream));
+    int rc = gtx_sort_device(c, f.keyed.get(), n_refs, nClasses + 1, f.order.get(), f.sorted.get()); if (rc) return rc;
+    HIPCHK(c, gtx::launch_filter_index(f.sorted.get(), n_refs, nClasses, f.first.get(), f.start.get(), f.runmax.get(), c->stream));
+    unsigned bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, f.bad.get(), sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, GTX_E_RANGE, "gtx_window_refs: a class id outside [0, n_classes)");
+  }
+  f.nClasses = nClasses; f.nBlk = (int)blk.size(); f.step = step; f.size = size; f.extent = blk.empty() ? 0 : blk.back().end;
+  f.set = true;
+  return GTX_OK;
+}
+
+int gtx_window_filter_device(gtx_ctx *c, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t capacity, void *d_ordinals, void *d_values,
+                             int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  FilterState &f = c->flt;
+  if (!f.set) return fail(c, GTX_E_STATE, "gtx_window_filter: gtx_window_refs has not been called");
+  if (n_windows < 0 || capacity < 0 || !n_kept) return fail(c, GTX_E_ARG, "gtx_window_filter: bad window count or capacity, or no n_kept");
+  if (n_windows > 0 && (!d_windows || ((uintptr_t)d_windows & 15))) return fail(c, GTX_E_ARG, "gtx_window_filter: the vector must be 16-byte aligned device memory");
+  if (capacity > 0 && (!d_ordinals || !d_values)) return fail(c, GTX_E_ARG, "gtx_window_filter: null output");
+  if (f.extent > n_windows) return fail(c, GTX_E_ARG, "gtx_window_filter: a class of the prepared geometry reaches beyond n_windows");
+  *n_kept = 0;
+  if (n_windows == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int64_t nt = gtx::filter_tiles(n_windows);
+  if (!f.total) HIPCHK(c, f.total.alloc(1));
+  if ((size_t)nt > f.count.cap || (size_t)nt + 1 > f.base.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, f.count.reserve((size_t)nt)); HIPCHK(c, f.base.reserve((size_t)nt + 1));
+  }
+  gtx::FilterRefs r = {f.start.get(), f.runmax.get(), f.first.get(), f.blkOff.get(), f.blkEnd.get(), f.blkCls.get(), f.nBlk, f.step, f.size};
+  HIPCHK(c, gtx::launch_window_filter(r, (const u64 *)d_windows, n_windows, min_value, f.count.get(), f.base.get(), capacity, (long long *)d_ordinals,
+                                      (u64 *)d_values, c->stream));
+  HIPCHK(c, hipMemcpyAsync(f.total.get(), f.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_kept = *f.total.get();
+  return GTX_OK;
+}
+
+int gtx_window_filter(gtx_ctx *c, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t capacity, int64_t *ordinals, uint64_t *values,
+                      int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  FilterState &f = c->flt;
+  if (!f.set) return fail(c, GTX_E_STATE, "gtx_window_filter: gtx_window_refs has not been called");
+  if (capacity < 0 || (capacity > 0 && (!ordinals || !values))) return fail(c, GTX_E_ARG, "gtx_window_filter: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((size_t)capacity > f.ord.cap || (size_t)capacity > f.val.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, f.ord.reserve((size_t)capacity)); HIPCHK(c, f.val.reserve((size_t)capacity));
+  }
+  int rc = gtx_window_filter_device(c, d_windows, n_windows, min_value, capacity, f.ord.get(), f.val.get(), n_kept); if (rc) return rc;
+  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
+  if (got) {
+    HIPCHK(c, hipMemcpy(ordinals, f.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(values, f.val.get(), got * sizeof(u64), hipMemcpyDeviceToHost));
   }
   return GTX_OK;
 }

@@ -216,6 +216,15 @@ struct ScanState {
 // the window selection's tile counts and bases, its tables, the total on the host, the host entry's results
 struct SelectState { DevBuf<unsigned> count; DevBuf<long long> base, ord; DevBuf<int> tab, rows; PinBuf<long long> total; };
 
+// the window filter: the region set gtx_window_refs prepared (its triples as given, keyed and sorted; starts, running maxima of the
+// stops, the classes' first regions; the classes that have windows in offset order) with the geometry it was prepared for, the
+// passes' tile counts and bases, the total on the host, the host entry's results
+struct FilterState {
+  bool set = false; int nClasses = 0, nBlk = 0, step = 0, size = 0; int64_t extent = 0;
+  DevBuf<int> tri, keyed, sorted, start, runmax, first, blkCls; DevBuf<unsigned> order, bad; DevBuf<long long> blkOff, blkEnd;
+  DevBuf<unsigned> count; DevBuf<long long> base, ord; DevBuf<u64> val; PinBuf<long long> total;
+};
+
 // link: the scans' per-tile values and break bit map, the info block and its page-locked copy (handed to the caller's struct by
 // gtx_sync after a device call), the host entry's inputs and group records
 struct LinkState {
@@ -322,6 +331,7 @@ struct gtx_ctx {
   SignalState sig;
   ScanState scan;
   SelectState sel;
+  FilterState flt;
   TextState text;
   LinkState link;
   NeighbourState nbr;

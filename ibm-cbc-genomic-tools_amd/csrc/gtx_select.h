@@ -39,4 +39,8 @@ inline bool select_tables_in_lds(int nTested, int W, bool controls) { return (lo
 hipError_t launch_window_select(const SelectArgs &a, unsigned *tileCount, long long *tileBase, long long capacity, long long *ordinals, int *rows,
                                 hipStream_t st);
 
+// the passes' middle step on its own (the window filter, gtx_filter.hip, is of the same shape): base [tiles + 1] = the exclusive sums of
+// count [tiles], base[tiles] their total
+hipError_t launch_tile_prefix(const unsigned *tileCount, long long tiles, long long *tileBase, hipStream_t st);
+
 }  // namespace gtx

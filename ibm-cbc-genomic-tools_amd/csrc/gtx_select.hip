@@ -139,6 +139,12 @@ void launch_tested(const SelectArgs &a, bool ctl, bool lds, i64 nt, unsigned *ti
 
 }  // namespace
 
+hipError_t launch_tile_prefix(const unsigned *tileCount, long long tiles, long long *tileBase, hipStream_t st)
+{
+  hipLaunchKernelGGL(select_prefix_kernel, dim3(1), dim3(kPartThreads), 0, st, tileCount, tiles, tileBase);
+  return hipGetLastError();
+}
+
 hipError_t launch_window_select(const SelectArgs &a, unsigned *tileCount, long long *tileBase, long long capacity, long long *ordinals, int *rows,
                                 hipStream_t st)
 {

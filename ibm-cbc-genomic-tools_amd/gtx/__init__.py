@@ -30,6 +30,7 @@ LINK_TILE = 2048          # GTX_LINK_TILE: regions per block of link's scans
 ADJACENT_TILE = 2048      # GTX_ADJACENT_TILE: regions per block of the neighbour passes
 POINTS = {"1": 0, "2": 1, "5p": 2, "3p": 3}   # GTX_POINT_*: gdist's reference points
 SCAN_KEEP_SLOTS = 8       # GTX_SCAN_KEEP_SLOTS: window vectors a context keeps in HBM
+FILTER_TILE = 1024        # GTX_FILTER_TILE: windows per tile of the window filter's passes
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 ANNOTATE_CENTER = 1
 ANNOTATE_START = 2
@@ -145,6 +146,12 @@ ABI = {
                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_window_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_window_refs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32]),
+    "gtx_window_filter_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_window_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_link": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
@@ -832,6 +839,42 @@ class Engine:
             cap = int(kept.value)
         got = min(int(kept.value), cap)
         return ordinals[:got], rows[:got], int(kept.value)
+
+    def window_refs(self, refs, class_len, class_offsets, win_step, win_size):
+        """gtx_window_refs: prepares the regions `refs` ((n, 3) of class, start, stop; any order) on the device for window vectors
+        of this geometry (class c at class_offsets[c]): what window_filter tests against until the next call."""
+        refs = _triples(np.asarray(refs).reshape(-1, 3))
+        cl = np.ascontiguousarray(class_len, dtype=np.int32)
+        off = np.ascontiguousarray(class_offsets, dtype=np.int64)
+        if len(off) != len(cl):
+            raise ValueError("one offset per class")
+        self._chk(self.lib.gtx_window_refs(self.ctx, _ptr(refs) if len(refs) else None, len(refs), _ptr(cl), _ptr(off), len(cl), int(win_step), int(win_size)))
+
+    def window_filter(self, windows, min_value=0, n_windows=None, capacity=None, device_out=None):
+        """gtx_window_filter over a window vector in HBM: a kept slot (small int, n_windows taken from the slot) or a raw device
+        address (n_windows required).  Returns (ordinals int64, values uint64, number kept): the windows with a value >= min_value
+        that overlap a region of window_refs, in vector order; when the number kept exceeds `capacity` only the first `capacity`
+        are returned.  capacity=None grows and repeats the call until everything fits.  device_out=(d_ordinals, d_values):
+        gtx_window_filter_device into the caller's device buffers (capacity required), returns the number kept."""
+        if isinstance(windows, (int, np.integer)) and 0 <= int(windows) < SCAN_KEEP_SLOTS:
+            addr, n = self.scan_kept(int(windows))
+            n_windows = n if n_windows is None else n_windows
+        else:
+            addr = int(windows)
+        kept = ctypes.c_int64(0)
+        if device_out is not None:
+            self._chk(self.lib.gtx_window_filter_device(self.ctx, _ptr(addr), int(n_windows), int(min_value), int(capacity), _ptr(device_out[0]),
+                                                        _ptr(device_out[1]), ctypes.byref(kept)))
+            return int(kept.value)
+        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
+        while True:
+            ordinals, values = np.full(max(cap, 1), -1, dtype=np.int64), np.zeros(max(cap, 1), dtype=np.uint64)
+            self._chk(self.lib.gtx_window_filter(self.ctx, _ptr(addr), int(n_windows), int(min_value), cap, _ptr(ordinals), _ptr(values), ctypes.byref(kept)))
+            if capacity is not None or kept.value <= cap:
+                break
+            cap = int(kept.value)
+        got = min(int(kept.value), cap)
+        return ordinals[:got], values[:got], int(kept.value)
 
     def scan_device(self, d_reads, n_reads, class_len, win_step, win_size, d_out, preprocess="1", d_weights=None, flags=0):
         cl = np.ascontiguousarray(class_len, dtype=np.int32)

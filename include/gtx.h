@@ -716,6 +716,30 @@ int gtx_window_select_device(gtx_ctx *ctx, const void *const *d_tested, const vo
 int gtx_window_select(gtx_ctx *ctx, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows,
                       int32_t window_size, const int32_t *const *kcrit, int64_t capacity, int64_t *ordinals, int32_t *rows, int64_t *n_kept);
 
+/* Window filter: the -r filter of `genomic_scans counts` over a window vector in HBM -- GenomicRegionSetIndex::GetOverlap(&w, false,
+ * ignore_strand) (genomic_intervals.cpp:5489-5540) for single-interval regions, asked of every window at once.  gtx_window_refs
+ * prepares a region set on the device for one scan geometry: ref_triples (host memory, any order, duplicates allowed) are n_refs x
+ * (class, start, stop); a region takes part when stop >= 1 and start <= stop, a start below 1 counts as 1; a class id outside
+ * [0, n_classes) is GTX_E_RANGE.  class_len, class_offsets, win_step and win_size mean what they mean in gtx_scan: class c has
+ * gtx_scan_n_windows(class_len[c], win_step, win_size) windows at class_offsets[c] (offsets in any order; classes that share ordinals, a
+ * negative offset and n_refs >= 2^31 - 64 are GTX_E_ARG), window k of it is [win_step k + 1, win_step k + win_size].  n_refs = 0 is a
+ * valid set that keeps nothing.  What an earlier call prepared is replaced.
+ * gtx_window_filter_device: d_windows is a device vector of n_windows uint64 sums, 16-byte aligned (kept slots are).  A window is kept
+ * when its value is >= min_value and a region of its class has start <= the window's stop and stop >= the window's start; ordinals
+ * that belong to no class are never kept.  The kept windows come out in vector order: ordinals (int64[capacity]) and values
+ * (uint64[capacity]).  *n_kept is the number of kept windows whatever the capacity; when it exceeds capacity only the first `capacity`
+ * windows have been written and nothing behind them: grow the buffers and call again (the policy of gtx_window_select).  Before
+ * gtx_window_refs: GTX_E_STATE; an unaligned vector, a null output with capacity > 0 or a class that reaches beyond n_windows:
+ * GTX_E_ARG.  n_windows = 0 is valid.  The call returns when the result is complete; gtx_window_filter brings it to host memory.
+ * Three launches over tiles of GTX_FILTER_TILE windows (count, prefix, emit); a tile no region reaches is not loaded. */
+#define GTX_FILTER_TILE 1024
+int gtx_window_refs(gtx_ctx *ctx, const int32_t *ref_triples, int64_t n_refs, const int32_t *class_len, const int64_t *class_offsets,
+                    int32_t n_classes, int32_t win_step, int32_t win_size);
+int gtx_window_filter_device(gtx_ctx *ctx, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t capacity, void *d_ordinals,
+                             void *d_values, int64_t *n_kept);
+int gtx_window_filter(gtx_ctx *ctx, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t capacity, int64_t *ordinals,
+                      uint64_t *values, int64_t *n_kept);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* on = 1: every *_device call brackets its dominant kernel and the whole call with HIP events on the
