@@ -590,14 +590,17 @@ static int g_ngpu = 0;                                   // 0 = not set: GTX_NGP
 
 void GtxSetDevices(int n) { g_ngpu = n; }
 
-bool GtxScanFilterOnDevice()
+// one GPU, and the environment variable `off_switch` is not 0 (0: the per-window loop on the host)
+static bool OneGpuAndNotOff(const char *off_switch)
 {
-  const char *e = getenv("GTX_SCAN_FILTER_ON_DEVICE");      // 0: the per-window loop on the host
+  const char *e = getenv(off_switch);
   if (e && atoi(e) == 0) return false;
   int n = g_ngpu;
   if (n <= 0) { const char *g = getenv("GTX_NGPU"); n = g ? atoi(g) : 1; }
   return n <= 1;
 }
+bool GtxScanFilterOnDevice() { return OneGpuAndNotOff("GTX_SCAN_FILTER_ON_DEVICE"); }
+bool GtxPeaksOnDevice() { return OneGpuAndNotOff("GTX_PEAKS_ON_DEVICE"); }
 
 // Page-locked batch buffers for the bulk packer (gtxhost::BatchArena): two of them, filled in turn by DrainSet -- the packer
 // threads write the packed triples where the DMA engine reads them (gtx_host_alloc memory skips the library's staging copy, and
@@ -1612,9 +1615,11 @@ void GenomicRegionSetScanner::ComputeMappable(const std::vector<int32_t> &class_
     auto check = [&](int rc) { if (rc != GTX_OK) { fflush(stdout); fprintf(stderr, "\nError: [gtx %d] %s\n", rc, gtx_last_error(one)); exit(1); } };
     check(gtx_scan_begin(one, class_len.data(), n_chrom * ns, (int32_t)win_step, (int32_t)win_size, '1', GTX_ZERO_LENGTH_OK, 1, class_off.data()));
     if (n) check(gtx_scan_add(one, tri.data(), w.data(), n, order));
-    check(gtx_scan_end(one, (uint64_t *)values.data(), NULL));
+    if (keep_slot >= 0) check(gtx_scan_end_keep(one, keep_slot, NULL));
+    else check(gtx_scan_end(one, (uint64_t *)values.data(), NULL));
     return;
   }
+  if (keep_slot >= 0) { keep_error = "windows are kept on the device on one GPU only!"; return; }
   CheckGrp(grp, gtx_group_scan(grp, tri.data(), w.data(), n, class_len.data(), n_chrom * ns, (int32_t)win_step, (int32_t)win_size, '1',
                                GTX_ZERO_LENGTH_OK | (order ? 0u : GTX_READS_SORTED), (uint64_t *)values.data(), class_off.data()));
 }
@@ -1623,6 +1628,22 @@ void GenomicRegionSetScanner::KeepNextOnDevice(int slot)
 {
   if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) { std::cerr << "Error: [GenomicRegionSetScanner] no such device slot!\n"; exit(1); }
   g_keep_next = slot;
+}
+
+void GenomicRegionSetScanner::BringKeptToHost()
+{
+  if (!computed) Compute(false);
+  if (keep_slot < 0) return;
+  if (!keep_error.empty()) { std::cerr << "Error: " << keep_error << "\n"; exit(1); }
+  const long long total = WindowCount();
+  if (total > 0) {
+    gtx_ctx *one = gtx_group_ctx(Devices(), 0);
+    values.assign((size_t)total, 0);
+    if (gtx_scan_kept_read(one, keep_slot, (uint64_t *)values.data()) != GTX_OK || gtx_scan_drop(one, keep_slot) != GTX_OK) {   // (the slot's HBM is free again)
+      fflush(stdout); fprintf(stderr, "\nError: [gtx] %s\n", gtx_last_error(one)); exit(1);
+    }
+  }
+  keep_slot = -1;
 }
 
 long long GenomicRegionSetScanner::WindowCount()
@@ -1677,6 +1698,42 @@ bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_co
     cap = kept;
   }
   ordinals.resize((size_t)kept); rows.resize((size_t)kept * cols);
+  return true;
+}
+
+bool GtxSelectPeakWindows(GenomicRegionSetScanner *signal, GenomicRegionSetScanner *control, GenomicRegionSetScanner *uniq, long int win_size, long int min_reads,
+                          bool norm, double p_ratio, std::vector<long long> &ordinals, std::vector<long long> &rows, std::string *error)
+{
+  ordinals.clear(); rows.clear();
+  if (signal == NULL || control == NULL || win_size < 1) { *error = "[GtxSelectPeakWindows] a signal, a control and a positive window size!"; return false; }
+  gtx_group *grp = Devices();
+  if (gtx_group_size(grp) != 1) { *error = "this operation runs on one GPU only!"; return false; }
+  gtx_ctx *one = gtx_group_ctx(grp, 0);
+  GenomicRegionSetScanner *scanners[3] = {signal, control, uniq};
+  const void *d_vec[3] = {};
+  long long n = -1;
+  for (int f = 0; f < 3; f++) {
+    if (scanners[f] == NULL) continue;
+    const long long nf = scanners[f]->WindowCount();
+    if (!scanners[f]->KeepError().empty()) { *error = scanners[f]->KeepError(); return false; }
+    void *d = NULL; int64_t kept = 0;                                // (bounds without a window: nothing was scanned, nothing is selected)
+    if (nf > 0 && (scanners[f]->KeptSlot() < 0 || gtx_scan_kept(one, scanners[f]->KeptSlot(), &d, &kept) != GTX_OK || (long long)kept != nf)) {
+      *error = "[GtxSelectPeakWindows] an input's windows are not on the device!"; return false;
+    }
+    if (n >= 0 && nf != n) { *error = "[GtxSelectPeakWindows] the inputs differ in their number of windows!"; return false; }
+    n = nf; d_vec[f] = d;
+  }
+  if (n == 0) return true;
+  int64_t cap = std::max<int64_t>(1 << 16, n / 64), kept = 0;        // a retry with the reported count when this was too small
+  for (;;) {
+    ordinals.resize((size_t)cap); rows.resize((size_t)cap * 3);
+    const int rc = gtx_peak_select(one, d_vec[0], d_vec[1], d_vec[2], n, win_size, min_reads, norm ? 1 : 0, p_ratio, cap, (int64_t *)ordinals.data(),
+                                   (int64_t *)rows.data(), &kept);
+    if (rc != GTX_OK) { *error = std::string("[gtx] ") + gtx_last_error(one); return false; }
+    if (kept <= cap) break;
+    cap = kept;
+  }
+  ordinals.resize((size_t)kept); rows.resize((size_t)kept * 3);
   return true;
 }
 

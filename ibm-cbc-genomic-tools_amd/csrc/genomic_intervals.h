@@ -325,9 +325,12 @@ class GenomicRegionSetScanner
   // MI355X path: the windows of the NEXT scanner that is constructed stay in slot `slot` (0..7) of the device context instead of
   // coming to the host (gtx_scan_end_keep) -- said before the constructor because the unsorted scanner scans in its constructor, as
   // the reference's does.  TotalLabelValue() works as before; Next() and PrintRemaining() have no values to hand out and end the
-  // run; the windows are read through GtxSelectWindows.  One GPU only (KeepError() says so otherwise).
+  // run; the windows are read through GtxSelectWindows, GtxSelectPeakWindows or PrintFiltered.  One GPU only (KeepError() says so otherwise).
   static void KeepNextOnDevice(int slot);
   int KeptSlot() const { return keep_slot; }
+  // ... and back: the kept windows come to the host after all (gtx_scan_kept_read; the slot is dropped) and Next() hands them out as if they had never been
+  // kept -- for the caller that learns only after the scans (an input error waiting in one of them) that it has to walk the windows
+  void BringKeptToHost();
   long long WindowCount();                                        // windows of all blocks together (computes)
   const std::string &KeepError() const { return keep_error; }
   // "chr strand start stop" of the window with this ordinal in iteration order (0-based over all blocks): what PrintInterval()
@@ -442,6 +445,14 @@ unsigned long int GtxSignalBins(GenomicRegionSetOverlaps *overlaps, const GtxSig
 bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_control, const std::vector<std::vector<int> > &tables, long int win_size,
                       std::vector<long long> &ordinals, std::vector<int> &rows, std::string *error);
 
+// The head of the per-window loop of genomic_scans peaks (PeakFinder, gtools/genomic_scans.cpp:304-311) on the device: signal, control and
+// uniq (the mappability track; may be NULL) are scanners made behind KeepNextOnDevice with slots of their own over the same bounds and
+// geometry.  Returns the ordinals of the windows with v1 >= min_reads in window order and per kept window v1, v2, v0 after clamp and
+// norm (gtx_peak_select; the result buffers grow and the call is repeated when they were too small).  False with *error set when the
+// scanners cannot be selected over (more than one GPU, unequal window counts, windows not on the device).
+bool GtxSelectPeakWindows(GenomicRegionSetScanner *signal, GenomicRegionSetScanner *control, GenomicRegionSetScanner *uniq, long int win_size, long int min_reads,
+                          bool norm, double p_ratio, std::vector<long long> &ordinals, std::vector<long long> &rows, std::string *error);
+
 // genomic_intervals.h:2815, .cpp:6218-6297: the upstream regions of a gene set, one per region of RefRegSet (single-interval regions
 // only: anything else is that region's error), labelled "upstream:LABEL" on the gene's chromosome and strand -- on '+'
 // [max(start - max, 1), max(start - 1, 1)], otherwise [stop + 1, stop + max], the stop clamped to (*bounds)[chromosome] when bounds
@@ -467,7 +478,8 @@ void GtxPrintAnnotations(GenomicRegionSet *TestRegSet, GenomicRegionSet *RefRegS
                          bool ignore_strand, bool distance_flag, long int proximal_dist, bool print_header, const char *bin_bits);
 
 bool GtxScanFilterOnDevice();                                  // MI355X path: may `genomic_scans counts -r` filter on the device?  One GPU, and GTX_SCAN_FILTER_ON_DEVICE is not 0
-void GtxSetDevices(int n_gpus);                                // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
+bool GtxPeaksOnDevice();                                       // MI355X path: may `genomic_scans peaks` select its candidate windows on the device?  One GPU, and GTX_PEAKS_ON_DEVICE is not 0
+void GtxSetDevices(int n_gpus);                               // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxAcceptSAM(bool on);                                      // false: a SAM file is "unsupported input format!" (drivers that print query lines; default true)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)
 void GtxFinish(int code);                                        // flush and leave without the teardown (see genomic_intervals.cpp)

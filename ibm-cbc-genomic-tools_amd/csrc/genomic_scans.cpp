@@ -2,8 +2,10 @@
 // (reference driver: gtools/genomic_scans.cpp:73-150 options, :399-436 RunCounts, :209-380 PeakFinder, :449-470).
 // Sliding-window read counts over the chromosomes of a genome file; the histogram + window sums
 // run on the GPU behind the reference's GenomicRegionSetScanner classes.  `peaks` scans a signal and a control
-// read set the same way -- and, when given, a mappability track with the sorted scanner's operator 'p' -- and tests every
-// window on the host (tail probabilities: gtx_stats.h, GSL is not linked); the -r reference filter of `counts` runs on the
+// read set the same way -- and, when given, a mappability track with the sorted scanner's operator 'p' --, selects the windows that
+// pass the clamp, -norm and -min on the device over the kept scans (one GPU, with a control; GTX_PEAKS_ON_DEVICE=0, no control or an input
+// error waiting in a sorted scan: the per-window loop on the host) and tests those on the host (tail probabilities: gtx_stats.h, GSL is
+// not linked); the -r reference filter of `counts` runs on the
 // device over the kept window vector (one GPU; GTX_SCAN_FILTER_ON_DEVICE=0: the per-window loop on the host), with -Sref it is the
 // reference's merge with the sorted stream, one window at a time on the host.
 #include <stdio.h>
@@ -13,6 +15,7 @@
 #include <time.h>
 #include <unistd.h>
 #include <algorithm>
+#include <cmath>
 #include <list>
 #include <random>
 #include <string>
@@ -61,6 +64,51 @@ static double ComputeQValues(const std::vector<double> &pval, const std::vector<
   return -1.0;
 }
 
+// the two tail probabilities of a window that passed -min (genomic_scans.cpp:312-345): the signal against the control, and the control
+// against the signal for the q-values.  v1, v2, v0: the signal's, the control's and the mappability track's counts after clamp and norm
+struct TailInputs { std::string method; double p_signal, p_control; long n_signal_reads, n_control_reads; };
+
+static void WindowTails(long int v1, long int v2, long int v0, const TailInputs &t, double *pval1_out, double *pval2_out)
+{
+  const std::string &method = t.method;
+  const double p_signal = t.p_signal, p_control = t.p_control;
+  const long n_signal_reads = t.n_signal_reads, n_control_reads = t.n_control_reads;
+  double pval1, pval2;
+  if (P_COMPARE) {
+    if (method == "binomial") {
+      float pp_control = ((float)v2 + 1.0) / (v0 + 1.0);
+      pval1 = gtxstats::BinomialQ(v1, std::max((double)pp_control, p_signal), v0 + 1);
+      float pp_signal = ((float)v1 + 1.0) / (v0 + 1.0);
+      pval2 = gtxstats::BinomialQ(v2, std::max((double)pp_signal, p_control), v0 + 1);
+    } else if (method == "poisson") {
+      const long pseudo = 5;
+      pval1 = gtxstats::PoissonQ(v1 + pseudo, (double)(v2 + pseudo));
+      pval2 = gtxstats::PoissonQ(v2 + pseudo, (double)(v1 + pseudo));
+    } else if (method == "binomial2") {
+      double pp_control = (double)(v2 + 1) / n_control_reads, pp_signal = (double)(v1 + 1) / n_signal_reads;
+      pval1 = gtxstats::BinomialQ(v1 + 1, pp_control, n_signal_reads);
+      pval2 = gtxstats::BinomialQ(v2 + 1, pp_signal, n_control_reads);
+    } else if (method == "cbinomial") {
+      pval1 = gtxstats::BinomialQ(v1 + 1, 0.5, v1 + v2 + 2);
+      pval2 = gtxstats::BinomialQ(v2 + 1, 0.5, v1 + v2 + 2);
+    } else if (method == "normal") {
+      double pp_control = (double)(v2 + 1) / n_control_reads, pp_signal = (double)(v1 + 1) / n_signal_reads;
+      pval1 = gtxstats::GaussianQ((v1 + 1 - n_signal_reads * pp_control) / sqrt(n_signal_reads * pp_control));
+      pval2 = gtxstats::GaussianQ((v2 + 1 - n_control_reads * pp_signal) / sqrt(n_control_reads * pp_signal));
+    } else { fprintf(stderr, "Error: unknown probability distribution!\n"); exit(1); }
+  } else {
+    if (method == "binomial") {
+      pval1 = gtxstats::BinomialQ(v1, p_signal, v0 + 1);
+      pval2 = gtxstats::BinomialQ(v2, p_control, v0 + 1);
+    } else if (method == "poisson") {
+      const long pseudo = 5;
+      pval1 = gtxstats::PoissonQ(v1 + pseudo, (double)(v2 + pseudo));
+      pval2 = gtxstats::PoissonQ(v2 + pseudo, (double)(v1 + pseudo));
+    } else { fprintf(stderr, "Error: unknown probability distribution!\n"); exit(1); }
+  }
+  *pval1_out = pval1; *pval2_out = pval2;
+}
+
 static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_reg_file)
 {
   const char preprocess = (P_SORTED || uniq_reg_file != NULL) ? '1' : 'c';       // (genomic_scans.cpp:236-237)
@@ -68,12 +116,15 @@ static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_re
   const unsigned long effective_genome_size = uniq_reg_file == NULL ? CalcBoundSize(bounds) : CalcRegSize(uniq_reg_file);
   fprintf(stderr, "* Effective genome size = %lu\n", effective_genome_size);
 
-  auto make = [&](GenomicRegionSet *set) -> GenomicRegionSetScanner * {
+  // with a control on one GPU the three scans stay in HBM (slots 0, 1, 2) and the candidate windows are selected there
+  const bool keep_scans = control_reg_file != NULL && GtxPeaksOnDevice();
+  auto make = [&](GenomicRegionSet *set, int slot) -> GenomicRegionSetScanner * {
+    if (keep_scans) GenomicRegionSetScanner::KeepNextOnDevice(slot);
     if (P_SORTED) return new SortedGenomicRegionSetScanner(set, bounds, P_WIN_DIST, P_WIN_SIZE, P_MAX_LABEL_VALUE, P_IGNORE_STRAND, preprocess);
     return new UnsortedGenomicRegionSetScanner(set, bounds, P_WIN_DIST, P_WIN_SIZE, P_MAX_LABEL_VALUE, P_IGNORE_STRAND, preprocess);
   };
   GenomicRegionSet SignalRegSet(signal_reg_file, BUFFER_SIZE, P_VERBOSE, false, true);
-  GenomicRegionSetScanner *signal_scanner = make(&SignalRegSet);
+  GenomicRegionSetScanner *signal_scanner = make(&SignalRegSet, 0);
   long n_signal_reads = signal_scanner->TotalLabelValue();                     // the whole signal scan runs here, on the GPU
   if (signal_scanner->InputErrorPending()) n_signal_reads = CountGenomicRegions(signal_reg_file, P_MAX_LABEL_VALUE);   // (the reference's own pass, :245)
   const double p_signal = (double)n_signal_reads / effective_genome_size;
@@ -83,7 +134,7 @@ static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_re
   double p_control = p_signal;
   if (control_reg_file != NULL) {
     ControlRegSet = new GenomicRegionSet(control_reg_file, BUFFER_SIZE, P_VERBOSE, false, true);
-    control_scanner = make(ControlRegSet);
+    control_scanner = make(ControlRegSet, 1);
     n_control_reads = control_scanner->TotalLabelValue();
     if (control_scanner->InputErrorPending()) n_control_reads = CountGenomicRegions(control_reg_file, P_MAX_LABEL_VALUE);
     p_control = (double)n_control_reads / effective_genome_size;
@@ -95,7 +146,16 @@ static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_re
 
   // the mappability track: always the sorted scanner, operator 'p', label values not used (genomic_scans.cpp:265-267)
   GenomicRegionSet *UniqRegSet = uniq_reg_file == NULL ? NULL : new GenomicRegionSet(uniq_reg_file, BUFFER_SIZE, P_VERBOSE, false, true);
+  if (keep_scans && uniq_reg_file != NULL) GenomicRegionSetScanner::KeepNextOnDevice(2);
   GenomicRegionSetScanner *uniq_scanner = uniq_reg_file == NULL ? NULL : new SortedGenomicRegionSetScanner(UniqRegSet, bounds, P_WIN_DIST, P_WIN_SIZE, 1, P_IGNORE_STRAND, 'p');
+  // an input error waiting in a sorted scanner is met by the walk below, window by window: the scans come to the host after all.  So
+  // they do under -norm with a ratio the device call refuses (an input without reads: inf, 0 or NaN), which the loop runs to its end
+  const bool on_device = keep_scans && !signal_scanner->InputErrorPending() && !control_scanner->InputErrorPending() &&
+                         !(uniq_scanner && uniq_scanner->InputErrorPending()) && (!P_NORM || (std::isfinite(p_ratio) && p_ratio > 0.0));
+  if (keep_scans && !on_device) {
+    signal_scanner->BringKeptToHost(); control_scanner->BringKeptToHost();
+    if (uniq_scanner) uniq_scanner->BringKeptToHost();
+  }
 
   // without a control the reference draws one Poisson number per window from its clock-seeded generator (:299);
   // here from a generator seeded the same way unless GTX_SEED fixes it
@@ -104,8 +164,29 @@ static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_re
 
   std::vector<double> pval1_list, pval2_list;
   std::vector<GenomicInterval *> interval_list;
-  const std::string method = P_METHOD;
+  std::vector<long long> ordinal_list;                              // (device path: the printed windows by ordinal)
+  const TailInputs tails = {P_METHOD, p_signal, p_control, n_signal_reads, n_control_reads};
   long int v1, v2, v0;
+  if (on_device) {
+    // the loop's head (clamp, -norm, -min) for all windows at once; the tails over the windows that passed, in window order
+    std::vector<long long> ordinals, rows;
+    std::string error;
+    if (!GtxSelectPeakWindows(signal_scanner, control_scanner, uniq_scanner, P_WIN_SIZE, P_MIN_READS, P_NORM, p_ratio, ordinals, rows, &error)) {
+      fflush(stdout); fprintf(stderr, "Error: %s\n", error.c_str()); exit(1);
+    }
+    char mark[96];
+    snprintf(mark, sizeof mark, "peaks: %zu of %lld windows selected on the device", ordinals.size(), signal_scanner->WindowCount());
+    GtxMark(mark);
+    for (size_t k = 0; k < ordinals.size(); k++) {
+      double pval1, pval2;
+      WindowTails((long int)rows[3 * k], (long int)rows[3 * k + 1], (long int)rows[3 * k + 2], tails, &pval1, &pval2);
+      if (pval1 <= P_PVAL_CUTOFF) {
+        ordinal_list.push_back(ordinals[k]);
+        pval1_list.push_back(pval1);
+        pval2_list.push_back(pval2);
+      }
+    }
+  } else
   while ((v1 = signal_scanner->Next()) != -1) {
     v2 = control_scanner ? control_scanner->Next() : background(rng);
     v0 = uniq_scanner == NULL ? P_WIN_SIZE : uniq_scanner->Next();
@@ -114,38 +195,7 @@ static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_re
     if (P_NORM) { if (p_ratio < 1.0) v2 = (long int)floor((float)v2 * p_ratio); else v1 = (long int)floor((float)v1 / p_ratio); }
     if (v1 < P_MIN_READS) continue;
     double pval1, pval2;
-    if (P_COMPARE) {
-      if (method == "binomial") {
-        float pp_control = ((float)v2 + 1.0) / (v0 + 1.0);
-        pval1 = gtxstats::BinomialQ(v1, std::max((double)pp_control, p_signal), v0 + 1);
-        float pp_signal = ((float)v1 + 1.0) / (v0 + 1.0);
-        pval2 = gtxstats::BinomialQ(v2, std::max((double)pp_signal, p_control), v0 + 1);
-      } else if (method == "poisson") {
-        const long pseudo = 5;
-        pval1 = gtxstats::PoissonQ(v1 + pseudo, (double)(v2 + pseudo));
-        pval2 = gtxstats::PoissonQ(v2 + pseudo, (double)(v1 + pseudo));
-      } else if (method == "binomial2") {
-        double pp_control = (double)(v2 + 1) / n_control_reads, pp_signal = (double)(v1 + 1) / n_signal_reads;
-        pval1 = gtxstats::BinomialQ(v1 + 1, pp_control, n_signal_reads);
-        pval2 = gtxstats::BinomialQ(v2 + 1, pp_signal, n_control_reads);
-      } else if (method == "cbinomial") {
-        pval1 = gtxstats::BinomialQ(v1 + 1, 0.5, v1 + v2 + 2);
-        pval2 = gtxstats::BinomialQ(v2 + 1, 0.5, v1 + v2 + 2);
-      } else if (method == "normal") {
-        double pp_control = (double)(v2 + 1) / n_control_reads, pp_signal = (double)(v1 + 1) / n_signal_reads;
-        pval1 = gtxstats::GaussianQ((v1 + 1 - n_signal_reads * pp_control) / sqrt(n_signal_reads * pp_control));
-        pval2 = gtxstats::GaussianQ((v2 + 1 - n_control_reads * pp_signal) / sqrt(n_control_reads * pp_signal));
-      } else { fprintf(stderr, "Error: unknown probability distribution!\n"); exit(1); }
-    } else {
-      if (method == "binomial") {
-        pval1 = gtxstats::BinomialQ(v1, p_signal, v0 + 1);
-        pval2 = gtxstats::BinomialQ(v2, p_control, v0 + 1);
-      } else if (method == "poisson") {
-        const long pseudo = 5;
-        pval1 = gtxstats::PoissonQ(v1 + pseudo, (double)(v2 + pseudo));
-        pval2 = gtxstats::PoissonQ(v2 + pseudo, (double)(v1 + pseudo));
-      } else { fprintf(stderr, "Error: unknown probability distribution!\n"); exit(1); }
-    }
+    WindowTails(v1, v2, v0, tails, &pval1, &pval2);
     if (pval1 <= P_PVAL_CUTOFF) {
       interval_list.push_back(signal_scanner->GetInterval());
       pval1_list.push_back(pval1);
@@ -153,9 +203,13 @@ static int RunPeaks(char *signal_reg_file, char *control_reg_file, char *uniq_re
     }
   }
   const double pval_cutoff = ComputeQValues(pval1_list, pval2_list, 1, P_QVAL_CUTOFF);
-  for (size_t k = 0; k < interval_list.size(); k++) {
-    if (pval1_list[k] <= pval_cutoff) { printf("%.4e\t", pval1_list[k]); interval_list[k]->PrintInterval(); printf("\n"); }
-    delete interval_list[k];
+  for (size_t k = 0; k < pval1_list.size(); k++) {
+    if (pval1_list[k] <= pval_cutoff) {
+      printf("%.4e\t", pval1_list[k]);
+      if (on_device) signal_scanner->PrintIntervalAt(stdout, ordinal_list[k]); else interval_list[k]->PrintInterval();
+      printf("\n");
+    }
+    if (!on_device) delete interval_list[k];
   }
   GtxFinish(0);
   delete signal_scanner; delete control_scanner; delete ControlRegSet; delete uniq_scanner; delete UniqRegSet; delete bounds;

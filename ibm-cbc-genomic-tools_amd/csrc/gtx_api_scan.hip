@@ -1,10 +1,12 @@
 // gtx_api_scan.hip -- the C ABI's scans: gtx_scan* over reads on the device, in host buffers or fed as a stream, the window vectors
-// kept in HBM, and the window selection and the window filter over them.  Host code only (the kernels: gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip,
-// gtx_select.hip, gtx_filter.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
+// kept in HBM, and the window selection, the window filter and the peak candidate selection over them.  Host code only (the kernels:
+// gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip, gtx_select.hip, gtx_filter.hip, gtx_peaks.hip); the context and the helpers shared
+// with the other families are in gtx_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <stdio.h>
+#include <cmath>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -12,6 +14,7 @@
 #include "gtx_kernels.h"
 #include "gtx_select.h"
 #include "gtx_filter.h"
+#include "gtx_peaks.h"
 #include "gtx_internal.h"
 #include "gtx_ctx.h"
 
@@ -384,6 +387,19 @@ int gtx_scan_kept(gtx_ctx *c, int slot, void **d_ptr, int64_t *n_windows)
   return GTX_OK;
 }
 
+int gtx_scan_kept_read(gtx_ctx *c, int slot, uint64_t *out)
+{
+  if (!c) return GTX_E_ARG;
+  if (slot < 0 || slot >= GTX_SCAN_KEEP_SLOTS) return fail(c, GTX_E_ARG, "gtx_scan_kept_read: slot out of range");
+  if (!c->scan.kept[slot]) return fail(c, GTX_E_STATE, "gtx_scan_kept_read: the slot is empty");
+  const int64_t n = c->scan.keptLen[slot];
+  if (n > 0 && !out) return fail(c, GTX_E_ARG, "gtx_scan_kept_read: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n > 0) HIPCHK(c, hipMemcpyAsync(out, c->scan.kept[slot].get(), (size_t)n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return GTX_OK;
+}
+
 int gtx_scan_drop(gtx_ctx *c, int slot)
 {
   if (!c) return GTX_E_ARG;
@@ -557,6 +573,59 @@ int gtx_window_filter(gtx_ctx *c, const void *d_windows, int64_t n_windows, uint
   if (got) {
     HIPCHK(c, hipMemcpy(ordinals, f.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(values, f.val.get(), got * sizeof(u64), hipMemcpyDeviceToHost));
+  }
+  return GTX_OK;
+}
+
+// ---- peak candidates (gtx_peaks.hip) ----
+static_assert(GTX_PEAK_TILE == gtx::kPeakTile, "include/gtx.h names the peak selection's tile");
+
+int gtx_peak_select_device(gtx_ctx *c, const void *d_signal, const void *d_control, const void *d_uniq, int64_t n_windows, int64_t win_size,
+                           int64_t min_reads, int norm, double p_ratio, int64_t capacity, void *d_ordinals, void *d_rows, int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  if (n_windows < 0 || capacity < 0 || !n_kept) return fail(c, GTX_E_ARG, "gtx_peak_select: bad window count or capacity, or no n_kept");
+  if (win_size < 1) return fail(c, GTX_E_ARG, "gtx_peak_select: the window size must be positive");
+  if (norm && !(std::isfinite(p_ratio) && p_ratio > 0.0)) return fail(c, GTX_E_ARG, "gtx_peak_select: -norm needs a finite positive ratio");
+  if (!d_signal || !d_control || ((uintptr_t)d_signal & 15) || ((uintptr_t)d_control & 15) || ((uintptr_t)d_uniq & 15))
+    return fail(c, GTX_E_ARG, "gtx_peak_select: signal and control (and the mappability track) must be 16-byte aligned device memory");
+  if (capacity > 0 && (!d_ordinals || !d_rows)) return fail(c, GTX_E_ARG, "gtx_peak_select: null output");
+  *n_kept = 0;
+  if (n_windows == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  PeakState &p = c->peak;
+  const int64_t nt = gtx::peak_tiles(n_windows);
+  if (!p.total) HIPCHK(c, p.total.alloc(1));
+  if ((size_t)nt > p.count.cap || (size_t)nt + 1 > p.base.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, p.count.reserve((size_t)nt)); HIPCHK(c, p.base.reserve((size_t)nt + 1));
+  }
+  gtx::PeakArgs a = {(const u64 *)d_signal, (const u64 *)d_control, (const u64 *)d_uniq, n_windows, win_size, min_reads,
+                     norm ? (p_ratio < 1.0 ? 1 : 2) : 0, p_ratio};
+  HIPCHK(c, gtx::launch_peak_select(a, p.count.get(), p.base.get(), capacity, (long long *)d_ordinals, (long long *)d_rows, c->stream));
+  HIPCHK(c, hipMemcpyAsync(p.total.get(), p.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_kept = *p.total.get();
+  return GTX_OK;
+}
+
+int gtx_peak_select(gtx_ctx *c, const void *d_signal, const void *d_control, const void *d_uniq, int64_t n_windows, int64_t win_size,
+                    int64_t min_reads, int norm, double p_ratio, int64_t capacity, int64_t *ordinals, int64_t *rows, int64_t *n_kept)
+{
+  if (!c) return GTX_E_ARG;
+  if (capacity < 0 || (capacity > 0 && (!ordinals || !rows))) return fail(c, GTX_E_ARG, "gtx_peak_select: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  PeakState &p = c->peak;
+  if ((size_t)capacity > p.ord.cap || (size_t)capacity * 3 > p.rows.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, p.ord.reserve((size_t)capacity)); HIPCHK(c, p.rows.reserve((size_t)capacity * 3));
+  }
+  int rc = gtx_peak_select_device(c, d_signal, d_control, d_uniq, n_windows, win_size, min_reads, norm, p_ratio, capacity, p.ord.get(), p.rows.get(), n_kept);
+  if (rc) return rc;
+  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
+  if (got) {
+    HIPCHK(c, hipMemcpy(ordinals, p.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rows, p.rows.get(), got * 3 * sizeof(long long), hipMemcpyDeviceToHost));
   }
   return GTX_OK;
 }

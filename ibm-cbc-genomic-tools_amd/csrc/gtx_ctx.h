@@ -225,6 +225,9 @@ struct FilterState {
   DevBuf<unsigned> count; DevBuf<long long> base, ord; DevBuf<u64> val; PinBuf<long long> total;
 };
 
+// the peak candidate selection: the passes' tile counts and bases, the total on the host, the host entry's results
+struct PeakState { DevBuf<unsigned> count; DevBuf<long long> base, ord, rows; PinBuf<long long> total; };
+
 // link: the scans' per-tile values and break bit map, the info block and its page-locked copy (handed to the caller's struct by
 // gtx_sync after a device call), the host entry's inputs and group records
 struct LinkState {
@@ -332,6 +335,7 @@ struct gtx_ctx {
   ScanState scan;
   SelectState sel;
   FilterState flt;
+  PeakState peak;
   TextState text;
   LinkState link;
   NeighbourState nbr;

@@ -31,6 +31,7 @@ ADJACENT_TILE = 2048      # GTX_ADJACENT_TILE: regions per block of the neighbou
 POINTS = {"1": 0, "2": 1, "5p": 2, "3p": 3}   # GTX_POINT_*: gdist's reference points
 SCAN_KEEP_SLOTS = 8       # GTX_SCAN_KEEP_SLOTS: window vectors a context keeps in HBM
 FILTER_TILE = 1024        # GTX_FILTER_TILE: windows per tile of the window filter's passes
+PEAK_TILE = 1024          # GTX_PEAK_TILE: windows per tile of the peak candidate selection's passes
 OFFSET_OPS = {"1": 1, "2": 2, "5p": 3, "3p": 4}
 ANNOTATE_CENTER = 1
 ANNOTATE_START = 2
@@ -152,6 +153,11 @@ ABI = {
                                                 ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_window_filter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_scan_kept_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gtx_peak_select_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_peak_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                       ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_link": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
@@ -800,6 +806,13 @@ class Engine:
         self._chk(self.lib.gtx_scan_kept(self.ctx, int(slot), ctypes.byref(d), ctypes.byref(n)))
         return int(d.value or 0), int(n.value)
 
+    def scan_kept_read(self, slot):
+        """gtx_scan_kept_read: a kept slot's window sums in host memory (uint64, layout of scan); the slot stays as it is"""
+        _, n = self.scan_kept(slot)
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        self._chk(self.lib.gtx_scan_kept_read(self.ctx, int(slot), _ptr(out)))
+        return out[:n]
+
     def scan_drop(self, slot=-1):
         """free a kept slot (-1: all of them)"""
         self._chk(self.lib.gtx_scan_drop(self.ctx, int(slot)))
@@ -875,6 +888,43 @@ class Engine:
             cap = int(kept.value)
         got = min(int(kept.value), cap)
         return ordinals[:got], values[:got], int(kept.value)
+
+    def _peak_vectors(self, signal, control, uniq, n_windows):
+        def addr(v):
+            if v is not None and isinstance(v, (int, np.integer)) and 0 <= int(v) < SCAN_KEEP_SLOTS:
+                return self.scan_kept(int(v))
+            return (None if v is None else int(v)), None
+        s, c, u = addr(signal), addr(control), addr(uniq)
+        if n_windows is None and s[1] is None:
+            raise ValueError("n_windows is required when the signal is a raw device address and not a kept slot")
+        return s[0], c[0], u[0], (s[1] if n_windows is None else n_windows)
+
+    def peak_select(self, signal, control, win_size, min_reads, uniq=None, norm=False, p_ratio=1.0, n_windows=None, capacity=None):
+        """gtx_peak_select over window vectors in HBM: kept slots (small ints, n_windows taken from the signal's slot) or raw device
+        addresses (n_windows required); uniq (the mappability track) may be None.  Returns (ordinals int64, rows int64 [kept, 3] of
+        v1, v2, v0 after clamp and norm, number kept): the windows with v1 >= min_reads in window order; when the number kept
+        exceeds `capacity` only the first `capacity` are returned.  capacity=None grows and repeats the call until everything fits."""
+        s, c, u, n_windows = self._peak_vectors(signal, control, uniq, n_windows)
+        kept = ctypes.c_int64(0)
+        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
+        while True:
+            ordinals, rows = np.full(max(cap, 1), -1, dtype=np.int64), np.full((max(cap, 1), 3), -1, dtype=np.int64)
+            self._chk(self.lib.gtx_peak_select(self.ctx, _ptr(s), _ptr(c), _ptr(u), int(n_windows), int(win_size), int(min_reads), int(bool(norm)),
+                                               float(p_ratio), cap, _ptr(ordinals), _ptr(rows), ctypes.byref(kept)))
+            if capacity is not None or kept.value <= cap:
+                break
+            cap = int(kept.value)
+        got = min(int(kept.value), cap)
+        return ordinals[:got], rows[:got], int(kept.value)
+
+    def peak_select_device(self, signal, control, win_size, min_reads, capacity, d_ordinals, d_rows, uniq=None, norm=False, p_ratio=1.0, n_windows=None):
+        """gtx_peak_select_device: the same selection into the caller's device buffers (int64[capacity], int64[capacity * 3]); returns
+        the number kept, whatever the capacity."""
+        s, c, u, n_windows = self._peak_vectors(signal, control, uniq, n_windows)
+        kept = ctypes.c_int64(0)
+        self._chk(self.lib.gtx_peak_select_device(self.ctx, _ptr(s), _ptr(c), _ptr(u), int(n_windows), int(win_size), int(min_reads), int(bool(norm)),
+                                                  float(p_ratio), int(capacity), _ptr(d_ordinals), _ptr(d_rows), ctypes.byref(kept)))
+        return int(kept.value)
 
     def scan_device(self, d_reads, n_reads, class_len, win_step, win_size, d_out, preprocess="1", d_weights=None, flags=0):
         cl = np.ascontiguousarray(class_len, dtype=np.int32)

@@ -697,6 +697,10 @@ int gtx_scan_end(gtx_ctx *ctx, uint64_t *windows_out, int64_t *label_sum);
 int gtx_scan_end_keep(gtx_ctx *ctx, int slot, int64_t *label_sum);
 int gtx_scan_kept(gtx_ctx *ctx, int slot, void **d_windows, int64_t *n_windows);
 int gtx_scan_drop(gtx_ctx *ctx, int slot);
+/* A kept slot's window sums brought to host memory after all (layout of gtx_scan; the slot stays as it is): for the caller that
+ * finds out only after the scan that it has to walk the windows itself.  An empty slot is GTX_E_STATE, a NULL buffer for a slot that
+ * holds windows GTX_E_ARG. */
+int gtx_scan_kept_read(gtx_ctx *ctx, int slot, uint64_t *windows_out);
 
 /* Window selection: the data pass of `genomic_apps peakdiff` (ScanReadFiles, genomic_apps.cpp:385-412) over window vectors in HBM.
  * d_tested: n_tested (1..4) device vectors of n_windows uint64 sums; d_control: NULL (or all entries NULL), or one control vector per
@@ -739,6 +743,26 @@ int gtx_window_filter_device(gtx_ctx *ctx, const void *d_windows, int64_t n_wind
                              void *d_values, int64_t *n_kept);
 int gtx_window_filter(gtx_ctx *ctx, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t capacity, int64_t *ordinals,
                       uint64_t *values, int64_t *n_kept);
+
+/* Peak candidates: the head of the per-window loop of `genomic_scans peaks` (PeakFinder, genomic_scans.cpp:304-311) over window
+ * vectors in HBM.  d_signal, d_control and d_uniq (the mappability track; may be NULL) are device vectors of n_windows uint64 window
+ * sums, 16-byte aligned (kept slots are), read as signed 64-bit values.  Per window
+ *   v0 = d_uniq ? uniq[w] : win_size;   v1 = min(signal[w], v0);   v2 = min(control[w], v0)
+ *   norm != 0:  p_ratio < 1.0 ?  v2 = (long)floor((float)v2 * p_ratio)  :  v1 = (long)floor((float)v1 / p_ratio)
+ * and the window is kept when v1 >= min_reads.  The conversion to float is the reference's (a count rounds to 24 bits before it is
+ * scaled), the product and the quotient are in double.  The kept windows come out in window order: ordinals (int64[capacity]) and rows
+ * (int64[capacity * 3]: v1, v2, v0 after clamp and norm).  *n_kept is the number of kept windows whatever the capacity; when it
+ * exceeds capacity only the first `capacity` windows have been written and nothing behind them: grow the buffers and call again (the
+ * policy of gtx_window_select).  n_windows = 0 is valid.  GTX_E_ARG: a NULL or unaligned signal or control, an unaligned d_uniq, a NULL
+ * output with capacity > 0, a negative n_windows or capacity, no n_kept, win_size < 1, or -- with norm set -- a p_ratio that is not
+ * finite and positive.  gtx_peak_select_device writes device buffers and returns when the result is complete; gtx_peak_select brings
+ * the result to host memory.  Three launches over tiles of GTX_PEAK_TILE windows (count, prefix, emit); the emit pass loads only the
+ * tiles that keep a window. */
+#define GTX_PEAK_TILE 1024
+int gtx_peak_select_device(gtx_ctx *ctx, const void *d_signal, const void *d_control, const void *d_uniq, int64_t n_windows, int64_t win_size,
+                           int64_t min_reads, int norm, double p_ratio, int64_t capacity, void *d_ordinals, void *d_rows, int64_t *n_kept);
+int gtx_peak_select(gtx_ctx *ctx, const void *d_signal, const void *d_control, const void *d_uniq, int64_t n_windows, int64_t win_size,
+                    int64_t min_reads, int norm, double p_ratio, int64_t capacity, int64_t *ordinals, int64_t *rows, int64_t *n_kept);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 
