@@ -280,12 +280,42 @@ GenomicRegionSAM::~GenomicRegionSAM()
   GtxRegionFree(CIGAR); GtxRegionFree(RNEXT); GtxRegionFree(SEQ); GtxRegionFree(QUAL); GtxRegionFree(OPTIONAL);
 }
 
+GenomicRegionGFF::GenomicRegionGFF(char *inp, long int n_line)
+{
+  this->n_line = n_line;
+  SOURCE = FEATURE = SCORE = COMMENT = NULL; FRAME = 0;
+  gtxhost::GffFields f; std::string msg;
+  if (gtxhost::ParseGffLine(inp, &f, &msg) != gtxhost::GFF_OK) PrintError(msg);
+  n_tokens = f.n_tokens;
+  LABEL = CopyString(f.label ? f.label : "_");
+  SOURCE = CopyString(f.source); FEATURE = CopyString(f.feature); SCORE = CopyString(f.score); FRAME = f.frame;
+  COMMENT = f.comment ? CopyString(f.comment) : NULL;
+  I.push_back(new GenomicInterval(f.seqname, f.strand, f.start, f.stop, n_line));
+}
+
+GenomicRegionGFF::~GenomicRegionGFF()
+{
+  GtxRegionFree(SOURCE); GtxRegionFree(FEATURE); GtxRegionFree(SCORE); GtxRegionFree(COMMENT);
+}
+
+// a strand-aware run over the regions of an in-memory GFF set: a strand byte other than '+' or '-' is an input error at its line
+// (the engine has two strand classes per chromosome; see gtxhost::GffStrandMessage).  Call before anything renumbers n_line.
+static void CheckGffStrands(GenomicRegionSet *set)
+{
+  if (set->format != "GFF" || !set->load_in_memory) return;
+  for (long int k = 0; k < set->n_regions; k++) {
+    const char s = set->R[k]->I.front()->STRAND;
+    if (s != '+' && s != '-') set->R[k]->PrintError(gtxhost::GffStrandMessage(s));
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // GenomicRegionSet
 // ---------------------------------------------------------------------------------------------------
 void StdoutIsOurs();   // (below, with the GPU start-up)
-static bool g_accept_sam = true;
-void GtxAcceptSAM(bool on) { g_accept_sam = on; }
+static bool g_accept_sam = true, g_accept_gff = true;            // (the two formats only the reductions read)
+void GtxAcceptSAM(bool on) { g_accept_sam = on; g_accept_gff = on; }   // (the drivers that print lines refuse both)
+bool GtxAcceptGFF(bool on) { const bool was = g_accept_gff; g_accept_gff = on; return was; }
 
 GenomicRegionSet::GenomicRegionSet(char *file, unsigned long int buffer_size, bool verbose, bool load_in_memory, bool hide_header)
 {
@@ -343,8 +373,8 @@ void GenomicRegionSet::PrintError(std::string error_msg)
   exit(1);
 }
 
-// genomic_intervals.cpp:3736-3759: by the number of TAB-separated tokens of the first data line (SAM: 11 or more, a 6th token
-// without '+' or '-')
+// genomic_intervals.cpp:3736-3759: by the number of TAB-separated tokens of the first data line (SAM: 11 or more, GFF: 8 to 10, a 6th
+// token without '+' or '-')
 void GenomicRegionSet::DetectFormat(const char *line)
 {
   if (line[0] == '>' || line[0] == '@' || (line[0] == '#' && line[1] == '#')) PrintError("unsupported input format!\n");
@@ -358,13 +388,15 @@ void GenomicRegionSet::DetectFormat(const char *line)
     bed = tok.find('+') != std::string::npos || tok.find('-') != std::string::npos;
   }
   if (!bed && g_accept_sam && gtxhost::LooksLikeSam(line)) { format = "SAM"; return; }
-  if (!bed) PrintError("unsupported input format!\n");     // REG / GFF are outside the path
+  if (!bed && g_accept_gff && gtxhost::LooksLikeGff(line)) { format = "GFF"; return; }
+  if (!bed) PrintError("unsupported input format!\n");     // REG is outside the path
   format = "BED";
 }
 
 GenomicRegion *GenomicRegionSet::CreateRegion(char *line, long int n_line)
 {
   if (format == "SAM") return new GenomicRegionSAM(line, n_line);
+  if (format == "GFF") return new GenomicRegionGFF(line, n_line);
   return new GenomicRegionBED(line, n_line);
 }
 
@@ -403,12 +435,21 @@ void GenomicRegionSet::Init()
       line = src->Next();
     }
   }
-  while (!sam_header && line && (strncmp(line, "browser ", 8) == 0 || strncmp(line, "track ", 6) == 0)) {
+  bool gff_header = false;
+  if (line && line[0] == '#' && line[1] == '#' && g_accept_gff) {   // a GFF header (ProcessFileHeader :3725-3728): the file is GFF whatever follows;
+    gff_header = true;                                          // the leading run of '##' lines is echoed unless hidden (a later one is a data line)
+    while (line && line[0] == '#' && line[1] == '#') {
+      if (!hide_header) { StdoutIsOurs(); printf("%s\n", line); }
+      line = src->Next();
+    }
+  }
+  while (!sam_header && !gff_header && line && (strncmp(line, "browser ", 8) == 0 || strncmp(line, "track ", 6) == 0)) {
     if (!hide_header) { StdoutIsOurs(); printf("%s\n", line); }
     line = src->Next();
   }
   if (!line) { format = "EMPTY"; n_regions = 0; }
   else if (sam_header) format = "SAM";
+  else if (gff_header) format = "GFF";
   else DetectFormat(line);
 
   if (load_in_memory) {
@@ -708,7 +749,7 @@ static std::atomic<bool> g_drain_stop(false);                 // set by a sink t
 // anything else in it comes back and is packed here, with the reference's reading of it and the reference's errors.
 struct TextSink {
   std::function<bool()> usable;                                   // (asked behind prep(): one GPU)
-  std::function<int(const char *, size_t, int64_t, const gtx_text_rules &, uint32_t)> add;   // (the last argument: GTX_TEXT_SAM or 0, to go with the call's flags)
+  std::function<int(const char *, size_t, int64_t, const gtx_text_rules &, uint32_t)> add;   // (the last argument: GTX_TEXT_SAM, GTX_TEXT_GFF or 0, to go with the call's flags)
   std::function<bool(int)> needs_host;
 };
 
@@ -716,7 +757,7 @@ static bool TextOnDevice(GenomicRegionSet *set, const PackOptions &opt, const Te
 {
   static const char *e = getenv("GTX_TEXT_ON_DEVICE");        // 0: never; 1: whenever the input qualifies (tests); default: files of 32 MB or more
   if (!ts || (e && atoi(e) == 0)) return false;
-  if (set->load_in_memory || (set->format != "BED" && set->format != "SAM")) return false;
+  if (set->load_in_memory || (set->format != "BED" && set->format != "SAM" && set->format != "GFF")) return false;
   if (opt.guard || opt.collect_zero_length) return false;                 // (explode_blocks: a 12-column line sends its block back to the packer, which does it)
   if (!g_pool.buf[0] || !g_pool.buf[1] || !ts->usable()) return false;
   // a regular uncompressed file: worth it from 32 MB on.  A stream (stdin / a pipe, a .gz file, a FILE* of the caller's: -1) has no
@@ -733,6 +774,7 @@ static void DrainSet(GenomicRegionSet *set, PackOptions opt, Prep prep, Sink sin
 {
   g_drain_stop = false;
   opt.sam = set->format == "SAM";
+  opt.gff = set->format == "GFF" && !set->load_in_memory;        // (an in-memory set goes out again as BED lines, below)
   const size_t batch_reads = kBatchReads;
   PackedBatch two[2]; PackError err;
   // (a scanner's batch without a single region for the windows still carries the label values of its lines)
@@ -787,7 +829,7 @@ static void DrainSet(GenomicRegionSet *set, PackOptions opt, Prep prep, Sink sin
         continue;
       }
       rules.have_prev = b.have_prev; rules.prev_chrom = b.prev_chrom.c_str(); rules.prev_strand = b.prev_strand; rules.prev_start = b.prev_start;
-      ticket[cur] = text_sink->add(b.text, b.bytes, b.n_lines, rules, opt.sam ? GTX_TEXT_SAM : 0u);
+      ticket[cur] = text_sink->add(b.text, b.bytes, b.n_lines, rules, opt.sam ? GTX_TEXT_SAM : opt.gff ? GTX_TEXT_GFF : 0u);
       if (on_error) settle(cur);                                 // (a caller that goes on after an error wants nothing behind the offending line counted: one block at a time)
     }
     settle(0); settle(1);
@@ -835,6 +877,7 @@ static void DrainSet(GenomicRegionSet *set, PackOptions opt, Prep prep, Sink sin
     return;
   }
   // in-memory set: re-emit its regions as lines through the same packer rules
+  if (opt.strand_aware) CheckGffStrands(set);
   std::string text;
   for (GenomicRegion *r = set->Get(); r != NULL; r = set->Next()) {
     GenomicInterval *i = r->I.front();
@@ -864,7 +907,8 @@ static void DrainSet(GenomicRegionSet *set, PackOptions opt, Prep prep, Sink sin
     }
     text += i->CHROMOSOME; text += '\t';
     snprintf(buf, sizeof buf, "%ld\t%ld\t", i->START - 1, r->I.back()->STOP); text += buf;
-    text += r->LABEL; text += "\t0\t"; text += i->STRAND; text += '\n';
+    // (a GFF feature of another strand byte than '+' or '-' gets this far only when the strand is ignored: any legal BED strand will do)
+    text += r->LABEL; text += "\t0\t"; text += (set->format == "GFF" && i->STRAND != '-') ? '+' : i->STRAND; text += '\n';
   }
   BedPacker packer((LineSource *)NULL, opt);
   packer.PrimeBlock(text, 1);
@@ -885,9 +929,11 @@ static bool LooksSorted(const gtxhost::RawVec &tri)
   return true;
 }
 
-// the same hint from the text of a block: pairs of adjacent lines at ~4096 places, (chromosome token, column 2) compared
-static bool TextLooksSorted(const char *text, size_t bytes, bool sam = false)
+// the same hint from the text of a block: pairs of adjacent lines at ~4096 places, (chromosome token, start column) compared.
+// format: GTX_TEXT_SAM, GTX_TEXT_GFF or 0 for BED
+static bool TextLooksSorted(const char *text, size_t bytes, uint32_t format = 0)
 {
+  const bool sam = format == GTX_TEXT_SAM, gff = format == GTX_TEXT_GFF;
   if (bytes < 64) return true;
   const size_t stride = bytes > (4096u * 64u) ? bytes / 4096 : 64;
   int descents = 0;
@@ -898,7 +944,12 @@ static bool TextLooksSorted(const char *text, size_t bytes, bool sam = false)
     }
     const char *t = (const char *)memchr(l, '\t', (size_t)(e - l));
     if (!t) return false;
-    *tok = l; *len = (size_t)(t - l); *start = atol(t + 1);
+    *tok = l; *len = (size_t)(t - l);
+    if (gff) {                                                     // GFF: (seqname, START), columns 1 and 4
+      for (int k = 0; k < 2 && t; k++) t = (const char *)memchr(t + 1, '\t', (size_t)(e - t - 1));
+      if (!t) return false;
+    }
+    *start = atol(t + 1);
     return true;
   };
   for (size_t at = 0; at + 2 < bytes; at += stride) {
@@ -968,6 +1019,7 @@ unsigned long int *GenomicRegionSetOverlaps::Reduce(bool coverage, bool match_ga
   const long int M = IndexSet->n_regions;
   const SortedGenomicRegionSetOverlaps *merge = dynamic_cast<const SortedGenomicRegionSetOverlaps *>(this);
   const bool sorted = merge != NULL, by_strand = merge && merge->sorted_by_strand;
+  if (!ignore_strand) CheckGffStrands(IndexSet);
   for (long int k = 0; k < M; k++) IndexSet->R[k]->n_line = k;                       // :5309
   Mark("CountIndexOverlaps: start");
 
@@ -1122,7 +1174,7 @@ unsigned long int *GenomicRegionSetOverlaps::Reduce(bool coverage, bool match_ga
   text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules, uint32_t text_flags) {
     int ticket = -1;
     // (the sorted merge's input is in order, or the block comes back; the bin index takes any order: a look at the text decides the kernel)
-    const uint32_t flags = mode_flags | text_flags | ((sorted || TextLooksSorted(text, bytes, (text_flags & GTX_TEXT_SAM) != 0)) ? GTX_READS_SORTED : 0);
+    const uint32_t flags = mode_flags | text_flags | ((sorted || TextLooksSorted(text, bytes, text_flags & (GTX_TEXT_SAM | GTX_TEXT_GFF))) ? GTX_READS_SORTED : 0);
     CheckGrp(grp, gtx_group_count_add_text(grp, text, bytes, lines, &rules, flags, &ticket));
     return ticket;
   };
@@ -1489,7 +1541,7 @@ void GenomicRegionSetScanner::Compute(bool sorted_rules)
   text_sink.add = [&](const char *text, size_t bytes, int64_t lines, const gtx_text_rules &rules, uint32_t text_flags) {
     if (!preprocess_ok) { bad_preprocess = true; g_drain_stop = true; return -1; }
     int ticket = -1;
-    check_one(gtx_scan_add_text(one, text, bytes, lines, &rules, text_flags | ((sorted_rules || TextLooksSorted(text, bytes, (text_flags & GTX_TEXT_SAM) != 0)) ? 0u : GTX_READS_UNSORTED), &ticket));
+    check_one(gtx_scan_add_text(one, text, bytes, lines, &rules, text_flags | ((sorted_rules || TextLooksSorted(text, bytes, text_flags & (GTX_TEXT_SAM | GTX_TEXT_GFF))) ? 0u : GTX_READS_UNSORTED), &ticket));
     return ticket;
   };
   DrainSet(R, opt, device_side, [&](const PackedBatch &b) {
@@ -2024,7 +2076,9 @@ StringLIntMap *ReadBounds(char *genome_reg_file, bool verbose)
 {
   if (genome_reg_file == NULL || strlen(genome_reg_file) == 0) { std::cerr << "Error: genome region file is necessary for this operation!\n"; exit(1); }
   StringLIntMap *bounds = new StringLIntMap();
+  const bool gff_was = GtxAcceptGFF(false);                       // (a genome file is what it was: GFF is read as reads and reference regions only)
   GenomicRegionSet RegSet(genome_reg_file, 10000, verbose, false, true);
+  GtxAcceptGFF(gff_was);
   long int line = 1;
   for (GenomicRegion *r = RegSet.Get(); r != NULL; r = RegSet.Next(), line++) {
     std::string chr = r->I.front()->CHROMOSOME;
@@ -2209,8 +2263,9 @@ void BuildJoinIndex(GenomicRegionSetOverlaps *ov, bool ignore_strand, const char
                     GenomicRegionSet *second = NULL)
 {
   // the per-pair operations print query lines as BED text (and read their BED columns back): a SAM set of the class API's is refused
-  // here, with the message the CLIs give for it (GtxAcceptSAM)
-  if (ov->QuerySet->format == "SAM" || ov->IndexSet->format == "SAM") ov->QuerySet->PrintError("unsupported input format!\n");
+  // here, with the message the CLIs give for it (GtxAcceptSAM); so is a GFF set
+  for (GenomicRegionSet *s : {ov->QuerySet, ov->IndexSet})
+    if (s->format == "SAM" || s->format == "GFF") ov->QuerySet->PrintError("unsupported input format!\n");
   GenomicRegionSet *IS = ov->IndexSet;
   ix.n_primary = IS->n_regions;
   ix.regs.assign(IS->R, IS->R + IS->n_regions);

@@ -12,9 +12,9 @@
 // error of the reference (genomic_intervals.cpp:1001-1006).
 //
 // Scope: BED3..BED12 regions (BED12 blocks as multi-interval regions) and SAM
-// alignments (a spliced read as a multi-interval region), the
+// alignments (a spliced read as a multi-interval region) and, for the reductions, GFF / GTF features, the
 // reductions of count / rpkm / coverage / density and the scanners, and the per-pair iteration
-// (GetQuery / GetOverlap / NextOverlap) on the host.  REG/GFF/SEQ input, the ~45 Run*/Print*
+// (GetQuery / GetOverlap / NextOverlap) on the host.  REG/SEQ input, the ~45 Run*/Print*
 // text transforms of GenomicRegionSet and GenomicRegionSetIndex beyond the "does anything overlap"
 // query of the scanners' reference filter are outside the path; the device-side pair join is the
 // C ABI's gtx_join (include/gtx.h).
@@ -119,6 +119,18 @@ class GenomicRegionSAM : public GenomicRegion
   char *CIGAR, *RNEXT, *SEQ, *QUAL, *OPTIONAL;                    // OPTIONAL: NULL for an 11-column line
 };
 
+class GenomicRegionGFF : public GenomicRegion
+{
+ public:
+  // parses one GFF / GTF line (the line is modified); genomic_intervals.cpp:3501-3517.  One interval, (column 1, the first byte of
+  // column 7 as it stands, column 4, column 5): 1-based and inclusive as written.  LABEL is column 9, "_" for an 8-column line.
+  GenomicRegionGFF(char *inp, long int n_line);
+  ~GenomicRegionGFF();
+  long int n_tokens;
+  char *SOURCE, *FEATURE, *SCORE, *COMMENT;                       // COMMENT (column 10): NULL with fewer than 10 tokens
+  char FRAME;
+};
+
 // ---- GenomicRegionSet (genomic_intervals.h:1828) ------------------------------------------------------
 class GenomicRegionSet
 {
@@ -175,7 +187,7 @@ class GenomicRegionSet
   const std::string &CurrentLine() const { return cur_raw; }      // MI355X path: the unparsed line of the current region of a streamed text set
   long int StreamBytesLeft();                     // size of a streamed regular text file, -1 otherwise (MI355X build: the device-side tokenizer's test)
   long int n_regions;
-  std::string format;                                              // "BED", "SAM", "EMPTY" or "GTX" (a packed region file, gtx_bed.h)
+  std::string format;                                              // "BED", "SAM", "GFF", "EMPTY" or "GTX" (a packed region file, gtx_bed.h)
   GenomicRegion **R;
 
  private:
@@ -186,7 +198,7 @@ class GenomicRegionSet
   gtxhost::GtxView *packed;                                        // format "GTX"
   std::vector<std::pair<void *, size_t> > blocks_;                  // memory of the region objects built in parallel (GtxRegionAlloc)
   GenomicRegion *PackedRegion(long int record);                    // region object of one record of the packed file
-  GenomicRegion *CreateRegion(char *line, long int n_line);        // GenomicRegionBED or GenomicRegionSAM, by the set's format
+  GenomicRegion *CreateRegion(char *line, long int n_line);        // GenomicRegionBED, GenomicRegionSAM or GenomicRegionGFF, by the set's format
   std::string cur_raw;                                             // unparsed copy of the current line (streaming mode)
   long int r_index;
 };
@@ -480,7 +492,8 @@ void GtxPrintAnnotations(GenomicRegionSet *TestRegSet, GenomicRegionSet *RefRegS
 bool GtxScanFilterOnDevice();                                  // MI355X path: may `genomic_scans counts -r` filter on the device?  One GPU, and GTX_SCAN_FILTER_ON_DEVICE is not 0
 bool GtxPeaksOnDevice();                                       // MI355X path: may `genomic_scans peaks` select its candidate windows on the device?  One GPU, and GTX_PEAKS_ON_DEVICE is not 0
 void GtxSetDevices(int n_gpus);                               // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
-void GtxAcceptSAM(bool on);                                      // false: a SAM file is "unsupported input format!" (drivers that print query lines; default true)
+void GtxAcceptSAM(bool on);                                      // false: a SAM or GFF file is "unsupported input format!" (drivers that print query lines; default true)
+bool GtxAcceptGFF(bool on);                                      // the same for GFF alone, for the sets opened from then on; returns what it was (genomic_peakdiff, genome and -r files)
 void GtxMark(const char *what);                                  // GTX_TIMING=1: wall-clock mark on stderr (not in the reference)
 void GtxFinish(int code);                                        // flush and leave without the teardown (see genomic_intervals.cpp)
 

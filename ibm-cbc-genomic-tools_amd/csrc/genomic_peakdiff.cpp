@@ -57,6 +57,7 @@ struct ReadFile {
 
 int main(int argc, char *argv[])
 {
+  GtxAcceptGFF(false);                                        // (GFF input stays unsupported here; SAM is read as before)
   bool HELP, HELP2, VERBOSE, REUSE, IGNORE_STRAND;
   const char *RSCRIPT, *OUT_PREFIX, *GENOME_REG_FILE, *SCALING, *NORMALIZATION, *LABELS, *IMAGE_TYPE, *IMAGE_SIZE;
   long MAX_LABEL_VALUE, WIN_SIZE, WIN_DIST, FDR_BINS, IMAGE_RESOLUTION;

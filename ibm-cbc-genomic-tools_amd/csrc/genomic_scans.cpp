@@ -289,11 +289,13 @@ int main(int argc, char *argv[])
   GenomicRegionSet *RefRegSet = NULL;
   GenomicRegionSetIndex *RefIndex = NULL;
   if (strlen(REF_REG_FILE) > 0) {
+    const bool gff_was = GtxAcceptGFF(false);                 // (the -r file stays as it was: GFF is read as signal and control input only)
     if (REF_SORTED) RefRegSet = new GenomicRegionSet((char *)REF_REG_FILE, BUFFER_SIZE, VERBOSE, false, true);
     else {
       RefRegSet = new GenomicRegionSet((char *)REF_REG_FILE, BUFFER_SIZE, VERBOSE, true, true);
       RefIndex = new GenomicRegionSetIndex(RefRegSet, "17,20,23,26");
     }
+    GtxAcceptGFF(gff_was);
   }
   if (RefRegSet == NULL) scanner->PrintRemaining(stdout, (long int)MIN_READS);   // (no -r filter: the same lines, formatted in bulk)
   else if (device_filter) scanner->PrintFiltered(stdout, RefIndex, (long int)MIN_READS);

@@ -123,7 +123,7 @@ int gtx_link_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines
   *needs_host = 0;
   TextSlot *tp = nullptr; bool empty = false; int ticket = 0;
   // (the sorted scanner's rules: nothing about the interval is checked -- zero-length and inverted regions are link's to take)
-  { int rc = text_stage(c, text, bytes, nLines, r, false, 2, nullptr, false, &tp, &ticket, &empty); if (rc || empty) return rc; }
+  { int rc = text_stage(c, text, bytes, nLines, r, false, 2, nullptr, 0, &tp, &ticket, &empty); if (rc || empty) return rc; }
   TextSlot &t = *tp;
   HIPCHK(c, gtx::launch_link_append(t.tri.get(), nLines, c->link.textChrom, c->link.textByStrand, c->link.textTri.get() + 3 * c->link.textN,
                                     c->link.minus.get() + c->link.textN, t.flag.get(), c->stream));

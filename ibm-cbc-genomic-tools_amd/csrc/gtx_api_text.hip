@@ -1,4 +1,4 @@
-// gtx_api_text.hip -- the C ABI's text feed: blocks of region text (BED, SAM) tokenised on the device and counted, covered or scanned
+// gtx_api_text.hip -- the C ABI's text feed: blocks of region text (BED, SAM, GFF) tokenised on the device and counted, covered or scanned
 // where the triples are (gtx_*_add_text), and the subset of a block's lines by their hits (gtx_subset_*).  Host code only (the
 // kernels: gtx_text.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
 #include <hip/hip_runtime.h>
@@ -24,7 +24,7 @@ enum TextMode { TEXT_COUNT, TEXT_COVER, TEXT_SCAN };
 // of add_text and gtx_subset_text.  grouped: the strand-aware outputs (tri2 / w2) are made too when the rules are strand-aware.
 // *tp = the slot, *ticket its number; *empty: a block without lines -- nothing was enqueued but the slot's evParsed, its verdict is 0.
 int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, bool grouped, int scanRules,
-               unsigned long long *labelSum, bool sam, TextSlot **tp, int *ticket, bool *empty)
+               unsigned long long *labelSum, int format, TextSlot **tp, int *ticket, bool *empty)
 {
   HIPCHK(c, hipSetDevice(c->device));
   const int slot = (int)(c->text.seq & 1);
@@ -92,7 +92,7 @@ int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const
   gtxtext::TextDevice d; d.text = t.text.get(); d.segCount = t.seg.get(); d.nl = t.nl.get(); d.tri = t.tri.get(); d.w = t.w.get(); d.flag = t.flag.get();
   d.tri2 = grouped ? t.tri2.get() : nullptr; d.w2 = grouped ? t.w2.get() : nullptr; d.blkMinus = grouped ? t.blk.get() : nullptr;
   d.labelSum = labelSum; d.blockSum = t.sum.get();
-  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, scanRules, sam));
+  HIPCHK(c, gtxtext::launch_tokenize(d, tabs, *r, bytes, (unsigned)nLines, c->stream, scanRules, format));
   return GTX_OK;
 }
 
@@ -104,12 +104,13 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
   if (mode == TEXT_SCAN && r && (r->max_label_value > 1) != c->scan.cur.weighted) return fail(c, GTX_E_ARG, "gtx_scan_add_text: the rules' label weights do not match gtx_scan_begin's");
   if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names))
     { c->err = std::string(who) + ": bad argument"; return GTX_E_ARG; }
-  const bool sam = (flags & GTX_TEXT_SAM) != 0;                  // (the format of the text, not a flag of the count)
-  flags &= ~GTX_TEXT_SAM;
+  if ((flags & GTX_TEXT_SAM) && (flags & GTX_TEXT_GFF)) { c->err = std::string(who) + ": GTX_TEXT_SAM and GTX_TEXT_GFF exclude each other"; return GTX_E_ARG; }
+  const int format = (flags & GTX_TEXT_SAM) ? 1 : (flags & GTX_TEXT_GFF) ? 2 : 0;   // (the format of the text, not a flag of the count: launch_tokenize's numbers)
+  flags &= ~(GTX_TEXT_SAM | GTX_TEXT_GFF);
   TextSlot *tp = nullptr; bool empty = false;
   {
     int rc = text_stage(c, text, bytes, nLines, r, true, mode == TEXT_SCAN ? (c->scan.cur.a.sortedRule ? 2 : 1) : 0,
-                        mode == TEXT_SCAN ? c->scan.cur.labelSum.get() : nullptr, sam, &tp, ticket, &empty);
+                        mode == TEXT_SCAN ? c->scan.cur.labelSum.get() : nullptr, format, &tp, ticket, &empty);
     if (rc || empty) return rc;
   }
   TextSlot &t = *tp;
@@ -170,13 +171,13 @@ int gtx_subset_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, 
   if (!c) return GTX_E_ARG;
   if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_subset_text: gtx_set_refs has not been called");
   if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names) ||
-      (flags & GTX_TEXT_SAM) || r->max_label_value > 1)
+      (flags & (GTX_TEXT_SAM | GTX_TEXT_GFF)) || r->max_label_value > 1)
     return fail(c, GTX_E_ARG, "gtx_subset_text: bad argument");
   if (c->text.slot[c->text.seq & 1].subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_text: the result of the block before last has not been fetched (gtx_subset_result)");
   const int mode = join_mode(c, flags);
   { int rc = join_prepare(c); if (rc) return rc; }
   TextSlot *tp = nullptr; bool empty = false;
-  { int rc = text_stage(c, text, bytes, nLines, r, false, 0, nullptr, false, &tp, ticket, &empty); if (rc) return rc; }
+  { int rc = text_stage(c, text, bytes, nLines, r, false, 0, nullptr, 0, &tp, ticket, &empty); if (rc) return rc; }
   TextSlot &t = *tp;
   if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
   t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;

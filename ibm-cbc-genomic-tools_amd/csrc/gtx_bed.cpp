@@ -464,6 +464,43 @@ bool LooksLikeSam(const char *line)
   return memchr(p, '+', n) == nullptr && memchr(p, '-', n) == nullptr;
 }
 
+GffStatus ParseGffLine(char *line, GffFields *o, std::string *msg)
+{
+  o->n_tokens = CountTokensLike(line, '\t');
+  if (o->n_tokens < 8 || o->n_tokens > 10) { *msg = "wrong number of tokens for GFF format!"; return GFF_WRONG_TOKEN_COUNT; }
+  char *cur = line;
+  o->seqname = TakeToken(&cur, '\t');
+  o->source = TakeToken(&cur, '\t');
+  o->feature = TakeToken(&cur, '\t');
+  o->start = FastAtol(TakeToken(&cur, '\t'));                  // as written: 1-based, inclusive
+  o->stop = FastAtol(TakeToken(&cur, '\t'));
+  o->score = TakeToken(&cur, '\t');
+  o->strand = TakeToken(&cur, '\t')[0];                        // the byte as it stands ('.' stays '.', an empty token is NUL)
+  o->frame = TakeToken(&cur, '\t')[0];
+  o->label = o->n_tokens == 8 ? nullptr : TakeToken(&cur, '\t');
+  o->comment = o->n_tokens > 9 ? TakeToken(&cur, '\t') : nullptr;
+  return GFF_OK;
+}
+
+bool LooksLikeGff(const char *line)
+{
+  const int nt = CountTokensLike(line, '\t');
+  if (nt < 8 || nt > 10) return false;
+  const char *p = line; int tabs = 0;
+  while (*p && tabs < 5) { if (*p == '\t') tabs++; p++; }
+  while (*p == ' ') p++;
+  const size_t n = strcspn(p, "\t");
+  return memchr(p, '+', n) == nullptr && memchr(p, '-', n) == nullptr;   // (a score such as -1.5 or 1e-5 makes the file BED)
+}
+
+std::string GffStrandMessage(char strand)
+{
+  char what[16];
+  if (strand > ' ' && strand < 127) snprintf(what, sizeof what, "'%c'", strand);
+  else snprintf(what, sizeof what, "0x%02x", (unsigned)(unsigned char)strand);
+  return std::string("GFF strand ") + what + " is neither '+' nor '-': such a feature is counted only when the strand is ignored (-i)!";
+}
+
 void BedBlocks(const BedFields &f, std::vector<long> *iv)
 {
   iv->clear();
@@ -855,6 +892,20 @@ void ParsePiece(Piece *p, const PackOptions &o)
       f.start = iv.front(); f.stop = iv.back();
       chrom_len = strlen(s.rname);
       multi = iv.size() > 2;                                       // (one interval: a read like a BED6 line)
+    } else if (o.gff) {
+      char *nl = (char *)memchr(cur, '\n', (size_t)(p->end - cur));
+      if (!nl) break;
+      *nl = 0;
+      char *line = cur;
+      cur = nl + 1;
+      line_no++;
+      GffFields g; std::string msg;
+      if (ParseGffLine(line, &g, &msg) != GFF_OK) { SetErr(&p->err, line_no, msg); break; }
+      // two strand classes per chromosome: a strand-aware run has no place for a feature of a third one
+      if (o.strand_aware && g.strand != '+' && g.strand != '-') { SetErr(&p->err, line_no, GffStrandMessage(g.strand)); break; }
+      f.chrom = g.seqname; f.label = g.label; f.strand = g.strand; f.n_tokens = g.n_tokens;
+      f.start = g.start; f.stop = g.stop;
+      chrom_len = strlen(g.seqname);
     } else {
       char *next = fast_lines ? ParseTabbedLine(cur, p->end, &f, &chrom_len) : nullptr;
       if (next) { cur = next; line_no++; }
@@ -1183,6 +1234,11 @@ bool BedPacker::NextTextBlock(TextBlock *b)
     if (opt_.sam) {                                                  // (a spliced read's key is its first interval's: POS)
       if (!line.empty() && line.find('\0') == std::string::npos && ParseSamLine(&line[0], &sf, &iv, &msg) == SAM_OK) {
         seam_have_ = true; seam_chrom_ = sf.rname; seam_strand_ = sf.strand; seam_start_ = iv.front();
+      } else seam_ok_ = false;
+    } else if (opt_.gff) {
+      GffFields g;
+      if (!line.empty() && line.find('\0') == std::string::npos && ParseGffLine(&line[0], &g, &msg) == GFF_OK) {
+        seam_have_ = true; seam_chrom_ = g.seqname; seam_strand_ = g.strand; seam_start_ = g.start;
       } else seam_ok_ = false;
     } else if (!line.empty() && line.find('\0') == std::string::npos && ParseBedLine(&line[0], &f, &bad) == BED_OK && f.n_tokens != 12) {
       seam_have_ = true; seam_chrom_ = f.chrom; seam_strand_ = f.strand; seam_start_ = f.start;

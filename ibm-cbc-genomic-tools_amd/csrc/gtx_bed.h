@@ -106,6 +106,28 @@ SamStatus ParseSamLine(char *line, SamFields *out, std::vector<long> *iv, std::s
 // the first data line of a file is SAM (GenomicRegionSet::DetectFileFormat, genomic_intervals.cpp:3736-3759)
 bool LooksLikeSam(const char *line);
 
+// ---- one GFF / GTF line (GenomicRegionGFF::Read, genomic_intervals.cpp:3501-3517) -----------------------------
+// TAB-separated, blanks before a token skipped; 8, 9 or 10 tokens: seqname, source, feature, start, end, score, strand, frame
+// [, label [, comment]].  The interval is (seqname, strand, atol(start), atol(end)) as written: 1-based, inclusive.  The strand is
+// the first byte of column 7, kept raw (NUL for an empty token): '.' is not folded into '+' as BED's is.  label == NULL means "_"
+// (an 8-column line).
+struct GffFields {
+  char *seqname, *source, *feature, *score, *label, *comment;   // comment: NULL with fewer than 10 tokens
+  long start, stop;
+  char strand, frame;
+  int n_tokens;
+};
+enum GffStatus { GFF_OK = 0, GFF_WRONG_TOKEN_COUNT };
+// Parses in place (the line is cut into tokens).  On an error *msg receives what follows "Error: Line N: ".
+GffStatus ParseGffLine(char *line, GffFields *out, std::string *msg);
+// the first data line of a file is GFF (DetectFileFormat :3736-3759): 8, 9 or 10 TAB tokens, the 6th without '+' or '-'.  (A leading
+// "##" line makes the file GFF whatever follows, ProcessFileHeader :3725-3728: the caller's to see.)
+bool LooksLikeGff(const char *line);
+// This build's own input error (the engine has two strand classes per chromosome; the reference files a '.' feature as a third
+// strand that overlaps only its like): what follows "Error: Line N: " for a GFF strand byte other than '+' or '-' in a run that
+// does not ignore the strand.
+std::string GffStrandMessage(char strand);
+
 // ---- chromosome table: names in strcmp order, id = rank ------------------------------------------
 class ChromTable {
  public:
@@ -171,6 +193,7 @@ struct PackOptions {
   bool collect_blocks = false;       // ... count without -gaps: "some interval overlaps some interval" (:1167-1172) -- a region with several
                                      // intervals goes out on its own list (PackedBatch::m_*), after the same checks as any other region
   bool sam = false;                  // the lines are SAM alignments (ParseSamLine): a spliced read is a multi-interval region, as a BED12 line is
+  bool gff = false;                  // the lines are GFF / GTF features (ParseGffLine); with strand_aware, a strand byte other than '+' or '-' is an error
   int threads = 0;                   // 0 = hardware concurrency
   IndexGuard *guard = nullptr;       // PACK_OVERLAPS_SORTED with an out-of-order index set (forces one thread)
   bool keep_prefix_on_error = false; // an error leaves the regions of the lines in front of it in the batch (the sorted scanner streams: what it

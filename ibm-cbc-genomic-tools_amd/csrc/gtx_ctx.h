@@ -411,7 +411,7 @@ int join_mode(gtx_ctx *c, uint32_t flags);
 int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted);
 // gtx_api_text.hip
 int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, bool grouped, int scanRules,
-               unsigned long long *labelSum, bool sam, TextSlot **tp, int *ticket, bool *empty);
+               unsigned long long *labelSum, int format, TextSlot **tp, int *ticket, bool *empty);
 
 // Streams reads[0..n) (and weights) through the device in batches; launch(d_reads, d_weights, cnt, off) enqueues the
 // kernels of one batch on the context's stream.  Returns with everything enqueued; the caller's buffers are free again

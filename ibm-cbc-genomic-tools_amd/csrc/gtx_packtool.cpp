@@ -3,11 +3,13 @@
 // CPU test suite checks the packer (line handling, tokenising, order checks, error text and line numbers,
 // thread-count independence) on machines without an MI355X.
 //
-//   gtx_packtool MODE [-t THREADS] [-s] [-a] [-l MAXLABEL] [--sam] [-c CHROM,CHROM,...] [FILE]
+//   gtx_packtool MODE [-t THREADS] [-s] [-a] [-l MAXLABEL] [--sam | --gff] [-c CHROM,CHROM,...] [FILE]
 //     MODE   ou = overlaps/unsorted   os = overlaps/sorted   su = scan/unsorted   ss = scan/sorted
 //     -g / -m / -e   multi-interval regions: on their envelope (-gaps) / listed (count) / one read per interval (coverage)
 //     --sam  the file is SAM: its '@' header lines are skipped (they keep their line numbers; FILE only), the alignments read as
 //            GenomicRegionSAM does; a spliced read's intervals are printed as "# blocks class start end n s1 e1 s2 e2 ..."
+//     --gff  the file is GFF / GTF: its leading '##' lines are skipped (they keep their line numbers; FILE only), the features read as
+//            GenomicRegionGFF does; with -a a strand byte other than '+' or '-' is an error.  (`pack` takes no GFF.)
 //     -s sorted by strand   -a strand-aware classes   -c known chromosomes (default: all seen in FILE order? no:
 //        the list is required for reproducible class ids)
 //   output: one line per packed read "class start end [weight]", then "# lines=N"; errors like the CLIs.
@@ -29,7 +31,7 @@ using namespace gtxhost;
 #include <algorithm>
 #include <thread>
 #include <vector>
-static int SynthBed(bool refs, long long n, unsigned long long seed, const char *out_path, long read_len, bool sam = false)
+static int SynthBed(bool refs, long long n, unsigned long long seed, const char *out_path, long read_len, bool sam = false, bool gff = false)
 {
   static const struct { const char *name; long len; } chr[24] = {   // strcmp order
     {"chr1", 248956422}, {"chr10", 133797422}, {"chr11", 135086622}, {"chr12", 133275309}, {"chr13", 114364328}, {"chr14", 107043718},
@@ -53,7 +55,7 @@ static int SynthBed(bool refs, long long n, unsigned long long seed, const char 
     std::sort(s.begin(), s.end());
     if (refs) for (long long i = 0; i < k; i++) ln[(size_t)i] = 50 + (unsigned)(next() % 1950);
     std::string &t = text[c];
-    t.reserve((size_t)k * (refs ? 40 : sam ? (size_t)(2 * read_len + 100) : 30));
+    t.reserve((size_t)k * (refs ? 40 : sam ? (size_t)(2 * read_len + 100) : gff ? 130 : 30));
     if (sam) {                                                    // SAM: the same reads as alignments, r<i> FLAG 0|16 ... <LEN>M
       static const char base[4] = {'A', 'C', 'G', 'T'};
       std::string seq((size_t)read_len, 'A'), qual((size_t)read_len, 'F');
@@ -65,6 +67,16 @@ static int SynthBed(bool refs, long long n, unsigned long long seed, const char 
         t.append(head, (size_t)h); t += seq; t += '\t'; t += qual;
         h = snprintf(head, sizeof head, "\tNM:i:0\tMD:Z:%ld\tAS:i:%ld\n", read_len, read_len);
         t.append(head, (size_t)h);
+      }
+      return;
+    }
+    if (gff) {                                                    // GTF: the same reads as exon features, 9 columns, an attribute string for a label
+      char line[256];
+      for (long long i = 0; i < k; i++) {
+        const long long id = first[c] + i;
+        const int h = snprintf(line, sizeof line, "%s\tsynth\texon\t%u\t%llu\t.\t%c\t.\tgene_id \"G%lld\"; transcript_id \"T%lld.1\"; exon_number \"%d\";\n",
+                               chr[c].name, s[(size_t)i] + 1, (unsigned long long)s[(size_t)i] + (unsigned long long)read_len, (next() & 1) ? '-' : '+', id / 7, id / 3, (int)(id % 3) + 1);
+        t.append(line, (size_t)h);
       }
       return;
     }
@@ -90,6 +102,7 @@ static int SynthBed(bool refs, long long n, unsigned long long seed, const char 
     fprintf(o, "@HD\tVN:1.6\tSO:coordinate\n");
     for (int c = 0; c < 24; c++) fprintf(o, "@SQ\tSN:%s\tLN:%ld\n", chr[c].name, chr[c].len);
   }
+  if (gff) fprintf(o, "##gff-version 2\n##source-version gtx_packtool synthgff\n");
   for (int c = 0; c < 24; c++) if (fwrite(text[c].data(), 1, text[c].size(), o) != text[c].size()) { fprintf(stderr, "Error: cannot write file '%s'!\n", out_path); return 1; }
   return fclose(o) == 0 ? 0 : 1;
 }
@@ -157,6 +170,12 @@ int main(int argc, char **argv)
     if (argc < 5) { fprintf(stderr, "usage: gtx_packtool synthsam N SEED OUT.sam [LEN]\n"); return 2; }
     return SynthBed(false, atoll(argv[2]), strtoull(argv[3], NULL, 10), argv[4], argc > 5 ? atol(argv[5]) : 100, true);
   }
+  if (m == "synthgff") {
+    // gtx_packtool synthgff N SEED OUT.gtf [LEN]   the reads of `synth` as GTF exon features: a '##' header, 9 columns, strand + or -, an
+    //                                              attribute string (gene_id, transcript_id, exon_number) as the label (lines of ~100 bytes)
+    if (argc < 5) { fprintf(stderr, "usage: gtx_packtool synthgff N SEED OUT.gtf [LEN]\n"); return 2; }
+    return SynthBed(false, atoll(argv[2]), strtoull(argv[3], NULL, 10), argv[4], argc > 5 ? atol(argv[5]) : 100, false, true);
+  }
   if (m == "stats") {
     // the host-side tail probabilities of `genomic_scans peaks` (gtx_stats.h), one "b K P N" / "p K MU" / "g X" query per stdin line
     char kind; double x, y, z;
@@ -201,6 +220,7 @@ int main(int argc, char **argv)
     else if (!strcmp(argv[a], "-z")) opt.collect_zero_length = true;
     else if (!strcmp(argv[a], "-q")) quiet = true;
     else if (!strcmp(argv[a], "--sam")) opt.sam = true;
+    else if (!strcmp(argv[a], "--gff")) opt.gff = true;
     else if (!strcmp(argv[a], "-g")) opt.match_gaps = true;           // -gaps: a multi-interval region on its envelope
     else if (!strcmp(argv[a], "-m")) opt.collect_blocks = true;       // count without -gaps: multi-interval regions on their own list
     else if (!strcmp(argv[a], "-e")) opt.explode_blocks = true;       // coverage without -gaps: every interval a read of its own
@@ -220,10 +240,11 @@ int main(int argc, char **argv)
   else { src = LineSource::Open(file, &err); if (!src) { fprintf(stderr, "%s\n", err.c_str()); return 1; } }
   BedPacker packer_text(src, opt), packer_packed(packed, opt);
   BedPacker &packer = packed ? packer_packed : packer_text;
-  if (opt.sam && src && file) {                              // the '@' header is skipped (its lines counted): a first look counts them
+  if (opt.sam && opt.gff) { fprintf(stderr, "--sam and --gff exclude each other\n"); return 2; }
+  if ((opt.sam || opt.gff) && src && file) {                 // the '@' / '##' header is skipped (its lines counted): a first look counts them
     long h = 0;
     LineSource *peek = LineSource::Open(file, &err);
-    for (char *l = peek ? peek->Next() : NULL; l && l[0] == '@'; l = peek->Next()) h++;
+    for (char *l = peek ? peek->Next() : NULL; l && (opt.sam ? l[0] == '@' : (l[0] == '#' && l[1] == '#')); l = peek->Next()) h++;
     delete peek;
     for (long k = 0; k < h; k++) src->Next();
   }

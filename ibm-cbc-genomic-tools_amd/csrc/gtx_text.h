@@ -1,4 +1,4 @@
-// gtx_text.h -- launch interface of the device-side BED / SAM tokenizer (gtx_text.hip), used by gtx_api_text.hip and gtx_api_link.hip
+// gtx_text.h -- launch interface of the device-side BED / SAM / GFF tokenizer (gtx_text.hip), used by gtx_api_text.hip and gtx_api_link.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,8 +22,8 @@ struct TextTables {               // per reference set: hash table of the chromo
 };
 // scanRules: 0 = the overlap algorithms' rules (gtx_text_rules::sorted_rules), 1 = the unsorted scanner's (an interval with start > stop or
 // stop <= 0 is skipped silently, genomic_intervals.cpp:5039), 2 = the sorted scanner's (nothing about the interval is checked; order as sorted_rules)
-// sam: the lines are SAM alignments (GTX_TEXT_SAM), else BED
-hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules = 0, bool sam = false);
+// format: 0 = the lines are BED, 1 = SAM alignments (GTX_TEXT_SAM), 2 = GFF / GTF features (GTX_TEXT_GFF)
+hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules = 0, int format = 0);
 void build_tables(const gtx_text_rules &r, std::vector<int32_t> *table, unsigned *mask, std::string *blob);
 
 // ---- gtx_subset_text: the lines of a tokenised block that are kept, byte for byte ----

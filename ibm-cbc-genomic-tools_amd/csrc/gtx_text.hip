@@ -1,4 +1,4 @@
-// gtx_text.hip -- BED or SAM text to packed triples ON THE DEVICE (gtx_count_add_text / gtx_coverage_add_text of include/gtx.h).
+// gtx_text.hip -- BED, SAM or GFF text to packed triples ON THE DEVICE (gtx_count_add_text / gtx_coverage_add_text of include/gtx.h).
 //
 // What the reference does per query line (GenomicRegionBED::Read, gtools/genomic_intervals.cpp:2157-2182; tokenizer
 // core.cpp:577-625; FileBufferText::Next core.cpp:241-259): cut the line at tabs, atol() two columns, look the chromosome up,
@@ -23,6 +23,11 @@
 // whose 128 lines are longer than that on average goes to the host packer, as do spliced reads (N), '=' in a CIGAR, a SEQ of another
 // length than the CIGAR's fragment and everything else outside parse_sam_line's plain case.  The 11th and later columns are read only
 // as far as the newline pass reads every byte.
+// GFF / GTF (GTX_TEXT_GFF, GenomicRegionGFF::Read :3501-3517): the same passes and the same 72 KiB of staging (a GENCODE exon line is a
+// few hundred bytes); the parse block reads the seqname, columns 4 and 5 as they stand (1-based, inclusive) and the strand byte of
+// column 7 of each feature (parse_gff_line).  A line of another token count than 8, 9 or 10, a strand byte other than '+' or '-' (a '.'
+// is legal when the strand is ignored and an input error when it is not: the host decides), a sign on a coordinate and everything else
+// outside parse_gff_line's plain case go to the host packer.
 // The counting kernels then run on the triples where they are.
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -41,7 +46,7 @@ typedef unsigned long long u64;
 static constexpr int kSeg = 1024;                  // bytes per newline-count segment (one wave: 64 lanes x 16 bytes)
 static constexpr int kLines = 128;                 // lines per parse block
 static constexpr int kLdsText = 40 * 1024;         // bytes of text a parse block stages (lines of 320 bytes on average fit)
-static constexpr int kLdsSam = 72 * 1024;          // ... of SAM text (GTX_TEXT_SAM): lines of ~570 bytes on average fit -- a 150 bp read with
+static constexpr int kLdsSam = 72 * 1024;          // ... of SAM or GFF text (GTX_TEXT_SAM, GTX_TEXT_GFF): lines of ~570 bytes on average fit -- a 150 bp read with
                                                    // its QUAL and a few tags is 400-500 -- and two parse blocks still share a CU's 160 KiB
 
 __device__ __forceinline__ unsigned nl_mask16(const uint4 v)
@@ -266,10 +271,82 @@ __device__ __forceinline__ bool parse_sam_line(PTR s, unsigned b, unsigned e, bo
   return true;
 }
 
-template <bool SAM>
+// one GFF / GTF feature (GenomicRegionGFF::Read, genomic_intervals.cpp:3501-3517) in the plain case: 8, 9 or 10 TAB-separated tokens, the
+// first eight non-empty and without a blank, '\r' or NUL; columns 4 and 5 of 1-10 decimal digits; column 7 one byte, '+' or '-'; column 9,
+// when there is one, non-empty and not beginning with a byte <= ' ' (the host's tokenizer skips blanks in front of a token, atol more);
+// column 10, when there is one, non-empty; no '\r' at the end of the line.  (A NUL in column 9 or 10 only ends what the host reads of
+// text that makes no triple; one in front of an 11th tab makes the device the more cautious of the two.)  Out: the seqname's length (it
+// begins the line), start = column 4, stop = column 5 as written, the strand byte, hasLabel = there is a column 9, and its atol value
+// when wantLabel (the BED path's column 4 rules).
+template <class PTR>
+__device__ __forceinline__ bool parse_gff_line(PTR s, unsigned b, unsigned e, bool wantLabel, unsigned &nameLen, long long &S, long long &E,
+                                               int &strand, long long &label, bool &hasLabel)
+{
+  unsigned p = b;
+  auto token = [&](bool last) -> bool {                            // [p, tab or, for the last one, the line's end); p ends behind it
+    const unsigned q = p;
+    for (; p < e; p++) {
+      const unsigned char c = s[p];
+      if (c == '\t') break;
+      if (c == ' ' || c == '\r' || c == 0) return false;
+    }
+    return (last || p < e) && p > q;
+  };
+  auto number = [&](u64 &out) -> bool {                            // 1-10 digits, then the tab
+    const unsigned q = p; u64 v = 0;
+    while (p < e && (unsigned)(s[p] - '0') < 10u) { v = v * 10 + (unsigned)(s[p] - '0'); p++; }
+    if (p == q || p - q > 10 || p >= e || s[p] != '\t') return false;
+    out = v;
+    return true;
+  };
+  if (!token(false)) return false;                                 // seqname
+  nameLen = p - b;
+  p++;
+  if (!token(false)) return false;                                 // source
+  p++;
+  if (!token(false)) return false;                                 // feature
+  p++;
+  u64 v4, v5;
+  if (!number(v4)) return false;                                   // START
+  p++;
+  if (!number(v5)) return false;                                   // END
+  p++;
+  if (!token(false)) return false;                                 // score
+  p++;
+  if (p + 1 >= e || (s[p] != '+' && s[p] != '-') || s[p + 1] != '\t') return false;   // strand: one byte and the tab behind it
+  strand = s[p];
+  p += 2;
+  if (!token(true)) return false;                                  // frame: the last token of an 8-column line
+  label = 0; hasLabel = false;
+  if (p < e) {                                                     // s[p] == '\t': column 9, the label
+    const unsigned q = ++p;
+    if (q >= e || (unsigned char)s[q] <= ' ') return false;        // empty (the host counts 8 tokens), or atol and the tokenizer would skip bytes
+    while (p < e && s[p] != '\t') p++;
+    hasLabel = true;
+    if (wantLabel) {                                               // atol: optional sign, digits, the rest ignored; no digits = 0
+      unsigned r = q; bool neg = false;
+      if (s[r] == '-') { neg = true; r++; } else if (s[r] == '+') r++;
+      u64 v = 0; unsigned nd = 0;
+      while (r < p && (unsigned)(s[r] - '0') < 10u) { v = v * 10 + (unsigned)(s[r] - '0'); r++; if (++nd > 18) return false; }
+      label = neg ? -(long long)v : (long long)v;
+    }
+    if (p < e) {                                                   // column 10, the comment
+      const unsigned c = ++p;
+      while (p < e && s[p] != '\t') p++;
+      if (p == c || p < e) return false;                           // empty, or an 11th token: "wrong number of tokens" is the host's to say
+    }
+  }
+  if (s[e - 1] == '\r') return false;                              // CRLF
+  S = (long long)v4; E = (long long)v5;
+  return true;
+}
+
+enum { kFmtBed = 0, kFmtSam = 1, kFmtGff = 2 };                    // the `format` of launch_tokenize
+
+template <int FMT>
 __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
 {
-  constexpr int kStage = SAM ? kLdsSam : kLdsText;
+  constexpr int kStage = FMT == kFmtBed ? kLdsText : kLdsSam;
   __shared__ __attribute__((aligned(16))) unsigned char lds[kStage];
   __shared__ int tooLong;
   __shared__ unsigned long long sumLabels;
@@ -301,7 +378,8 @@ __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
     const unsigned b = (unsigned)((j ? (size_t)a.nl[j - 1] + 1 : 0) - a0), e = (unsigned)((size_t)a.nl[j] - a0);
     long long S = 0, E = 0, label = 0; int strand = '+'; unsigned nameOff = b, tokLen = 0; bool hasLabel = true;
     plain = false;
-    if (SAM) plain = parse_sam_line((const unsigned char *)lds, b, e, a.weighted != 0, nameOff, tokLen, S, E, strand, label);
+    if (FMT == kFmtSam) plain = parse_sam_line((const unsigned char *)lds, b, e, a.weighted != 0, nameOff, tokLen, S, E, strand, label);
+    else if (FMT == kFmtGff) plain = parse_gff_line((const unsigned char *)lds, b, e, a.weighted != 0, tokLen, S, E, strand, label, hasLabel);
     else {
       long long v2 = 0, v3 = 0; int nTok = 0;
       plain = parse_line((const unsigned char *)lds, b, e, a.weighted != 0, v2, v3, nTok, tokLen, strand, label);
@@ -320,7 +398,8 @@ __global__ __launch_bounds__(kLines) void text_parse_kernel(ParseArgs a)
         auto key_of = [&](auto src, unsigned pb, unsigned pe, unsigned &q0, unsigned &qlen, int &qs, long long &qS) -> bool {
           long long q2 = 0, q3 = 0, ql = 0; int qn = 0;
           q0 = pb; qs = '+';
-          if (SAM) return parse_sam_line(src, pb, pe, false, q0, qlen, qS, q3, qs, ql);
+          if (FMT == kFmtSam) return parse_sam_line(src, pb, pe, false, q0, qlen, qS, q3, qs, ql);
+          if (FMT == kFmtGff) { bool hl = false; return parse_gff_line(src, pb, pe, false, qlen, qS, q3, qs, ql, hl); }
           const bool ok = parse_line(src, pb, pe, false, q2, q3, qn, qlen, qs, ql);
           qS = q2 + 1;
           return ok;
@@ -430,7 +509,7 @@ __global__ __launch_bounds__(256) void text_void_kernel(int *__restrict__ tri, u
   for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nLines; j += (size_t)gridDim.x * 256) tri[3 * j] = -1;
 }
 
-hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules, bool sam)
+hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules, int format)
 {
   const unsigned nSeg = (unsigned)((bytes + kSeg - 1) / kSeg);
   nl_count_kernel<<<nSeg, 64, 0, st>>>(d.text, bytes, d.segCount);
@@ -451,8 +530,9 @@ hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_t
     hipError_t e = hipMemsetAsync(d.blkMinus, 0, sizeof(unsigned) * ((size_t)nBlocks + 1), st);
     if (e != hipSuccess) return e;
   }
-  if (sam) text_parse_kernel<true><<<nBlocks, kLines, 0, st>>>(a);
-  else text_parse_kernel<false><<<nBlocks, kLines, 0, st>>>(a);
+  if (format == kFmtSam) text_parse_kernel<kFmtSam><<<nBlocks, kLines, 0, st>>>(a);
+  else if (format == kFmtGff) text_parse_kernel<kFmtGff><<<nBlocks, kLines, 0, st>>>(a);
+  else text_parse_kernel<kFmtBed><<<nBlocks, kLines, 0, st>>>(a);
   text_void_kernel<<<256, 256, 0, st>>>(d.tri, nLines, d.flag, d.labelSum ? d.blockSum : nullptr, d.labelSum);
   if (a.blkMinus) {
     nl_scan_kernel<<<1, 1024, 0, st>>>(d.blkMinus, nBlocks);

@@ -22,6 +22,7 @@ OFFSET_SKIP_REF_GAPS = 64
 OFFSET_FROM_QUERY = 128
 SIGNAL_PER_REF = 256
 TEXT_SAM = 512            # gtx_*_add_text: the block is SAM alignments, not BED
+TEXT_GFF = 2048           # gtx_*_add_text: the block is GFF / GTF features, not BED
 SUBSET_INVERT = 1024      # gtx_subset_text: keep the lines without hits (-inv)
 LINK_SUM = 1              # gtx_link: fold the values (at most one of the three)
 LINK_MIN = 2
@@ -319,6 +320,17 @@ def window_select_limits():
     return int(t.value), int(w.value)
 
 
+def _text_format(sam, fmt=None):
+    """the format flag of a text block.  fmt, when given, is the flag as it goes to the library (0, TEXT_SAM, TEXT_GFF).  Else `sam`
+    decides as it always did -- any true value: SAM alignments -- except that one of the two format flags stands for itself, so that
+    a caller with one positional argument for the format can pass TEXT_GFF."""
+    if fmt is not None:
+        return int(fmt)
+    if not isinstance(sam, (bool, np.bool_)) and isinstance(sam, (int, np.integer)) and int(sam) in (TEXT_SAM, TEXT_GFF):
+        return int(sam)
+    return TEXT_SAM if sam else 0
+
+
 class Engine:
     """One context on one GPU (one per process in multi-GPU runs)."""
 
@@ -403,7 +415,7 @@ class Engine:
         self._chk(self.lib.gtx_count_end(self.ctx, _ptr(hits), ctypes.byref(info)))
         return hits[:self.n_refs], info.as_dict()
 
-    def _reduce_text(self, which, blocks, rules, flags, sam):
+    def _reduce_text(self, which, blocks, rules, flags, sam, fmt=None):
         begin, add, end = (getattr(self.lib, "gtx_%s_%s" % (which, f)) for f in ("begin", "add_text", "end"))
         blocks = list(blocks)
         per_block = rules if isinstance(rules, (list, tuple)) else [rules] * len(blocks)
@@ -413,7 +425,7 @@ class Engine:
         verdicts = []
         for text, r in zip(blocks, per_block):
             t = ctypes.c_int(-1)
-            self._chk(add(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(r), int(flags) | (TEXT_SAM if sam else 0), ctypes.byref(t)))
+            self._chk(add(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(r), int(flags) | _text_format(sam, fmt), ctypes.byref(t)))
             redo = ctypes.c_int(0)
             self._chk(self.lib.gtx_text_result(self.ctx, t.value, ctypes.byref(redo)))
             verdicts.append(redo.value)
@@ -422,15 +434,15 @@ class Engine:
         self._chk(end(self.ctx, _ptr(out), ctypes.byref(info)))
         return out[:self.n_refs], info.as_dict(), verdicts
 
-    def count_text(self, blocks, rules, flags=READS_SORTED, sam=False):
+    def count_text(self, blocks, rules, flags=READS_SORTED, sam=False, fmt=None):
         """gtx_count_begin / gtx_count_add_text per block of text (bytes of complete lines) / gtx_count_end; sam=True: SAM alignments
-        (GTX_TEXT_SAM).  rules: one TextRules for every block, or a list with one per block (each block's own seam key).
+        (GTX_TEXT_SAM); fmt=TEXT_GFF: GFF / GTF features (fmt: the format flag as it goes to the library).  rules: one TextRules for every block, or a list with one per block (each block's own seam key).
         Returns (hits, info, needs_host verdict per block) -- a block that comes back was not counted."""
-        return self._reduce_text("count", blocks, rules, flags, sam)
+        return self._reduce_text("count", blocks, rules, flags, sam, fmt)
 
-    def coverage_text(self, blocks, rules, flags=READS_SORTED, sam=False):
+    def coverage_text(self, blocks, rules, flags=READS_SORTED, sam=False, fmt=None):
         """the same through gtx_coverage_begin / gtx_coverage_add_text / gtx_coverage_end: (coverage, info, verdicts)"""
-        return self._reduce_text("coverage", blocks, rules, flags, sam)
+        return self._reduce_text("coverage", blocks, rules, flags, sam, fmt)
 
     def subset_text(self, blocks, rules, flags=0):
         """gtx_subset_text / gtx_subset_result per block of text (bytes of complete lines), two blocks in flight: per block
@@ -761,9 +773,9 @@ class Engine:
                                     preprocess.encode()[0:1], int(flags), _ptr(out), _ptr(off)))
         return out[:tot], off
 
-    def scan_stream(self, pieces, class_len, win_step, win_size, preprocess="1", weighted=False, flags=0, sam=False):
+    def scan_stream(self, pieces, class_len, win_step, win_size, preprocess="1", weighted=False, flags=0, sam=False, fmt=None):
         """gtx_scan_begin .. gtx_scan_end over `pieces`: (reads, weights | None, flags) tuples for packed host batches, or (text bytes,
-        TextRules, flags) for blocks of BED text tokenised on the device (sam=True: SAM alignments, GTX_TEXT_SAM).  Returns (windows,
+        TextRules, flags) for blocks of BED text tokenised on the device (sam=True: SAM alignments, GTX_TEXT_SAM; fmt=TEXT_GFF: GFF features).  Returns (windows,
         class offsets, label sum of the text blocks the device took, tickets' needs_host verdicts)."""
         cl = np.ascontiguousarray(class_len, dtype=np.int32)
         off, tot = scan_layout(cl, win_step, win_size)
@@ -773,7 +785,7 @@ class Engine:
         for a, b, fl in pieces:
             if isinstance(a, (bytes, bytearray)):
                 t = ctypes.c_int(-1)
-                self._chk(self.lib.gtx_scan_add_text(self.ctx, a, len(a), a.count(b"\n"), ctypes.byref(b), int(fl) | (TEXT_SAM if sam else 0), ctypes.byref(t)))
+                self._chk(self.lib.gtx_scan_add_text(self.ctx, a, len(a), a.count(b"\n"), ctypes.byref(b), int(fl) | _text_format(sam, fmt), ctypes.byref(t)))
                 redo = ctypes.c_int(0)
                 self._chk(self.lib.gtx_text_result(self.ctx, t.value, ctypes.byref(redo)))
                 verdicts.append(redo.value)

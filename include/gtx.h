@@ -546,8 +546,18 @@ typedef struct gtx_text_rules {
  * value as its label; order check and validity rules as for BED.  Spliced reads, '=' and every other line go back to the caller
  * (needs_host), as do blocks whose 128-line groups average more than ~570 bytes a line.  gtx_text_rules is the same. */
 #define GTX_TEXT_SAM       512u
+/* GTX_TEXT_GFF in the same flags (not together with GTX_TEXT_SAM: GTX_E_ARG): the block is GFF / GTF features (GenomicRegionGFF::Read
+ * genomic_intervals.cpp:3501-3517) without the leading '##' lines, not BED.  The plain case: 8, 9 or 10 TAB-separated columns, the
+ * first eight non-empty and without blanks, '\r' or NUL; columns 4 and 5 of 1-10 decimal digits without a sign, both below 2^31 - 2;
+ * column 7 exactly one byte, '+' or '-'; column 9, when present, non-empty and not beginning with a byte <= ' '; column 10, when
+ * present, non-empty; no '\r' at the end of the line.  A feature becomes (class of column 1 [+ n_chrom when strand_aware and column 7
+ * is '-'], column 4, column 5) as written -- 1-based, inclusive -- with column 9's atol value as its label (0 for an 8-column line;
+ * more than 18 digits are not plain); order check and validity rules as for BED.  A '.' or any other strand byte, a '#' comment, an
+ * 11th column and every other line go back to the caller (needs_host), as do blocks whose 128-line groups average more than ~570
+ * bytes a line.  gtx_text_rules is the same. */
+#define GTX_TEXT_GFF      2048u
 /* text: host memory (page-locked memory is read by the DMA engine directly and must stay untouched until gtx_text_result of the
- * ticket has returned).  flags as gtx_count_add / gtx_coverage_add, and GTX_TEXT_SAM.  Up to two blocks are in flight: the call waits for the block
+ * ticket has returned).  flags as gtx_count_add / gtx_coverage_add, and GTX_TEXT_SAM or GTX_TEXT_GFF.  Up to two blocks are in flight: the call waits for the block
  * before last. */
 int gtx_count_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
 int gtx_coverage_add_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
