@@ -1,4 +1,4 @@
-"""CPU suite: CreateGenomicRegionSetAnnotator of the class layer (csrc/genomic_intervals.cpp), called by tests/tools/annotator_caller.cpp
+"""CPU suite: CreateGenomicRegionSetAnnotator of the class layer (csrc/gtx_host_join.cpp), called by tests/tools/annotator_caller.cpp
 the way `genomic_regions annotator` calls it, against the restatement (tests/annotate_restate.py): the manifest's builder cases, and a
 few hundred seeded genes with min < max, with and without a genome file, with and without -i.  No GPU is involved: the trimming
 walks the class layer's own bin index on the host."""

@@ -1,5 +1,5 @@
 """genomic_adjacent (csrc/genomic_adjacent.cpp; GenomicRegionSet::RunGlobalInvert / RunGlobalCalcDistances / RunGlobalTest in
-csrc/genomic_intervals.cpp) against the restatement's rendering (tests/adjacent_restate.py), byte for byte: stdout, stderr and the exit
+csrc/gtx_host_link.cpp) against the restatement's rendering (tests/adjacent_restate.py), byte for byte: stdout, stderr and the exit
 code -- on the hand-derived vectors, on a random 50 000-line file per operation, and on files with an error in their middle."""
 import gzip
 import json

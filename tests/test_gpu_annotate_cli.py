@@ -1,4 +1,4 @@
-"""genomic_annotate (csrc/genomic_annotate.cpp; GtxPrintAnnotations and CreateGenomicRegionSetAnnotator in csrc/genomic_intervals.cpp,
+"""genomic_annotate (csrc/genomic_annotate.cpp; GtxPrintAnnotations and CreateGenomicRegionSetAnnotator in csrc/gtx_host_join.cpp,
 kept pairs from the device: gtx_join_annotate): stdout and stderr byte-equal to the restated lines (tests/annotate_restate.py) on the
 golden genes (tests/golden/genes.bed.gz) against a few thousand seeded test regions.  The pairs the restatement renders come from
 the oracle's `pairs` rows (oracle/gtx_oracle.c) for the genes and for the restated upstream set written out as BED; the manifest's

@@ -1,4 +1,4 @@
-"""genomic_apps profile / heatmap (csrc/genomic_apps.cpp, GtxSignalBins in csrc/genomic_intervals.cpp, bins from the device).
+"""genomic_apps profile / heatmap (csrc/genomic_apps.cpp, GtxSignalBins in csrc/gtx_host_join.cpp, bins from the device).
 Expected output: the reference regions are shifted here as the reference shifts them in memory (ShiftPos,
 genomic_intervals.cpp:524-531) and written with unique labels; the oracle's `pairs` on that file gives the (signal line,
 reference label) pairs in the bin index's order; GetOffsetFrom and the x / z / bin arithmetic in IEEE doubles come from

@@ -1,4 +1,4 @@
-"""genomic_overlaps overlap / intersect (csrc/genomic_overlaps.cpp, GtxPrintPairs in csrc/genomic_intervals.cpp, pairs from the
+"""genomic_overlaps overlap / intersect (csrc/genomic_overlaps.cpp, GtxPrintPairs in csrc/gtx_host_join.cpp, pairs from the
 device join).  Expected output: the oracle's `pairs` rows (query line, reference label, in the reference's order) rendered
 through a restatement of GenomicRegionBED::Print (genomic_intervals.cpp:2188-2220) and Constrain (:2543-2561) below; errors:
 the oracle's exit code and message, with the pairs before the error on stdout."""

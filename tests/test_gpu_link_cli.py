@@ -1,4 +1,4 @@
-"""genomic_regions link (csrc/genomic_regions.cpp, GenomicRegionSet::RunGlobalLink in csrc/genomic_intervals.cpp) against the
+"""genomic_regions link (csrc/genomic_regions.cpp, GenomicRegionSet::RunGlobalLink in csrc/gtx_host_link.cpp) against the
 restatement's rendering (tests/link_restate.py), byte for byte: stdout, stderr and the exit code.  Every run is made three ways -- the
 host packer (GTX_TEXT_ON_DEVICE=0), the device tokenizer (=1), and the tokenizer over blocks of 20 kB -- and GTX_TEXT_TRACE's line must
 say which way the text went (and, for a label function, where the fold ran): a run may not pass by quietly taking the other path.  A

@@ -1,4 +1,4 @@
-"""genomic_overlaps offset (csrc/genomic_overlaps.cpp, GtxPrintOffsets in csrc/genomic_intervals.cpp, offsets from the device).
+"""genomic_overlaps offset (csrc/genomic_overlaps.cpp, GtxPrintOffsets in csrc/gtx_host_join.cpp, offsets from the device).
 Expected output: the oracle's `pairs` rows in the reference's order (without -S `pairs REF TEST`, rows (test line, reference
 label); under -S `pairs -S TEST REF`, rows (reference line, test label)) rendered as gtools/genomic_overlaps.cpp:545-670 prints
 them, through the restatement of GetOffsetFrom / CalcOffsetsWithoutGaps in oracle/restate.py and C's float arithmetic below.  Error and edge cases are

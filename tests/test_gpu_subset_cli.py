@@ -1,4 +1,4 @@
-"""genomic_subset (csrc/genomic_subset.cpp, GtxPrintSubset in csrc/genomic_intervals.cpp): the test regions that overlap some
+"""genomic_subset (csrc/genomic_subset.cpp, GtxPrintSubset in csrc/gtx_host_join.cpp): the test regions that overlap some
 reference region, with -inv those that overlap none.  Expected output: the query lines whose count in the oracle's `qstats`
 (oracle/gtx_oracle.c: the reference's CountQueryOverlaps per query line) is > 0 (== 0 with -inv), each rendered through a
 restatement of GenomicRegionBED::Read and ::Print (genomic_intervals.cpp:2157-2218) below, the file's header lines first; errors:
@@ -320,6 +320,57 @@ def test_a_line_the_device_does_not_take_sends_its_block_back(files, kind, where
                 assert trace["block"] >= 3 and trace["on_device"] == trace["block"] - 1, (wname, trace)
                 assert trace["line"] <= at + 1 and sum(len(l) + 1 for l in lines[trace["line"] - 1:at + 1]) <= (1 << 20), (wname, trace)
         assert outs[0] == outs[1] == outs[2]
+
+
+def text_blocks(data, block_bytes=1 << 20):
+    """[first line, last line] (1-based) of the blocks the text path reads: the set's constructor takes line 1, then up to
+    block_bytes at a time, cut behind the last complete line (LineSource::ReadTextInto)"""
+    pos, line, out = data.index(b"\n") + 1, 2, []
+    while pos < len(data):
+        keep = data[pos:pos + block_bytes].rindex(b"\n") + 1
+        n = data.count(b"\n", pos, pos + keep)
+        out.append((line, line + n - 1))
+        pos += keep; line += n
+    return out
+
+
+COUNT_TRACE = re.compile(r"^\[gtx text\] blocks tokenised on the device: (\d+), sent back to the host packer: (\d+), packed on the host from the start: (\d+)\n", re.M)
+
+
+def test_a_refusal_in_the_second_of_two_blocks_in_flight(tmp_path):
+    """Three blocks of 1 MB, the one line the device does not take in the middle of block 2: its verdict comes in while block 3 is in
+    flight.  The two users of the text pump part ways there: genomic_overlaps count packs block 2 on the host and keeps block 3's
+    counts from the device; genomic_subset hands the file to the loop from block 2's first line on and drops what block 3 selected."""
+    rng = np.random.default_rng(7)
+    write(tmp_path / "refs.bed", bed_lines(rng, N_REF, SPAN, LMAX, prefix="r"))
+    lines = bed_lines(rng, 80_000, SPAN, LMAX)
+    blocks = text_blocks("".join(l + "\n" for l in lines).encode())
+    assert len(blocks) == 3, blocks
+    at = (blocks[1][0] + blocks[1][1]) // 2                                      # (file line, 1-based)
+    lines[at - 1] = odd_line("plus-sign", lines[at - 1])                        # (a sign: neither tokenizer takes it; a leading zero the count path does)
+    assert not lines[at - 1].split("\t")[1].startswith("+0")
+    write(tmp_path / "odd.bed", lines)
+    blocks = text_blocks((tmp_path / "odd.bed").read_bytes())                    # (the line is shorter now)
+    assert len(blocks) == 3 and blocks[1][0] + 100 < at < blocks[1][1] - 100, blocks   # in block 2, off its seams
+
+    def count(env):
+        e = dict(os.environ, GTX_TEXT_TRACE="1", **env)
+        r = subprocess.run([os.path.join(CSRC, "genomic_overlaps"), "count", "-i", "refs.bed", "odd.bed"], capture_output=True, cwd=tmp_path, env=e)
+        err = r.stderr.decode()
+        m = COUNT_TRACE.search(err)
+        return r.returncode, r.stdout, COUNT_TRACE.sub("", err), None if m is None else tuple(int(g) for g in m.groups())
+
+    rc0, out0, err0, trace0 = count({"GTX_TEXT_ON_DEVICE": "0"})
+    rc1, out1, err1, trace1 = count(WAYS[2][1])
+    assert (rc0, err0, trace0) == (0, "", None) and len(out0) > 0
+    assert (rc1, err1, trace1) == (0, "", (2, 1, 0))
+    assert out1 == out0
+
+    rc0, out0, err0, trace0 = tool(["-i", "refs.bed", "odd.bed"], tmp_path, WAYS[0][1])
+    rc1, out1, err1, trace1 = tool(["-i", "refs.bed", "odd.bed"], tmp_path, WAYS[2][1])
+    assert (rc0, err0, trace0) == (0, "", None) and 0.1 < out0.count("\n") / len(lines) < 0.9
+    assert (rc1, err1) == (0, "") and trace1 == dict(on_device=1, block=2, line=blocks[1][0])
+    assert out1 == out0
 
 
 # ---- errors: exit 1, the reference's message and line number, the lines selected before it on stdout ----
