@@ -4,6 +4,7 @@
 // for the span's first region from one extra load; the gap pass takes the class of the region behind the same way.
 #include <climits>
 #include "gtx_adjacent.h"
+#include "gtx_compact.h"
 
 namespace gtx {
 namespace {
@@ -75,8 +76,6 @@ __global__ __launch_bounds__(kAdjThreads) void adjacent_pair_kernel(const int *_
     tileSums[blockIdx.x] = t;
   }
 }
-
-constexpr int kPartThreads = 1024, kPartBatch = 8;
 
 // the tiles' sums added up in one block
 __global__ __launch_bounds__(kPartThreads) void adjacent_reduce_kernel(const uint2 *__restrict__ tileSums, i64 nt, AdjInfo *info)
@@ -181,42 +180,15 @@ __global__ __launch_bounds__(kAdjThreads) void adjacent_gap_kernel(const int *__
   }
 }
 
-// exclusive sum of the spans' counts in one block, each lane over a run of consecutive spans with its loads out eight at a time
-// (gtx_select.hip: select_prefix_kernel); base[ns] = all gaps.  Then what is reported: without a bad region all of them, else the
-// gaps owned by the regions in front of the first bad one, U -- those of the spans in front of U's and of the regions of U's span
-// below U, counted here by one lane each.
+// exclusive sum of the spans' counts in one block (block_exclusive_sum, gtx_compact.h); base[ns] = all gaps.  Then what is reported:
+// without a bad region all of them, else the gaps owned by the regions in front of the first bad one, U -- those of the spans in
+// front of U's and of the regions of U's span below U, counted here by one lane each.
 __global__ __launch_bounds__(kPartThreads) void adjacent_prefix_kernel(const unsigned *__restrict__ count, i64 ns, i64 *__restrict__ base, const int *__restrict__ tri,
                                                                       i64 n, const i64 *__restrict__ bounds, int nBounds, GapInfo *info)
 {
   __shared__ i64 sh[kPartThreads];
   const int tid = threadIdx.x;
-  const i64 per = (ns + kPartThreads - 1) / kPartThreads, b = min((i64)tid * per, ns), e = min(b + per, ns);
-  i64 a = 0;
-  for (i64 k = b; k < e; k += kPartBatch) {
-    unsigned v[kPartBatch];
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? count[k + j] : 0u;
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) a += v[j];
-  }
-  sh[tid] = a;
-  __syncthreads();
-  for (int dd = 1; dd < kPartThreads; dd <<= 1) {
-    const i64 o = tid >= dd ? sh[tid - dd] : 0;
-    __syncthreads();
-    sh[tid] += o;
-    __syncthreads();
-  }
-  i64 run = tid > 0 ? sh[tid - 1] : 0;
-  for (i64 k = b; k < e; k += kPartBatch) {
-    unsigned v[kPartBatch];
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? count[k + j] : 0u;
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) if (k + j < e) { base[k + j] = run; run += v[j]; }
-  }
-  if (tid == kPartThreads - 1) base[ns] = sh[tid];
-  __syncthreads();
+  block_exclusive_sum(count, ns, base, sh);
   const u64 U = info->firstBad;
   const i64 spanOfU = U == ~0ull ? 0 : (i64)(U / kAdjSpan);
   i64 mine = 0;

@@ -410,6 +410,50 @@ int gtx_scan_drop(gtx_ctx *c, int slot)
   return GTX_OK;
 }
 
+} // extern "C" (templates below)
+
+// ---- the tile compactions (gtx_compact.h): window selection, window filter, peak candidates ----
+// A device entry behind its argument checks: the passes' scratch for n_windows (a pass may still be reading what it held: a sync in
+// front of a growth), launch(tileCount, tileBase) enqueued, the number kept fetched.  It returns with the stream idle.
+template <class Launch>
+static int compact_device(gtx_ctx *c, int64_t n_windows, int64_t *n_kept, Launch launch)
+{
+  CompactState &s = c->cmp;
+  const size_t nt = (size_t)gtx::compact_tiles(n_windows);
+  if (!s.total) HIPCHK(c, s.total.alloc(1));
+  if (nt > s.count.cap || nt + 1 > s.base.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, s.count.reserve(nt)); HIPCHK(c, s.base.reserve(nt + 1));
+  }
+  HIPCHK(c, launch(s.count.get(), s.base.get()));
+  HIPCHK(c, hipMemcpyAsync(s.total.get(), s.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_kept = *s.total.get();
+  return GTX_OK;
+}
+
+// A host entry behind its argument checks: device(d_ordinals, d_rows), the device entry, into the context's buffers for `capacity`
+// rows of rowBytes; then the first min(kept, capacity) ordinals and rows out.
+template <class Device>
+static int compact_host(gtx_ctx *c, int64_t capacity, size_t rowBytes, int64_t *ordinals, void *rows, int64_t *n_kept, Device device)
+{
+  CompactState &s = c->cmp;
+  HIPCHK(c, hipSetDevice(c->device));
+  if ((size_t)capacity > s.ord.cap || (size_t)capacity * rowBytes > s.rows.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, s.ord.reserve((size_t)capacity)); HIPCHK(c, s.rows.reserve((size_t)capacity * rowBytes));
+  }
+  int rc = device(s.ord.get(), s.rows.get()); if (rc) return rc;
+  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
+  if (got) {
+    HIPCHK(c, hipMemcpy(ordinals, s.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(rows, s.rows.get(), got * rowBytes, hipMemcpyDeviceToHost));
+  }
+  return GTX_OK;
+}
+
+extern "C" {
+
 // ---- window selection (gtx_select.hip) ----
 int gtx_window_select_limits(int32_t *tile, int32_t *lds_max_w)
 {
@@ -439,20 +483,16 @@ int gtx_window_select_device(gtx_ctx *c, const void *const *d_tested, const void
   if (n_windows == 0) return GTX_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t stride = ctl ? (size_t)W + 1 : 1;
-  const int64_t nt = gtx::select_tiles(n_windows);
-  if (!c->sel.total) HIPCHK(c, c->sel.total.alloc(1));
-  if (stride * n_tested > c->sel.tab.cap || (size_t)nt > c->sel.count.cap || (size_t)nt + 1 > c->sel.base.cap) {
+  if (stride * n_tested > c->sel.tab.cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, c->sel.tab.reserve(stride * n_tested)); HIPCHK(c, c->sel.count.reserve((size_t)nt)); HIPCHK(c, c->sel.base.reserve((size_t)nt + 1));
+    HIPCHK(c, c->sel.tab.reserve(stride * n_tested));
   }
   // (the tables are pageable host memory: these copies return when the source has been read)
   for (int f = 0; f < n_tested; f++) HIPCHK(c, hipMemcpyAsync(c->sel.tab.get() + f * stride, kcrit[f], stride * sizeof(int), hipMemcpyHostToDevice, c->stream));
   a.tab = c->sel.tab.get(); a.nTested = n_tested; a.W = W; a.n = n_windows;
-  HIPCHK(c, gtx::launch_window_select(a, c->sel.count.get(), c->sel.base.get(), capacity, (long long *)d_ordinals, (int *)d_rows, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->sel.total.get(), c->sel.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n_kept = *c->sel.total.get();
-  return GTX_OK;
+  return compact_device(c, n_windows, n_kept, [&](unsigned *count, long long *base) {
+    return gtx::launch_window_select(a, count, base, capacity, (long long *)d_ordinals, (int *)d_rows, c->stream);
+  });
 }
 
 int gtx_window_select(gtx_ctx *c, const void *const *d_tested, const void *const *d_control, int32_t n_tested, int64_t n_windows, int32_t W,
@@ -461,19 +501,10 @@ int gtx_window_select(gtx_ctx *c, const void *const *d_tested, const void *const
   if (!c) return GTX_E_ARG;
   if (capacity < 0 || (capacity > 0 && (!ordinals || !rows))) return fail(c, GTX_E_ARG, "gtx_window_select: null output");
   if (n_tested < 1 || n_tested > gtx::kSelectMaxTested) return fail(c, GTX_E_ARG, "gtx_window_select: 1 to 4 tested vectors, their tables and n_kept are required");
-  HIPCHK(c, hipSetDevice(c->device));
   const size_t cols = (size_t)n_tested * ((d_control && d_control[0]) ? 2 : 1);
-  if ((size_t)capacity > c->sel.ord.cap || (size_t)capacity * cols > c->sel.rows.cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, c->sel.ord.reserve((size_t)capacity)); HIPCHK(c, c->sel.rows.reserve((size_t)capacity * cols));
-  }
-  int rc = gtx_window_select_device(c, d_tested, d_control, n_tested, n_windows, W, kcrit, capacity, c->sel.ord.get(), c->sel.rows.get(), n_kept); if (rc) return rc;
-  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
-  if (got) {
-    HIPCHK(c, hipMemcpy(ordinals, c->sel.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(rows, c->sel.rows.get(), got * cols * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  return GTX_OK;
+  return compact_host(c, capacity, cols * sizeof(int), ordinals, rows, n_kept, [&](void *d_ordinals, void *d_rows) {
+    return gtx_window_select_device(c, d_tested, d_control, n_tested, n_windows, W, kcrit, capacity, d_ordinals, d_rows, n_kept);
+  });
 }
 
 // ---- window filter (gtx_filter.hip) ----
@@ -541,19 +572,10 @@ int gtx_window_filter_device(gtx_ctx *c, const void *d_windows, int64_t n_window
   *n_kept = 0;
   if (n_windows == 0) return GTX_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  const int64_t nt = gtx::filter_tiles(n_windows);
-  if (!f.total) HIPCHK(c, f.total.alloc(1));
-  if ((size_t)nt > f.count.cap || (size_t)nt + 1 > f.base.cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, f.count.reserve((size_t)nt)); HIPCHK(c, f.base.reserve((size_t)nt + 1));
-  }
   gtx::FilterRefs r = {f.start.get(), f.runmax.get(), f.first.get(), f.blkOff.get(), f.blkEnd.get(), f.blkCls.get(), f.nBlk, f.step, f.size};
-  HIPCHK(c, gtx::launch_window_filter(r, (const u64 *)d_windows, n_windows, min_value, f.count.get(), f.base.get(), capacity, (long long *)d_ordinals,
-                                      (u64 *)d_values, c->stream));
-  HIPCHK(c, hipMemcpyAsync(f.total.get(), f.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n_kept = *f.total.get();
-  return GTX_OK;
+  return compact_device(c, n_windows, n_kept, [&](unsigned *count, long long *base) {
+    return gtx::launch_window_filter(r, (const u64 *)d_windows, n_windows, min_value, count, base, capacity, (long long *)d_ordinals, (u64 *)d_values, c->stream);
+  });
 }
 
 int gtx_window_filter(gtx_ctx *c, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t capacity, int64_t *ordinals, uint64_t *values,
@@ -563,18 +585,9 @@ int gtx_window_filter(gtx_ctx *c, const void *d_windows, int64_t n_windows, uint
   FilterState &f = c->flt;
   if (!f.set) return fail(c, GTX_E_STATE, "gtx_window_filter: gtx_window_refs has not been called");
   if (capacity < 0 || (capacity > 0 && (!ordinals || !values))) return fail(c, GTX_E_ARG, "gtx_window_filter: null output");
-  HIPCHK(c, hipSetDevice(c->device));
-  if ((size_t)capacity > f.ord.cap || (size_t)capacity > f.val.cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, f.ord.reserve((size_t)capacity)); HIPCHK(c, f.val.reserve((size_t)capacity));
-  }
-  int rc = gtx_window_filter_device(c, d_windows, n_windows, min_value, capacity, f.ord.get(), f.val.get(), n_kept); if (rc) return rc;
-  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
-  if (got) {
-    HIPCHK(c, hipMemcpy(ordinals, f.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(values, f.val.get(), got * sizeof(u64), hipMemcpyDeviceToHost));
-  }
-  return GTX_OK;
+  return compact_host(c, capacity, sizeof(u64), ordinals, values, n_kept, [&](void *d_ordinals, void *d_values) {
+    return gtx_window_filter_device(c, d_windows, n_windows, min_value, capacity, d_ordinals, d_values, n_kept);
+  });
 }
 
 // ---- peak candidates (gtx_peaks.hip) ----
@@ -593,20 +606,11 @@ int gtx_peak_select_device(gtx_ctx *c, const void *d_signal, const void *d_contr
   *n_kept = 0;
   if (n_windows == 0) return GTX_OK;
   HIPCHK(c, hipSetDevice(c->device));
-  PeakState &p = c->peak;
-  const int64_t nt = gtx::peak_tiles(n_windows);
-  if (!p.total) HIPCHK(c, p.total.alloc(1));
-  if ((size_t)nt > p.count.cap || (size_t)nt + 1 > p.base.cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, p.count.reserve((size_t)nt)); HIPCHK(c, p.base.reserve((size_t)nt + 1));
-  }
   gtx::PeakArgs a = {(const u64 *)d_signal, (const u64 *)d_control, (const u64 *)d_uniq, n_windows, win_size, min_reads,
                      norm ? (p_ratio < 1.0 ? 1 : 2) : 0, p_ratio};
-  HIPCHK(c, gtx::launch_peak_select(a, p.count.get(), p.base.get(), capacity, (long long *)d_ordinals, (long long *)d_rows, c->stream));
-  HIPCHK(c, hipMemcpyAsync(p.total.get(), p.base.get() + nt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n_kept = *p.total.get();
-  return GTX_OK;
+  return compact_device(c, n_windows, n_kept, [&](unsigned *count, long long *base) {
+    return gtx::launch_peak_select(a, count, base, capacity, (long long *)d_ordinals, (long long *)d_rows, c->stream);
+  });
 }
 
 int gtx_peak_select(gtx_ctx *c, const void *d_signal, const void *d_control, const void *d_uniq, int64_t n_windows, int64_t win_size,
@@ -614,20 +618,9 @@ int gtx_peak_select(gtx_ctx *c, const void *d_signal, const void *d_control, con
 {
   if (!c) return GTX_E_ARG;
   if (capacity < 0 || (capacity > 0 && (!ordinals || !rows))) return fail(c, GTX_E_ARG, "gtx_peak_select: null output");
-  HIPCHK(c, hipSetDevice(c->device));
-  PeakState &p = c->peak;
-  if ((size_t)capacity > p.ord.cap || (size_t)capacity * 3 > p.rows.cap) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, p.ord.reserve((size_t)capacity)); HIPCHK(c, p.rows.reserve((size_t)capacity * 3));
-  }
-  int rc = gtx_peak_select_device(c, d_signal, d_control, d_uniq, n_windows, win_size, min_reads, norm, p_ratio, capacity, p.ord.get(), p.rows.get(), n_kept);
-  if (rc) return rc;
-  const size_t got = (size_t)std::min<int64_t>(*n_kept, capacity);
-  if (got) {
-    HIPCHK(c, hipMemcpy(ordinals, p.ord.get(), got * sizeof(long long), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(rows, p.rows.get(), got * 3 * sizeof(long long), hipMemcpyDeviceToHost));
-  }
-  return GTX_OK;
+  return compact_host(c, capacity, 3 * sizeof(long long), ordinals, rows, n_kept, [&](void *d_ordinals, void *d_rows) {
+    return gtx_peak_select_device(c, d_signal, d_control, d_uniq, n_windows, win_size, min_reads, norm, p_ratio, capacity, d_ordinals, d_rows, n_kept);
+  });
 }
 
 }  // extern "C"

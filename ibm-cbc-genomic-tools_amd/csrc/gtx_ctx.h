@@ -213,20 +213,21 @@ struct ScanState {
   DevBuf<u64> kept[GTX_SCAN_KEEP_SLOTS]; int64_t keptLen[GTX_SCAN_KEEP_SLOTS] = {};
 };
 
-// the window selection's tile counts and bases, its tables, the total on the host, the host entry's results
-struct SelectState { DevBuf<unsigned> count; DevBuf<long long> base, ord; DevBuf<int> tab, rows; PinBuf<long long> total; };
+// What the tile compactions (gtx_compact.h: window selection, window filter, peak candidates) share: the passes' tile counts and
+// bases, the total on the host, and the host entries' results -- ordinals, and the rows beside them in a buffer sized in bytes.  One
+// set serves all of them because each of their six entry points ends in a stream sync before it returns and none keeps a result on
+// the device for a later call.
+struct CompactState { DevBuf<unsigned> count; DevBuf<long long> base, ord; DevBuf<char> rows; PinBuf<long long> total; };
+
+// the window selection's tables
+struct SelectState { DevBuf<int> tab; };
 
 // the window filter: the region set gtx_window_refs prepared (its triples as given, keyed and sorted; starts, running maxima of the
-// stops, the classes' first regions; the classes that have windows in offset order) with the geometry it was prepared for, the
-// passes' tile counts and bases, the total on the host, the host entry's results
+// stops, the classes' first regions; the classes that have windows in offset order) with the geometry it was prepared for
 struct FilterState {
   bool set = false; int nClasses = 0, nBlk = 0, step = 0, size = 0; int64_t extent = 0;
   DevBuf<int> tri, keyed, sorted, start, runmax, first, blkCls; DevBuf<unsigned> order, bad; DevBuf<long long> blkOff, blkEnd;
-  DevBuf<unsigned> count; DevBuf<long long> base, ord; DevBuf<u64> val; PinBuf<long long> total;
 };
-
-// the peak candidate selection: the passes' tile counts and bases, the total on the host, the host entry's results
-struct PeakState { DevBuf<unsigned> count; DevBuf<long long> base, ord, rows; PinBuf<long long> total; };
 
 // link: the scans' per-tile values and break bit map, the info block and its page-locked copy (handed to the caller's struct by
 // gtx_sync after a device call), the host entry's inputs and group records
@@ -333,9 +334,9 @@ struct gtx_ctx {
   JoinState join;
   SignalState sig;
   ScanState scan;
+  CompactState cmp;
   SelectState sel;
   FilterState flt;
-  PeakState peak;
   TextState text;
   LinkState link;
   NeighbourState nbr;

@@ -12,18 +12,16 @@
 //
 // A window [a, b] of class c overlaps a region exactly when j = upper_bound(start of c, b) lies behind first[c] and runmax[j - 1] >= a.
 //
-// The pass over the windows, in the shape of gtx_select.hip: filter_kernel<false> counts per tile of kFilterTile windows (one wave per
-// tile), the tile prefix (launch_tile_prefix, gtx_select.h), filter_kernel<true> emits ordinal and value at base[tile] + rank while
-// that is below the caller's capacity.  No block waits for another: every dependency between tiles is a kernel boundary.  A tile
-// first asks for its first and last window together (two searches the whole wave makes, 64 probes a step); when no region reaches it,
-// it is done without loading a window.
+// The pass over the windows is a rule of the tile compaction (gtx_compact.h): a kept window comes out with its ordinal and its value.
+// A tile first asks for its first and last window together (two searches the whole wave makes, 64 probes a step); when no region
+// reaches it, it is done without loading a window.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gtx_compact.h"
 
 namespace gtx {
 
-constexpr int kFilterThreads = 256, kFilterRows = 8;
-constexpr int kFilterTile = 64 * 2 * kFilterRows;                   // windows per wave: kFilterRows rows of two windows per lane
+constexpr int kFilterTile = kCompactTile;                            // (include/gtx.h names it: GTX_FILTER_TILE)
 
 // the prepared region set and the layout of the window vector it was prepared for
 struct FilterRefs {
@@ -34,13 +32,11 @@ struct FilterRefs {
   int nBlk, step, size;
 };
 
-inline long long filter_tiles(long long n) { return (n + kFilterTile - 1) / kFilterTile; }
-
 // tri [n x 3] -> keyed [n x 3] for the sort with nClasses + 1 classes; *bad != 0 afterwards: a class id outside [0, nClasses)
 hipError_t launch_filter_prepare(const int *tri, long long n, int nClasses, int *keyed, unsigned *bad, hipStream_t st);
 // sorted [n x 3] (the sort's output) -> first [nClasses + 2], start [n], runmax [n].  n >= 1
 hipError_t launch_filter_index(const int *sorted, long long n, int nClasses, int *first, int *start, int *runmax, hipStream_t st);
-// tileCount [tiles], tileBase [tiles + 1]: scratch.  ordinals int64 [capacity], values uint64 [capacity].  n >= 1.  The number kept is
+// tileCount [tiles], tileBase [tiles + 1]: scratch, tiles = compact_tiles(n).  ordinals int64 [capacity], values uint64 [capacity].  n >= 1.  The number kept is
 // tileBase[tiles] once the stream has run.
 hipError_t launch_window_filter(const FilterRefs &r, const unsigned long long *windows, long long n, unsigned long long minValue, unsigned *tileCount,
                                 long long *tileBase, long long capacity, long long *ordinals, unsigned long long *values, hipStream_t st);

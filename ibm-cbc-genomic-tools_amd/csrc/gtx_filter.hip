@@ -1,18 +1,13 @@
-// Kernels of the window filter (see gtx_filter.h).  A tile is kFilterTile windows and belongs to one wave, laid out as the selection's
-// (gtx_select.hip): kFilterRows rows of 128 consecutive windows, lane l of a row reading windows 2 l and 2 l + 1 with one 16-byte load,
-// the rank of a kept window the wave-uniform count of the rows in front plus the popcounts of the row's two ballots below its lane.
+// Kernels of the window filter (see gtx_filter.h): the reference side, and the pass over the windows as a rule of the tile compaction
+// (gtx_compact.h, which has the shape of the passes).
 #include <limits.h>
 #include "gtx_filter.h"
-#include "gtx_select.h"
 
 namespace gtx {
 namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kWaves = kFilterThreads / 64;
 
 // ---- the reference side ----
 // a region that takes part keeps its class, its start clamped to 1; any other goes into class nClasses, behind all of them
@@ -38,7 +33,7 @@ __global__ __launch_bounds__(256) void filter_first_kernel(const int *__restrict
 }
 
 // start[i], and runmax[i] = the largest stop among the sorted regions of i's class up to i: a segmented scan in one block, each thread
-// over a run of consecutive regions (the shape of the tile prefix, gtx_select.hip).  A run's summary is {a class begins inside it,
+// over a run of consecutive regions (the shape of the tile prefix, gtx_compact.h).  A run's summary is {a class begins inside it,
 // the largest stop since the last such beginning}; summaries combine left to right.
 constexpr int kRunThreads = 1024;
 __global__ __launch_bounds__(kRunThreads) void filter_runmax_kernel(const int *__restrict__ sorted, i64 n, int *__restrict__ start, int *__restrict__ runmax)
@@ -76,14 +71,6 @@ __global__ __launch_bounds__(kRunThreads) void filter_runmax_kernel(const int *_
 }
 
 // ---- the pass over the windows ----
-// windows i and i + 1 of the vector (i even, the vector 16-byte aligned); what lies behind the end reads as 0
-__device__ __forceinline__ u64x2 load_pair(const u64 *__restrict__ p, i64 i, i64 n)
-{
-  if (i + 1 < n) return __builtin_nontemporal_load((const u64x2 *)(p + i));
-  u64x2 v; v.x = i < n ? __builtin_nontemporal_load(p + i) : 0ull; v.y = 0ull;
-  return v;
-}
-
 // lo + the number of arr[lo .. hi) that are <= key (arr ascending), found by the whole wave with 64 probes a step: every lane calls
 // it with the same arguments and gets the same answer
 __device__ __forceinline__ int wave_upper_bound(const int *__restrict__ arr, int lo, int hi, i64 key, int lane)
@@ -131,61 +118,42 @@ __device__ __forceinline__ bool overlaps_any(const FilterRefs &r, int b0, int b1
   return overlaps(r, s, i);
 }
 
-// EMIT = false: the tile's number of kept windows.  EMIT = true: the kept windows' ordinals and values at tileBase[tile] + rank.
-template <bool EMIT>
-__global__ __launch_bounds__(kFilterThreads) void filter_kernel(FilterRefs r, const u64 *__restrict__ win, i64 n, u64 minValue, i64 nt, unsigned *__restrict__ tileCount,
-                                                                const i64 *__restrict__ tileBase, i64 capacity, i64 *__restrict__ ordinals, u64 *__restrict__ values)
-{
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const i64 t = (i64)blockIdx.x * kWaves + w;
-  if (t >= nt) return;
-  i64 base = 0;
-  if (EMIT) {
-    base = tileBase[t];
-    if (tileBase[t + 1] == base || base >= capacity) return;         // nothing kept here, or everything behind the caller's room
-  }
-  const i64 tileStart = t * kFilterTile, tileEnd = min(tileStart + kFilterTile, n);
-  // the classes the tile meets: b0 .. b1 of the classes in offset order (disjoint, none empty)
-  int b0 = 0, b1 = r.nBlk;
-  while (b0 < b1) { const int mid = b0 + ((b1 - b0) >> 1); if (r.blkEnd[mid] <= tileStart) b0 = mid + 1; else b1 = mid; }
-  while (b1 < r.nBlk && r.blkOff[b1] < tileEnd) b1++;
-  const bool one = b1 == b0 + 1;
+// A window is kept when its value reaches minValue and a region overlaps it; its row is the value.
+struct FilterRule : CompactRule {
+  FilterRefs r;
+  const u64 *win;
+  u64 minValue;
+  // of the wave's tile (tile): the classes it meets, b0 .. b1 of the classes in offset order (disjoint, none empty); whether that is
+  // one class, and then its span
+  int b0, b1;
+  bool one;
+  Span s;
+  typedef u64 Payload;
+
   // per class, the tile's first and last window together: does any region reach them?
-  bool reach = false;
-  Span s = {0, 0, 0, 0, 0};
-  for (int b = b0; b < b1; b++) {
-    const i64 off = r.blkOff[b], end = r.blkEnd[b];
-    const int c = r.blkCls[b], first = r.first[c];
-    const i64 k0 = max(tileStart, off) - off, k1 = min(tileEnd, end) - 1 - off;
-    const int hi = wave_upper_bound(r.start, first, r.first[c + 1], (i64)r.step * k1 + r.size, lane);
-    if (hi == first || r.runmax[hi - 1] < (i64)r.step * k0 + 1) continue;
-    reach = true;
-    if (one) { s.off = off; s.end = end; s.first = first; s.hi = hi; s.lo = wave_upper_bound(r.start, first, hi, (i64)r.step * k0 + r.size, lane); }
-  }
-  if (!reach) {                                                       // (the windows are not loaded)
-    if (!EMIT && lane == 0) tileCount[t] = 0;
-    return;
-  }
-  unsigned before = 0;                                                // kept in the rows in front (wave-uniform)
-#pragma unroll 2
-  for (int row = 0; row < kFilterRows; row++) {
-    if (tileStart + (i64)row * 128 >= tileEnd) break;
-    const i64 i = tileStart + (i64)row * 128 + 2 * lane;
-    const u64x2 v = load_pair(win, i, n);
-    bool keep0 = i < n && v.x >= minValue, keep1 = i + 1 < n && v.y >= minValue;
-    if (keep0) keep0 = one ? overlaps(r, s, i) : overlaps_any(r, b0, b1, i);
-    if (keep1) keep1 = one ? overlaps(r, s, i + 1) : overlaps_any(r, b0, b1, i + 1);
-    const u64 m0 = __ballot(keep0), m1 = __ballot(keep1);
-    if (EMIT) {
-      const u64 below = (1ull << lane) - 1;
-      const i64 g0 = base + before + __popcll(m0 & below) + __popcll(m1 & below), g1 = g0 + (keep0 ? 1 : 0);
-      if (keep0 && g0 < capacity) { ordinals[g0] = i; values[g0] = v.x; }
-      if (keep1 && g1 < capacity) { ordinals[g1] = i + 1; values[g1] = v.y; }
+  __device__ __forceinline__ bool tile(i64 tileStart, i64 tileEnd, int lane)
+  {
+    b0 = 0; b1 = r.nBlk;
+    while (b0 < b1) { const int mid = b0 + ((b1 - b0) >> 1); if (r.blkEnd[mid] <= tileStart) b0 = mid + 1; else b1 = mid; }
+    while (b1 < r.nBlk && r.blkOff[b1] < tileEnd) b1++;
+    one = b1 == b0 + 1;
+    bool reach = false;
+    s = {0, 0, 0, 0, 0};
+    for (int b = b0; b < b1; b++) {
+      const i64 off = r.blkOff[b], end = r.blkEnd[b];
+      const int c = r.blkCls[b], first = r.first[c];
+      const i64 k0 = max(tileStart, off) - off, k1 = min(tileEnd, end) - 1 - off;
+      const int hi = wave_upper_bound(r.start, first, r.first[c + 1], (i64)r.step * k1 + r.size, lane);
+      if (hi == first || r.runmax[hi - 1] < (i64)r.step * k0 + 1) continue;
+      reach = true;
+      if (one) { s.off = off; s.end = end; s.first = first; s.hi = hi; s.lo = wave_upper_bound(r.start, first, hi, (i64)r.step * k0 + r.size, lane); }
     }
-    before += (unsigned)(__popcll(m0) + __popcll(m1));
+    return reach;
   }
-  if (!EMIT && lane == 0) tileCount[t] = before;
-}
+  __device__ __forceinline__ void load(i64 i, i64 n, u64 &p0, u64 &p1) const { const u64x2 v = load_pair(win, i, n); p0 = v.x; p1 = v.y; }
+  __device__ __forceinline__ bool keep(i64 i, const u64 &v) const { return v >= minValue && (one ? overlaps(r, s, i) : overlaps_any(r, b0, b1, i)); }
+  __device__ __forceinline__ void emit(u64 *__restrict__ values, i64 g, i64, const u64 &v) const { values[g] = v; }
+};
 
 inline unsigned stride_grid(i64 n) { return (unsigned)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384); }
 
@@ -207,15 +175,9 @@ hipError_t launch_filter_index(const int *sorted, long long n, int nClasses, int
 hipError_t launch_window_filter(const FilterRefs &r, const unsigned long long *windows, long long n, unsigned long long minValue, unsigned *tileCount,
                                 long long *tileBase, long long capacity, long long *ordinals, unsigned long long *values, hipStream_t st)
 {
-  const i64 nt = filter_tiles(n);
-  const unsigned grid = (unsigned)((nt + kWaves - 1) / kWaves);
-  hipLaunchKernelGGL(filter_kernel<false>, dim3(grid), dim3(kFilterThreads), 0, st, r, windows, n, minValue, nt, tileCount, (const i64 *)nullptr, capacity,
-                     (i64 *)nullptr, (u64 *)nullptr);
-  const hipError_t e = launch_tile_prefix(tileCount, nt, tileBase, st);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(filter_kernel<true>, dim3(grid), dim3(kFilterThreads), 0, st, r, windows, n, minValue, nt, (unsigned *)nullptr, (const i64 *)tileBase, capacity,
-                     ordinals, values);
-  return hipGetLastError();
+  FilterRule rule = {};
+  rule.r = r; rule.win = windows; rule.minValue = minValue;
+  return launch_compact(rule, n, tileCount, tileBase, capacity, ordinals, values, st);
 }
 
 }  // namespace gtx

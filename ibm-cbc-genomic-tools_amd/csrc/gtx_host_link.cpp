@@ -545,7 +545,7 @@ void GenomicRegionSet::RunGlobalInvert(StringLIntMap *bounds)
   gtx_gaps_info info = {0, -1, 0};
   std::vector<uint32_t> owner; std::vector<int32_t> gstart, gstop;
   gtx_ctx *ctx = AdjacentContext();
-  for (int64_t cap = (int64_t)(n / 2 + 1024); n > 0; cap = info.n_gaps) {       // (the policy of gtx_window_select: at most one repeat)
+  for (int64_t cap = (int64_t)(n / 2 + 1024); n > 0; cap = info.n_gaps) {       // (the policy of WithRoomFor, gtx_host_scan.cpp: at most one repeat)
     owner.resize((size_t)cap); gstart.resize((size_t)cap); gstop.resize((size_t)cap);
     DieGtx(ctx, gtx_gaps(ctx, in.tri.data(), (int64_t)n, size.data(), (int32_t)size.size(), cap, owner.data(), gstart.data(), gstop.data(), &info));
     if (info.n_gaps <= cap) break;

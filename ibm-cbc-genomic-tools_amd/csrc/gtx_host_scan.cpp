@@ -259,6 +259,38 @@ void GenomicRegionSetScanner::PrintIntervalAt(FILE *out_file, long long window)
   fprintf(out_file, "%s %c %lld %lld", chrom_names[b / ns].c_str(), (b % ns) ? '-' : '+', (long long)win_step * k + 1, (long long)win_step * k + win_size);
 }
 
+// The window vectors scanners[0 .. count) kept on the device of `one` (a null scanner is skipped: d_vec stays null) and *n, the number
+// of windows they all have.  False with *error set, `who` in front of it, when one is not there or they differ.
+static bool KeptVectors(gtx_ctx *one, GenomicRegionSetScanner **scanners, int count, const char *who, const void **d_vec, long long *n, std::string *error)
+{
+  *n = -1;
+  for (int f = 0; f < count; f++) {
+    if (scanners[f] == NULL) continue;
+    const long long nf = scanners[f]->WindowCount();
+    if (!scanners[f]->KeepError().empty()) { *error = scanners[f]->KeepError(); return false; }
+    void *d = NULL; int64_t kept = 0;                                // (bounds without a window: nothing was scanned, nothing is selected)
+    if (nf > 0 && (scanners[f]->KeptSlot() < 0 || gtx_scan_kept(one, scanners[f]->KeptSlot(), &d, &kept) != GTX_OK || (long long)kept != nf)) {
+      *error = std::string(who) + " an input's windows are not on the device!"; return false;
+    }
+    if (*n >= 0 && nf != *n) { *error = std::string(who) + " the inputs differ in their number of windows!"; return false; }
+    *n = nf; d_vec[f] = d;
+  }
+  return true;
+}
+
+// The room a selector of n windows is given for its results: max(1 << 16, n / 64) windows at first.  call(cap, &kept) resizes the
+// result buffers to cap rows and runs the entry; when it reports more kept than that, it is repeated once with the reported count.
+template <class Call>
+static int WithRoomFor(long long n, int64_t *kept, Call call)
+{
+  int64_t cap = std::max<int64_t>(1 << 16, n / 64);
+  for (;;) {
+    const int rc = call(cap, kept);
+    if (rc != GTX_OK || *kept <= cap) return rc;
+    cap = *kept;
+  }
+}
+
 bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_control, const std::vector<std::vector<int> > &tables, long int win_size,
                       std::vector<long long> &ordinals, std::vector<int> &rows, std::string *error)
 {
@@ -272,29 +304,18 @@ bool GtxSelectWindows(GenomicRegionSetScanner **scanners, int n_tested, int n_co
   const void *d_vec[8] = {};
   const int32_t *tab[4] = {};
   long long n = -1;
-  for (int f = 0; f < n_tested + n_control; f++) {
-    const long long nf = scanners[f]->WindowCount();
-    if (!scanners[f]->KeepError().empty()) { *error = scanners[f]->KeepError(); return false; }
-    void *d = NULL; int64_t kept = 0;                                // (bounds without a window: nothing was scanned, nothing is selected)
-    if (nf > 0 && (scanners[f]->KeptSlot() < 0 || gtx_scan_kept(one, scanners[f]->KeptSlot(), &d, &kept) != GTX_OK || (long long)kept != nf)) {
-      *error = "[GtxSelectWindows] an input's windows are not on the device!"; return false;
-    }
-    if (n >= 0 && nf != n) { *error = "[GtxSelectWindows] the inputs differ in their number of windows!"; return false; }
-    n = nf; d_vec[f] = d;
-  }
+  if (!KeptVectors(one, scanners, n_tested + n_control, "[GtxSelectWindows]", d_vec, &n, error)) return false;
   for (int f = 0; f < n_tested; f++) {
     if (tables[(size_t)f].size() != (size_t)(n_control ? win_size + 1 : 1)) { *error = "[GtxSelectWindows] a table of the wrong size!"; return false; }
     tab[f] = tables[(size_t)f].data();
   }
   const size_t cols = (size_t)(n_tested + n_control);
-  int64_t cap = std::max<int64_t>(1 << 16, n / 64), kept = 0;        // a retry with the reported count when this was too small
-  for (;;) {
+  int64_t kept = 0;
+  const int rc = WithRoomFor(n, &kept, [&](int64_t cap, int64_t *k) {
     ordinals.resize((size_t)cap); rows.resize((size_t)cap * cols);
-    const int rc = gtx_window_select(one, d_vec, n_control ? d_vec + n_tested : NULL, n_tested, n, (int32_t)win_size, tab, cap, (int64_t *)ordinals.data(), rows.data(), &kept);
-    if (rc != GTX_OK) { *error = std::string("[gtx] ") + gtx_last_error(one); return false; }
-    if (kept <= cap) break;
-    cap = kept;
-  }
+    return gtx_window_select(one, d_vec, n_control ? d_vec + n_tested : NULL, n_tested, n, (int32_t)win_size, tab, cap, (int64_t *)ordinals.data(), rows.data(), k);
+  });
+  if (rc != GTX_OK) { *error = std::string("[gtx] ") + gtx_last_error(one); return false; }
   ordinals.resize((size_t)kept); rows.resize((size_t)kept * cols);
   return true;
 }
@@ -310,27 +331,14 @@ bool GtxSelectPeakWindows(GenomicRegionSetScanner *signal, GenomicRegionSetScann
   GenomicRegionSetScanner *scanners[3] = {signal, control, uniq};
   const void *d_vec[3] = {};
   long long n = -1;
-  for (int f = 0; f < 3; f++) {
-    if (scanners[f] == NULL) continue;
-    const long long nf = scanners[f]->WindowCount();
-    if (!scanners[f]->KeepError().empty()) { *error = scanners[f]->KeepError(); return false; }
-    void *d = NULL; int64_t kept = 0;                                // (bounds without a window: nothing was scanned, nothing is selected)
-    if (nf > 0 && (scanners[f]->KeptSlot() < 0 || gtx_scan_kept(one, scanners[f]->KeptSlot(), &d, &kept) != GTX_OK || (long long)kept != nf)) {
-      *error = "[GtxSelectPeakWindows] an input's windows are not on the device!"; return false;
-    }
-    if (n >= 0 && nf != n) { *error = "[GtxSelectPeakWindows] the inputs differ in their number of windows!"; return false; }
-    n = nf; d_vec[f] = d;
-  }
+  if (!KeptVectors(one, scanners, 3, "[GtxSelectPeakWindows]", d_vec, &n, error)) return false;
   if (n == 0) return true;
-  int64_t cap = std::max<int64_t>(1 << 16, n / 64), kept = 0;        // a retry with the reported count when this was too small
-  for (;;) {
+  int64_t kept = 0;
+  const int rc = WithRoomFor(n, &kept, [&](int64_t cap, int64_t *k) {
     ordinals.resize((size_t)cap); rows.resize((size_t)cap * 3);
-    const int rc = gtx_peak_select(one, d_vec[0], d_vec[1], d_vec[2], n, win_size, min_reads, norm ? 1 : 0, p_ratio, cap, (int64_t *)ordinals.data(),
-                                   (int64_t *)rows.data(), &kept);
-    if (rc != GTX_OK) { *error = std::string("[gtx] ") + gtx_last_error(one); return false; }
-    if (kept <= cap) break;
-    cap = kept;
-  }
+    return gtx_peak_select(one, d_vec[0], d_vec[1], d_vec[2], n, win_size, min_reads, norm ? 1 : 0, p_ratio, cap, (int64_t *)ordinals.data(), (int64_t *)rows.data(), k);
+  });
+  if (rc != GTX_OK) { *error = std::string("[gtx] ") + gtx_last_error(one); return false; }
   ordinals.resize((size_t)kept); rows.resize((size_t)kept * 3);
   return true;
 }
@@ -429,13 +437,11 @@ void GenomicRegionSetScanner::PrintFiltered(FILE *out_file, GenomicRegionSetInde
     DieGtx(one, gtx_window_refs(one, tri.data(), (int64_t)(tri.size() / 3), class_len.data(), class_off.data(), n_chrom * ns, (int32_t)win_step, (int32_t)win_size));
     std::vector<long long> ordinals;
     std::vector<unsigned long long> kept_values;
-    int64_t cap = std::max<int64_t>(1 << 16, total / 64), kept = 0;    // a retry with the reported count when this was too small
-    for (;;) {
+    int64_t kept = 0;
+    DieGtx(one, WithRoomFor(total, &kept, [&](int64_t cap, int64_t *k) {
       ordinals.resize((size_t)cap); kept_values.resize((size_t)cap);
-      DieGtx(one, gtx_window_filter(one, d_windows, (int64_t)total, floor_value, cap, (int64_t *)ordinals.data(), (uint64_t *)kept_values.data(), &kept));
-      if (kept <= cap) break;
-      cap = kept;
-    }
+      return gtx_window_filter(one, d_windows, (int64_t)total, floor_value, cap, (int64_t *)ordinals.data(), (uint64_t *)kept_values.data(), k);
+    }));
     std::vector<char> buf; buf.reserve(8u << 20);
     auto put_num = [&](long long v) {
       char tmp[24]; int n = 0;

@@ -4,6 +4,7 @@
 // carries.
 #include <climits>
 #include "gtx_link.h"
+#include "gtx_compact.h"
 
 namespace gtx {
 namespace {
@@ -120,9 +121,8 @@ __global__ __launch_bounds__(kLinkThreads) void link_scan_kernel(const int *__re
   if (threadIdx.x == 0) { unsigned t = 0; for (int j = 0; j < kWaves; j++) t += shHeads[j]; tileHeads[blockIdx.x] = t; }
 }
 
-// The two scans over per-tile values run in one block of kPartThreads lanes, each over a run of consecutive tiles: the loads of a
-// run go out eight at a time (they do not depend on one another; one at a time the kernel is a chain of memory latencies).
-constexpr int kPartThreads = 1024, kPartBatch = 8;
+// The two scans over per-tile values run in one block of kPartThreads lanes, each over a run of consecutive tiles with its loads out
+// kPartBatch at a time (gtx_compact.h).
 
 // exclusive scan of the tiles' aggregates
 __global__ __launch_bounds__(kPartThreads) void link_prefix_kernel(const int2 *__restrict__ agg, i64 nt, int2 *__restrict__ prefix)
@@ -164,35 +164,8 @@ __global__ __launch_bounds__(kPartThreads) void link_heads_kernel(const unsigned
                                                                   const u64 *__restrict__ bits, LinkInfo *info)
 {
   __shared__ i64 sh[kPartThreads];
-  const int tid = threadIdx.x;
-  const i64 per = (nt + kPartThreads - 1) / kPartThreads, b = min((i64)tid * per, nt), e = min(b + per, nt);
-  i64 a = 0;
-  for (i64 k = b; k < e; k += kPartBatch) {
-    unsigned v[kPartBatch];
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? heads[k + j] : 0u;
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) a += v[j];
-  }
-  sh[tid] = a;
-  __syncthreads();
-  for (int dd = 1; dd < kPartThreads; dd <<= 1) {
-    const i64 o = tid >= dd ? sh[tid - dd] : 0;
-    __syncthreads();
-    sh[tid] += o;
-    __syncthreads();
-  }
-  i64 run = tid > 0 ? sh[tid - 1] : 0;
-  for (i64 k = b; k < e; k += kPartBatch) {
-    unsigned v[kPartBatch];
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? heads[k + j] : 0u;
-#pragma unroll
-    for (int j = 0; j < kPartBatch; j++) if (k + j < e) { base[k + j] = run; run += v[j]; }
-  }
-  if (tid == kPartThreads - 1) base[nt] = sh[tid];
-  __syncthreads();
-  if (tid == 0) {
+  block_exclusive_sum(heads, nt, base, sh);
+  if (threadIdx.x == 0) {
     const u64 U = info->firstUnsorted;
     if (U == ~0ull) { info->nGroups = base[nt]; info->firstUnsortedOut = -1; }
     else {

@@ -10,23 +10,16 @@
 // The conversion to float is the reference's (a count rounds to 24 bits before it is scaled); the product and the quotient are in
 // double.  This file is compiled with -ffp-contract=off: the floor decides an integer, nothing may be fused around it.
 //
-// The kept windows come out in window order, in the shape of gtx_select.hip:
-//
-//   peak_kernel<.., false>     per tile of kPeakTile windows the number kept (one wave per tile: ballots and popcounts)
-//   launch_tile_prefix         exclusive sum of the tile counts (gtx_select.h); base[tiles] = the number kept
-//   peak_kernel<.., true>      a tile whose count is zero is not loaded; otherwise the rule once more, and a kept window goes to
-//                              base[tile] + its rank inside the tile while that is below the caller's capacity: its ordinal and the
-//                              row v1, v2, v0
-//
-// No block waits for another and none reads what a block of its own launch wrote: every dependency between tiles is a kernel
-// boundary.  Per window 16 bytes are read (24 with U) by each of the two passes that load it, 32 bytes are written per kept window.
+// The kept windows come out in window order, each with its ordinal and the row v1, v2, v0: a rule of the tile compaction
+// (gtx_compact.h).  Per window 16 bytes are read (24 with U) by each of the two passes that load it, 32 bytes are written per kept
+// window.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gtx_compact.h"
 
 namespace gtx {
 
-constexpr int kPeakThreads = 256, kPeakRows = 8;
-constexpr int kPeakTile = 64 * 2 * kPeakRows;                       // windows per wave: kPeakRows rows of two windows per lane
+constexpr int kPeakTile = kCompactTile;                              // (include/gtx.h names it: GTX_PEAK_TILE)
 
 struct PeakArgs {
   const unsigned long long *signal, *control, *uniq;                 // 16-byte aligned, n windows each; uniq may be null
@@ -35,9 +28,7 @@ struct PeakArgs {
   double ratio;
 };
 
-inline long long peak_tiles(long long n) { return (n + kPeakTile - 1) / kPeakTile; }
-
-// tileCount [tiles], tileBase [tiles + 1]: scratch.  ordinals [capacity] int64, rows [capacity * 3] int64.  n >= 1.  The number kept
+// tileCount [tiles], tileBase [tiles + 1]: scratch, tiles = compact_tiles(n).  ordinals [capacity] int64, rows [capacity * 3] int64.  n >= 1.  The number kept
 // is tileBase[tiles] once the stream has run.
 hipError_t launch_peak_select(const PeakArgs &a, unsigned *tileCount, long long *tileBase, long long capacity, long long *ordinals, long long *rows,
                               hipStream_t st);

@@ -2,23 +2,17 @@
 // table rule, and their clamped counts -- the data pass of the reference's `genomic_apps peakdiff` (ScanReadFiles,
 // genomic_apps.cpp:385-412) with its binomial tail folded into tables of critical counts (gtx_peakdiff.h).  With W the window size,
 // k_f = min(v_f, W) the clamped sum of tested vector f and c_f = min(ctl_f, W) that of its control, a window is kept when
-// k_f >= kcrit_f[c_f] for any f (kcrit_f[0] when there are no controls).  The kept windows come out in window order: reduce-then-scan
-// over fixed tiles, the shape of gtx_link.hip:
+// k_f >= kcrit_f[c_f] for any f (kcrit_f[0] when there are no controls).  The kept windows come out in window order, each with its
+// ordinal and one row of clamped counts (tested vectors, then controls): a rule of the tile compaction, gtx_compact.h.
 //
-//   select_kernel<.., false>   per tile of kSelectTile windows the number kept (one wave per tile: ballots and popcounts)
-//   select_prefix_kernel       exclusive sum of the tile counts (one block); base[tiles] = the number kept
-//   select_kernel<.., true>    the rule once more; a kept window goes to base[tile] + its rank inside the tile, while that is below the
-//                              caller's capacity: its ordinal and one row of clamped counts (tested vectors, then controls)
-//
-// No block waits for another and none reads what a block of its own launch wrote: every dependency between tiles is a kernel
-// boundary.  The tables are copied into LDS while they fit kSelectLdsBytes, and are read from global memory (L2) beyond that.
+// The tables are copied into LDS while they fit kSelectLdsBytes, and are read from global memory (L2) beyond that.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gtx_compact.h"
 
 namespace gtx {
 
-constexpr int kSelectThreads = 256, kSelectRows = 8;
-constexpr int kSelectTile = 64 * 2 * kSelectRows;                   // windows per wave: kSelectRows rows of two windows per lane
+constexpr int kSelectTile = kCompactTile;                            // (gtx_window_select_limits reports it)
 constexpr int kSelectMaxTested = 4;
 constexpr int kSelectLdsBytes = 64 * 1024;                           // tables of nTested * (W + 1) * 4 bytes up to this sit in LDS
 constexpr int kSelectLdsMaxW = kSelectLdsBytes / (4 * kSelectMaxTested) - 1;   // ... i.e. with four tested vectors and controls, W up to this
@@ -31,16 +25,11 @@ struct SelectArgs {
   long long n;
 };
 
-inline long long select_tiles(long long n) { return (n + kSelectTile - 1) / kSelectTile; }
 inline bool select_tables_in_lds(int nTested, int W, bool controls) { return (long long)nTested * (controls ? W + 1 : 1) * 4 <= kSelectLdsBytes; }
 
-// tileCount [tiles], tileBase [tiles + 1]: scratch.  ordinals [capacity] int64, rows [capacity * (controls ? 2 : 1) * nTested] int32.
-// n >= 1.  The number kept is tileBase[tiles] once the stream has run.
+// tileCount [tiles], tileBase [tiles + 1]: scratch, tiles = compact_tiles(n).  ordinals [capacity] int64, rows [capacity * (controls ? 2 : 1) * nTested]
+// int32.  n >= 1.  The number kept is tileBase[tiles] once the stream has run.
 hipError_t launch_window_select(const SelectArgs &a, unsigned *tileCount, long long *tileBase, long long capacity, long long *ordinals, int *rows,
                                 hipStream_t st);
-
-// the passes' middle step on its own (the window filter, gtx_filter.hip, is of the same shape): base [tiles + 1] = the exclusive sums of
-// count [tiles], base[tiles] their total
-hipError_t launch_tile_prefix(const unsigned *tileCount, long long tiles, long long *tileBase, hipStream_t st);
 
 }  // namespace gtx

@@ -829,6 +829,29 @@ class Engine:
         """free a kept slot (-1: all of them)"""
         self._chk(self.lib.gtx_scan_drop(self.ctx, int(slot)))
 
+    def _kept_or_address(self, v):
+        """(device address, number of windows or None) of a window vector given as a kept slot (small int) or a raw device address"""
+        if v is None:
+            return None, None
+        if isinstance(v, (int, np.integer)) and 0 <= int(v) < SCAN_KEEP_SLOTS:
+            return self.scan_kept(int(v))
+        return int(v), None
+
+    def _grow_and_repeat(self, call, n_windows, capacity, make):
+        """A host selector entry with room for `capacity` rows, or, with capacity None, for max(1024, n_windows // 64) rows and then
+        for as many as it reported until everything fits.  make(cap) -> (ordinals, rows); call(cap, ordinals, rows, kept) -> rc.
+        Returns (ordinals, rows, number kept), the arrays cut to what was written."""
+        kept = ctypes.c_int64(0)
+        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
+        while True:
+            ordinals, rows = make(max(cap, 1))
+            self._chk(call(cap, ordinals, rows, kept))
+            if capacity is not None or kept.value <= cap:
+                break
+            cap = int(kept.value)
+        got = min(int(kept.value), cap)
+        return ordinals[:got], rows[:got], int(kept.value)
+
     def window_select(self, tested, tables, window_size, controls=None, n_windows=None, capacity=None, device_out=None):
         """gtx_window_select over window vectors in HBM.  tested / controls: kept slots (small ints, n_windows taken from the slot) or
         raw device addresses (n_windows required); tables: per tested vector its critical counts (window_size + 1 entries with
@@ -836,12 +859,8 @@ class Engine:
         `capacity` only the first `capacity` windows are returned.  capacity=None grows and repeats the call until everything fits.
         device_out=(d_ordinals, d_rows): gtx_window_select_device into the caller's device buffers (capacity required), returns the
         number kept."""
-        def addr(v):
-            if isinstance(v, (int, np.integer)) and 0 <= int(v) < SCAN_KEEP_SLOTS:
-                return self.scan_kept(int(v))
-            return int(v), None
-        t = [addr(v) for v in tested]
-        c = None if controls is None else [(None, None) if v is None else addr(v) for v in controls]
+        t = [self._kept_or_address(v) for v in tested]
+        c = None if controls is None else [self._kept_or_address(v) for v in controls]
         if n_windows is None:
             n_windows = t[0][1]
         nt = len(t)
@@ -850,20 +869,15 @@ class Engine:
         tabs = [np.ascontiguousarray(x, dtype=np.int32) for x in tables]
         d_k = (ctypes.c_void_p * max(len(tabs), 1))(*[x.ctypes.data for x in tabs])
         cols = nt * (2 if c is not None and any(a for a, _ in c) else 1)
-        kept = ctypes.c_int64(0)
         if device_out is not None:
+            kept = ctypes.c_int64(0)
             self._chk(self.lib.gtx_window_select_device(self.ctx, d_t, d_c, nt, int(n_windows), int(window_size), d_k, int(capacity), _ptr(device_out[0]),
                                                         _ptr(device_out[1]), ctypes.byref(kept)))
             return int(kept.value)
-        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
-        while True:
-            ordinals, rows = np.full(max(cap, 1), -1, dtype=np.int64), np.full((max(cap, 1), max(cols, 1)), -1, dtype=np.int32)
-            self._chk(self.lib.gtx_window_select(self.ctx, d_t, d_c, nt, int(n_windows), int(window_size), d_k, cap, _ptr(ordinals), _ptr(rows), ctypes.byref(kept)))
-            if capacity is not None or kept.value <= cap:
-                break
-            cap = int(kept.value)
-        got = min(int(kept.value), cap)
-        return ordinals[:got], rows[:got], int(kept.value)
+        return self._grow_and_repeat(
+            lambda cap, ordinals, rows, kept: self.lib.gtx_window_select(self.ctx, d_t, d_c, nt, int(n_windows), int(window_size), d_k, cap, _ptr(ordinals),
+                                                                         _ptr(rows), ctypes.byref(kept)),
+            n_windows, capacity, lambda cap: (np.full(cap, -1, dtype=np.int64), np.full((cap, max(cols, 1)), -1, dtype=np.int32)))
 
     def window_refs(self, refs, class_len, class_offsets, win_step, win_size):
         """gtx_window_refs: prepares the regions `refs` ((n, 3) of class, start, stop; any order) on the device for window vectors
@@ -881,32 +895,21 @@ class Engine:
         that overlap a region of window_refs, in vector order; when the number kept exceeds `capacity` only the first `capacity`
         are returned.  capacity=None grows and repeats the call until everything fits.  device_out=(d_ordinals, d_values):
         gtx_window_filter_device into the caller's device buffers (capacity required), returns the number kept."""
-        if isinstance(windows, (int, np.integer)) and 0 <= int(windows) < SCAN_KEEP_SLOTS:
-            addr, n = self.scan_kept(int(windows))
-            n_windows = n if n_windows is None else n_windows
-        else:
-            addr = int(windows)
-        kept = ctypes.c_int64(0)
+        addr, n = self._kept_or_address(windows)
+        if n_windows is None:
+            n_windows = n
         if device_out is not None:
+            kept = ctypes.c_int64(0)
             self._chk(self.lib.gtx_window_filter_device(self.ctx, _ptr(addr), int(n_windows), int(min_value), int(capacity), _ptr(device_out[0]),
                                                         _ptr(device_out[1]), ctypes.byref(kept)))
             return int(kept.value)
-        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
-        while True:
-            ordinals, values = np.full(max(cap, 1), -1, dtype=np.int64), np.zeros(max(cap, 1), dtype=np.uint64)
-            self._chk(self.lib.gtx_window_filter(self.ctx, _ptr(addr), int(n_windows), int(min_value), cap, _ptr(ordinals), _ptr(values), ctypes.byref(kept)))
-            if capacity is not None or kept.value <= cap:
-                break
-            cap = int(kept.value)
-        got = min(int(kept.value), cap)
-        return ordinals[:got], values[:got], int(kept.value)
+        return self._grow_and_repeat(
+            lambda cap, ordinals, values, kept: self.lib.gtx_window_filter(self.ctx, _ptr(addr), int(n_windows), int(min_value), cap, _ptr(ordinals),
+                                                                           _ptr(values), ctypes.byref(kept)),
+            n_windows, capacity, lambda cap: (np.full(cap, -1, dtype=np.int64), np.zeros(cap, dtype=np.uint64)))
 
     def _peak_vectors(self, signal, control, uniq, n_windows):
-        def addr(v):
-            if v is not None and isinstance(v, (int, np.integer)) and 0 <= int(v) < SCAN_KEEP_SLOTS:
-                return self.scan_kept(int(v))
-            return (None if v is None else int(v)), None
-        s, c, u = addr(signal), addr(control), addr(uniq)
+        s, c, u = self._kept_or_address(signal), self._kept_or_address(control), self._kept_or_address(uniq)
         if n_windows is None and s[1] is None:
             raise ValueError("n_windows is required when the signal is a raw device address and not a kept slot")
         return s[0], c[0], u[0], (s[1] if n_windows is None else n_windows)
@@ -917,17 +920,10 @@ class Engine:
         v1, v2, v0 after clamp and norm, number kept): the windows with v1 >= min_reads in window order; when the number kept
         exceeds `capacity` only the first `capacity` are returned.  capacity=None grows and repeats the call until everything fits."""
         s, c, u, n_windows = self._peak_vectors(signal, control, uniq, n_windows)
-        kept = ctypes.c_int64(0)
-        cap = int(capacity) if capacity is not None else max(1024, int(n_windows) // 64)
-        while True:
-            ordinals, rows = np.full(max(cap, 1), -1, dtype=np.int64), np.full((max(cap, 1), 3), -1, dtype=np.int64)
-            self._chk(self.lib.gtx_peak_select(self.ctx, _ptr(s), _ptr(c), _ptr(u), int(n_windows), int(win_size), int(min_reads), int(bool(norm)),
-                                               float(p_ratio), cap, _ptr(ordinals), _ptr(rows), ctypes.byref(kept)))
-            if capacity is not None or kept.value <= cap:
-                break
-            cap = int(kept.value)
-        got = min(int(kept.value), cap)
-        return ordinals[:got], rows[:got], int(kept.value)
+        return self._grow_and_repeat(
+            lambda cap, ordinals, rows, kept: self.lib.gtx_peak_select(self.ctx, _ptr(s), _ptr(c), _ptr(u), int(n_windows), int(win_size), int(min_reads),
+                                                                       int(bool(norm)), float(p_ratio), cap, _ptr(ordinals), _ptr(rows), ctypes.byref(kept)),
+            n_windows, capacity, lambda cap: (np.full(cap, -1, dtype=np.int64), np.full((cap, 3), -1, dtype=np.int64)))
 
     def peak_select_device(self, signal, control, win_size, min_reads, capacity, d_ordinals, d_rows, uniq=None, norm=False, p_ratio=1.0, n_windows=None):
         """gtx_peak_select_device: the same selection into the caller's device buffers (int64[capacity], int64[capacity * 3]); returns

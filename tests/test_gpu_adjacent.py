@@ -321,3 +321,27 @@ def test_bad_arguments(eng):
     assert check_gaps(eng, tri, [2**31 - 3])[1] == -1                # the largest bound; the context is still good
     assert check_gaps(eng, tri, []) == (0, 0, 2)                     # no bounds at all: the first head has none
     check_pairs(eng, tri)
+
+
+@pytest.fixture(scope="module")
+def many_spans():
+    """1025 spans of 512 regions and one more region, over 24 classes at a density where the spans differ in their number of gaps"""
+    n = 1025 * 512 + 1
+    return sorted_regions(78, n, 24, 2 * n, 1, 60).astype(np.int64)
+
+
+@pytest.mark.parametrize("bad", [False, True], ids=["clean", "bad-in-the-last-tile"])
+def test_more_spans_than_threads_in_the_gaps_prefix(eng, many_spans, bad):
+    """The one-block exclusive sum of the spans' gap counts (block_exclusive_sum, csrc/gtx_compact.h) with two spans to a thread and
+    the upper half of its threads without one.  With a region of span 1024 that starts before its predecessor, the gaps that count
+    are read behind that sum at a base that is not zero, and those of its span below it are added."""
+    tri = many_spans.copy()
+    at = 1024 * 512 + 300
+    if bad:
+        tri[at, 0] = tri[at - 1, 0]
+        tri[at, 1] = tri[at - 1, 1] - 1
+    n_gaps, first_bad, kind = check_gaps(eng, tri, [BIG] * 24)
+    assert (first_bad, kind) == ((at, 1) if bad else (-1, 0))
+    assert len(tri) // 8 < n_gaps < len(tri)
+    per_span = np.bincount(eng.gaps(tri, [BIG] * 24)[0] // 512, minlength=1026)
+    assert len(set(per_span[:1024].tolist())) > 8                                # the spans' counts vary

@@ -256,3 +256,25 @@ def test_bad_arguments(eng):
     with pytest.raises(gtx.GtxError):
         eng.link(tri, vals, 0, 8)                                    # no such flag
     check(eng, tri)                                                  # the context is still good
+
+
+@pytest.fixture(scope="module")
+def many_tiles():
+    """1025 T + 1 regions over 24 classes at a density where the tiles differ in their number of heads"""
+    n = 1025 * T + 1
+    return sorted_regions(77, n, 24, 2 * n, 1, 60).astype(np.int64)
+
+
+@pytest.mark.parametrize("unsorted", [False, True], ids=["sorted", "unsorted-in-the-last-tile"])
+def test_more_tiles_than_threads_in_the_heads_prefix(eng, many_tiles, unsorted):
+    """The one-block exclusive sum of the tiles' heads (block_exclusive_sum, csrc/gtx_compact.h) with two tiles to a thread and the
+    upper half of its threads without one.  With the last region unsorted, the groups that count are read behind that sum at a
+    base that is not zero."""
+    tri = many_tiles.copy()
+    if unsorted:
+        tri[-1, 0] = tri[-2, 0]
+        tri[-1, 1] = tri[-2, 1] - 1
+    groups = check(eng, tri)
+    assert len(tri) // 8 < groups < len(tri) - len(tri) // 8
+    heads = np.bincount(eng.link(tri)[0] // T, minlength=1026)
+    assert len(set(heads[:1025].tolist())) > 8                                   # the tiles' counts vary
