@@ -327,6 +327,9 @@ class GenomicRegionSetScanner
   // MI355X path: every remaining window with a value >= min_value as "value\tchr strand start stop\n" -- what a caller's
   // Next() / PrintInterval() loop prints (genomic_scans.cpp:421-428), formatted in bulk (three stdio calls per window are half a
   // second for the three million windows of a genome at -w 1000)
+  // A scanner made behind KeepNextOnDevice renders them on the device (gtx_lines_layout / gtx_window_lines, the text streamed to
+  // out_file), in the host loop's order of events: the windows in front of a sorted scanner's input error, then the error; a value of
+  // -1 ends the output.  A layout the renderer refuses (a chromosome name beyond its limit) brings the windows to the host first.
   void PrintRemaining(FILE *out_file, long int min_value);
   // MI355X path: the same lines for the windows that overlap a region of `index` -- what a caller's Next(index) / PrintInterval()
   // loop prints (genomic_scans.cpp:411-428) -- with the filter on the device (gtx_window_refs / gtx_window_filter): the scanner was
@@ -371,6 +374,8 @@ class GenomicRegionSetScanner
   // line and notes where the walk stops: all windows of the blocks before halt_block, halt_win windows of that block, then the error.
   bool halt_set; size_t halt_block; long int halt_win; long int halt_line; bool halt_no_prefix; std::string halt_msg;
   void RaiseHalt();
+  bool LinesLayoutOnDevice(struct gtx_ctx *one);
+  bool PrintRemainingOnDevice(FILE *out_file, long int min_value);   // PrintRemaining through the renderer; false: the host loop has to                         // the blocks as the line renderer's layout; false: refused
   int keep_slot;                                                  // -1: the windows come to `values`
   std::string keep_error;
 };
@@ -490,6 +495,8 @@ void GtxPrintAnnotations(GenomicRegionSet *TestRegSet, GenomicRegionSet *RefRegS
                          bool ignore_strand, bool distance_flag, long int proximal_dist, bool print_header, const char *bin_bits);
 
 bool GtxScanFilterOnDevice();                                  // MI355X path: may `genomic_scans counts -r` filter on the device?  One GPU, and GTX_SCAN_FILTER_ON_DEVICE is not 0
+bool GtxScanLinesOnDevice();                                   // MI355X path: may `genomic_scans counts` render its output lines on the device?  One GPU, and GTX_SCAN_LINES_ON_DEVICE is not 0
+void GtxScanLinesFallback(const char *why);                    // ... the lines are about to be formatted by the host loop after all: under GTX_SCAN_LINES_ON_DEVICE=2 an error that says why, and the end of the run
 bool GtxPeaksOnDevice();                                       // MI355X path: may `genomic_scans peaks` select its candidate windows on the device?  One GPU, and GTX_PEAKS_ON_DEVICE is not 0
 void GtxSetDevices(int n_gpus);                               // MI355X path: GPUs the reductions are spread over (--ngpu; not in the reference)
 void GtxAcceptSAM(bool on);                                      // false: a SAM or GFF file is "unsupported input format!" (drivers that print query lines; default true)

@@ -7,7 +7,10 @@
 // error waiting in a sorted scan: the per-window loop on the host) and tests those on the host (tail probabilities: gtx_stats.h, GSL is
 // not linked); the -r reference filter of `counts` runs on the
 // device over the kept window vector (one GPU; GTX_SCAN_FILTER_ON_DEVICE=0: the per-window loop on the host), with -Sref it is the
-// reference's merge with the sorted stream, one window at a time on the host.
+// reference's merge with the sorted stream, one window at a time on the host.  The output lines of `counts` are written as text on the
+// device from the kept windows (gtx_window_lines; with -r from what the filter kept, gtx_window_filter_lines) and streamed to stdout
+// (one GPU; GTX_SCAN_LINES_ON_DEVICE=0, -Sref, -op p, or a chromosome name the renderer does not take: the host loop; =2: an error
+// where the host loop would run).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -281,7 +284,12 @@ int main(int argc, char *argv[])
   GenomicRegionSet InputRegSet(INPUT_REG_FILE, BUFFER_SIZE, VERBOSE, false, true);
   // -r without -Sref: the windows stay in HBM and the filter runs there (PrintFiltered)
   const bool device_filter = strlen(REF_REG_FILE) > 0 && !REF_SORTED && PREPROCESS != 'p' && GtxScanFilterOnDevice();
-  if (device_filter) GenomicRegionSetScanner::KeepNextOnDevice(0);
+  // no -r: the windows stay in HBM as well and the output lines are written there (PrintRemaining); what cannot take that route
+  // keeps the host loop -- under GTX_SCAN_LINES_ON_DEVICE=2 it is an error instead
+  const bool device_lines = strlen(REF_REG_FILE) == 0 && PREPROCESS != 'p' && GtxScanLinesOnDevice();
+  if (!device_lines && !(device_filter && GtxScanLinesOnDevice()))
+    GtxScanLinesFallback(!GtxScanLinesOnDevice() ? "switched off, or more than one GPU" : PREPROCESS == 'p' ? "-op p" : "-Sref, or the filter is not on the device");
+  if (device_filter || device_lines) GenomicRegionSetScanner::KeepNextOnDevice(0);
   GenomicRegionSetScanner *scanner;
   if (SORTED) scanner = new SortedGenomicRegionSetScanner(&InputRegSet, bounds, WIN_DIST, WIN_SIZE, MAX_LABEL_VALUE, IGNORE_STRAND, PREPROCESS);
   else scanner = new UnsortedGenomicRegionSetScanner(&InputRegSet, bounds, WIN_DIST, WIN_SIZE, MAX_LABEL_VALUE, IGNORE_STRAND, PREPROCESS);

@@ -1,12 +1,13 @@
 // gtx_api_scan.hip -- the C ABI's scans: gtx_scan* over reads on the device, in host buffers or fed as a stream, the window vectors
-// kept in HBM, and the window selection, the window filter and the peak candidate selection over them.  Host code only (the kernels:
-// gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip, gtx_select.hip, gtx_filter.hip, gtx_peaks.hip); the context and the helpers shared
+// kept in HBM, the window selection, the window filter and the peak candidate selection over them, and their output lines as text.  Host code only (the kernels:
+// gtx_kernels.hip, gtx_bucket.hip, gtx_scanown.hip, gtx_select.hip, gtx_filter.hip, gtx_peaks.hip, gtx_lines.hip); the context and the helpers shared
 // with the other families are in gtx_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <stdio.h>
 #include <cmath>
+#include <chrono>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -15,6 +16,7 @@
 #include "gtx_select.h"
 #include "gtx_filter.h"
 #include "gtx_peaks.h"
+#include "gtx_lines.h"
 #include "gtx_internal.h"
 #include "gtx_ctx.h"
 
@@ -621,6 +623,246 @@ int gtx_peak_select(gtx_ctx *c, const void *d_signal, const void *d_control, con
   return compact_host(c, capacity, 3 * sizeof(long long), ordinals, rows, n_kept, [&](void *d_ordinals, void *d_rows) {
     return gtx_peak_select_device(c, d_signal, d_control, d_uniq, n_windows, win_size, min_reads, norm, p_ratio, capacity, d_ordinals, d_rows, n_kept);
   });
+}
+
+}  // extern "C"
+
+extern "C" {
+
+// ---- output lines (gtx_lines.hip) ----
+static_assert(GTX_LINES_TILE == gtx::kLinesTile && GTX_LINES_MAX_NAME == gtx::kLinesMaxName, "include/gtx.h names the line renderer's tile and name limit");
+
+static int decimal_digits(unsigned long long u) { int d = 1; while (u >= 10) { u /= 10; d++; } return d; }
+
+int gtx_lines_layout(gtx_ctx *c, const int64_t *block_offset, int32_t n_blocks, const char *names_blob, const int32_t *name_off, const char *strand,
+                     int64_t win_step, int64_t win_size)
+{
+  if (!c) return GTX_E_ARG;
+  LinesState &s = c->lines;
+  s.set = false;
+  if (n_blocks < 1 || !block_offset || !name_off || !strand || (!names_blob && name_off[n_blocks] > 0)) return fail(c, GTX_E_ARG, "gtx_lines_layout: blocks, names and strands are required");
+  if (win_step < 1 || win_size < 1 || win_step > INT32_MAX || win_size > INT32_MAX) return fail(c, GTX_E_ARG, "gtx_lines_layout: window step and size must be positive and below 2^31");
+  if (block_offset[0] != 0 || name_off[0] < 0) return fail(c, GTX_E_ARG, "gtx_lines_layout: offsets start at 0");
+  int maxLine = 0;
+  for (int b = 0; b < n_blocks; b++) {
+    const int64_t nb = block_offset[b + 1] - block_offset[b];
+    const int len = name_off[b + 1] - name_off[b];
+    if (nb < 0 || block_offset[b + 1] > (1ll << 40)) return fail(c, GTX_E_ARG, "gtx_lines_layout: block offsets must ascend and stay at or below 2^40");
+    if (len < 0) return fail(c, GTX_E_ARG, "gtx_lines_layout: name offsets must ascend");
+    if (len > gtx::kLinesMaxName) return fail(c, GTX_E_ARG, "gtx_lines_layout: a name is longer than GTX_LINES_MAX_NAME");
+    if (strand[b] != '+' && strand[b] != '-') return fail(c, GTX_E_ARG, "gtx_lines_layout: a strand is '+' or '-'");
+    const unsigned long long k = (unsigned long long)std::max<int64_t>(nb - 1, 0);
+    maxLine = std::max(maxLine, 20 + 1 + len + 3 + decimal_digits(win_step * k + 1) + 1 + decimal_digits(win_step * k + win_size) + 1);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));                          // a pass may still be reading what the buffers held
+  HIPCHK(c, upload(s.blockOff, (const long long *)block_offset, (size_t)n_blocks + 1));
+  HIPCHK(c, upload(s.nameOff, (const int *)name_off, (size_t)n_blocks + 1));
+  HIPCHK(c, s.names.alloc((size_t)std::max(name_off[n_blocks], 1)));
+  if (name_off[n_blocks] > 0) HIPCHK(c, hipMemcpy(s.names.get(), names_blob, (size_t)name_off[n_blocks], hipMemcpyHostToDevice));
+  HIPCHK(c, upload(s.strand, strand, (size_t)n_blocks));
+  s.nBlocks = n_blocks; s.maxLine = maxLine; s.total = block_offset[n_blocks]; s.step = win_step; s.size = win_size;
+  s.set = true;
+  return GTX_OK;
+}
+
+int64_t gtx_lines_max_bytes(gtx_ctx *c)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->lines.set) return fail(c, GTX_E_STATE, "gtx_lines_max_bytes: gtx_lines_layout has not been called");
+  return c->lines.maxLine;
+}
+
+int gtx_set_lines_chunk(gtx_ctx *c, int64_t bytes)
+{
+  if (!c) return GTX_E_ARG;
+  if (bytes < 1) return fail(c, GTX_E_ARG, "gtx_set_lines_chunk: a positive number of bytes");
+  c->lines.chunkBytes = bytes;
+  return GTX_OK;
+}
+
+} // extern "C"
+
+// One range of the renderer enqueued on the context's stream behind its argument checks: count, the two prefix scans, emit, and the
+// range's totals (lines, bytes, the all-ones word) on their way into totals[3 * slot ..].  ordinals null: the vector rule.
+static int lines_enqueue(gtx_ctx *c, const void *d_ordinals, const void *d_values, int64_t first, int64_t count, int64_t limit, int64_t min_value, void *d_text, int slot,
+                         bool emit = true)
+{
+  LinesState &s = c->lines;
+  const size_t nt = (size_t)gtx::lines_tiles(first, first + count);
+  if (!s.endWord) HIPCHK(c, s.endWord.alloc(1));
+  if (!s.totals) HIPCHK(c, s.totals.alloc(6));
+  if (nt > s.tileLines.cap || nt + 1 > s.baseLines.cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, s.tileLines.reserve(nt)); HIPCHK(c, s.tileBytes.reserve(nt)); HIPCHK(c, s.baseLines.reserve(nt + 1)); HIPCHK(c, s.baseBytes.reserve(nt + 1));
+  }
+  gtx::LinesArgs a = {};
+  a.L = {s.blockOff.get(), s.nameOff.get(), s.names.get(), s.strand.get(), s.nBlocks, s.maxLine, s.step, s.size};
+  a.values = (const u64 *)d_values; a.ordinals = (const long long *)d_ordinals;
+  a.first = first; a.end = first + count; a.limit = std::min<int64_t>(limit, s.total); a.minValue = min_value;
+  a.tileLines = s.tileLines.get(); a.tileBytes = s.tileBytes.get(); a.baseBytes = s.baseBytes.get(); a.endWord = s.endWord.get(); a.text = (char *)d_text;
+  if (emit) HIPCHK(c, hipMemsetAsync(s.endWord.get(), 0xff, sizeof(u64), c->stream));
+  HIPCHK(c, gtx::launch_lines_count(a, c->stream));
+  HIPCHK(c, gtx::launch_tile_prefix(s.tileLines.get(), (long long)nt, s.baseLines.get(), c->stream));
+  HIPCHK(c, gtx::launch_tile_prefix(s.tileBytes.get(), (long long)nt, s.baseBytes.get(), c->stream));
+  if (emit) HIPCHK(c, gtx::launch_lines_emit(a, c->stream));
+  u64 *tot = s.totals.get() + 3 * slot;
+  HIPCHK(c, hipMemcpyAsync(tot, s.baseLines.get() + nt, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(tot + 1, s.baseBytes.get() + nt, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  if (emit) HIPCHK(c, hipMemcpyAsync(tot + 2, s.endWord.get(), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  return GTX_OK;
+}
+
+// ... and waited for.  An all-ones value in the range: the emit pass has rendered what lies in front of it (it reads the word); the
+// lines and bytes of that part are counted once more with the limit at that ordinal.
+static int lines_finish(gtx_ctx *c, const void *d_ordinals, const void *d_values, int64_t first, int64_t count, int64_t min_value, int slot, int64_t *n_lines,
+                        int64_t *n_bytes, int64_t *end_at)
+{
+  const u64 *tot = c->lines.totals.get() + 3 * slot;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *end_at = tot[2] == ~0ull ? -1 : (int64_t)tot[2];
+  if (*end_at >= 0) {
+    int rc = lines_enqueue(c, d_ordinals, d_values, first, count, *end_at, min_value, nullptr, slot, false); if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  *n_lines = (int64_t)tot[0]; *n_bytes = (int64_t)tot[1];
+  return GTX_OK;
+}
+
+static int lines_check(gtx_ctx *c, const char *who, const void *d_ordinals, const void *d_values, int64_t first, int64_t count, bool pairs)
+{
+  if (!c->lines.set) { c->err = std::string(who) + ": gtx_lines_layout has not been called"; return GTX_E_STATE; }
+  if (first < 0 || count < 0 || first > INT64_MAX - count) { c->err = std::string(who) + ": bad range"; return GTX_E_ARG; }
+  if (count > 0 && (!d_values || ((uintptr_t)d_values & 15) || (pairs && (!d_ordinals || ((uintptr_t)d_ordinals & 15))))) { c->err = std::string(who) + ": the vectors must be 16-byte aligned device memory"; return GTX_E_ARG; }
+  if (!pairs && first + count > c->lines.total) { c->err = std::string(who) + ": the range reaches beyond the layout's windows"; return GTX_E_ARG; }
+  return GTX_OK;
+}
+
+static int lines_device(gtx_ctx *c, const char *who, const void *d_ordinals, const void *d_values, int64_t first, int64_t count, int64_t limit, int64_t min_value,
+                        void *d_text, int64_t capacity, int64_t *n_lines, int64_t *n_bytes, int64_t *end_at, bool pairs)
+{
+  if (!c) return GTX_E_ARG;
+  int rc = lines_check(c, who, d_ordinals, d_values, first, count, pairs); if (rc) return rc;
+  if (!n_lines || !n_bytes || !end_at || capacity < 0) { c->err = std::string(who) + ": n_lines, n_bytes and end_at are required, and a capacity"; return GTX_E_ARG; }
+  if (count > capacity / c->lines.maxLine) { c->err = std::string(who) + ": count x gtx_lines_max_bytes exceeds the capacity"; return GTX_E_ARG; }
+  if (count > 0 && (!d_text || ((uintptr_t)d_text & 15))) { c->err = std::string(who) + ": the text buffer must be 16-byte aligned device memory"; return GTX_E_ARG; }
+  *n_lines = 0; *n_bytes = 0; *end_at = -1;
+  if (count == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = lines_enqueue(c, d_ordinals, d_values, first, count, limit, min_value, d_text, 0); if (rc) return rc;
+  return lines_finish(c, d_ordinals, d_values, first, count, min_value, 0, n_lines, n_bytes, end_at);
+}
+
+// The streaming entries: ranges of whole tiles through two device and two page-locked buffers.  Range r + 1 is enqueued before the
+// sink is given range r - 1, behind the copy of r - 1 out of the device buffer it writes (an event the stream waits for).
+static int lines_stream(gtx_ctx *c, const char *who, const void *d_ordinals, const void *d_values, int64_t n, int64_t limit, int64_t min_value, gtx_lines_sink sink,
+                        void *user, int64_t *n_lines, int64_t *n_bytes, int64_t *end_at, bool pairs)
+{
+  if (!c) return GTX_E_ARG;
+  int rc = lines_check(c, who, d_ordinals, d_values, 0, n, pairs); if (rc) return rc;
+  if (!sink) { c->err = std::string(who) + ": a sink is required"; return GTX_E_ARG; }
+  LinesState &s = c->lines;
+  int64_t lines = 0, bytes = 0, ended = -1;
+  if (n_lines) *n_lines = 0;
+  if (n_bytes) *n_bytes = 0;
+  if (end_at) *end_at = -1;
+  if (n == 0) return GTX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int64_t per = std::max<int64_t>(1, s.chunkBytes / ((int64_t)s.maxLine * gtx::kLinesTile)) * gtx::kLinesTile;   // entries per range: whole tiles
+  const size_t room = (size_t)std::min(per, n) * (size_t)s.maxLine;
+  if (room > s.text[0].cap || room > s.pin[0].cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+    for (int k = 0; k < 2; k++) { HIPCHK(c, s.text[k].reserve(room)); HIPCHK(c, s.pin[k].reserve(room)); }
+  }
+  for (int k = 0; k < 2; k++) if (!s.evCopied[k]) HIPCHK(c, hipEventCreateWithFlags(&s.evCopied[k], hipEventDisableTiming));
+  const int64_t ranges = (n + per - 1) / per;
+  int64_t got[2] = {0, 0};                                             // the bytes of the ranges in the two page-locked buffers
+  // GTX_LINES_TIMING=1: where the host waited -- for a range's passes, for its copy, in the sink -- on stderr when the stream ends
+  static const bool timing = getenv("GTX_LINES_TIMING") != nullptr;
+  double waited[3] = {0, 0, 0};
+  auto timed = [&](int what, auto &&fn) { const auto t0 = std::chrono::steady_clock::now(); auto r = fn(); waited[what] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); return r; };
+  auto sink_range = [&](int64_t r) -> int {
+    const int k = (int)(r & 1);
+    HIPCHK(c, timed(1, [&] { return hipEventSynchronize(s.evCopied[k]); }));
+    if (got[k] > 0 && timed(2, [&] { return sink(user, s.pin[k].get(), (size_t)got[k]); }) != 0) {
+      (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stage.copyStream);
+      c->err = std::string(who) + ": the sink refused the text"; return GTX_E_SINK;
+    }
+    return GTX_OK;
+  };
+  rc = lines_enqueue(c, d_ordinals, d_values, 0, std::min(per, n), limit, min_value, s.text[0].get(), 0); if (rc) return rc;
+  int64_t last = ranges - 1;
+  for (int64_t r = 0; r < ranges; r++) {
+    const int k = (int)(r & 1);
+    const int64_t first = r * per, count = std::min(per, n - first);
+    int64_t nl = 0, nb = 0;
+    rc = timed(0, [&] { return lines_finish(c, d_ordinals, d_values, first, count, min_value, k, &nl, &nb, &ended); }); if (rc) return rc;
+    lines += nl; bytes += nb; got[k] = nb;
+    if (nb > 0) HIPCHK(c, hipMemcpyAsync(s.pin[k].get(), s.text[k].get(), (size_t)nb, hipMemcpyDeviceToHost, c->stage.copyStream));
+    HIPCHK(c, hipEventRecord(s.evCopied[k], c->stage.copyStream));
+    if (ended >= 0) last = r;
+    if (r < last) {
+      if (r >= 1) HIPCHK(c, hipStreamWaitEvent(c->stream, s.evCopied[k ^ 1], 0));   // the copy of r - 1 out of the buffer r + 1 is rendered into
+      rc = lines_enqueue(c, d_ordinals, d_values, first + per, std::min(per, n - first - per), limit, min_value, s.text[k ^ 1].get(), k ^ 1); if (rc) return rc;
+    }
+    if (r >= 1) { rc = sink_range(r - 1); if (rc) return rc; }
+    if (r == last) break;
+  }
+  rc = sink_range(last); if (rc) return rc;
+  if (timing) fprintf(stderr, "[gtx lines] %lld ranges, %lld lines, %lld bytes: waited %.3f s for the passes, %.3f s for the copies, %.3f s in the sink\n",
+                      (long long)(last + 1), (long long)lines, (long long)bytes, waited[0], waited[1], waited[2]);
+  if (n_lines) *n_lines = lines;
+  if (n_bytes) *n_bytes = bytes;
+  if (end_at) *end_at = ended;
+  return GTX_OK;
+}
+
+extern "C" {
+
+int gtx_window_lines_device(gtx_ctx *c, const void *d_windows, int64_t first, int64_t count, int64_t limit, int64_t min_value, void *d_text, int64_t capacity,
+                            int64_t *n_lines, int64_t *n_bytes, int64_t *end_at)
+{
+  return lines_device(c, "gtx_window_lines_device", nullptr, d_windows, first, count, limit, min_value, d_text, capacity, n_lines, n_bytes, end_at, false);
+}
+
+int gtx_pair_lines_device(gtx_ctx *c, const void *d_ordinals, const void *d_values, int64_t first, int64_t count, int64_t limit, void *d_text, int64_t capacity,
+                          int64_t *n_lines, int64_t *n_bytes, int64_t *end_at)
+{
+  return lines_device(c, "gtx_pair_lines_device", d_ordinals, d_values, first, count, limit, 0, d_text, capacity, n_lines, n_bytes, end_at, true);
+}
+
+int gtx_window_lines(gtx_ctx *c, const void *d_windows, int64_t n_windows, int64_t limit, int64_t min_value, gtx_lines_sink sink, void *user, int64_t *n_lines,
+                     int64_t *n_bytes, int64_t *end_at)
+{
+  return lines_stream(c, "gtx_window_lines", nullptr, d_windows, n_windows, limit, min_value, sink, user, n_lines, n_bytes, end_at, false);
+}
+
+int gtx_pair_lines(gtx_ctx *c, const void *d_ordinals, const void *d_values, int64_t n, int64_t limit, gtx_lines_sink sink, void *user, int64_t *n_lines,
+                   int64_t *n_bytes, int64_t *end_at)
+{
+  return lines_stream(c, "gtx_pair_lines", d_ordinals, d_values, n, limit, 0, sink, user, n_lines, n_bytes, end_at, true);
+}
+
+// the filter into the compactions' own result buffers (room for max(2^16, n / 64) windows, grown once to what the filter reports),
+// the pair rule over them: neither ordinals nor values come to the host
+int gtx_window_filter_lines(gtx_ctx *c, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t limit, gtx_lines_sink sink, void *user,
+                            int64_t *n_lines, int64_t *n_bytes, int64_t *end_at)
+{
+  if (!c) return GTX_E_ARG;
+  if (!c->lines.set) return fail(c, GTX_E_STATE, "gtx_window_filter_lines: gtx_lines_layout has not been called");
+  CompactState &s = c->cmp;
+  HIPCHK(c, hipSetDevice(c->device));
+  int64_t cap = std::max<int64_t>(1 << 16, n_windows / 64), kept = 0;
+  for (;;) {
+    if ((size_t)cap > s.ord.cap || (size_t)cap * sizeof(u64) > s.rows.cap) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, s.ord.reserve((size_t)cap)); HIPCHK(c, s.rows.reserve((size_t)cap * sizeof(u64)));
+    }
+    int rc = gtx_window_filter_device(c, d_windows, n_windows, min_value, cap, s.ord.get(), s.rows.get(), &kept); if (rc) return rc;
+    if (kept <= cap) break;
+    cap = kept;
+  }
+  return lines_stream(c, "gtx_window_filter_lines", s.ord.get(), s.rows.get(), kept, limit, 0, sink, user, n_lines, n_bytes, end_at, true);
 }
 
 }  // extern "C"

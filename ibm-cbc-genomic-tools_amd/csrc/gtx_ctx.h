@@ -229,6 +229,18 @@ struct FilterState {
   DevBuf<int> tri, keyed, sorted, start, runmax, first, blkCls; DevBuf<unsigned> order, bad; DevBuf<long long> blkOff, blkEnd;
 };
 
+// the line renderer (gtx_lines.hip): the layout gtx_lines_layout uploaded with what the host keeps of it, the passes' per-tile lines
+// and bytes with their sums, the all-ones word, the totals of two ranges in flight on the host (lines, bytes, end word each), and the
+// streaming entries' two device and two page-locked text buffers with the events of their copies
+struct LinesState {
+  bool set = false; int nBlocks = 0, maxLine = 0; int64_t total = 0, step = 0, size = 0, chunkBytes = 64ll << 20;
+  DevBuf<long long> blockOff; DevBuf<int> nameOff; DevBuf<char> names, strand;
+  DevBuf<unsigned> tileLines, tileBytes; DevBuf<long long> baseLines, baseBytes; DevBuf<unsigned long long> endWord;
+  PinBuf<unsigned long long> totals;
+  DevBuf<char> text[2]; PinBuf<char> pin[2]; hipEvent_t evCopied[2] = {nullptr, nullptr};
+  ~LinesState() { for (int k = 0; k < 2; k++) if (evCopied[k]) (void)hipEventDestroy(evCopied[k]); }
+};
+
 // link: the scans' per-tile values and break bit map, the info block and its page-locked copy (handed to the caller's struct by
 // gtx_sync after a device call), the host entry's inputs and group records
 struct LinkState {
@@ -337,6 +349,7 @@ struct gtx_ctx {
   CompactState cmp;
   SelectState sel;
   FilterState flt;
+  LinesState lines;
   TextState text;
   LinkState link;
   NeighbourState nbr;

@@ -57,6 +57,15 @@ static bool OneGpuAndNotOff(const char *off_switch)
 }
 bool GtxScanFilterOnDevice() { return OneGpuAndNotOff("GTX_SCAN_FILTER_ON_DEVICE"); }
 bool GtxPeaksOnDevice() { return OneGpuAndNotOff("GTX_PEAKS_ON_DEVICE"); }
+bool GtxScanLinesOnDevice() { return OneGpuAndNotOff("GTX_SCAN_LINES_ON_DEVICE"); }
+void GtxScanLinesFallback(const char *why)
+{
+  const char *e = getenv("GTX_SCAN_LINES_ON_DEVICE");
+  if (!e || atoi(e) != 2) return;
+  fflush(stdout);
+  fprintf(stderr, "Error: GTX_SCAN_LINES_ON_DEVICE=2, and the output lines would fall back to the host loop (%s)!\n", why);
+  exit(1);
+}
 
 // the page-locked batch buffers (gtx_host.h)
 static const size_t kBatchReads = getenv("GTX_HOST_BATCH_READS") && atol(getenv("GTX_HOST_BATCH_READS")) > 0 ? (size_t)atol(getenv("GTX_HOST_BATCH_READS")) : (8u << 20);   // reads per batch handed to the device

@@ -369,9 +369,60 @@ long int GenomicRegionSetScanner::Next()
   return -1;
 }
 
+// the renderer's sink: the text to a FILE
+static int WriteLines(void *user, const char *text, size_t bytes) { return fwrite(text, 1, bytes, (FILE *)user) == bytes ? 0 : 1; }
+
+bool GenomicRegionSetScanner::LinesLayoutOnDevice(gtx_ctx *one)
+{
+  const size_t ns = ignore_strand ? 1 : 2, nb = n_windows.size();
+  std::vector<int64_t> off(nb + 1);
+  std::vector<int32_t> name_off(nb + 1, 0);
+  std::string blob, strand;
+  for (size_t b = 0; b < nb; b++) {
+    off[b] = block_offset[b];
+    blob += chrom_names[b / ns]; name_off[b + 1] = (int32_t)blob.size(); strand += (b % ns) ? '-' : '+';
+  }
+  off[nb] = nb ? block_offset[nb - 1] + n_windows[nb - 1] : 0;
+  const int rc = nb ? gtx_lines_layout(one, off.data(), (int32_t)nb, blob.data(), name_off.data(), strand.data(), win_step, win_size) : GTX_E_ARG;
+  if (rc != GTX_OK && rc != GTX_E_ARG) DieGtx(one, rc);
+  return rc == GTX_OK;
+}
+
+// PrintRemaining for a scanner whose windows were kept, from the first window on.  False: the windows are on the host now (a layout
+// the renderer refuses, or a walk that has begun) and the host loop prints them.
+bool GenomicRegionSetScanner::PrintRemainingOnDevice(FILE *out_file, long int min_value)
+{
+  if (!keep_error.empty()) { std::cerr << "Error: " << keep_error << "\n"; exit(1); }
+  gtx_ctx *one = gtx_group_ctx(Devices(), 0);
+  const long long total = WindowCount();
+  if (cur_block != 0 || cur_win != 0 || (total > 0 && !LinesLayoutOnDevice(one))) {
+    GtxScanLinesFallback("a layout the renderer does not take");
+    BringKeptToHost();
+    return false;
+  }
+  // a sorted scanner's input error: the windows in front of where the walk meets it, then the error
+  const long long limit = halt_set ? std::min<long long>(total, block_offset[halt_block] + halt_win) : total;
+  int64_t end_at = -1;
+  if (total > 0 && limit > 0) {
+    void *d_windows = NULL; int64_t n_kept_windows = 0;
+    DieGtx(one, gtx_scan_kept(one, keep_slot, &d_windows, &n_kept_windows));
+    DieGtx(one, gtx_window_lines(one, d_windows, (int64_t)total, (int64_t)limit, (int64_t)min_value, WriteLines, out_file, NULL, NULL, &end_at));
+  }
+  bool raise = halt_set;
+  if (end_at >= 0) {                                                 // the loop stops behind that window and looks at the halt position once more
+    const size_t b = (size_t)(std::upper_bound(block_offset.begin(), block_offset.end(), (long long)end_at) - block_offset.begin()) - 1;
+    const long int w = (long int)(end_at - block_offset[b]) + 1;
+    raise = halt_set && (b > halt_block || (b == halt_block && w >= halt_win));
+  }
+  cur_block = n_windows.size(); cur_win = 0;
+  if (raise) { fflush(out_file); RaiseHalt(); }
+  return true;
+}
+
 void GenomicRegionSetScanner::PrintRemaining(FILE *out_file, long int min_value)
 {
   if (!computed) Compute(false);
+  if (keep_slot >= 0 && PrintRemainingOnDevice(out_file, min_value)) return;
   if (keep_slot >= 0) { std::cerr << "Error: [GenomicRegionSetScanner] the windows were kept on the device!\n"; exit(1); }
   const int ns = ignore_strand ? 1 : 2;
   std::vector<char> buf; buf.reserve(8u << 20);
@@ -435,36 +486,45 @@ void GenomicRegionSetScanner::PrintFiltered(FILE *out_file, GenomicRegionSetInde
       tri.push_back((int32_t)std::max<long int>(i->START, 1)); tri.push_back((int32_t)std::min<long int>(i->STOP, INT_MAX - 1));
     }
     DieGtx(one, gtx_window_refs(one, tri.data(), (int64_t)(tri.size() / 3), class_len.data(), class_off.data(), n_chrom * ns, (int32_t)win_step, (int32_t)win_size));
-    std::vector<long long> ordinals;
-    std::vector<unsigned long long> kept_values;
-    int64_t kept = 0;
-    DieGtx(one, WithRoomFor(total, &kept, [&](int64_t cap, int64_t *k) {
-      ordinals.resize((size_t)cap); kept_values.resize((size_t)cap);
-      return gtx_window_filter(one, d_windows, (int64_t)total, floor_value, cap, (int64_t *)ordinals.data(), (uint64_t *)kept_values.data(), k);
-    }));
-    std::vector<char> buf; buf.reserve(8u << 20);
-    auto put_num = [&](long long v) {
-      char tmp[24]; int n = 0;
-      unsigned long long u = (unsigned long long)v;
-      do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
-      while (n) buf.push_back(tmp[--n]);
-    };
-    size_t b = 0;
-    for (int64_t j = 0; j < kept; j++) {
-      const long long at = ordinals[(size_t)j];
-      if (at >= limit) break;
-      const unsigned long long v = kept_values[(size_t)j];
-      if (v == ~0ull) { ended = true; break; }
-      if ((long long)v < 0) continue;                                // (a caller's loop compares as long int)
-      while (b + 1 < block_offset.size() && block_offset[b + 1] <= at) b++;   // (empty blocks share an offset: the last one at or below holds it)
-      const long long k = at - block_offset[b];
-      const std::string &chrom = chrom_names[b / (size_t)ns];
-      put_num((long long)v); buf.push_back('\t');
-      buf.insert(buf.end(), chrom.begin(), chrom.end()); buf.push_back(' '); buf.push_back((b % (size_t)ns) ? '-' : '+'); buf.push_back(' ');
-      put_num(win_step * k + 1); buf.push_back(' '); put_num(win_step * k + win_size); buf.push_back('\n');
-      if (buf.size() > (7u << 20)) { fwrite(buf.data(), 1, buf.size(), out_file); buf.clear(); }
+    // the lines on the device too (the pair rule over what the filter kept there), unless that is switched off or the layout refused
+    const bool lines = GtxScanLinesOnDevice() && LinesLayoutOnDevice(one);
+    if (lines) {
+      int64_t end_at = -1;
+      DieGtx(one, gtx_window_filter_lines(one, d_windows, (int64_t)total, floor_value, (int64_t)limit, WriteLines, out_file, NULL, NULL, &end_at));
+      ended = end_at >= 0;
+    } else {
+      GtxScanLinesFallback(GtxScanLinesOnDevice() ? "a layout the renderer does not take" : "switched off, or more than one GPU");
+      std::vector<long long> ordinals;
+      std::vector<unsigned long long> kept_values;
+      int64_t kept = 0;
+      DieGtx(one, WithRoomFor(total, &kept, [&](int64_t cap, int64_t *k) {
+        ordinals.resize((size_t)cap); kept_values.resize((size_t)cap);
+        return gtx_window_filter(one, d_windows, (int64_t)total, floor_value, cap, (int64_t *)ordinals.data(), (uint64_t *)kept_values.data(), k);
+      }));
+      std::vector<char> buf; buf.reserve(8u << 20);
+      auto put_num = [&](long long v) {
+        char tmp[24]; int n = 0;
+        unsigned long long u = (unsigned long long)v;
+        do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
+        while (n) buf.push_back(tmp[--n]);
+      };
+      size_t b = 0;
+      for (int64_t j = 0; j < kept; j++) {
+        const long long at = ordinals[(size_t)j];
+        if (at >= limit) break;
+        const unsigned long long v = kept_values[(size_t)j];
+        if (v == ~0ull) { ended = true; break; }
+        if ((long long)v < 0) continue;                                // (a caller's loop compares as long int)
+        while (b + 1 < block_offset.size() && block_offset[b + 1] <= at) b++;   // (empty blocks share an offset: the last one at or below holds it)
+        const long long k = at - block_offset[b];
+        const std::string &chrom = chrom_names[b / (size_t)ns];
+        put_num((long long)v); buf.push_back('\t');
+        buf.insert(buf.end(), chrom.begin(), chrom.end()); buf.push_back(' '); buf.push_back((b % (size_t)ns) ? '-' : '+'); buf.push_back(' ');
+        put_num(win_step * k + 1); buf.push_back(' '); put_num(win_step * k + win_size); buf.push_back('\n');
+        if (buf.size() > (7u << 20)) { fwrite(buf.data(), 1, buf.size(), out_file); buf.clear(); }
+      }
+      if (!buf.empty()) fwrite(buf.data(), 1, buf.size(), out_file);
     }
-    if (!buf.empty()) fwrite(buf.data(), 1, buf.size(), out_file);
   }
   cur_block = n_windows.size(); cur_win = 0;
   if (halt_set && !ended) { fflush(out_file); RaiseHalt(); }

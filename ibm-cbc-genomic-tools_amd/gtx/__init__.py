@@ -101,6 +101,10 @@ class TextRules(ctypes.Structure):
 
 
 # name -> (restype, argtypes); must list every symbol include/gtx.h declares
+# int sink(void *user, const char *text, size_t bytes) of gtx_window_lines / gtx_pair_lines
+LINES_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
+LINES_TILE, LINES_MAX_NAME, E_SINK = 1024, 48, -5
+
 ABI = {
     "gtx_version": (ctypes.c_int, []),
     "gtx_create": (ctypes.c_void_p, [ctypes.c_int]),
@@ -159,6 +163,20 @@ ABI = {
                                               ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_peak_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_lines_layout": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64,
+                                        ctypes.c_int64]),
+    "gtx_lines_max_bytes": (ctypes.c_int64, [ctypes.c_void_p]),
+    "gtx_set_lines_chunk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "gtx_window_lines_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_pair_lines_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_window_lines": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, LINES_SINK, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_pair_lines": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, LINES_SINK, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_window_filter_lines": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int64, LINES_SINK, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_sort_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_link": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
@@ -907,6 +925,75 @@ class Engine:
             lambda cap, ordinals, values, kept: self.lib.gtx_window_filter(self.ctx, _ptr(addr), int(n_windows), int(min_value), cap, _ptr(ordinals),
                                                                            _ptr(values), ctypes.byref(kept)),
             n_windows, capacity, lambda cap: (np.full(cap, -1, dtype=np.int64), np.zeros(cap, dtype=np.uint64)))
+
+    def lines_layout(self, block_offset, names, strands, win_step, win_size):
+        """gtx_lines_layout: the blocks the line renderer prints by.  block_offset: n_blocks + 1 ordinals ascending from 0; names: one
+        str or bytes per block; strands: one '+' or '-' per block.  Returns gtx_lines_max_bytes, the longest line of the layout."""
+        off = np.ascontiguousarray(block_offset, dtype=np.int64)
+        nm = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        st = strands.encode() if isinstance(strands, str) else bytes(strands)
+        if len(nm) != len(off) - 1 or len(st) != len(nm):
+            raise ValueError("one name and one strand per block, one offset more")
+        name_off = np.zeros(len(nm) + 1, dtype=np.int32)
+        name_off[1:] = np.cumsum([len(x) for x in nm])
+        self._chk(self.lib.gtx_lines_layout(self.ctx, _ptr(off), len(nm), b"".join(nm), _ptr(name_off), st, int(win_step), int(win_size)))
+        return self.lines_max_bytes()
+
+    def lines_max_bytes(self):
+        n = int(self.lib.gtx_lines_max_bytes(self.ctx))
+        self._chk(min(n, 0))
+        return n
+
+    def set_lines_chunk(self, n_bytes):
+        """bytes of bound per range of window_lines / pair_lines (whole tiles; at least one tile)"""
+        self._chk(self.lib.gtx_set_lines_chunk(self.ctx, int(n_bytes)))
+
+    def window_lines_device(self, windows, first, count, limit, min_value, d_text, capacity):
+        """gtx_window_lines_device: the kept lines of windows [first, first + count) of a kept slot or a raw device address into the
+        caller's device buffer.  Returns (lines, bytes, end_at)."""
+        addr, _ = self._kept_or_address(windows)
+        nl, nb, end = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(-1)
+        self._chk(self.lib.gtx_window_lines_device(self.ctx, _ptr(addr), int(first), int(count), int(limit), int(min_value), _ptr(d_text), int(capacity),
+                                                   ctypes.byref(nl), ctypes.byref(nb), ctypes.byref(end)))
+        return int(nl.value), int(nb.value), int(end.value)
+
+    def pair_lines_device(self, d_ordinals, d_values, first, count, limit, d_text, capacity):
+        """gtx_pair_lines_device: the same for entries [first, first + count) of (ordinal, value) pairs on the device"""
+        nl, nb, end = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(-1)
+        self._chk(self.lib.gtx_pair_lines_device(self.ctx, _ptr(d_ordinals), _ptr(d_values), int(first), int(count), int(limit), _ptr(d_text), int(capacity),
+                                                 ctypes.byref(nl), ctypes.byref(nb), ctypes.byref(end)))
+        return int(nl.value), int(nb.value), int(end.value)
+
+    def _lines_stream(self, call, sink):
+        """sink(bytes) -> falsy to go on; without one the chunks are collected.  Returns (chunks or None, lines, bytes, end_at)."""
+        chunks = []
+        take = sink if sink is not None else chunks.append
+        cb = LINES_SINK(lambda user, text, n: int(bool(take(ctypes.string_at(text, n)))))
+        nl, nb, end = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(-1)
+        self._chk(call(cb, ctypes.byref(nl), ctypes.byref(nb), ctypes.byref(end)))
+        return (chunks if sink is None else None), int(nl.value), int(nb.value), int(end.value)
+
+    def window_lines(self, windows, limit, min_value, n_windows=None, sink=None):
+        """gtx_window_lines: all kept lines of a window vector (kept slot, or raw device address with n_windows) streamed in order to
+        sink(bytes) (a truthy return ends the call with an error), or collected: returns (list of chunks or None, lines, bytes, end_at)."""
+        addr, n = self._kept_or_address(windows)
+        if n_windows is None:
+            n_windows = n
+        return self._lines_stream(lambda cb, nl, nb, end: self.lib.gtx_window_lines(self.ctx, _ptr(addr), int(n_windows), int(limit), int(min_value), cb, None,
+                                                                                    nl, nb, end), sink)
+
+    def pair_lines(self, d_ordinals, d_values, n, limit, sink=None):
+        """gtx_pair_lines: the same over n (ordinal, value) pairs on the device"""
+        return self._lines_stream(lambda cb, nl, nb, end: self.lib.gtx_pair_lines(self.ctx, _ptr(d_ordinals), _ptr(d_values), int(n), int(limit), cb, None,
+                                                                                  nl, nb, end), sink)
+
+    def window_filter_lines(self, windows, min_value, limit, n_windows=None, sink=None):
+        """gtx_window_filter_lines: window_filter (after window_refs) and pair_lines in one call, the kept windows staying on the device"""
+        addr, n = self._kept_or_address(windows)
+        if n_windows is None:
+            n_windows = n
+        return self._lines_stream(lambda cb, nl, nb, end: self.lib.gtx_window_filter_lines(self.ctx, _ptr(addr), int(n_windows), int(min_value), int(limit), cb,
+                                                                                           None, nl, nb, end), sink)
 
     def _peak_vectors(self, signal, control, uniq, n_windows):
         s, c, u = self._kept_or_address(signal), self._kept_or_address(control), self._kept_or_address(uniq)

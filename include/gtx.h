@@ -774,6 +774,53 @@ int gtx_peak_select_device(gtx_ctx *ctx, const void *d_signal, const void *d_con
 int gtx_peak_select(gtx_ctx *ctx, const void *d_signal, const void *d_control, const void *d_uniq, int64_t n_windows, int64_t win_size,
                     int64_t min_reads, int norm, double p_ratio, int64_t capacity, int64_t *ordinals, int64_t *rows, int64_t *n_kept);
 
+/* Output lines on the device: what `genomic_scans counts` prints (GenomicRegionSetScanner::PrintRemaining / PrintFiltered), rendered
+ * as text from a window vector in HBM or from the (ordinal, value) pairs gtx_window_filter_device left there.
+ * gtx_lines_layout uploads the blocks of a scan geometry (host memory): block_offset[n_blocks + 1] ascending from 0 (block b holds
+ * the ordinals block_offset[b] .. block_offset[b + 1]; empty blocks share an offset, the last entry is the number of windows), block
+ * b's name names_blob[name_off[b] .. name_off[b + 1]) and strand[b] ('+' or '-').  The line of ordinal `at` of block b, with
+ * k = at - block_offset[b], is   VALUE '\t' NAME ' ' STRAND ' ' win_step k + 1 ' ' win_step k + win_size '\n'   -- VALUE a signed
+ * 64-bit decimal.  GTX_E_ARG: a name longer than GTX_LINES_MAX_NAME (the caller then formats on the host), n_blocks < 1, offsets that
+ * do not ascend from 0, a strand that is neither, win_step or win_size < 1, or more than 2^40 windows.  gtx_lines_max_bytes: the
+ * longest line that layout can produce (GTX_E_STATE before a layout).
+ * gtx_window_lines_device (the vector rule): d_windows is a device vector of uint64 sums, 16-byte aligned, holding at least
+ * first + count entries; window i of [first, first + count) is kept when i < limit and (int64) w[i] >= min_value.  The first window
+ * in front of `limit` whose value is all-ones is never printed and ends the output whatever min_value is; *end_at is its ordinal, or
+ * -1.  The kept lines are written to d_text (device memory, 16-byte aligned) back to back in window order: *n_lines of them, *n_bytes
+ * bytes.  GTX_E_ARG when count * gtx_lines_max_bytes exceeds capacity (a caller sizes its ranges by that bound and never repeats a
+ * call), for an unaligned pointer, and when first + count reaches beyond the layout's windows.  Nothing is written at or beyond
+ * d_text + capacity; bytes between *n_bytes and the next 16-byte boundary are unspecified, what lies behind that boundary is untouched.
+ * gtx_pair_lines_device (the pair rule): entries j of [first, first + count) of d_ordinals (int64, ascending) and d_values (uint64),
+ * both 16-byte aligned; entry j is kept when 0 <= ordinal[j] < limit and (int64) value[j] >= 0; an all-ones value in front of the
+ * limit ends the output (*end_at: its ordinal).
+ * Both return when the result is complete.  Count, two prefix scans, emit over tiles of GTX_LINES_TILE entries cut at multiples of
+ * GTX_LINES_TILE of the entry index: a tile without a kept line is not loaded again.
+ * gtx_window_lines / gtx_pair_lines stream all lines to `sink` in order: ranges of whole tiles, at most gtx_set_lines_chunk bytes of
+ * bound each (default 64 MiB; at least one tile's bound is always taken), are rendered into two device buffers in turn, copied into
+ * two page-locked buffers and handed to sink(user, text, bytes); range r + 1 renders while r is copied and r - 1 is in the sink.  No
+ * line straddles two calls of the sink; a range without a line makes no call.  A sink that returns non-zero ends the call at once
+ * with GTX_E_SINK.  The all-ones rule ends the stream.  *n_lines and *n_bytes (either may be NULL) are the totals, *end_at as above.
+ * gtx_window_filter_lines is gtx_window_filter_device (after gtx_window_refs) into buffers of the context, then gtx_pair_lines over
+ * them: the lines of `genomic_scans counts -r` without the kept ordinals and values crossing to the host. */
+#define GTX_E_SINK         -5   /* the caller's sink refused the text */
+#define GTX_LINES_TILE 1024
+#define GTX_LINES_MAX_NAME 48
+typedef int (*gtx_lines_sink)(void *user, const char *text, size_t bytes);
+int gtx_lines_layout(gtx_ctx *ctx, const int64_t *block_offset, int32_t n_blocks, const char *names_blob, const int32_t *name_off, const char *strand,
+                     int64_t win_step, int64_t win_size);
+int64_t gtx_lines_max_bytes(gtx_ctx *ctx);
+int gtx_set_lines_chunk(gtx_ctx *ctx, int64_t bytes);
+int gtx_window_lines_device(gtx_ctx *ctx, const void *d_windows, int64_t first, int64_t count, int64_t limit, int64_t min_value, void *d_text,
+                            int64_t capacity, int64_t *n_lines, int64_t *n_bytes, int64_t *end_at);
+int gtx_pair_lines_device(gtx_ctx *ctx, const void *d_ordinals, const void *d_values, int64_t first, int64_t count, int64_t limit, void *d_text,
+                          int64_t capacity, int64_t *n_lines, int64_t *n_bytes, int64_t *end_at);
+int gtx_window_lines(gtx_ctx *ctx, const void *d_windows, int64_t n_windows, int64_t limit, int64_t min_value, gtx_lines_sink sink, void *user,
+                     int64_t *n_lines, int64_t *n_bytes, int64_t *end_at);
+int gtx_pair_lines(gtx_ctx *ctx, const void *d_ordinals, const void *d_values, int64_t n, int64_t limit, gtx_lines_sink sink, void *user,
+                   int64_t *n_lines, int64_t *n_bytes, int64_t *end_at);
+int gtx_window_filter_lines(gtx_ctx *ctx, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t limit, gtx_lines_sink sink, void *user,
+                            int64_t *n_lines, int64_t *n_bytes, int64_t *end_at);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* on = 1: every *_device call brackets its dominant kernel and the whole call with HIP events on the
