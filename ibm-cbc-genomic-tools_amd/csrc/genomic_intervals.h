@@ -169,6 +169,23 @@ class GenomicRegionSet
   void RunGlobalInvert(StringLIntMap *bounds);
   void RunGlobalCalcDistances(char *op1, char *op2);
   void RunGlobalTest(bool sorted_by_strand);
+  // The reference's line-based interval operations `shift` / `shiftp`, `pos`, `center`, `fix` and `bounds` (genomic_intervals.cpp
+  // :4133-4139, :4079-4086, :3966-3972, :4042-4048, :3954-3960 over GenomicRegionBED's members :2340-2480): every region through the
+  // operation and printed again with GenomicRegionBED::Print.  Same signatures, output and errors; an operator word of RunModifyPos
+  // that is none of 1, 2, 5p, 3p, c is "Error: unknown operation!".  MI355X path, for a streamed BED set (anything else is
+  // "unsupported input format!").  Two paths.  The host loop, region by region: the only path for space-separated lines, BED12, 7 to
+  // 11 columns, a strand spelled ".", "1" or "-1", non-canonical numbers, and every input error with its line number behind the output
+  // in front of it.  The text path, for a file of 32 MB or more, stdin or a .gz file (GTX_TEXT_ON_DEVICE=1: of any size, =0: never, and
+  // then no device is looked for at all) on one GPU: blocks of the text through gtx_rewrite_text (include/gtx.h), the rewritten text
+  // written as it comes back, in block order.  A block that holds a line the device does not take comes back and is rendered by the
+  // host loop for that block alone, with its own line numbers; the next block goes to the device again.  GTX_TEXT_TRACE=1 reports
+  // "[gtx regions] blocks rewritten on the device: N, came back: K" on stderr.  A short stream (stdin or .gz that ends inside its first block
+  // of less than 32 MB, GTX_TEXT_ON_DEVICE not 1) is rendered by the loop before the device has its text, and counts under K.  Amounts beyond +-2^62 take the host loop.
+  void RunShiftPos(long int start_shift, long int stop_shift, bool strand_aware);
+  void RunModifyPos(const char *position_op, long int position_shift);
+  void RunCenter();
+  void RunFix();
+  void RunBounds(StringLIntMap *bounds);
 
   // MI355X path: hands the not yet consumed part of a streaming set (the current region's raw
   // line first) to the bulk packer.  After this call Get()/Next() report the end of the set.

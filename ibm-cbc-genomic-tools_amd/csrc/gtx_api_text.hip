@@ -13,6 +13,7 @@
 #include "gtx_join.h"
 #include "gtx_query.h"
 #include "gtx_text.h"
+#include "gtx_rewrite.h"
 #include "gtx_ctx.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -222,6 +223,90 @@ int gtx_subset_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t
   if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
   *out_bytes = n;
   if (n_selected) *n_selected = (int64_t)t.hostTotal.get()[1];
+  return GTX_OK;
+}
+
+// text -> triples in line order (the tokenizer's plain case, the class of every line) -> plan, two prefixes, emit (gtx_rewrite.h);
+// everything enqueued, the verdict and the totals on their way to the host behind it
+int gtx_rewrite_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_rewrite_op *op, int *ticket)
+{
+  if (!c) return GTX_E_ARG;
+  const int64_t kMaxAmount = 1ll << 62;                                    // columns of 10 digits stay far inside 64 bits with it
+  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || op->kind < GTX_REWRITE_SHIFT || op->kind > GTX_REWRITE_BOUNDS ||
+      op->a > kMaxAmount || op->a < -kMaxAmount || op->b > kMaxAmount || op->b < -kMaxAmount ||
+      (op->kind == GTX_REWRITE_POS && (op->pos_op < GTX_REWRITE_POS_1 || op->pos_op > GTX_REWRITE_POS_C)) ||
+      (op->kind == GTX_REWRITE_BOUNDS && (op->n_chrom < 0 || (op->n_chrom > 0 && (!op->chrom_names || !op->chrom_len)))))
+    return fail(c, GTX_E_ARG, "gtx_rewrite_text: bad argument");
+  if (c->text.slot[c->text.seq & 1].rewritePending) return fail(c, GTX_E_STATE, "gtx_rewrite_text: the result of the block before last has not been fetched (gtx_rewrite_result)");
+  const bool bounds = op->kind == GTX_REWRITE_BOUNDS;
+  gtx_text_rules r; memset(&r, 0, sizeof r);
+  r.chrom_names = bounds ? op->chrom_names : nullptr; r.n_chrom = bounds ? op->n_chrom : 0; r.max_label_value = 1;
+  TextSlot *tp = nullptr; bool empty = false;
+  // (the sorted scanner's rules: nothing about the interval is checked, and without sorted_rules nothing about the order)
+  { int rc = text_stage(c, text, bytes, nLines, &r, false, 2, nullptr, 0, &tp, ticket, &empty); if (rc) return rc; }
+  TextSlot &t = *tp;
+  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
+  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
+  t.rewritePending = true;
+  if (empty) return GTX_OK;
+  if (bounds) {                                                            // the lengths per class: uploaded when they change
+    std::vector<long long> len(op->chrom_len, op->chrom_len + op->n_chrom);
+    if (len != c->text.h_chromLen || !c->text.chromLen) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, c->text.chromLen.alloc(len.size() + 1));
+      if (!len.empty()) HIPCHK(c, hipMemcpy(c->text.chromLen.get(), len.data(), sizeof(long long) * len.size(), hipMemcpyHostToDevice));
+      c->text.h_chromLen = len;
+    }
+  }
+  const size_t nTiles = gtx::rewrite_tiles((unsigned)nLines), need = gtx_rewrite_max_bytes(bytes, nLines) + 32;
+  if ((size_t)nLines > t.rwRec.cap) HIPCHK(c, t.rwRec.alloc(t.w.cap));
+  if (2 * nTiles > t.rwTile.cap) { HIPCHK(c, t.rwTile.alloc(2 * nTiles + (nTiles >> 2))); HIPCHK(c, t.rwBase.alloc(2 * (nTiles + 1) + (nTiles >> 2))); }
+  if (need > t.out.cap) HIPCHK(c, t.out.alloc(need + (need >> 3)));
+  gtx::RewriteOp k; k.kind = op->kind; k.posOp = op->pos_op; k.a = op->a; k.b = op->b; k.chromLen = bounds ? c->text.chromLen.get() : nullptr; k.nChrom = bounds ? op->n_chrom : 0;
+  gtx::RewriteDevice d; d.text = t.text.get(); d.bytes = bytes; d.nl = t.nl.get(); d.nLines = (unsigned)nLines; d.tri = t.tri.get(); d.flag = t.flag.get();
+  d.rec = t.rwRec.get(); d.tileBytes = t.rwTile.get(); d.tileLines = t.rwTile.get() + nTiles; d.baseBytes = t.rwBase.get(); d.baseLines = t.rwBase.get() + nTiles + 1;
+  d.out = t.out.get();
+  prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and emit launches alone, on the text where it is)
+  HIPCHK(c, prof_mark(c, 1, c->stream));
+  HIPCHK(c, gtx::launch_rewrite(d, k, c->stream));
+  HIPCHK(c, prof_mark(c, 2, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], d.baseLines + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, prof_end(c, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  return GTX_OK;
+}
+
+int gtx_rewrite_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed)
+{
+  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_rewrite_result: bad argument") : GTX_E_ARG;
+  TextSlot &t = c->text.slot[ticket];
+  if (!t.evParsed || !t.rewritePending) return fail(c, GTX_E_STATE, "gtx_rewrite_result: no such block");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(t.evParsed));
+  t.rewritePending = false;
+  *needs_host = *t.hostFlag.get();
+  *out_bytes = 0;
+  if (n_printed) *n_printed = 0;
+  if (*needs_host) return GTX_OK;
+  const size_t n = (size_t)t.hostTotal.get()[0];
+  if (n > 0 && (!out || n > capacity)) return fail(c, GTX_E_ARG, "gtx_rewrite_result: out is missing or smaller than the block's text (gtx_rewrite_max_bytes)");
+  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
+  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
+  *out_bytes = n;
+  if (n_printed) *n_printed = (int64_t)t.hostTotal.get()[1];
+  return GTX_OK;
+}
+
+size_t gtx_rewrite_max_bytes(size_t bytes, int64_t n_lines) { return bytes + (size_t)gtx::kRewriteGrow * (size_t)(n_lines > 0 ? n_lines : 0); }
+
+int gtx_rewrite_limits(int32_t *tile, int32_t *stage)
+{
+  if (tile) *tile = gtx::kRewriteTile;
+  if (stage) *stage = gtx::kRewriteStage;
   return GTX_OK;
 }
 }

@@ -18,7 +18,7 @@
 #include "gtx_adjacent.h"
 #include "gtx_internal.h"
 
-namespace gtx { struct JoinInfo; struct SignalInfo; }   // (gtx_join.h, gtx_signal.h: held here by pointer only)
+namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h: held here by pointer only)
 
 #pragma GCC visibility push(hidden)
 
@@ -156,6 +156,9 @@ struct TextSlot {
   // gtx_subset_text: the lines' hits, the tiles' kept bytes / lines, the kept text and its
   // totals on the host; whether the slot holds a subset block whose result has not been fetched
   DevBuf<unsigned> hits; DevBuf<unsigned long long> tile; DevBuf<char> out; PinBuf<unsigned long long> hostTotal; bool subsetPending = false;
+  // gtx_rewrite_text: the lines' records, the tiles' bytes | lines and their prefixes (`out` and `hostTotal` as for the subset);
+  // whether the slot holds a rewritten block whose result has not been fetched
+  DevBuf<gtx::RewriteRec> rwRec; DevBuf<unsigned> rwTile; DevBuf<long long> rwBase; bool rewritePending = false;
 };
 
 // What a device call found, on its way to the caller's struct: the info block the kernels write, its page-locked copy, and the
@@ -281,6 +284,7 @@ struct TextState {
   long long seq = 0;
   DevBuf<int> table; DevBuf<char> names; unsigned mask = 0, blobLen = 0;
   std::string blob;                                   // the chromosome names the device tables were built from
+  DevBuf<long long> chromLen; std::vector<long long> h_chromLen;   // gtx_rewrite_text, bounds: the lengths per class, and what was uploaded
 };
 
 // measurement (prof_begin / prof_mark / prof_end below)

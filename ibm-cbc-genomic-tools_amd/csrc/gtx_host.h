@@ -44,6 +44,21 @@ void CheckGffStrands(GenomicRegionSet *set);
 
 inline bool FitsPacked(long int v) { return v < INT_MAX - 1 && v > INT_MIN + 1; }   // the packed 32-bit representation takes it
 
+// ---- gtx_host_join.cpp: a BED line printed again, for the drivers that print query lines -------------------------------------
+// what GenomicRegionBED::Print (genomic_intervals.cpp:2188-2220) needs of a query, kept until it is printed
+struct PairQuery {
+  std::string chrom, label, rgb;
+  char strand;
+  long int n_tokens, score, thick_start, thick_end;
+  std::vector<long int> iv;                                        // start, stop of every interval
+  static PairQuery From(GenomicRegion *q, const std::string &current_line);   // of the BED region a loop hands out and its raw line
+};
+// GenomicRegionBED::Print of a region with these intervals and this label
+void PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> &iv, const std::string &label, long int score,
+              long int thick_start, long int thick_end);
+void WriteOut(std::string &out, size_t above = 0);                // the text so far to stdout once it is longer than `above`
+void ExitOnLoadError(const LoadError &err);                       // the error a loop stopped at, as the reference prints it (after the output before it)
+
 // ---- gtx_host_device.cpp: the GPU context shared by the classes, the page-locked pool, the hand-over ------------------------
 inline void Mark(const char *what) { GtxMark(what); }
 void GtxWarmUp();                                                 // HIP start-up on its own thread, from the first region set on

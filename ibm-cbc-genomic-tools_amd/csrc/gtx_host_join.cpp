@@ -13,15 +13,6 @@ using namespace gtx_host;
 // genomic_overlaps overlap / intersect: the device join under the reference's per-query loop
 // ---------------------------------------------------------------------------------------------------
 namespace {
-// what GenomicRegionBED::Print (genomic_intervals.cpp:2188-2220) needs of a query, kept until its batch is joined
-struct PairQuery {
-  std::string chrom, label, rgb;
-  char strand;
-  long int n_tokens, score, thick_start, thick_end;
-  std::vector<long int> iv;                                        // start, stop of every interval
-  static PairQuery From(GenomicRegion *q, const std::string &current_line);   // of the BED region the loop hands out and its raw line
-};
-
 // columns 5, 7, 8, 9 of the raw line as GenomicRegionBED::Read takes them (:2157-2182: blank- or tab-separated, atol)
 void ParseTail(const std::string &raw, PairQuery &q)
 {
@@ -41,6 +32,8 @@ void ParseTail(const std::string &raw, PairQuery &q)
   q.rgb = tok.size() > 8 ? tok[8] : std::string();
 }
 
+}  // namespace
+
 PairQuery PairQuery::From(GenomicRegion *q, const std::string &current_line)
 {
   GenomicInterval *f = q->I.front();
@@ -52,11 +45,12 @@ PairQuery PairQuery::From(GenomicRegion *q, const std::string &current_line)
   return pq;
 }
 
+namespace {
 void AppendNum(std::string &out, long int v) { char b[24]; int n = snprintf(b, sizeof b, "%ld", v); out.append(b, (size_t)n); }
+}  // namespace
 
-// GenomicRegionBED::Print of a region with these intervals and this label
-void PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> &iv, const std::string &label, long int score,
-              long int thick_start, long int thick_end)
+void gtx_host::PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> &iv, const std::string &label, long int score,
+                        long int thick_start, long int thick_end)
 {
   out += q.chrom; out += '\t'; AppendNum(out, iv[0] - 1); out += '\t'; AppendNum(out, iv.back());
   const long int nt = q.n_tokens;
@@ -85,6 +79,7 @@ void PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> 
   out += '\n';
 }
 
+namespace {
 // the index side of the join: classes, envelopes, intervals, order keys.  A class is the chromosome's rank in strcmp order, plus the
 // number of chromosomes on '-' unless -i: the numbering of Reduce, the scanners and the device tokenizer (gtx_subset_text).  It is a
 // partition label: strands come from gtx_set_ref_strands and QueryBatch::qstrand, the order of a query's pairs from gtx_set_ref_order's
@@ -189,11 +184,14 @@ void SetRefStrands(const JoinIndex &ix)
   ix.Chk(gtx_set_ref_strands(ix.ctx, strand.data()));
 }
 
-// the text so far to stdout once it is longer than `above`
-void WriteOut(std::string &out, size_t above = 0)
+}  // namespace
+
+void gtx_host::WriteOut(std::string &out, size_t above)
 {
   if (out.size() > above) { fwrite(out.data(), 1, out.size(), stdout); out.clear(); }
 }
+
+namespace {
 
 // the index set of the overlaps object on the device (gtx_set_refs_ex, gtx_set_ref_order; the caller sets the blocks).  With
 // single_if_invalid a region that is not compatible, sorted and non-overlapping is given its envelope alone: no pair of it can be
@@ -315,8 +313,9 @@ void RunQueryLoop(GenomicRegionSetOverlaps *ov, const JoinIndex &ix, LoadError &
   tls_load_error = NULL;
 }
 
-// the error the loop stopped at, as the reference prints it (after the output before it)
-void ExitOnLoadError(const LoadError &err)
+}  // namespace
+
+void gtx_host::ExitOnLoadError(const LoadError &err)
 {
   fflush(stdout);
   if (!err.set) return;
@@ -324,7 +323,6 @@ void ExitOnLoadError(const LoadError &err)
   if (err.with_prefix) fprintf(stderr, "Error: Line %ld: %s\n", err.line, err.msg.c_str()); else fprintf(stderr, "%s\n", err.msg.c_str());
   exit(1);
 }
-}  // namespace
 
 void GtxPrintPairs(GenomicRegionSetOverlaps *ov, bool intersect, bool match_gaps, bool ignore_strand, bool merge_labels, const char *bin_bits)
 {

@@ -1,0 +1,258 @@
+// gtx_host_regionops.cpp -- the line-based interval operations of genomic_regions on a streamed BED set: shift, shiftp, pos, center,
+// fix and bounds (GenomicRegionSet::RunShiftPos, RunModifyPos, RunCenter, RunFix, RunBounds).  See genomic_intervals.h; shared pieces
+// in gtx_host.h.
+#include "gtx_host.h"
+
+#include <algorithm>
+
+using namespace gtx_host;
+
+namespace {
+
+struct RegionOp { int kind; std::string pos_word; long int a, b; StringLIntMap *bounds; };
+
+// GenomicRegion::Union (genomic_intervals.cpp:1649-1671) on (start, stop) pairs: BED intervals share chromosome and strand
+void Union(std::vector<long int> &iv)
+{
+  const size_t n = iv.size() / 2;
+  if (n <= 1) return;
+  std::vector<std::pair<long int, long int> > v(n);
+  for (size_t k = 0; k < n; k++) v[k] = std::make_pair(iv[2 * k], iv[2 * k + 1]);
+  std::stable_sort(v.begin(), v.end(), [](const std::pair<long int, long int> &x, const std::pair<long int, long int> &y) { return x.first < y.first; });
+  iv.clear();
+  long int start = v[0].first, stop = v[0].second;
+  for (size_t k = 1; k < n; k++) {
+    if (stop < v[k].first) { iv.push_back(start); iv.push_back(stop); start = v[k].first; stop = v[k].second; }
+    else stop = std::max(stop, v[k].second);
+  }
+  iv.push_back(start); iv.push_back(stop);
+}
+
+// GenomicRegion::Fix (:1419-1425): the intervals with start < 1 or start > stop are removed
+void Fix(std::vector<long int> &iv)
+{
+  size_t w = 0;
+  for (size_t k = 0; k + 1 < iv.size(); k += 2)
+    if (iv[k] >= 1 && iv[k] <= iv[k + 1]) { iv[w++] = iv[k]; iv[w++] = iv[k + 1]; }
+  iv.resize(w);
+}
+
+// GenomicRegionBED::UpdateThick (:2326-2333)
+void UpdateThick(PairQuery &q)
+{
+  if (q.iv.empty()) return;
+  q.thick_start = std::max(q.thick_start, q.iv.front() - 1);
+  q.thick_end = std::min(q.thick_end, q.iv.back());
+  if (q.thick_end <= q.thick_start) q.thick_start = q.thick_end = q.iv.front() - 1;
+}
+
+// the operation on a region as GenomicRegionBED's members apply it (:2340-2480 over :524-568, :1280-1301); false: nothing is printed
+bool Apply(const RegionOp &op, PairQuery &q)
+{
+  std::vector<long int> &iv = q.iv;
+  const size_t n = iv.size() / 2;
+  switch (op.kind) {
+    case GTX_REWRITE_SHIFT: case GTX_REWRITE_SHIFTP:
+      for (size_t k = 0; k < n; k++) {
+        if (op.kind == GTX_REWRITE_SHIFTP && q.strand == '-') { iv[2 * k] -= op.b; iv[2 * k + 1] -= op.a; }
+        else { iv[2 * k] += op.a; iv[2 * k + 1] += op.b; }
+      }
+      Union(iv); UpdateThick(q);
+      break;
+    case GTX_REWRITE_POS:
+      for (size_t k = 0; k < n; k++) {
+        long int &s = iv[2 * k], &e = iv[2 * k + 1];
+        if (op.pos_word == "c") { const long int m = s + (e - s + 1) / 2; s = m - op.a; e = m + op.a; }
+        else {
+          const bool choose_start = op.pos_word == "1" || (q.strand == '+' && op.pos_word == "5p") || (q.strand == '-' && op.pos_word == "3p");
+          if (choose_start) e = s + op.a; else s = e - op.a;
+        }
+      }
+      Union(iv);                                                  // (no UpdateThick: :2441)
+      break;
+    case GTX_REWRITE_CENTER:
+      for (size_t k = 0; k < n; k++) { const long int h = (iv[2 * k + 1] - iv[2 * k]) / 2; iv[2 * k] += h; iv[2 * k + 1] -= h; }
+      UpdateThick(q);
+      break;
+    case GTX_REWRITE_FIX: Fix(iv); UpdateThick(q); break;
+    default: {
+      if (!op.bounds) return false;
+      StringLIntMap::iterator it = op.bounds->find(q.chrom);
+      if (it == op.bounds->end()) return false;                   // (:3959: not printed at all)
+      const long int len = it->second;
+      for (size_t k = 0; k < n; k++) {
+        long int &s = iv[2 * k], &e = iv[2 * k + 1];
+        if (s > len || e < 1 || e < s) s = e = 0;
+        else if (s < 1 || e > len) { s = std::max(s, 1L); e = std::min(e, len); }
+      }
+      Fix(iv); UpdateThick(q);
+    }
+  }
+  return !iv.empty();
+}
+
+// GenomicRegionBED::Print (:2188-2218) of the region as it is now.  A 12-column region whose blocks overlap ends the run in the
+// middle of its line, as the reference's does (:2207)
+void Print(std::string &out, const PairQuery &q, long int n_line)
+{
+  const size_t at = out.size();
+  PrintBed(out, q, q.iv, q.label, q.score, q.thick_start, q.thick_end);
+  if (q.n_tokens != 12) return;
+  for (size_t k = 1; k < q.iv.size() / 2; k++) {
+    if (q.iv[2 * k] > q.iv[2 * k - 1]) continue;
+    size_t cut = out.rfind('\t');                                 // in front of the block starts: "0", then k - 1 of them
+    for (size_t j = 0; j < k; j++) cut = out.find_first_of(",\n", cut + 1);
+    out.resize(std::max(cut, at));
+    WriteOut(out); fflush(stdout);
+    fprintf(stderr, "Line %lu: exons cannot overlap!\n", (unsigned long)n_line);
+    exit(1);
+  }
+}
+
+// one region through the operation and out
+void Render(std::string &out, const RegionOp &op, GenomicRegion *r, const std::string &raw)
+{
+  PairQuery q = PairQuery::From(r, raw);
+  if (Apply(op, q)) Print(out, q, r->n_line);
+  WriteOut(out, 1u << 22);
+}
+
+// the host loop over what is left of the set, region by region with the reference's print; an input error ends it behind the
+// output in front of the line
+void HostLoop(GenomicRegionSet *set, const RegionOp &op)
+{
+  std::string out;
+  LoadError err;
+  tls_load_error = &err;
+  try {
+    for (GenomicRegion *r = set->Get(); r != NULL; r = set->Next()) Render(out, op, r, set->CurrentLine());
+  } catch (const LoadAbort &) {}
+  tls_load_error = NULL;
+  WriteOut(out);
+  ExitOnLoadError(err);
+}
+
+// the same for the lines of one block of text that came back from the device, with their own line numbers
+void HostBlock(const char *text, size_t bytes, long int first_line, const RegionOp &op)
+{
+  std::string out, raw, line;
+  LoadError err;
+  tls_load_error = &err;
+  try {
+    long int no = first_line;
+    for (const char *p = text, *end = text + bytes; p < end; no++) {
+      const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
+      if (!nl) break;
+      raw.assign(p, nl); line = raw;
+      GenomicRegionBED r(&line[0], no);
+      Render(out, op, &r, raw);
+      p = nl + 1;
+    }
+  } catch (const LoadAbort &) {}
+  tls_load_error = NULL;
+  WriteOut(out);
+  if (err.set) ExitOnLoadError(err);
+}
+
+// May the set's text go to the device as it is?  A streamed BED file, stdin or .gz (a regular file: of 32 MB or more, or
+// GTX_TEXT_ON_DEVICE=1; never with GTX_TEXT_ON_DEVICE=0), on one GPU, amounts the device's arithmetic takes
+bool TextUsable(GenomicRegionSet *set, const RegionOp &op)
+{
+  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
+  const long left = set->StreamBytesLeft();
+  if (left >= 0 && left < (long)TextPolicy().threshold_bytes) return false;
+  if (gtx_group_size(devices) != 1) return false;
+  if (g_pool_future.valid()) g_pool_future.get();
+  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
+  const long int lim = 1L << 62;
+  return op.a <= lim && op.a >= -lim && op.b <= lim && op.b >= -lim;
+}
+
+// the set's text block by block through gtx_rewrite_text, the rewritten text to stdout in block order; a block that comes back is
+// rendered here, alone, and the next one goes to the device again
+void TextLoop(GenomicRegionSet *set, const RegionOp &op)
+{
+  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
+  std::string first; long int first_no = 0;
+  LineSource *src = set->DetachStream(&first, &first_no);
+  if (first_no <= 0) return;
+  // the names and lengths of bounds, in the map's (strcmp) order
+  ChromTable chroms;
+  std::vector<const char *> names; std::vector<int64_t> lens;
+  if (op.kind == GTX_REWRITE_BOUNDS && op.bounds)
+    for (StringLIntMap::iterator it = op.bounds->begin(); it != op.bounds->end(); it++) { chroms.Add(it->first.c_str()); names.push_back(it->first.c_str()); lens.push_back(it->second); }
+  chroms.Freeze();
+  gtx_rewrite_op dev; memset(&dev, 0, sizeof dev);
+  dev.kind = op.kind; dev.a = op.a; dev.b = op.b;
+  dev.pos_op = op.pos_word == "2" ? GTX_REWRITE_POS_2 : op.pos_word == "5p" ? GTX_REWRITE_POS_5P : op.pos_word == "3p" ? GTX_REWRITE_POS_3P : op.pos_word == "c" ? GTX_REWRITE_POS_C : GTX_REWRITE_POS_1;
+  dev.chrom_names = names.empty() ? NULL : names.data(); dev.chrom_len = lens.empty() ? NULL : lens.data(); dev.n_chrom = (int32_t)names.size();
+  PackOptions opt;
+  opt.chroms = &chroms;
+  BedPacker packer(src, opt);
+  TextPump pump(packer, opt);
+  long int on_device = 0, came_back = 0;
+  bool first_block = true;
+  char *out = NULL; size_t out_cap = 0;
+  pump.settle = [&](const TextPump::Block &b, int ticket) {
+    const size_t need = gtx_rewrite_max_bytes(b.bytes, b.n_lines);
+    if (need > out_cap) {
+      if (out) gtx_host_free(ctx, out);
+      out_cap = need + (need >> 3);
+      out = (char *)gtx_host_alloc(ctx, out_cap);
+      if (!out) DieGtx(ctx, GTX_E_HIP);
+    }
+    int redo = 0; size_t got = 0;
+    DieGtx(ctx, gtx_rewrite_result(ctx, ticket, &redo, out, out_cap, &got, NULL));
+    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, op); }
+    else { on_device++; if (got) fwrite(out, 1, got, stdout); }
+    return true;
+  };
+  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
+    int ticket = -1;
+    // a short stream: the host loop is done before the device has the text
+    const bool here = first_block && b.text != first.data() && b.bytes < TextPolicy().threshold_bytes && packer.SourceAtEnd();
+    if (b.text != first.data()) first_block = false;
+    // (counted with the blocks that came back: the trace says how many blocks the loop rendered, whichever way they got to it)
+    if (here) { pump.SettleAll(); came_back++; HostBlock(b.text, b.bytes, b.first_line, op); return ticket; }
+    DieGtx(ctx, gtx_rewrite_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
+    return ticket;
+  };
+  // the line the set's constructor has read for its format check: a block of one line
+  first += '\n';
+  TextPump::Block &one = pump.blk[0];
+  one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
+  pump.Add(0);
+  pump.Run(1);
+  if (out) gtx_host_free(ctx, out);
+  fflush(stdout);
+  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx regions] blocks rewritten on the device: %ld, came back: %ld\n", on_device, came_back);
+}
+
+void Run(GenomicRegionSet *set, const RegionOp &op)
+{
+  if (set->n_regions == 0) return;
+  if (set->format != "BED") set->PrintError("unsupported input format!\n");
+  if (set->load_in_memory) set->PrintError("the interval operations stream their input on the MI355X path: open the set with load_in_memory = false!");
+  // GTX_TEXT_ON_DEVICE=0: the host loop and nothing else.  Otherwise the device is looked for whatever the input's size: without
+  // one the run ends with the library's error, as every other operation's does
+  if (!TextPolicy().never && TextUsable(set, op)) TextLoop(set, op);
+  else HostLoop(set, op);
+}
+
+}  // namespace
+
+void GenomicRegionSet::RunShiftPos(long int start_shift, long int stop_shift, bool strand_aware)
+{
+  Run(this, RegionOp{strand_aware ? GTX_REWRITE_SHIFTP : GTX_REWRITE_SHIFT, "", start_shift, stop_shift, NULL});
+}
+
+void GenomicRegionSet::RunModifyPos(const char *position_op, long int position_shift)
+{
+  const std::string w = position_op;
+  if (w != "1" && w != "2" && w != "5p" && w != "3p" && w != "c") { fflush(stdout); fprintf(stderr, "Error: unknown operation!\n"); exit(1); }   // (:4081)
+  Run(this, RegionOp{GTX_REWRITE_POS, w, position_shift, 0, NULL});
+}
+
+void GenomicRegionSet::RunCenter() { Run(this, RegionOp{GTX_REWRITE_CENTER, "", 0, 0, NULL}); }
+void GenomicRegionSet::RunFix() { Run(this, RegionOp{GTX_REWRITE_FIX, "", 0, 0, NULL}); }
+void GenomicRegionSet::RunBounds(StringLIntMap *bounds) { Run(this, RegionOp{GTX_REWRITE_BOUNDS, "", 0, 0, bounds}); }

@@ -38,6 +38,7 @@
 #include "gtx.h"
 #include "gtx_internal.h"
 #include "gtx_text.h"
+#include "gtx_textline.h"
 
 namespace gtxtext {
 
@@ -544,33 +545,6 @@ hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_t
 // ---- gtx_subset_text ----
 static constexpr int kTile = 256;                  // lines per tile of the select / gather passes
 
-// does Print re-render the line [b, e) as it stands?  (see gtx_text.h)
-__device__ __forceinline__ bool verbatim_line(const unsigned char *__restrict__ s, unsigned b, unsigned e)
-{
-  int tok = 1;
-  unsigned q = b;                                                 // the token's first byte
-  for (unsigned p = b;; p++) {
-    if (p < e && s[p] != '\t') { if (s[p] <= ' ') return false; continue; }
-    const unsigned n = p - q;
-    if (n == 0 || tok > 6) return false;
-    if (tok == 2 || tok == 3) {
-      for (unsigned k = q; k < p; k++) if ((unsigned)(s[k] - '0') >= 10u) return false;
-      if (n > 1 && s[q] == '0') return false;
-    } else if (tok == 5) {
-      const bool neg = s[q] == '-';
-      const unsigned r = q + (neg ? 1 : 0), nd = p - r;
-      if (nd == 0 || nd > 18) return false;
-      for (unsigned k = r; k < p; k++) if ((unsigned)(s[k] - '0') >= 10u) return false;
-      if (s[r] == '0' && (nd > 1 || neg)) return false;
-    } else if (tok == 6) {
-      if (n != 1 || (s[q] != '+' && s[q] != '-')) return false;
-    }
-    if (p >= e) break;
-    tok++; q = p + 1;
-  }
-  return tok >= 3;
-}
-
 __global__ __launch_bounds__(kTile) void text_verbatim_kernel(const char *__restrict__ text, const unsigned *__restrict__ nl, unsigned nLines,
                                                                int *flag)
 {
@@ -578,7 +552,8 @@ __global__ __launch_bounds__(kTile) void text_verbatim_kernel(const char *__rest
   const unsigned j = blockIdx.x * kTile + threadIdx.x;
   if (j >= nLines) return;
   const unsigned b = j ? nl[j - 1] + 1 : 0, e = nl[j];
-  if (!verbatim_line((const unsigned char *)text, b, e)) atomicOr(flag, 16);
+  LineCols cols;
+  if (!verbatim_line((const unsigned char *)text, b, e, cols)) atomicOr(flag, 16);
 }
 
 // the kept bytes of line j of the tile (0: not kept, or behind the last line) and where the line begins

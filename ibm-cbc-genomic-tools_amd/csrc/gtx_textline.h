@@ -1,0 +1,47 @@
+// gtx_textline.h -- the one predicate "GenomicRegionBED::Print would render this line as it stands" (see gtx_text.h), for the
+// kernels that write text out from text in: the subset's gather (gtx_text.hip) and the column rewrite (gtx_rewrite.hip).  Device code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace gtxtext {
+
+// what the walk over a verbatim line has seen of it: the length of column 1, where the tail begins (the byte behind column 3, a tab
+// or the line's end, as an offset from the line's first byte), columns 2 and 3 as numbers, the number of tokens and the strand of
+// column 6 ('+' with fewer than 6 columns, genomic_intervals.cpp:2165)
+struct LineCols { unsigned nameLen, tailOff; long long v2, v3; int nTok, strand; };
+
+// does Print re-render the line [b, e) of s as it stands?  (gtx_text.h has the conditions.)  cols is filled as far as the walk got.
+template <class PTR>
+__device__ __forceinline__ bool verbatim_line(PTR s, unsigned b, unsigned e, LineCols &cols)
+{
+  int tok = 1;
+  unsigned q = b;                                                 // the token's first byte
+  cols.nameLen = 0; cols.tailOff = 0; cols.v2 = 0; cols.v3 = 0; cols.nTok = 0; cols.strand = '+';
+  for (unsigned p = b;; p++) {
+    if (p < e && s[p] != '\t') { if (s[p] <= ' ') return false; continue; }
+    const unsigned n = p - q;
+    if (n == 0 || tok > 6) return false;
+    if (tok == 1) cols.nameLen = n;
+    else if (tok == 2 || tok == 3) {
+      unsigned long long v = 0;
+      for (unsigned k = q; k < p; k++) { if ((unsigned)(s[k] - '0') >= 10u) return false; v = v * 10 + (unsigned)(s[k] - '0'); }
+      if (n > 1 && s[q] == '0') return false;
+      if (tok == 2) cols.v2 = (long long)v; else { cols.v3 = (long long)v; cols.tailOff = p - b; }
+    } else if (tok == 5) {
+      const bool neg = s[q] == '-';
+      const unsigned r = q + (neg ? 1 : 0), nd = p - r;
+      if (nd == 0 || nd > 18) return false;
+      for (unsigned k = r; k < p; k++) if ((unsigned)(s[k] - '0') >= 10u) return false;
+      if (s[r] == '0' && (nd > 1 || neg)) return false;
+    } else if (tok == 6) {
+      if (n != 1 || (s[q] != '+' && s[q] != '-')) return false;
+      cols.strand = s[q];
+    }
+    if (p >= e) break;
+    tok++; q = p + 1;
+  }
+  cols.nTok = tok;
+  return tok >= 3;
+}
+
+}  // namespace gtxtext

@@ -100,6 +100,28 @@ class TextRules(ctypes.Structure):
         return r
 
 
+REWRITE_SHIFT, REWRITE_SHIFTP, REWRITE_POS, REWRITE_CENTER, REWRITE_FIX, REWRITE_BOUNDS = range(6)   # gtx_rewrite_op.kind
+REWRITE_KINDS = {"shift": REWRITE_SHIFT, "shiftp": REWRITE_SHIFTP, "pos": REWRITE_POS, "center": REWRITE_CENTER, "fix": REWRITE_FIX, "bounds": REWRITE_BOUNDS}
+REWRITE_POS_OPS = {"1": 0, "2": 1, "5p": 2, "3p": 3, "c": 4}                                          # gtx_rewrite_op.pos_op
+
+
+class RewriteOp(ctypes.Structure):
+    """gtx_rewrite_op (include/gtx.h): one operation of genomic_regions over columns 2 and 3"""
+    _fields_ = [("kind", ctypes.c_int32), ("pos_op", ctypes.c_int32), ("a", ctypes.c_int64), ("b", ctypes.c_int64),
+                ("chrom_names", ctypes.POINTER(ctypes.c_char_p)), ("chrom_len", ctypes.POINTER(ctypes.c_int64)), ("n_chrom", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, kind, a=0, b=0, pos_op="1", genome=None):
+        """kind: a word of REWRITE_KINDS; genome: {name: length} for bounds"""
+        o = cls()
+        o.kind = REWRITE_KINDS[kind]; o.pos_op = REWRITE_POS_OPS[pos_op]; o.a = int(a); o.b = int(b)
+        names = sorted(genome) if genome else []
+        o._names = (ctypes.c_char_p * max(len(names), 1))(*[n.encode() for n in names])   # (kept alive with the object)
+        o._lens = (ctypes.c_int64 * max(len(names), 1))(*[int(genome[n]) for n in names])
+        o.chrom_names = o._names; o.chrom_len = o._lens; o.n_chrom = len(names)
+        return o
+
+
 # name -> (restype, argtypes); must list every symbol include/gtx.h declares
 # int sink(void *user, const char *text, size_t bytes) of gtx_window_lines / gtx_pair_lines
 LINES_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -235,6 +257,10 @@ ABI = {
     "gtx_text_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "gtx_subset_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "gtx_subset_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_rewrite_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_rewrite_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_rewrite_max_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int64]),
+    "gtx_rewrite_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_ref_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_join_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "gtx_join": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
@@ -328,6 +354,14 @@ def scan_layout(class_len, win_step, win_size):
         off.append(tot)
         tot += lib.gtx_scan_n_windows(int(ln), int(win_step), int(win_size))
     return np.asarray(off, dtype=np.int64), tot
+
+
+def rewrite_limits():
+    """(tile, stage) of gtx_rewrite_limits: lines per tile of the rewrite's passes; bytes of a tile's text, and of its output,
+    that the stage holds"""
+    t, b = ctypes.c_int32(), ctypes.c_int32()
+    load().gtx_rewrite_limits(ctypes.byref(t), ctypes.byref(b))
+    return int(t.value), int(b.value)
 
 
 def window_select_limits():
@@ -477,6 +511,31 @@ class Engine:
                 collect(*tickets.pop(0))
             t = ctypes.c_int(-1)
             self._chk(self.lib.gtx_subset_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(rules), int(flags), ctypes.byref(t)))
+            tickets.append((text, t.value))
+        for x in tickets:
+            collect(*x)
+        return results
+
+    def rewrite_text(self, blocks, op, guard=64):
+        """gtx_rewrite_text / gtx_rewrite_result per block of text (bytes of complete lines), two blocks in flight: per block
+        (needs_host, the printed text, the number of printed lines, whether the bytes behind the text's 16-byte unit were left
+        alone).  out is gtx_rewrite_max_bytes long, rounded up to 16, with `guard` bytes of 0xA5 behind it: the caller's buffer, not the
+        device buffer the kernels store into."""
+        tickets, results = [], []
+
+        def collect(text, t):
+            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
+            cap = (int(self.lib.gtx_rewrite_max_bytes(len(text), text.count(b"\n"))) + 15) // 16 * 16
+            out = ctypes.create_string_buffer(b"\xa5" * (cap + guard), cap + guard)
+            self._chk(self.lib.gtx_rewrite_result(self.ctx, t, ctypes.byref(redo), out, cap, ctypes.byref(nb), ctypes.byref(ns)))
+            raw = out.raw
+            behind = (nb.value + 15) // 16 * 16
+            results.append((redo.value, raw[:nb.value], ns.value, raw[behind:] == b"\xa5" * (cap + guard - behind)))
+        for text in blocks:
+            if len(tickets) == 2:
+                collect(*tickets.pop(0))
+            t = ctypes.c_int(-1)
+            self._chk(self.lib.gtx_rewrite_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
             tickets.append((text, t.value))
         for x in tickets:
             collect(*x)

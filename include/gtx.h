@@ -579,6 +579,55 @@ int gtx_text_result(gtx_ctx *ctx, int ticket, int *needs_host);
 int gtx_subset_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket);
 int gtx_subset_result(gtx_ctx *ctx, int ticket, int *needs_host, char *out /* >= bytes of the block */, size_t *out_bytes,
                       int64_t *n_selected /* may be NULL */);
+/* genomic_regions shift | shiftp | pos | center | fix | bounds on text (gtools/genomic_regions.cpp:726-727, :721, :704, :708, :703;
+ * GenomicRegionSet::RunShiftPos, RunModifyPos, RunCenter, RunFix, RunBounds genomic_intervals.cpp:3954-4140): a block of complete BED
+ * lines goes to the device as for gtx_subset_text (same buffers contract, two blocks in flight, tickets in order; no reference set
+ * and no count call need be open) and every line is printed again with columns 2 and 3 rewritten, or dropped.  With s = column 2 + 1,
+ * e = column 3 (:2163-2164), the strand '+' unless column 6 is "-" (:2165), in signed 64-bit arithmetic whose division truncates:
+ *   GTX_REWRITE_SHIFT    s' = s + a, e' = e + b                                   (:524-531 with strand_aware = false)
+ *   GTX_REWRITE_SHIFTP   on '-': s' = s - b, e' = e - a; else as SHIFT              (a = the 5' shift, b = the 3' shift)
+ *   GTX_REWRITE_POS      pos_op C: m = s + (e - s + 1) / 2, s' = m - a, e' = m + a; else with choose_start = pos_op 1, or 5P on '+',
+ *                        or 3P on '-': e' = s + a when it holds, s' = e - a when not  (:537-550; a = the -c shift)
+ *   GTX_REWRITE_CENTER   s' = s + (e - s) / 2, e' = e - (e - s) / 2                 (:1293-1301)
+ *   GTX_REWRITE_FIX      the line as it is when s >= 1 and s <= e, else dropped     (:333-338, :1419-1425)
+ *   GTX_REWRITE_BOUNDS   dropped when column 1 is none of chrom_names (:3959) or s > L, e < 1 or e < s with L = chrom_len of that name
+ *                        (:560-563, then Fix); else s' = max(s, 1), e' = min(e, L), dropped when that leaves s' > e' (:564-568, Fix)
+ * A printed line is column 1, TAB, s' - 1, TAB, e' -- both "%ld", so s' - 1 may be 0 or negative -- and then the input's own bytes
+ * from behind column 3 to the newline (GenomicRegionBED::Print :2188-2218): a 4-column line keeps its label, a 5-column line keeps
+ * its score, a 6-column line its strand, and a 3-column line prints no label (the "_" the reader gives it is never printed, :2192).
+ * That copy is Print's rendering only of a line gtx_subset_text would copy (the same predicate: the tokenizer's plain case, 3 to 6
+ * tab-separated tokens without blanks, '\r' or control bytes, columns 2 and 3 canonical decimals of at most 10 digits below
+ * 2^31 - 2, column 5 a canonical long, column 6 exactly "+" or "-"); a block with ANY other line, or with a tile of consecutive lines
+ * (gtx_rewrite_limits) whose text or whose output is longer than the stage, yields nothing: gtx_rewrite_result says
+ * needs_host with *out_bytes = 0 and the caller renders that block by its own means.  GTX_E_ARG: an amount beyond +-2^62 (the
+ * caller's own loop takes those), a kind or pos_op that is none of the above.
+ * gtx_rewrite_result waits for the block of that ticket; out (capacity bytes of it, gtx_rewrite_max_bytes(bytes, n_lines) of the
+ * block always suffice: a line grows by at most the two rendered numbers) receives exactly *out_bytes bytes, the printed lines in
+ * order; *n_printed (may be NULL) their number.  A result larger than capacity is GTX_E_ARG and nothing is written.  The result of a
+ * ticket must be fetched before the block after next is added.
+ * gtx_rewrite_limits: the lines per tile of the passes and the bytes of a tile's text, and of its output, that the stage holds.
+ * Under gtx_profile_enable a gtx_rewrite_text call is bracketed too: ms_stream_kernel is the plan, prefix and emit launches alone, on
+ * text that is already in HBM behind its newline index and tokenizer; ms_total adds the copies of the verdict and the totals. */
+#define GTX_REWRITE_SHIFT  0
+#define GTX_REWRITE_SHIFTP 1
+#define GTX_REWRITE_POS    2
+#define GTX_REWRITE_CENTER 3
+#define GTX_REWRITE_FIX    4
+#define GTX_REWRITE_BOUNDS 5
+#define GTX_REWRITE_POS_1  0
+#define GTX_REWRITE_POS_2  1
+#define GTX_REWRITE_POS_5P 2
+#define GTX_REWRITE_POS_3P 3
+#define GTX_REWRITE_POS_C  4
+typedef struct gtx_rewrite_op {
+  int32_t kind, pos_op;                        /* GTX_REWRITE_*, GTX_REWRITE_POS_* (read under GTX_REWRITE_POS only) */
+  int64_t a, b;                                /* the two amounts (see above); unused ones are ignored but must be in range */
+  const char *const *chrom_names; const int64_t *chrom_len; int32_t n_chrom;   /* GTX_REWRITE_BOUNDS: the genome's names and lengths */
+} gtx_rewrite_op;
+int gtx_rewrite_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_rewrite_op *op, int *ticket);
+int gtx_rewrite_result(gtx_ctx *ctx, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed /* may be NULL */);
+size_t gtx_rewrite_max_bytes(size_t bytes, int64_t n_lines);
+int gtx_rewrite_limits(int32_t *tile, int32_t *stage);
 /* The same in a group that holds all its members (between gtx_group_count_begin / gtx_group_coverage_begin and their _end): a block goes
  * to the members in turn, whatever the classes of its lines -- the read stream split evenly over members that each hold the whole
  * reference set (SURVEY 8(e)'s second partition) -- and a count call that took text blocks ends with the ncclReduce(sum) of the
