@@ -186,6 +186,15 @@ class GenomicRegionSet
   void RunCenter();
   void RunFix();
   void RunBounds(StringLIntMap *bounds);
+  // The reference's `win` (genomic_intervals.cpp:4449-4455 over GenomicRegionBED::PrintWindows :2520-2532): every region of a streamed
+  // BED set cut into sliding windows of win_size positions win_step apart, win_small keeping the windows the region's end cuts short
+  // -- `bedtools makewindows`.  Same signature and output.  MI355X path: whenever a device is usable, whatever the input's size (the
+  // output decides what a run costs), the text goes to the device block by block (gtx_windows_text) and the windows of a block are
+  // rendered there and streamed to stdout (gtx_windows_result); a block with a line the device does not take comes back and is
+  // rendered by the host loop alone.  GTX_TEXT_ON_DEVICE=0 keeps the host loop and looks for no device; sizes below 1 or above 2^31
+  // and steps above 2^31 take it too.  GTX_TEXT_TRACE=1 reports "[gtx windows] blocks expanded on the device: N, came back: K".
+  // win_step < 1, with which the reference's loop never ends, is refused with one error line and exit status 1.
+  void RunSlidingWindows(long int win_step, long int win_size, bool win_small);
 
   // MI355X path: hands the not yet consumed part of a streaming set (the current region's raw
   // line first) to the bulk packer.  After this call Get()/Next() report the end of the set.

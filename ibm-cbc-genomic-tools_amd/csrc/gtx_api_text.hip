@@ -1,6 +1,7 @@
 // gtx_api_text.hip -- the C ABI's text feed: blocks of region text (BED, SAM, GFF) tokenised on the device and counted, covered or scanned
-// where the triples are (gtx_*_add_text), and the subset of a block's lines by their hits (gtx_subset_*).  Host code only (the
-// kernels: gtx_text.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
+// where the triples are (gtx_*_add_text), the subset of a block's lines by their hits (gtx_subset_*), their columns rewritten
+// (gtx_rewrite_*) and their sliding windows (gtx_windows_*).  Host code only (the kernels: gtx_text.hip, gtx_rewrite.hip,
+// gtx_windows.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include "gtx_query.h"
 #include "gtx_text.h"
 #include "gtx_rewrite.h"
+#include "gtx_windows.h"
 #include "gtx_ctx.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -145,6 +147,16 @@ static int add_text(gtx_ctx *c, TextMode mode, const char *text, size_t bytes, i
   t.busy = true;
   c->streamSeen += nLines;
   return GTX_OK;
+}
+
+// the sliding windows' view of a slot whose block gtx_windows_text has planned (gtx_windows.h)
+static gtx::WindowsDevice windows_device(const TextSlot &t)
+{
+  const size_t nTiles = gtx::windows_tiles(t.wnLines);
+  gtx::WindowsDevice d; d.text = t.text.get(); d.bytes = t.wnBytes; d.nl = t.nl.get(); d.nLines = t.wnLines; d.flag = t.flag.get();
+  d.rec = t.wnRec.get(); d.tileWindows = t.wnTile.get(); d.tileBytes = t.wnTile.get() + nTiles; d.baseWindows = t.wnBase.get(); d.baseBytes = t.wnBase.get() + nTiles + 1;
+  d.lineWin = t.wnLine.get(); d.lineByte = t.wnLine.get() + (size_t)t.wnLines + 1;
+  return d;
 }
 
 extern "C" {
@@ -307,6 +319,127 @@ int gtx_rewrite_limits(int32_t *tile, int32_t *stage)
 {
   if (tile) *tile = gtx::kRewriteTile;
   if (stage) *stage = gtx::kRewriteStage;
+  return GTX_OK;
+}
+
+// text -> triples in line order (the tokenizer's plain case) -> plan, two 64-bit prefixes, the lines' bases (gtx_windows.h);
+// everything enqueued, the verdict and the totals on their way to the host behind it.  Nothing is rendered before gtx_windows_result
+int gtx_windows_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_windows_op *op, int *ticket)
+{
+  if (!c) return GTX_E_ARG;
+  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || op->win_size < 1 || op->win_size > (1ll << 31) ||
+      op->win_step < 1 || op->win_step > (1ll << 31))
+    return fail(c, GTX_E_ARG, "gtx_windows_text: bad argument");
+  if (c->text.slot[c->text.seq & 1].windowsPending) return fail(c, GTX_E_STATE, "gtx_windows_text: the result of the block before last has not been fetched (gtx_windows_result)");
+  gtx_text_rules r; memset(&r, 0, sizeof r);
+  r.max_label_value = 1;
+  TextSlot *tp = nullptr; bool empty = false;
+  // (the sorted scanner's rules, as for the rewrite: nothing about the interval is checked, and nothing about the order)
+  { int rc = text_stage(c, text, bytes, nLines, &r, false, 2, nullptr, 0, &tp, ticket, &empty); if (rc) return rc; }
+  TextSlot &t = *tp;
+  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
+  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
+  t.windowsPending = true;
+  t.wnSize = op->win_size; t.wnStep = op->win_step; t.wnSmall = op->small ? 1 : 0; t.wnBytes = bytes; t.wnLines = (unsigned)nLines;
+  if (empty) { t.wnLines = 0; return GTX_OK; }
+  const size_t nTiles = gtx::windows_tiles((unsigned)nLines);
+  if ((size_t)nLines > t.wnRec.cap) { HIPCHK(c, t.wnRec.alloc(t.w.cap)); HIPCHK(c, t.wnLine.alloc(2 * (t.w.cap + 1))); }
+  if (2 * nTiles > t.wnTile.cap) { HIPCHK(c, t.wnTile.alloc(2 * nTiles + (nTiles >> 2))); HIPCHK(c, t.wnBase.alloc(2 * (nTiles + 1) + (nTiles >> 2))); }
+  const gtx::WindowsDevice d = windows_device(t);
+  const gtx::WindowsOp k{t.wnSize, t.wnStep, t.wnSmall};
+  prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and base launches alone, on the text where it is)
+  HIPCHK(c, prof_mark(c, 1, c->stream));
+  HIPCHK(c, gtx::launch_windows_plan(d, k, c->stream));
+  HIPCHK(c, prof_mark(c, 2, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseWindows + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, prof_end(c, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  return GTX_OK;
+}
+
+// The block's windows in ranges of whole output tiles through two device and two page-locked buffers, as gtx_window_lines streams
+// its lines: range r + 1 is enqueued before the sink is given range r - 1, behind the copy of r - 1 out of the device buffer it
+// writes.  A range's place in the output is the sum of the ranges in front, known when it is enqueued.
+int gtx_windows_result(gtx_ctx *c, int ticket, int *needs_host, gtx_lines_sink sink, void *user, int64_t *n_windows, int64_t *n_bytes)
+{
+  if (!c || !needs_host || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_windows_result: bad argument") : GTX_E_ARG;
+  TextSlot &t = c->text.slot[ticket];
+  TextState &s = c->text;
+  if (!t.evParsed || !t.windowsPending) return fail(c, GTX_E_STATE, "gtx_windows_result: no such block");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(t.evParsed));
+  t.windowsPending = false;
+  *needs_host = *t.hostFlag.get();
+  if (n_windows) *n_windows = 0;
+  if (n_bytes) *n_bytes = 0;
+  if (*needs_host) return GTX_OK;
+  const int64_t total = (int64_t)t.hostTotal.get()[0], totalBytes = (int64_t)t.hostTotal.get()[1];
+  if (total == 0) return GTX_OK;
+  if (!sink) return fail(c, GTX_E_ARG, "gtx_windows_result: a sink is required");
+  const int64_t W = gtx::kWindowsOutTile, allTiles = (total + W - 1) / W;
+  const int64_t per = std::min(allTiles, std::max<int64_t>(1, c->lines.chunkBytes / gtx::kWindowsRunBytes));   // output tiles per range
+  const size_t room = (size_t)per * gtx::kWindowsRunBytes + 32;
+  if (room > s.wnOut[0].cap || room > s.wnPin[0].cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream));
+    for (int k = 0; k < 2; k++) { HIPCHK(c, s.wnOut[k].reserve(room)); HIPCHK(c, s.wnPin[k].reserve(room)); }
+  }
+  for (int k = 0; k < 2; k++) if (!s.wnCopied[k]) HIPCHK(c, hipEventCreateWithFlags(&s.wnCopied[k], hipEventDisableTiming));
+  if (!s.wnRange) { HIPCHK(c, s.wnRange.alloc(2)); HIPCHK(c, s.wnHostRange.alloc(2)); }
+  const gtx::WindowsDevice d = windows_device(t);
+  const gtx::WindowsOp op{t.wnSize, t.wnStep, t.wnSmall};
+  const int64_t ranges = (allTiles + per - 1) / per;
+  int64_t got[2] = {0, 0}, done = 0;                                       // the bytes of the ranges in the two page-locked buffers; of all ranges finished
+  auto enqueue = [&](int64_t r, int64_t base) -> int {                     // (gtx_profile_*: a range's emit launch alone is one profiled call)
+    const int k = (int)(r & 1);
+    const gtx::WindowsRange rg{r * per * W, std::min(per, allTiles - r * per), base, total, s.wnOut[k].get(), s.wnRange.get() + k};
+    prof_begin(c);
+    HIPCHK(c, prof_mark(c, 1, c->stream));
+    HIPCHK(c, gtx::launch_windows_emit(d, op, rg, c->stream));
+    HIPCHK(c, prof_mark(c, 2, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.wnHostRange.get() + k, s.wnRange.get() + k, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, prof_end(c, c->stream));
+    return GTX_OK;
+  };
+  auto sink_range = [&](int64_t r) -> int {
+    const int k = (int)(r & 1);
+    HIPCHK(c, hipEventSynchronize(s.wnCopied[k]));
+    if (got[k] > 0 && sink(user, s.wnPin[k].get(), (size_t)got[k]) != 0) {
+      (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stage.copyStream);
+      c->err = "gtx_windows_result: the sink refused the text"; return GTX_E_SINK;
+    }
+    return GTX_OK;
+  };
+  int rc = enqueue(0, 0); if (rc) return rc;
+  for (int64_t r = 0; r < ranges; r++) {
+    const int k = (int)(r & 1);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    got[k] = (int64_t)s.wnHostRange.get()[k];
+    if (got[k] < 0 || (size_t)got[k] + 32 > room) { (void)hipStreamSynchronize(c->stage.copyStream); return fail(c, GTX_E_STATE, "gtx_windows_result: a range outside its bound"); }
+    HIPCHK(c, hipMemcpyAsync(s.wnPin[k].get(), s.wnOut[k].get(), (size_t)got[k], hipMemcpyDeviceToHost, c->stage.copyStream));
+    HIPCHK(c, hipEventRecord(s.wnCopied[k], c->stage.copyStream));
+    done += got[k];
+    if (r + 1 < ranges) {
+      if (r >= 1) HIPCHK(c, hipStreamWaitEvent(c->stream, s.wnCopied[k ^ 1], 0));   // the copy of r - 1 out of the buffer r + 1 is rendered into
+      rc = enqueue(r + 1, done); if (rc) return rc;
+    }
+    if (r >= 1) { rc = sink_range(r - 1); if (rc) return rc; }
+  }
+  rc = sink_range(ranges - 1); if (rc) return rc;
+  if (done != totalBytes) return fail(c, GTX_E_STATE, "gtx_windows_result: the ranges' bytes differ from the plan's");
+  if (n_windows) *n_windows = total;
+  if (n_bytes) *n_bytes = done;
+  return GTX_OK;
+}
+
+int gtx_windows_limits(int32_t *line_tile, int32_t *out_tile, int32_t *max_fixed)
+{
+  if (line_tile) *line_tile = gtx::kWindowsLineTile;
+  if (out_tile) *out_tile = gtx::kWindowsOutTile;
+  if (max_fixed) *max_fixed = gtx::kWindowsMaxFixed;
   return GTX_OK;
 }
 }

@@ -47,19 +47,22 @@ constexpr int kPartThreads = 1024, kPartBatch = 8;
 
 // base [tiles + 1] = the exclusive sums of count [tiles], base[tiles] their total (defined in gtx_select.hip)
 hipError_t launch_tile_prefix(const unsigned *tileCount, long long tiles, long long *tileBase, hipStream_t st);
+// the same over 64-bit counts, for tiles whose count need not fit 32 bits (the sliding windows' plan, gtx_windows.hip)
+hipError_t launch_tile_prefix64(const unsigned long long *tileCount, long long tiles, long long *tileBase, hipStream_t st);
 
 // The body of that scan, for a block of kPartThreads threads with sh [kPartThreads] in LDS: base[k] = count[0] + .. + count[k - 1] for
-// k = 0 .. n.  It ends in a barrier: behind it every thread may read base[0 .. n] and sh is free.
-__device__ __forceinline__ void block_exclusive_sum(const unsigned *__restrict__ count, long long n, long long *__restrict__ base, long long *sh)
+// k = 0 .. n.  It ends in a barrier: behind it every thread may read base[0 .. n] and sh is free.  COUNT: unsigned, or unsigned long long.
+template <class COUNT>
+__device__ __forceinline__ void block_exclusive_sum(const COUNT *__restrict__ count, long long n, long long *__restrict__ base, long long *sh)
 {
   typedef long long i64;
   const int tid = threadIdx.x;
   const i64 per = (n + kPartThreads - 1) / kPartThreads, b = min((i64)tid * per, n), e = min(b + per, n);
   i64 a = 0;
   for (i64 k = b; k < e; k += kPartBatch) {
-    unsigned v[kPartBatch];
+    COUNT v[kPartBatch];
 #pragma unroll
-    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? count[k + j] : 0u;
+    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? count[k + j] : (COUNT)0;
 #pragma unroll
     for (int j = 0; j < kPartBatch; j++) a += v[j];
   }
@@ -73,9 +76,9 @@ __device__ __forceinline__ void block_exclusive_sum(const unsigned *__restrict__
   }
   i64 run = tid > 0 ? sh[tid - 1] : 0;
   for (i64 k = b; k < e; k += kPartBatch) {
-    unsigned v[kPartBatch];
+    COUNT v[kPartBatch];
 #pragma unroll
-    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? count[k + j] : 0u;
+    for (int j = 0; j < kPartBatch; j++) v[j] = k + j < e ? count[k + j] : (COUNT)0;
 #pragma unroll
     for (int j = 0; j < kPartBatch; j++) if (k + j < e) { base[k + j] = run; run += v[j]; }
   }

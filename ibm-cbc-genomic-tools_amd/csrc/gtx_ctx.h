@@ -18,7 +18,7 @@
 #include "gtx_adjacent.h"
 #include "gtx_internal.h"
 
-namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h: held here by pointer only)
+namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; struct WindowsRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h, gtx_windows.h: held here by pointer only)
 
 #pragma GCC visibility push(hidden)
 
@@ -159,6 +159,11 @@ struct TextSlot {
   // gtx_rewrite_text: the lines' records, the tiles' bytes | lines and their prefixes (`out` and `hostTotal` as for the subset);
   // whether the slot holds a rewritten block whose result has not been fetched
   DevBuf<gtx::RewriteRec> rwRec; DevBuf<unsigned> rwTile; DevBuf<long long> rwBase; bool rewritePending = false;
+  // gtx_windows_text: the lines' records, the tiles' windows | bytes and their prefixes, the lines' bases (windows | bytes); what
+  // gtx_windows_result needs of the call to render the block (`hostTotal`: the block's windows and bytes); whether the slot holds
+  // a planned block whose result has not been fetched
+  DevBuf<gtx::WindowsRec> wnRec; DevBuf<unsigned long long> wnTile; DevBuf<long long> wnBase, wnLine; bool windowsPending = false;
+  long long wnSize = 0, wnStep = 0; int wnSmall = 0; size_t wnBytes = 0; unsigned wnLines = 0;
 };
 
 // What a device call found, on its way to the caller's struct: the info block the kernels write, its page-locked copy, and the
@@ -285,6 +290,11 @@ struct TextState {
   DevBuf<int> table; DevBuf<char> names; unsigned mask = 0, blobLen = 0;
   std::string blob;                                   // the chromosome names the device tables were built from
   DevBuf<long long> chromLen; std::vector<long long> h_chromLen;   // gtx_rewrite_text, bounds: the lengths per class, and what was uploaded
+  // gtx_windows_result: two device and two page-locked buffers for the ranges of a block's windows in flight, the events of their
+  // copies, the ranges' bytes on the device and on the host
+  DevBuf<char> wnOut[2]; PinBuf<char> wnPin[2]; hipEvent_t wnCopied[2] = {nullptr, nullptr};
+  DevBuf<unsigned long long> wnRange; PinBuf<unsigned long long> wnHostRange;
+  ~TextState() { for (int k = 0; k < 2; k++) if (wnCopied[k]) (void)hipEventDestroy(wnCopied[k]); }
 };
 
 // measurement (prof_begin / prof_mark / prof_end below)

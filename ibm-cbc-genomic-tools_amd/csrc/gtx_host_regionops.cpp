@@ -1,6 +1,6 @@
 // gtx_host_regionops.cpp -- the line-based interval operations of genomic_regions on a streamed BED set: shift, shiftp, pos, center,
-// fix and bounds (GenomicRegionSet::RunShiftPos, RunModifyPos, RunCenter, RunFix, RunBounds).  See genomic_intervals.h; shared pieces
-// in gtx_host.h.
+// fix and bounds (GenomicRegionSet::RunShiftPos, RunModifyPos, RunCenter, RunFix, RunBounds), and win, the one that prints many lines
+// per line (RunSlidingWindows).  See genomic_intervals.h; shared pieces in gtx_host.h.
 #include "gtx_host.h"
 
 #include <algorithm>
@@ -117,15 +117,18 @@ void Render(std::string &out, const RegionOp &op, GenomicRegion *r, const std::s
   WriteOut(out, 1u << 22);
 }
 
+// what a loop does with one region and its raw line: its output appended to `out`
+typedef std::function<void(std::string &out, GenomicRegion *r, const std::string &raw)> Renderer;
+
 // the host loop over what is left of the set, region by region with the reference's print; an input error ends it behind the
 // output in front of the line
-void HostLoop(GenomicRegionSet *set, const RegionOp &op)
+void HostLoop(GenomicRegionSet *set, const Renderer &render)
 {
   std::string out;
   LoadError err;
   tls_load_error = &err;
   try {
-    for (GenomicRegion *r = set->Get(); r != NULL; r = set->Next()) Render(out, op, r, set->CurrentLine());
+    for (GenomicRegion *r = set->Get(); r != NULL; r = set->Next()) render(out, r, set->CurrentLine());
   } catch (const LoadAbort &) {}
   tls_load_error = NULL;
   WriteOut(out);
@@ -133,7 +136,7 @@ void HostLoop(GenomicRegionSet *set, const RegionOp &op)
 }
 
 // the same for the lines of one block of text that came back from the device, with their own line numbers
-void HostBlock(const char *text, size_t bytes, long int first_line, const RegionOp &op)
+void HostBlock(const char *text, size_t bytes, long int first_line, const Renderer &render)
 {
   std::string out, raw, line;
   LoadError err;
@@ -145,7 +148,7 @@ void HostBlock(const char *text, size_t bytes, long int first_line, const Region
       if (!nl) break;
       raw.assign(p, nl); line = raw;
       GenomicRegionBED r(&line[0], no);
-      Render(out, op, &r, raw);
+      render(out, &r, raw);
       p = nl + 1;
     }
   } catch (const LoadAbort &) {}
@@ -170,7 +173,7 @@ bool TextUsable(GenomicRegionSet *set, const RegionOp &op)
 
 // the set's text block by block through gtx_rewrite_text, the rewritten text to stdout in block order; a block that comes back is
 // rendered here, alone, and the next one goes to the device again
-void TextLoop(GenomicRegionSet *set, const RegionOp &op)
+void TextLoop(GenomicRegionSet *set, const RegionOp &op, const Renderer &render)
 {
   gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
   std::string first; long int first_no = 0;
@@ -203,7 +206,7 @@ void TextLoop(GenomicRegionSet *set, const RegionOp &op)
     }
     int redo = 0; size_t got = 0;
     DieGtx(ctx, gtx_rewrite_result(ctx, ticket, &redo, out, out_cap, &got, NULL));
-    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, op); }
+    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render); }
     else { on_device++; if (got) fwrite(out, 1, got, stdout); }
     return true;
   };
@@ -213,7 +216,7 @@ void TextLoop(GenomicRegionSet *set, const RegionOp &op)
     const bool here = first_block && b.text != first.data() && b.bytes < TextPolicy().threshold_bytes && packer.SourceAtEnd();
     if (b.text != first.data()) first_block = false;
     // (counted with the blocks that came back: the trace says how many blocks the loop rendered, whichever way they got to it)
-    if (here) { pump.SettleAll(); came_back++; HostBlock(b.text, b.bytes, b.first_line, op); return ticket; }
+    if (here) { pump.SettleAll(); came_back++; HostBlock(b.text, b.bytes, b.first_line, render); return ticket; }
     DieGtx(ctx, gtx_rewrite_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
     return ticket;
   };
@@ -235,8 +238,93 @@ void Run(GenomicRegionSet *set, const RegionOp &op)
   if (set->load_in_memory) set->PrintError("the interval operations stream their input on the MI355X path: open the set with load_in_memory = false!");
   // GTX_TEXT_ON_DEVICE=0: the host loop and nothing else.  Otherwise the device is looked for whatever the input's size: without
   // one the run ends with the library's error, as every other operation's does
-  if (!TextPolicy().never && TextUsable(set, op)) TextLoop(set, op);
-  else HostLoop(set, op);
+  const Renderer render = [&op](std::string &out, GenomicRegion *r, const std::string &raw) { Render(out, op, r, raw); };
+  if (!TextPolicy().never && TextUsable(set, op)) TextLoop(set, op, render);
+  else HostLoop(set, render);
+}
+
+// ---- win ---------------------------------------------------------------------------------------------------------------------
+struct WindowsOp { long int step, size; bool small; };
+
+// GenomicRegionBED::PrintWindows (:2520-2532) of a region, in arithmetic that cannot overflow: z <= STOP holds wherever a
+// difference to STOP is taken, and a size below 1 never ends the loop (z + size - 1 <= STOP then)
+void RenderWindows(std::string &out, const WindowsOp &op, GenomicRegion *r, const std::string &raw)
+{
+  if (r->I.size() != 1) r->PrintError("this operation requires single-interval regions!\n");
+  const PairQuery q = PairQuery::From(r, raw);
+  const long int start = q.iv[0], stop = q.iv[1];
+  std::string tail;
+  if (q.n_tokens >= 4) {
+    tail += '\t'; tail += q.label;
+    if (q.n_tokens >= 6) { char b[32]; snprintf(b, sizeof b, "\t%ld\t%c", q.score, q.strand); tail += b; }
+  }
+  tail += '\n';
+  char num[48];
+  for (long int z = start; z <= stop;) {
+    const unsigned long room = (unsigned long)stop - (unsigned long)z;           // STOP - z, exact
+    const bool cut = op.size >= 1 && (unsigned long)(op.size - 1) > room;        // z + size - 1 > STOP
+    if (cut && !op.small) break;
+    const long int e = cut ? stop : (long int)((unsigned long)z + (unsigned long)op.size - 1ul);
+    out += q.chrom;
+    out.append(num, (size_t)snprintf(num, sizeof num, "\t%ld\t%ld", z - 1, e));
+    out += tail;
+    WriteOut(out, 1u << 22);
+    if ((unsigned long)op.step > room) break;                                    // the next z lies behind STOP
+    z += op.step;
+  }
+}
+
+int WriteSink(void *user, const char *text, size_t bytes) { return fwrite(text, 1, bytes, (FILE *)user) == bytes ? 0 : 1; }
+
+// the set's text block by block through gtx_windows_text; gtx_windows_result streams a block's windows to stdout, in block order.  A
+// block that comes back is rendered here, alone, and the next one goes to the device again
+void WindowsTextLoop(GenomicRegionSet *set, const WindowsOp &op, const Renderer &render)
+{
+  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
+  std::string first; long int first_no = 0;
+  LineSource *src = set->DetachStream(&first, &first_no);
+  if (first_no <= 0) return;
+  ChromTable chroms;
+  chroms.Freeze();
+  gtx_windows_op dev; memset(&dev, 0, sizeof dev);
+  dev.win_size = op.size; dev.win_step = op.step; dev.small = op.small ? 1 : 0;
+  PackOptions opt;
+  opt.chroms = &chroms;
+  BedPacker packer(src, opt);
+  TextPump pump(packer, opt);
+  long int on_device = 0, came_back = 0;
+  pump.settle = [&](const TextPump::Block &b, int ticket) {
+    int redo = 0;
+    DieGtx(ctx, gtx_windows_result(ctx, ticket, &redo, WriteSink, stdout, NULL, NULL));
+    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render); }
+    else on_device++;
+    return true;
+  };
+  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
+    int ticket = -1;
+    DieGtx(ctx, gtx_windows_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
+    return ticket;
+  };
+  // the line the set's constructor has read for its format check: a block of one line
+  first += '\n';
+  TextPump::Block &one = pump.blk[0];
+  one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
+  pump.Add(0);
+  pump.Run(1);
+  fflush(stdout);
+  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx windows] blocks expanded on the device: %ld, came back: %ld\n", on_device, came_back);
+}
+
+// May the set's text go to the device?  Whatever its size -- the output, not the input, decides what a run costs -- on one GPU, with
+// a size and a step the device's arithmetic takes
+bool WindowsUsable(const WindowsOp &op)
+{
+  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
+  if (gtx_group_size(devices) != 1) return false;
+  if (g_pool_future.valid()) g_pool_future.get();
+  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
+  const long int lim = 1L << 31;
+  return op.size >= 1 && op.size <= lim && op.step <= lim;
 }
 
 }  // namespace
@@ -256,3 +344,16 @@ void GenomicRegionSet::RunModifyPos(const char *position_op, long int position_s
 void GenomicRegionSet::RunCenter() { Run(this, RegionOp{GTX_REWRITE_CENTER, "", 0, 0, NULL}); }
 void GenomicRegionSet::RunFix() { Run(this, RegionOp{GTX_REWRITE_FIX, "", 0, 0, NULL}); }
 void GenomicRegionSet::RunBounds(StringLIntMap *bounds) { Run(this, RegionOp{GTX_REWRITE_BOUNDS, "", 0, 0, bounds}); }
+
+void GenomicRegionSet::RunSlidingWindows(long int win_step, long int win_size, bool win_small)
+{
+  // (the reference's loop does not advance with a distance below 1 and never returns: nothing bounded matches it)
+  if (win_step < 1) { fflush(stdout); fprintf(stderr, "Error: window distance must be at least 1!\n"); exit(1); }
+  if (n_regions == 0) return;
+  if (format != "BED") PrintError("unsupported input format!\n");
+  if (load_in_memory) PrintError("the interval operations stream their input on the MI355X path: open the set with load_in_memory = false!");
+  const WindowsOp op{win_step, win_size, win_small};
+  const Renderer render = [&op](std::string &out, GenomicRegion *r, const std::string &raw) { RenderWindows(out, op, r, raw); };
+  if (!TextPolicy().never && WindowsUsable(op)) WindowsTextLoop(this, op, render);
+  else HostLoop(this, render);
+}

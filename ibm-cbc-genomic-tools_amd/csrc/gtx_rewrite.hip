@@ -12,26 +12,8 @@ typedef unsigned uint32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kStageBytes = kRewriteStage + 32;   // a stage begins at the 16-byte line below its first byte and is filled in whole units
 
-__device__ __forceinline__ int digits(u64 u)
-{
-  int d = 1;
-  for (u64 p = 10; d < 20 && u >= p; p *= 10) d++;
-  return d;
-}
-__device__ __forceinline__ int signed_len(i64 v) { return v < 0 ? 1 + digits(0ull - (u64)v) : digits((u64)v); }
-
-// "%ld" of v at p; returns the byte behind it
-__device__ __forceinline__ unsigned char *put_signed(unsigned char *p, i64 v)
-{
-  u64 u = (u64)v;
-  if (v < 0) { *p++ = '-'; u = 0ull - u; }
-  const int d = digits(u);
-  int k = d;
-  while (u >> 32) { p[--k] = (unsigned char)('0' + (int)(u % 10)); u /= 10; }
-  unsigned w = (unsigned)u;
-  while (k > 0) { p[--k] = (unsigned char)('0' + (int)(w % 10)); w /= 10; }
-  return p + d;
-}
+using gtxtext::signed_len;
+using gtxtext::put_signed;
 
 // the text of lines [j0, j1) into lds, from the 16-byte line below its first byte: lds[k] = text[a0 + k]
 __device__ __forceinline__ void stage_text(unsigned char *lds, const char *__restrict__ text, size_t bytes, size_t a0, size_t t1)

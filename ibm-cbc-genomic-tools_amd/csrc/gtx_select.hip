@@ -55,7 +55,8 @@ struct SelectRule : CompactRule {
   }
 };
 
-__global__ __launch_bounds__(kPartThreads) void select_prefix_kernel(const unsigned *__restrict__ count, i64 nt, i64 *__restrict__ base)
+template <class COUNT>
+__global__ __launch_bounds__(kPartThreads) void select_prefix_kernel(const COUNT *__restrict__ count, i64 nt, i64 *__restrict__ base)
 {
   __shared__ i64 sh[kPartThreads];
   block_exclusive_sum(count, nt, base, sh);
@@ -79,7 +80,13 @@ hipError_t launch_tested(const SelectArgs &a, bool ctl, bool lds, unsigned *tile
 
 hipError_t launch_tile_prefix(const unsigned *tileCount, long long tiles, long long *tileBase, hipStream_t st)
 {
-  hipLaunchKernelGGL(select_prefix_kernel, dim3(1), dim3(kPartThreads), 0, st, tileCount, tiles, tileBase);
+  hipLaunchKernelGGL(select_prefix_kernel<unsigned>, dim3(1), dim3(kPartThreads), 0, st, tileCount, tiles, tileBase);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_prefix64(const unsigned long long *tileCount, long long tiles, long long *tileBase, hipStream_t st)
+{
+  hipLaunchKernelGGL(select_prefix_kernel<unsigned long long>, dim3(1), dim3(kPartThreads), 0, st, tileCount, tiles, tileBase);
   return hipGetLastError();
 }
 

@@ -122,6 +122,17 @@ class RewriteOp(ctypes.Structure):
         return o
 
 
+class WindowsOp(ctypes.Structure):
+    """gtx_windows_op (include/gtx.h): -s, -d and --small of genomic_regions win"""
+    _fields_ = [("win_size", ctypes.c_int64), ("win_step", ctypes.c_int64), ("small", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, size=1, step=1, small=False):
+        o = cls()
+        o.win_size = int(size); o.win_step = int(step); o.small = int(bool(small))
+        return o
+
+
 # name -> (restype, argtypes); must list every symbol include/gtx.h declares
 # int sink(void *user, const char *text, size_t bytes) of gtx_window_lines / gtx_pair_lines
 LINES_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -261,6 +272,9 @@ ABI = {
     "gtx_rewrite_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_rewrite_max_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int64]),
     "gtx_rewrite_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_windows_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_windows_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, LINES_SINK, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_windows_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_ref_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_join_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "gtx_join": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
@@ -362,6 +376,14 @@ def rewrite_limits():
     t, b = ctypes.c_int32(), ctypes.c_int32()
     load().gtx_rewrite_limits(ctypes.byref(t), ctypes.byref(b))
     return int(t.value), int(b.value)
+
+
+def windows_limits():
+    """(line_tile, out_tile, max_fixed) of gtx_windows_limits: lines per tile of the sliding windows' plan, windows per output tile
+    of their emit pass, and the longest fixed part (column 1, two tabs, the tail, the newline) of a line the device takes"""
+    t, w, f = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    load().gtx_windows_limits(ctypes.byref(t), ctypes.byref(w), ctypes.byref(f))
+    return int(t.value), int(w.value), int(f.value)
 
 
 def window_select_limits():
@@ -539,6 +561,48 @@ class Engine:
             tickets.append((text, t.value))
         for x in tickets:
             collect(*x)
+        return results
+
+    def windows_text(self, blocks, op, chunk=None, refuse_at=None):
+        """gtx_windows_text / gtx_windows_result per block of text (bytes of complete lines), two blocks in flight: per block
+        (needs_host, the windows' text, the number of windows, the number of sink calls).  chunk: gtx_set_lines_chunk first.
+        refuse_at: the sink refuses its refuse_at-th call (counted from 1 over all blocks): the blocks still in flight are dropped
+        and the GtxError of GTX_E_SINK is raised."""
+        if chunk is not None:
+            self.set_lines_chunk(chunk)
+        tickets, results, calls = [], [], [0]
+
+        def collect(text, t, refuse=False):
+            parts, mine = [], [0]
+
+            def take(user, p, n):
+                calls[0] += 1; mine[0] += 1
+                if refuse or calls[0] == refuse_at:
+                    return 1
+                parts.append(ctypes.string_at(p, n))
+                return 0
+            redo, nw, nb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+            rc = self.lib.gtx_windows_result(self.ctx, t, ctypes.byref(redo), LINES_SINK(take), None, ctypes.byref(nw), ctypes.byref(nb))
+            if refuse:
+                return
+            self._chk(rc)
+            out = b"".join(parts)
+            if nb.value != len(out):
+                raise GtxError("gtx_windows_result: n_bytes %d, the sink was given %d" % (nb.value, len(out)))
+            results.append((redo.value, out, nw.value, mine[0]))
+        try:
+            for text in blocks:
+                if len(tickets) == 2:
+                    collect(*tickets.pop(0))
+                t = ctypes.c_int(-1)
+                self._chk(self.lib.gtx_windows_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
+                tickets.append((text, t.value))
+            while tickets:
+                collect(*tickets.pop(0))
+        except GtxError:
+            for x in tickets:                                         # (a refused block is dropped by the call itself)
+                collect(*x, refuse=True)
+            raise
         return results
 
     def count(self, reads, weights=None, flags=READS_SORTED):

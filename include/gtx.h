@@ -870,6 +870,38 @@ int gtx_pair_lines(gtx_ctx *ctx, const void *d_ordinals, const void *d_values, i
 int gtx_window_filter_lines(gtx_ctx *ctx, const void *d_windows, int64_t n_windows, uint64_t min_value, int64_t limit, gtx_lines_sink sink, void *user,
                             int64_t *n_lines, int64_t *n_bytes, int64_t *end_at);
 
+/* genomic_regions win on text (gtools/genomic_regions.cpp:397-403, :647-651, :734; GenomicRegionSet::RunSlidingWindows
+ * genomic_intervals.cpp:4449-4455 over GenomicRegionBED::PrintWindows :2520-2532): every line of a block of complete BED lines cut
+ * into sliding windows of win_size positions, win_step apart -- what `bedtools makewindows` does.  The block goes to the device as
+ * for gtx_rewrite_text (same buffers contract, two blocks in flight, tickets in order).  With START = column 2 + 1, STOP = column 3
+ * the windows of a line begin at z = START, START + win_step, .. <= STOP; without `small` the first z with z + win_size - 1 > STOP
+ * ends them.  A window prints column 1, TAB, z - 1, TAB, min(z + win_size - 1, STOP), then with 4 or more columns TAB and column 4,
+ * with 6 columns TAB column 5 TAB column 6 as well -- a 5-column line loses its score -- and a newline.  A line with START > STOP
+ * prints nothing.  The lines the device takes are those of gtx_rewrite_text (the tokenizer's plain case); a block with ANY other
+ * line, with a line whose fixed part (column 1, two tabs, the printed columns behind column 3 with their tabs, the newline) is longer
+ * than max_fixed of gtx_windows_limits, or with a tile of line_tile consecutive lines whose text is longer than the rewrite's stage,
+ * comes back: gtx_windows_result says needs_host, calls no sink and reports zero totals, and the caller renders the block by its own
+ * means.  GTX_E_ARG unless 1 <= win_size, win_step <= 2^31 (the caller's own loop takes the rest).
+ * gtx_windows_text copies the block in and enqueues the newline index, the tokenizer, the plan of the lines (windows and bytes per
+ * line from closed forms of digit counts, nothing loops over windows) and its prefixes.  gtx_windows_result waits for the plan and
+ * then streams the block's windows in order to `sink` as gtx_window_lines streams its lines: ranges of whole output tiles of
+ * out_tile windows, at most gtx_set_lines_chunk bytes of bound each (a tile's bound is out_tile x (max_fixed + 20); one tile is
+ * always taken), range r + 1 rendering while range r is copied.  No line straddles two calls of the sink; a block without a window
+ * makes no call (sink may then be NULL).  A sink that returns non-zero ends the call with GTX_E_SINK; the block is dropped and the
+ * context stays usable.  *n_windows and *n_bytes (either may be NULL) are the block's totals, equal to what the sink was given.  The
+ * result of a ticket must be fetched before the block after next is added.
+ * Under gtx_profile_enable a gtx_windows_text call is bracketed as gtx_rewrite_text is (ms_stream_kernel: plan, prefixes and the
+ * lines' bases alone on text that is already in HBM), and every range of gtx_windows_result is a profiled call of its own
+ * (ms_stream_kernel: the range's emit launch alone). */
+typedef struct gtx_windows_op {
+  int64_t win_size, win_step;                  /* -s and -d of the reference */
+  int32_t small;                               /* --small: the windows that STOP cuts short are printed too */
+} gtx_windows_op;
+int gtx_windows_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_windows_op *op, int *ticket);
+int gtx_windows_result(gtx_ctx *ctx, int ticket, int *needs_host, gtx_lines_sink sink, void *user, int64_t *n_windows /* may be NULL */,
+                       int64_t *n_bytes /* may be NULL */);
+int gtx_windows_limits(int32_t *line_tile, int32_t *out_tile, int32_t *max_fixed);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* on = 1: every *_device call brackets its dominant kernel and the whole call with HIP events on the
