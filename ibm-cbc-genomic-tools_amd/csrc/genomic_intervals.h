@@ -88,6 +88,12 @@ class GenomicRegion
   bool OverlapsWith(GenomicRegion *r, bool ignore_strand);        // :1167-1172 (any interval pair)
   long int CalcOverlap(GenomicRegion *r, bool ignore_strand);     // :1196-1202 (sum over interval pairs)
   int CalcDirection(GenomicRegion *r, bool sorted_by_strand);     // :1225-1236 (on the envelopes)
+  // :1256-1274: the region as a BED line with score 1000 -- 6 columns, 9 with a colour, 12 for several intervals (which must be
+  // compatible, sorted and disjoint: an error at the region's line otherwise); convert_chromosome: "chr" in front, MT as chrM
+  void PrintBEDFormat(char *color, bool convert_chromosome);
+  // :961-971: "LABEL TAB chromosome strand START STOP" of every interval, or, compact, one chromosome and strand (an error when the
+  // intervals differ in them) and the starts and the stops as two comma-separated lists
+  void PrintREG(bool compact = false);
 
   static void *operator new(size_t n) { return GtxRegionAlloc(n); }
   static void operator delete(void *p) { GtxRegionFree(p); }
@@ -195,6 +201,17 @@ class GenomicRegionSet
   // and steps above 2^31 take it too.  GTX_TEXT_TRACE=1 reports "[gtx windows] blocks expanded on the device: N, came back: K".
   // win_step < 1, with which the reference's loop never ends, is refused with one error line and exit status 1.
   void RunSlidingWindows(long int win_step, long int win_size, bool win_small);
+  // The reference's `bed` and `reg` (genomic_intervals.cpp:3940-3948, :4097-4103): every region of a streamed SAM, GFF / GTF or BED
+  // set printed with PrintBEDFormat or PrintREG; RunConvertToBED prints "browser position P" and "track name='T' itemRgb=On
+  // visibility=1" first when position / title are not empty and the set has a region.  Same signatures and output.  MI355X path:
+  // whenever a device is usable the text goes to the device block by block (gtx_convert_text) and comes back as the printed lines;
+  // a block with a line the device does not take -- a spliced read, BED12, a '.' strand: everything that is not a plain
+  // single-interval line -- comes back and is rendered by the host loop alone, with its own line numbers and the reference's errors.
+  // GTX_TEXT_ON_DEVICE=0 keeps the host loop and looks for no device; a BED set into BED lines (the generic print of a BED region,
+  // not GenomicRegionBED's) and a colour longer than gtx_convert_limits' take it too.  GTX_TEXT_TRACE=1 reports "[gtx convert] blocks
+  // converted on the device: N, came back: K".
+  void RunConvertToBED(char *title, char *color, char *position, bool convert_chromosome);
+  void RunConvertToREG(bool compact = false);
 
   // MI355X path: hands the not yet consumed part of a streaming set (the current region's raw
   // line first) to the bulk packer.  After this call Get()/Next() report the end of the set.

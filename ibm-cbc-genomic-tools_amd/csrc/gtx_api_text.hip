@@ -1,7 +1,8 @@
 // gtx_api_text.hip -- the C ABI's text feed: blocks of region text (BED, SAM, GFF) tokenised on the device and counted, covered or scanned
 // where the triples are (gtx_*_add_text), the subset of a block's lines by their hits (gtx_subset_*), their columns rewritten
-// (gtx_rewrite_*) and their sliding windows (gtx_windows_*).  Host code only (the kernels: gtx_text.hip, gtx_rewrite.hip,
-// gtx_windows.hip); the context and the helpers shared with the other families are in gtx_ctx.h.
+// (gtx_rewrite_*), their sliding windows (gtx_windows_*) and their conversion to BED or REG lines (gtx_convert_*).  Host code only
+// (the kernels: gtx_text.hip, gtx_rewrite.hip, gtx_windows.hip, gtx_convert.hip); the context and the helpers shared with the other
+// families are in gtx_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -16,6 +17,7 @@
 #include "gtx_text.h"
 #include "gtx_rewrite.h"
 #include "gtx_windows.h"
+#include "gtx_convert.h"
 #include "gtx_ctx.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -319,6 +321,88 @@ int gtx_rewrite_limits(int32_t *tile, int32_t *stage)
 {
   if (tile) *tile = gtx::kRewriteTile;
   if (stage) *stage = gtx::kRewriteStage;
+  return GTX_OK;
+}
+
+// text of any of the three formats -> the tokenizer's verdict (its plain case; no names, so its triples are not read) -> plan, prefix,
+// emit (gtx_convert.h); everything enqueued, the verdict and the total on their way to the host behind it
+int gtx_convert_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_convert_op *op, uint32_t flags, int *ticket)
+{
+  if (!c) return GTX_E_ARG;
+  const bool sam = (flags & GTX_TEXT_SAM) != 0, gff = (flags & GTX_TEXT_GFF) != 0;
+  const size_t colorLen = op && op->color ? strlen(op->color) : 0;
+  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || (flags & ~(GTX_TEXT_SAM | GTX_TEXT_GFF)) || (sam && gff) ||
+      (op->to != GTX_CONVERT_BED && op->to != GTX_CONVERT_REG) || (op->to == GTX_CONVERT_BED && !sam && !gff) || colorLen > (size_t)gtx::kConvertMaxColor)
+    return fail(c, GTX_E_ARG, "gtx_convert_text: bad argument");
+  if (c->text.slot[c->text.seq & 1].convertPending) return fail(c, GTX_E_STATE, "gtx_convert_text: the result of the block before last has not been fetched (gtx_convert_result)");
+  const int format = sam ? 1 : gff ? 2 : 0;                                // (launch_tokenize's numbers)
+  gtx_text_rules r; memset(&r, 0, sizeof r);
+  r.max_label_value = 1;
+  TextSlot *tp = nullptr; bool empty = false;
+  // (the sorted scanner's rules, as for the rewrite: nothing about the interval is checked, and nothing about the order)
+  { int rc = text_stage(c, text, bytes, nLines, &r, false, 2, nullptr, format, &tp, ticket, &empty); if (rc) return rc; }
+  TextSlot &t = *tp;
+  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
+  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
+  t.convertPending = true;
+  if (empty) return GTX_OK;
+  const size_t nTiles = gtx::convert_tiles((unsigned)nLines), need = gtx_convert_max_bytes(bytes, nLines, op) + 32;
+  if ((size_t)nLines > t.cvRec.cap) HIPCHK(c, t.cvRec.alloc(t.w.cap));
+  if (nTiles > t.cvTile.cap) { HIPCHK(c, t.cvTile.alloc(nTiles + (nTiles >> 2))); HIPCHK(c, t.cvBase.alloc(nTiles + 1 + (nTiles >> 2))); }
+  if (need > t.out.cap) HIPCHK(c, t.out.alloc(need + (need >> 3)));
+  gtx::ConvertOp k; memset(&k, 0, sizeof k);
+  k.to = op->to == GTX_CONVERT_REG ? gtx::kConvertReg : gtx::kConvertBed; k.ucsc = op->ucsc_names ? 1 : 0;
+  k.colorLen = k.to == gtx::kConvertBed ? (int)colorLen : 0;              // (reg's -c prints a single-interval region as it stands)
+  if (k.colorLen) memcpy(k.color, op->color, colorLen);
+  gtx::ConvertDevice d; d.text = t.text.get(); d.bytes = bytes; d.nl = t.nl.get(); d.nLines = (unsigned)nLines; d.format = format; d.flag = t.flag.get();
+  d.rec = t.cvRec.get(); d.tileBytes = t.cvTile.get(); d.baseBytes = t.cvBase.get(); d.out = t.out.get();
+  t.hostTotal.get()[1] = (unsigned long long)nLines;                       // (every line of a plain block is printed)
+  prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and emit launches alone, on the text where it is)
+  HIPCHK(c, prof_mark(c, 1, c->stream));
+  HIPCHK(c, gtx::launch_convert(d, k, c->stream));
+  HIPCHK(c, prof_mark(c, 2, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, prof_end(c, c->stream));
+  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
+  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
+  t.busy = true;
+  return GTX_OK;
+}
+
+int gtx_convert_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed)
+{
+  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_convert_result: bad argument") : GTX_E_ARG;
+  TextSlot &t = c->text.slot[ticket];
+  if (!t.evParsed || !t.convertPending) return fail(c, GTX_E_STATE, "gtx_convert_result: no such block");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(t.evParsed));
+  t.convertPending = false;
+  *needs_host = *t.hostFlag.get();
+  *out_bytes = 0;
+  if (n_printed) *n_printed = 0;
+  if (*needs_host) return GTX_OK;
+  const size_t n = (size_t)t.hostTotal.get()[0];
+  if (n > 0 && (!out || n > capacity)) return fail(c, GTX_E_ARG, "gtx_convert_result: out is missing or smaller than the block's text (gtx_convert_max_bytes)");
+  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
+  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
+  *out_bytes = n;
+  if (n_printed) *n_printed = (int64_t)t.hostTotal.get()[1];
+  return GTX_OK;
+}
+
+size_t gtx_convert_max_bytes(size_t bytes, int64_t n_lines, const gtx_convert_op *op)
+{
+  const size_t colorLen = op && op->color ? strlen(op->color) : 0;
+  const size_t grow = (size_t)gtx::kConvertGrow + (colorLen ? (size_t)gtx::kConvertGrowColor + colorLen : 0);
+  return bytes + grow * (size_t)(n_lines > 0 ? n_lines : 0);
+}
+
+int gtx_convert_limits(int32_t *tile, int32_t *stage, int32_t *max_color)
+{
+  if (tile) *tile = gtx::kConvertTile;
+  if (stage) *stage = gtx::kConvertStage;
+  if (max_color) *max_color = gtx::kConvertMaxColor;
   return GTX_OK;
 }
 

@@ -18,7 +18,7 @@
 #include "gtx_adjacent.h"
 #include "gtx_internal.h"
 
-namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; struct WindowsRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h, gtx_windows.h: held here by pointer only)
+namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; struct WindowsRec; struct ConvertRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h, gtx_windows.h, gtx_convert.h: held here by pointer only)
 
 #pragma GCC visibility push(hidden)
 
@@ -164,6 +164,9 @@ struct TextSlot {
   // a planned block whose result has not been fetched
   DevBuf<gtx::WindowsRec> wnRec; DevBuf<unsigned long long> wnTile; DevBuf<long long> wnBase, wnLine; bool windowsPending = false;
   long long wnSize = 0, wnStep = 0; int wnSmall = 0; size_t wnBytes = 0; unsigned wnLines = 0;
+  // gtx_convert_text: the lines' records, the tiles' bytes and their prefix (`out` and `hostTotal` as for the subset); whether the
+  // slot holds a converted block whose result has not been fetched
+  DevBuf<gtx::ConvertRec> cvRec; DevBuf<unsigned> cvTile; DevBuf<long long> cvBase; bool convertPending = false;
 };
 
 // What a device call found, on its way to the caller's struct: the info block the kernels write, its page-locked copy, and the

@@ -1,6 +1,7 @@
 // gtx_host_regionops.cpp -- the line-based interval operations of genomic_regions on a streamed BED set: shift, shiftp, pos, center,
-// fix and bounds (GenomicRegionSet::RunShiftPos, RunModifyPos, RunCenter, RunFix, RunBounds), and win, the one that prints many lines
-// per line (RunSlidingWindows).  See genomic_intervals.h; shared pieces in gtx_host.h.
+// fix and bounds (GenomicRegionSet::RunShiftPos, RunModifyPos, RunCenter, RunFix, RunBounds), win, the one that prints many lines
+// per line (RunSlidingWindows), and bed and reg, which print a SAM, GFF or BED set in another format (RunConvertToBED,
+// RunConvertToREG).  See genomic_intervals.h; shared pieces in gtx_host.h.
 #include "gtx_host.h"
 
 #include <algorithm>
@@ -136,7 +137,7 @@ void HostLoop(GenomicRegionSet *set, const Renderer &render)
 }
 
 // the same for the lines of one block of text that came back from the device, with their own line numbers
-void HostBlock(const char *text, size_t bytes, long int first_line, const Renderer &render)
+void HostBlock(const char *text, size_t bytes, long int first_line, const Renderer &render, const std::string &format = "BED")
 {
   std::string out, raw, line;
   LoadError err;
@@ -147,8 +148,9 @@ void HostBlock(const char *text, size_t bytes, long int first_line, const Render
       const char *nl = (const char *)memchr(p, '\n', (size_t)(end - p));
       if (!nl) break;
       raw.assign(p, nl); line = raw;
-      GenomicRegionBED r(&line[0], no);
-      render(out, &r, raw);
+      if (format == "SAM") { GenomicRegionSAM r(&line[0], no); render(out, &r, raw); }
+      else if (format == "GFF") { GenomicRegionGFF r(&line[0], no); render(out, &r, raw); }
+      else { GenomicRegionBED r(&line[0], no); render(out, &r, raw); }
       p = nl + 1;
     }
   } catch (const LoadAbort &) {}
@@ -327,7 +329,162 @@ bool WindowsUsable(const WindowsOp &op)
   return op.size >= 1 && op.size <= lim && op.step <= lim;
 }
 
+// ---- bed, reg ------------------------------------------------------------------------------------------------------------------
+struct ConvertSpec { bool to_reg, compact, ucsc; std::string color; };
+
+// GenomicRegion::PrintBEDFormat (:1256-1274) appended to out.  (The reference's "exons cannot overlap!" behind the first check
+// cannot be reached: intervals that pass it do not overlap.)
+void RenderBedFormat(std::string &out, GenomicRegion *r, const std::string &color, bool convert_chromosome)
+{
+  if (!r->IsCompatibleSortedAndNonoverlapping()) r->PrintError("region intervals must be compatible, sorted and non-overlapping for this operation!");
+  char num[96];
+  const GenomicInterval *a = r->I.front(), *z = r->I.back();
+  if (convert_chromosome) { out += "chr"; out += strcmp(a->CHROMOSOME, "MT") == 0 ? "M" : a->CHROMOSOME; }   // PrintChromosome (:5968-5972)
+  else out += a->CHROMOSOME;
+  out.append(num, (size_t)snprintf(num, sizeof num, "\t%ld\t%ld\t", a->START - 1, z->STOP));
+  out += r->LABEL;
+  out.append(num, (size_t)snprintf(num, sizeof num, "\t%ld\t%c", 1000L, a->STRAND));
+  if (!color.empty() || r->I.size() > 1) {
+    out.append(num, (size_t)snprintf(num, sizeof num, "\t%ld\t%ld\t", a->START - 1, z->STOP));
+    out += color.empty() ? "0" : color;
+  }
+  if (r->I.size() > 1) {
+    out.append(num, (size_t)snprintf(num, sizeof num, "\t%lu\t", (unsigned long)r->I.size()));
+    for (size_t k = 0; k < r->I.size(); k++) out.append(num, (size_t)snprintf(num, sizeof num, "%ld%s", r->I[k]->STOP - r->I[k]->START + 1, k + 1 == r->I.size() ? "" : ","));
+    out += "\t0";
+    for (size_t k = 1; k < r->I.size(); k++) out.append(num, (size_t)snprintf(num, sizeof num, ",%ld", r->I[k]->START - a->START));
+  }
+  out += '\n';
+}
+
+// GenomicRegion::PrintREG (:961-971) appended to out: Print (:843-849) or, compact, the starts and the stops as two lists
+void RenderReg(std::string &out, GenomicRegion *r, bool compact)
+{
+  if (r->I.empty()) return;
+  char num[96];
+  const size_t n = r->I.size();
+  if (compact) {
+    for (size_t k = 1; k < n; k++)
+      if (strcmp(r->I[0]->CHROMOSOME, r->I[k]->CHROMOSOME) != 0 || r->I[0]->STRAND != r->I[k]->STRAND)
+        r->PrintError("region intervals must have the same chromosome/strand to perform conversion into compact REG format!");
+    out += r->LABEL; out += '\t'; out += r->I[0]->CHROMOSOME; out += ' '; out += r->I[0]->STRAND; out += ' ';
+    for (size_t k = 0; k < n; k++) out.append(num, (size_t)snprintf(num, sizeof num, "%ld%c", r->I[k]->START, k + 1 == n ? ' ' : ','));
+    for (size_t k = 0; k < n; k++) out.append(num, (size_t)snprintf(num, sizeof num, "%ld%s", r->I[k]->STOP, k + 1 == n ? "" : ","));
+    out += '\n';
+    return;
+  }
+  out += r->LABEL; out += '\t';
+  for (size_t k = 0; k < n; k++) {
+    out += r->I[k]->CHROMOSOME;
+    out.append(num, (size_t)snprintf(num, sizeof num, " %c %ld %ld", r->I[k]->STRAND, r->I[k]->START, r->I[k]->STOP));
+    if (k + 1 < n) out += ' ';
+  }
+  out += '\n';
+}
+
+// May the set's text go to the device?  Whatever its size, on one GPU, with a colour the device's constant piece holds
+bool ConvertUsable(const ConvertSpec &spec)
+{
+  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
+  if (gtx_group_size(devices) != 1) return false;
+  if (g_pool_future.valid()) g_pool_future.get();
+  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
+  int32_t max_color = 0;
+  gtx_convert_limits(NULL, NULL, &max_color);
+  return spec.color.size() <= (size_t)max_color;
+}
+
+// the set's text block by block through gtx_convert_text, the printed text to stdout in block order; a block that comes back is
+// rendered here, alone, and the next one goes to the device again
+void ConvertTextLoop(GenomicRegionSet *set, const ConvertSpec &spec, const Renderer &render)
+{
+  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
+  const std::string format = set->format;
+  const uint32_t fmt = format == "SAM" ? GTX_TEXT_SAM : format == "GFF" ? GTX_TEXT_GFF : 0u;
+  std::string first; long int first_no = 0;
+  LineSource *src = set->DetachStream(&first, &first_no);
+  if (first_no <= 0) return;
+  ChromTable chroms;
+  chroms.Freeze();
+  gtx_convert_op dev; memset(&dev, 0, sizeof dev);
+  dev.to = spec.to_reg ? GTX_CONVERT_REG : GTX_CONVERT_BED; dev.ucsc_names = spec.ucsc ? 1 : 0; dev.color = spec.to_reg ? NULL : spec.color.c_str();
+  PackOptions opt;
+  opt.chroms = &chroms; opt.sam = format == "SAM"; opt.gff = format == "GFF";
+  BedPacker packer(src, opt);
+  TextPump pump(packer, opt);
+  long int on_device = 0, came_back = 0;
+  char *out = NULL; size_t out_cap = 0;
+  pump.settle = [&](const TextPump::Block &b, int ticket) {
+    const size_t need = gtx_convert_max_bytes(b.bytes, b.n_lines, &dev);
+    if (need > out_cap) {
+      if (out) gtx_host_free(ctx, out);
+      out_cap = need + (need >> 3);
+      out = (char *)gtx_host_alloc(ctx, out_cap);
+      if (!out) DieGtx(ctx, GTX_E_HIP);
+    }
+    int redo = 0; size_t got = 0;
+    DieGtx(ctx, gtx_convert_result(ctx, ticket, &redo, out, out_cap, &got, NULL));
+    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render, format); }
+    else { on_device++; if (got) fwrite(out, 1, got, stdout); }
+    return true;
+  };
+  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
+    int ticket = -1;
+    DieGtx(ctx, gtx_convert_text(ctx, b.text, b.bytes, b.n_lines, &dev, fmt, &ticket));
+    return ticket;
+  };
+  // the line the set's constructor has read for its format check: a block of one line
+  first += '\n';
+  TextPump::Block &one = pump.blk[0];
+  one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
+  pump.Add(0);
+  pump.Run(1);
+  if (out) gtx_host_free(ctx, out);
+  fflush(stdout);
+  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx convert] blocks converted on the device: %ld, came back: %ld\n", on_device, came_back);
+}
+
+void RunConvert(GenomicRegionSet *set, const ConvertSpec &spec, const std::string &front)
+{
+  if (set->n_regions == 0) return;
+  if (set->format != "BED" && set->format != "SAM" && set->format != "GFF") set->PrintError("unsupported input format!\n");
+  if (set->load_in_memory) set->PrintError("the conversions stream their input on the MI355X path: open the set with load_in_memory = false!");
+  // a single-interval region on the device; everything the reference prints in more pieces than that, and every error, in the loop
+  const bool device = !TextPolicy().never && !(set->format == "BED" && !spec.to_reg) && ConvertUsable(spec);
+  if (!front.empty()) { StdoutIsOurs(); fwrite(front.data(), 1, front.size(), stdout); }
+  const Renderer render = [&spec](std::string &out, GenomicRegion *r, const std::string &) {
+    if (spec.to_reg) RenderReg(out, r, spec.compact); else RenderBedFormat(out, r, spec.color, spec.ucsc);
+    WriteOut(out, 1u << 22);
+  };
+  if (device) ConvertTextLoop(set, spec, render);
+  else HostLoop(set, render);
+}
+
 }  // namespace
+
+void GenomicRegion::PrintBEDFormat(char *color, bool convert_chromosome)
+{
+  std::string out;
+  RenderBedFormat(out, this, color ? color : "", convert_chromosome);
+  WriteOut(out);
+}
+
+void GenomicRegion::PrintREG(bool compact)
+{
+  std::string out;
+  RenderReg(out, this, compact);
+  WriteOut(out);
+}
+
+void GenomicRegionSet::RunConvertToBED(char *title, char *color, char *position, bool convert_chromosome)
+{
+  std::string front;                                              // (:3944-3945: in front of the first region of a set that has one)
+  if (position && strlen(position) > 0) { front += "browser position "; front += position; front += '\n'; }
+  if (title && strlen(title) > 0) { front += "track name='"; front += title; front += "' itemRgb=On visibility=1\n"; }
+  RunConvert(this, ConvertSpec{false, false, convert_chromosome, color ? color : ""}, front);
+}
+
+void GenomicRegionSet::RunConvertToREG(bool compact) { RunConvert(this, ConvertSpec{true, compact, false, ""}, ""); }
 
 void GenomicRegionSet::RunShiftPos(long int start_shift, long int stop_shift, bool strand_aware)
 {

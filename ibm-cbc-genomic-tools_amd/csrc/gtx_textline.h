@@ -1,6 +1,6 @@
 // gtx_textline.h -- the one predicate "GenomicRegionBED::Print would render this line as it stands" (see gtx_text.h), for the
-// kernels that write text out from text in: the subset's gather (gtx_text.hip), the column rewrite (gtx_rewrite.hip) and the sliding
-// windows (gtx_windows.hip); and the decimals the last two render.  Device code.
+// kernels that write text out from text in: the subset's gather (gtx_text.hip), the column rewrite (gtx_rewrite.hip), the sliding
+// windows (gtx_windows.hip) and the format conversion of BED lines (gtx_convert.hip); and the decimals the last three render.  Device code.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -133,6 +133,23 @@ class WindowsOp(ctypes.Structure):
         return o
 
 
+CONVERT_BED, CONVERT_REG = 0, 1                                                                       # gtx_convert_op.to
+
+
+class ConvertOp(ctypes.Structure):
+    """gtx_convert_op (include/gtx.h): the target format of genomic_convert, -chr and -c"""
+    _fields_ = [("to", ctypes.c_int32), ("ucsc_names", ctypes.c_int32), ("color", ctypes.c_char_p)]
+
+    @classmethod
+    def make(cls, to, ucsc_names=False, color=None):
+        """to: "bed" or "reg" (or the number as it goes to the library); color: bytes, str or None"""
+        o = cls()
+        o.to = {"bed": CONVERT_BED, "reg": CONVERT_REG}.get(to, to)
+        o.ucsc_names = int(bool(ucsc_names))
+        o.color = color.encode() if isinstance(color, str) else color
+        return o
+
+
 # name -> (restype, argtypes); must list every symbol include/gtx.h declares
 # int sink(void *user, const char *text, size_t bytes) of gtx_window_lines / gtx_pair_lines
 LINES_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
@@ -272,6 +289,10 @@ ABI = {
     "gtx_rewrite_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_rewrite_max_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int64]),
     "gtx_rewrite_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_convert_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "gtx_convert_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_convert_max_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p]),
+    "gtx_convert_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_windows_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_windows_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, LINES_SINK, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_windows_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -376,6 +397,14 @@ def rewrite_limits():
     t, b = ctypes.c_int32(), ctypes.c_int32()
     load().gtx_rewrite_limits(ctypes.byref(t), ctypes.byref(b))
     return int(t.value), int(b.value)
+
+
+def convert_limits():
+    """(tile, stage, max_color) of gtx_convert_limits: lines per tile of the conversion's passes; bytes of a tile's output that the
+    stage holds; the longest colour"""
+    t, b, m = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    load().gtx_convert_limits(ctypes.byref(t), ctypes.byref(b), ctypes.byref(m))
+    return int(t.value), int(b.value), int(m.value)
 
 
 def windows_limits():
@@ -558,6 +587,31 @@ class Engine:
                 collect(*tickets.pop(0))
             t = ctypes.c_int(-1)
             self._chk(self.lib.gtx_rewrite_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
+            tickets.append((text, t.value))
+        for x in tickets:
+            collect(*x)
+        return results
+
+    def convert_text(self, blocks, op, fmt=0, guard=64):
+        """gtx_convert_text / gtx_convert_result per block of text (bytes of complete lines; fmt: 0 for BED, TEXT_SAM or TEXT_GFF), two
+        blocks in flight: per block (needs_host, the printed text, the number of printed lines, whether the bytes behind the text's
+        16-byte unit were left alone).  out is gtx_convert_max_bytes long, rounded up to 16, with `guard` bytes of 0xA5 behind it:
+        the caller's buffer, not the device buffer the kernels store into."""
+        tickets, results = [], []
+
+        def collect(text, t):
+            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
+            cap = (int(self.lib.gtx_convert_max_bytes(len(text), text.count(b"\n"), ctypes.byref(op))) + 15) // 16 * 16
+            out = ctypes.create_string_buffer(b"\xa5" * (cap + guard), cap + guard)
+            self._chk(self.lib.gtx_convert_result(self.ctx, t, ctypes.byref(redo), out, cap, ctypes.byref(nb), ctypes.byref(ns)))
+            raw = out.raw
+            behind = (nb.value + 15) // 16 * 16
+            results.append((redo.value, raw[:nb.value], ns.value, raw[behind:] == b"\xa5" * (cap + guard - behind)))
+        for text in blocks:
+            if len(tickets) == 2:
+                collect(*tickets.pop(0))
+            t = ctypes.c_int(-1)
+            self._chk(self.lib.gtx_convert_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), int(fmt), ctypes.byref(t)))
             tickets.append((text, t.value))
         for x in tickets:
             collect(*x)

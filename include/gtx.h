@@ -628,6 +628,46 @@ int gtx_rewrite_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lin
 int gtx_rewrite_result(gtx_ctx *ctx, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed /* may be NULL */);
 size_t gtx_rewrite_max_bytes(size_t bytes, int64_t n_lines);
 int gtx_rewrite_limits(int32_t *tile, int32_t *stage);
+/* genomic_regions bed | reg on text (gtools/genomic_regions.cpp:710, :722; GenomicRegionSet::RunConvertToBED genomic_intervals.cpp
+ * :3940-3948, RunConvertToREG :4097-4103): a block of complete lines of BED (flags 0), SAM (GTX_TEXT_SAM) or GFF / GTF (GTX_TEXT_GFF)
+ * text without header lines goes to the device as for gtx_rewrite_text (same buffers contract, two blocks in flight, tickets in
+ * order) and every line is printed as a line of another format.  CHROM, START, STOP, STRAND and LABEL of a line are what the
+ * reference's readers give (:2771-2812 and :2870-2873, :3501-3517, :2157-2172): SAM -- RNAME, POS, POS + the CIGAR's reference length
+ * - 1 (as GTX_TEXT_SAM above states it; "*" counts as len(SEQ) M), '-' when FLAG & 0x10, QNAME; GFF -- columns 1, 4, 5, 7 and 9, "_"
+ * on an 8-column line; BED -- column 1, column 2 + 1, column 3, '-' when column 6 is "-", column 4 or "_" on a 3-column line.
+ *   GTX_CONVERT_BED   CHROM' TAB START-1 TAB STOP TAB LABEL TAB 1000 TAB STRAND [TAB START-1 TAB STOP TAB color] NL   (:1256-1274)
+ *                     the bracket when color is not empty; CHROM' is CHROM, under ucsc_names "chr" + CHROM with "MT" printed as
+ *                     "chrM" (:5968-5972); numbers are "%ld", so START-1 is -1 for a read with POS 0.  SAM and GFF text only: BED
+ *                     text is GTX_E_ARG (the reference prints a BED line through its own class, which is not converted here)
+ *   GTX_CONVERT_REG   LABEL TAB CHROM SP STRAND SP START SP STOP NL   (:961-971 over :843-849 and :344-347; the compact form of a
+ *                     single-interval region is the same bytes); ucsc_names and color are not read
+ * The track and browser lines in front of the first region (:3944-3945) are the caller's to print.  The lines the device takes are
+ * the tokenizer's plain case of the format, and for BED text those of gtx_rewrite_text; a block with ANY other line -- a spliced read,
+ * a '=' operation, a '.' strand, BED12 -- or with a tile of consecutive lines (gtx_convert_limits) whose output is longer than the
+ * stage, yields nothing: gtx_convert_result says needs_host with *out_bytes = 0 and the caller renders that block by its own means.
+ * GTX_E_ARG: both format flags, a flag that is neither, a `to` that is neither of the two, BED text with GTX_CONVERT_BED, a color
+ * longer than max_color of gtx_convert_limits.
+ * gtx_convert_result waits for the block of that ticket; out (capacity bytes of it) receives exactly *out_bytes bytes, the printed
+ * lines in order; *n_printed (may be NULL) their number, which is the block's.  A result larger than capacity is GTX_E_ARG and
+ * nothing is written.  The result of a ticket must be fetched before the block after next is added.
+ * gtx_convert_max_bytes(bytes, n_lines, op) always suffices.  A printed line holds its input line's chromosome and label, which are
+ * c and l bytes of that line, and beside them at most: bed -- 3 ("chr") + 1 + 10 + 1 + 10 + 1 + 6 ("\t1000\t") + 1 (strand) + 1
+ * (newline) = 34 bytes, one more where the label is the "_" the input does not hold (coordinates are below 2^31 - 2, so a number has
+ * at most 10 bytes, "-1" included), and with a color 1 + 10 + 1 + 10 + 1 = 23 and the color's bytes on top; reg -- 1 + 1 + 1 + 1 + 10
+ * + 1 + 10 + 1 = 26, one more for "_".  So the bound is bytes + n_lines * (35 [+ 23 + strlen(color)]).
+ * gtx_convert_limits: the lines per tile of the passes, the bytes of a tile's output that the stage holds, the longest color.
+ * Under gtx_profile_enable a gtx_convert_text call is bracketed as gtx_rewrite_text is (ms_stream_kernel: plan, prefix and emit). */
+#define GTX_CONVERT_BED 0
+#define GTX_CONVERT_REG 1
+typedef struct gtx_convert_op {
+  int32_t to;                                  /* GTX_CONVERT_BED | GTX_CONVERT_REG */
+  int32_t ucsc_names;                          /* -chr */
+  const char *color;                           /* NULL or "": none; at most gtx_convert_limits' max_color bytes, else GTX_E_ARG */
+} gtx_convert_op;
+int gtx_convert_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_convert_op *op, uint32_t flags, int *ticket);
+int gtx_convert_result(gtx_ctx *ctx, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed /* may be NULL */);
+size_t gtx_convert_max_bytes(size_t bytes, int64_t n_lines, const gtx_convert_op *op);
+int gtx_convert_limits(int32_t *tile, int32_t *stage, int32_t *max_color);
 /* The same in a group that holds all its members (between gtx_group_count_begin / gtx_group_coverage_begin and their _end): a block goes
  * to the members in turn, whatever the classes of its lines -- the read stream split evenly over members that each hold the whole
  * reference set (SURVEY 8(e)'s second partition) -- and a count call that took text blocks ends with the ncclReduce(sum) of the
