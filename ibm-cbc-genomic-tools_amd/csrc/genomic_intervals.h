@@ -212,6 +212,24 @@ class GenomicRegionSet
   // converted on the device: N, came back: K".
   void RunConvertToBED(char *title, char *color, char *position, bool convert_chromosome);
   void RunConvertToREG(bool compact = false);
+  // The reference's `split`, `connect`, `select`, `diff`, `n` and `strand` (genomic_intervals.cpp:4187-4193, :3999-4005, :4121-4127,
+  // :4011-4017, :4071-4078, :4350-4358 over GenomicRegionBED::RunSplit :2502-2505, GenomicRegion::Connect :1319-1339, Select :1493-1521,
+  // Diff :1345-1361, RunSize :1451-1454, ModifyStrand :1607-1620, with UpdateThick and Print) on a streamed BED set: the operations
+  // that look inside a 12-column line.  Same output and errors; RunModifyStrand has no `sorted` argument (the reference's temp-file
+  // merge is not offered), and a strand_op that is none of "+", "-", "r" changes nothing, as the reference's unsorted driver has it.
+  // Two conventions of this build where the reference prints an unset member: a 3-column line has the label "_", a line of fewer
+  // than 5 columns the score 0 (RunSplit and RunSize print them).  MI355X path: whenever a device is usable, whatever the input's
+  // size, the text goes to the device block by block (gtx_blocks_text, include/gtx.h, which has the plain line) and the printed
+  // lines are streamed to stdout (gtx_blocks_result); a block with a line the device does not take -- 7 to 11 columns, blanks as
+  // separators, a '.' strand, overlapping or unsorted blocks, an input error -- comes back and is rendered by the host loop alone,
+  // with its own line numbers.  GTX_TEXT_ON_DEVICE=0 keeps the host loop and looks for no device.  GTX_TEXT_TRACE=1 reports
+  // "[gtx blocks] blocks rendered on the device: N, came back: K".
+  void RunSplit(bool by_chrom_and_strand = false);
+  void RunConnect();
+  void RunSelect(bool first, bool last, bool from5p, bool from3p);
+  void RunDiff();
+  void RunSize();
+  void RunModifyStrand(const char *strand_op);
 
   // MI355X path: hands the not yet consumed part of a streaming set (the current region's raw
   // line first) to the bulk packer.  After this call Get()/Next() report the end of the set.

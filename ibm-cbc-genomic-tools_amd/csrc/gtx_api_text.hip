@@ -27,6 +27,7 @@ enum TextMode { TEXT_COUNT, TEXT_COVER, TEXT_SCAN };
 
 // A block of text into the slot whose turn it is, and tokenised there (launch_tokenize enqueued on the context's stream): the front
 // of add_text and gtx_subset_text.  grouped: the strand-aware outputs (tri2 / w2) are made too when the rules are strand-aware.
+// format: launch_tokenize's number, or -1 for the newline index alone (launch_newline_index; gtx_api_blocks.hip).
 // *tp = the slot, *ticket its number; *empty: a block without lines -- nothing was enqueued but the slot's evParsed, its verdict is 0.
 int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, bool grouped, int scanRules,
                unsigned long long *labelSum, int format, TextSlot **tp, int *ticket, bool *empty)
@@ -89,6 +90,10 @@ int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const
   HIPCHK(c, hipEventRecord(t.evCopied, c->stage.copyStream));
   HIPCHK(c, hipStreamWaitEvent(c->stream, t.evCopied, 0));
   HIPCHK(c, hipMemsetAsync(t.flag.get(), 0, sizeof(int), c->stream));
+  if (format < 0) {                                                        // the newline index alone (gtx_blocks_text reads the text itself)
+    HIPCHK(c, gtxtext::launch_newline_index(t.text.get(), bytes, t.seg.get(), t.nl.get(), (unsigned)nLines, c->stream));
+    return GTX_OK;
+  }
   grouped = grouped && r->strand_aware;
   if (grouped && (size_t)nLines > t.w2.cap) {
     t.tri2.reset(); t.blk.reset(); t.w2.reset();

@@ -18,7 +18,7 @@
 #include "gtx_adjacent.h"
 #include "gtx_internal.h"
 
-namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; struct WindowsRec; struct ConvertRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h, gtx_windows.h, gtx_convert.h: held here by pointer only)
+namespace gtx { struct JoinInfo; struct SignalInfo; struct RewriteRec; struct WindowsRec; struct ConvertRec; struct BlocksRec; }   // (gtx_join.h, gtx_signal.h, gtx_rewrite.h, gtx_windows.h, gtx_convert.h, gtx_blocks.h: held here by pointer only)
 
 #pragma GCC visibility push(hidden)
 
@@ -167,6 +167,11 @@ struct TextSlot {
   // gtx_convert_text: the lines' records, the tiles' bytes and their prefix (`out` and `hostTotal` as for the subset); whether the
   // slot holds a converted block whose result has not been fetched
   DevBuf<gtx::ConvertRec> cvRec; DevBuf<unsigned> cvTile; DevBuf<long long> cvBase; bool convertPending = false;
+  // gtx_blocks_text: the lines' records, the tiles' bytes | printed lines and their prefixes, split's bases of the lines (printed
+  // lines; bytes); what gtx_blocks_result needs of the call to render the block (`hostTotal`: the block's bytes and printed lines);
+  // whether the slot holds a planned block whose result has not been fetched
+  DevBuf<gtx::BlocksRec> blRec; DevBuf<unsigned> blTile, blLineOut; DevBuf<long long> blBase, blLineByte; bool blocksPending = false;
+  int blKind = 0, blSelect = 0, blStrand = 0; size_t blBytes = 0; unsigned blLines = 0;
 };
 
 // What a device call found, on its way to the caller's struct: the info block the kernels write, its page-locked copy, and the
@@ -297,6 +302,8 @@ struct TextState {
   // copies, the ranges' bytes on the device and on the host
   DevBuf<char> wnOut[2]; PinBuf<char> wnPin[2]; hipEvent_t wnCopied[2] = {nullptr, nullptr};
   DevBuf<unsigned long long> wnRange; PinBuf<unsigned long long> wnHostRange;
+  // gtx_blocks_result: the printed text of the block being fetched, on the device and page-locked
+  DevBuf<char> blOut; PinBuf<char> blPin;
   ~TextState() { for (int k = 0; k < 2; k++) if (wnCopied[k]) (void)hipEventDestroy(wnCopied[k]); }
 };
 

@@ -59,6 +59,19 @@ void PrintBed(std::string &out, const PairQuery &q, const std::vector<long int> 
 void WriteOut(std::string &out, size_t above = 0);                // the text so far to stdout once it is longer than `above`
 void ExitOnLoadError(const LoadError &err);                       // the error a loop stopped at, as the reference prints it (after the output before it)
 
+// ---- gtx_host_regionops.cpp: what the drivers that print a line per region share (with gtx_host_blocks.cpp) ------------------
+void UpdateThick(PairQuery &q);                                   // GenomicRegionBED::UpdateThick (:2326-2333)
+// GenomicRegionBED::Print (:2188-2218) of the region as it is now, appended to out; "exons cannot overlap!" ends the run behind the
+// half-printed line
+void Print(std::string &out, const PairQuery &q, long int n_line);
+// what a loop does with one region and its raw line: its output appended to `out`
+typedef std::function<void(std::string &out, GenomicRegion *r, const std::string &raw)> Renderer;
+// the host loop over what is left of the set, region by region; an input error ends it behind the output in front of the line
+void HostLoop(GenomicRegionSet *set, const Renderer &render);
+// the same for the lines of one block of text that came back from the device, with their own line numbers
+void HostBlock(const char *text, size_t bytes, long int first_line, const Renderer &render, const std::string &format = "BED");
+int WriteSink(void *user, const char *text, size_t bytes);       // a gtx_lines_sink that writes to the FILE * in `user`
+
 // ---- gtx_host_device.cpp: the GPU context shared by the classes, the page-locked pool, the hand-over ------------------------
 inline void Mark(const char *what) { GtxMark(what); }
 void GtxWarmUp();                                                 // HIP start-up on its own thread, from the first region set on

@@ -38,14 +38,18 @@ void Fix(std::vector<long int> &iv)
   iv.resize(w);
 }
 
+}  // namespace
+
 // GenomicRegionBED::UpdateThick (:2326-2333)
-void UpdateThick(PairQuery &q)
+void gtx_host::UpdateThick(PairQuery &q)
 {
   if (q.iv.empty()) return;
   q.thick_start = std::max(q.thick_start, q.iv.front() - 1);
   q.thick_end = std::min(q.thick_end, q.iv.back());
   if (q.thick_end <= q.thick_start) q.thick_start = q.thick_end = q.iv.front() - 1;
 }
+
+namespace {
 
 // the operation on a region as GenomicRegionBED's members apply it (:2340-2480 over :524-568, :1280-1301); false: nothing is printed
 bool Apply(const RegionOp &op, PairQuery &q)
@@ -92,9 +96,11 @@ bool Apply(const RegionOp &op, PairQuery &q)
   return !iv.empty();
 }
 
+}  // namespace
+
 // GenomicRegionBED::Print (:2188-2218) of the region as it is now.  A 12-column region whose blocks overlap ends the run in the
 // middle of its line, as the reference's does (:2207)
-void Print(std::string &out, const PairQuery &q, long int n_line)
+void gtx_host::Print(std::string &out, const PairQuery &q, long int n_line)
 {
   const size_t at = out.size();
   PrintBed(out, q, q.iv, q.label, q.score, q.thick_start, q.thick_end);
@@ -110,6 +116,8 @@ void Print(std::string &out, const PairQuery &q, long int n_line)
   }
 }
 
+namespace {
+
 // one region through the operation and out
 void Render(std::string &out, const RegionOp &op, GenomicRegion *r, const std::string &raw)
 {
@@ -118,12 +126,11 @@ void Render(std::string &out, const RegionOp &op, GenomicRegion *r, const std::s
   WriteOut(out, 1u << 22);
 }
 
-// what a loop does with one region and its raw line: its output appended to `out`
-typedef std::function<void(std::string &out, GenomicRegion *r, const std::string &raw)> Renderer;
+}  // namespace
 
 // the host loop over what is left of the set, region by region with the reference's print; an input error ends it behind the
 // output in front of the line
-void HostLoop(GenomicRegionSet *set, const Renderer &render)
+void gtx_host::HostLoop(GenomicRegionSet *set, const Renderer &render)
 {
   std::string out;
   LoadError err;
@@ -137,7 +144,7 @@ void HostLoop(GenomicRegionSet *set, const Renderer &render)
 }
 
 // the same for the lines of one block of text that came back from the device, with their own line numbers
-void HostBlock(const char *text, size_t bytes, long int first_line, const Renderer &render, const std::string &format = "BED")
+void gtx_host::HostBlock(const char *text, size_t bytes, long int first_line, const Renderer &render, const std::string &format)
 {
   std::string out, raw, line;
   LoadError err;
@@ -158,6 +165,8 @@ void HostBlock(const char *text, size_t bytes, long int first_line, const Render
   WriteOut(out);
   if (err.set) ExitOnLoadError(err);
 }
+
+namespace {
 
 // May the set's text go to the device as it is?  A streamed BED file, stdin or .gz (a regular file: of 32 MB or more, or
 // GTX_TEXT_ON_DEVICE=1; never with GTX_TEXT_ON_DEVICE=0), on one GPU, amounts the device's arithmetic takes
@@ -276,7 +285,11 @@ void RenderWindows(std::string &out, const WindowsOp &op, GenomicRegion *r, cons
   }
 }
 
-int WriteSink(void *user, const char *text, size_t bytes) { return fwrite(text, 1, bytes, (FILE *)user) == bytes ? 0 : 1; }
+}  // namespace
+
+int gtx_host::WriteSink(void *user, const char *text, size_t bytes) { return fwrite(text, 1, bytes, (FILE *)user) == bytes ? 0 : 1; }
+
+namespace {
 
 // the set's text block by block through gtx_windows_text; gtx_windows_result streams a block's windows to stdout, in block order.  A
 // block that comes back is rendered here, alone, and the next one goes to the device again

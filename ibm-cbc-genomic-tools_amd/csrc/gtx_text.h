@@ -24,6 +24,9 @@ struct TextTables {               // per reference set: hash table of the chromo
 // stop <= 0 is skipped silently, genomic_intervals.cpp:5039), 2 = the sorted scanner's (nothing about the interval is checked; order as sorted_rules)
 // format: 0 = the lines are BED, 1 = SAM alignments (GTX_TEXT_SAM), 2 = GFF / GTF features (GTX_TEXT_GFF)
 hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules = 0, int format = 0);
+// the first step of launch_tokenize on its own, for the passes that read the text themselves (gtx_blocks.h): nl[k] = the offset of
+// newline k for k < nLines, segCount [bytes / 1024 + 2] its scratch; segCount[(bytes + 1023) / 1024] = the newlines the text holds
+hipError_t launch_newline_index(const char *text, size_t bytes, unsigned *segCount, unsigned *nl, unsigned nLines, hipStream_t st);
 void build_tables(const gtx_text_rules &r, std::vector<int32_t> *table, unsigned *mask, std::string *blob);
 
 // ---- gtx_subset_text: the lines of a tokenised block that are kept, byte for byte ----

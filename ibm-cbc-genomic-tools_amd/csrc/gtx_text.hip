@@ -510,12 +510,20 @@ __global__ __launch_bounds__(256) void text_void_kernel(int *__restrict__ tri, u
   for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < nLines; j += (size_t)gridDim.x * 256) tri[3 * j] = -1;
 }
 
+hipError_t launch_newline_index(const char *text, size_t bytes, unsigned *segCount, unsigned *nl, unsigned nLines, hipStream_t st)
+{
+  const unsigned nSeg = (unsigned)((bytes + kSeg - 1) / kSeg);
+  nl_count_kernel<<<nSeg, 64, 0, st>>>(text, bytes, segCount);
+  nl_scan_kernel<<<1, 1024, 0, st>>>(segCount, nSeg);
+  nl_write_kernel<<<nSeg, 64, 0, st>>>(text, bytes, segCount, nl, nLines);
+  return hipGetLastError();
+}
+
 hipError_t launch_tokenize(const TextDevice &d, const TextTables &t, const gtx_text_rules &r, size_t bytes, unsigned nLines, hipStream_t st, int scanRules, int format)
 {
   const unsigned nSeg = (unsigned)((bytes + kSeg - 1) / kSeg);
-  nl_count_kernel<<<nSeg, 64, 0, st>>>(d.text, bytes, d.segCount);
-  nl_scan_kernel<<<1, 1024, 0, st>>>(d.segCount, nSeg);
-  nl_write_kernel<<<nSeg, 64, 0, st>>>(d.text, bytes, d.segCount, d.nl, nLines);
+  const hipError_t ei = launch_newline_index(d.text, bytes, d.segCount, d.nl, nLines, st);
+  if (ei != hipSuccess) return ei;
   ParseArgs a;
   a.text = d.text; a.bytes = bytes; a.nl = d.nl; a.nLines = nLines;
   a.segTotal = d.segCount + nSeg; a.table = (const ChromEntry *)t.table; a.tableMask = t.tableMask; a.names = t.names;

@@ -133,7 +133,26 @@ class WindowsOp(ctypes.Structure):
         return o
 
 
-CONVERT_BED, CONVERT_REG = 0, 1                                                                       # gtx_convert_op.to
+BLOCKS_KINDS = {"split": 0, "connect": 1, "select": 2, "diff": 3, "n": 4, "strand": 5}                # gtx_blocks_op.kind
+BLOCKS_FIRST, BLOCKS_LAST, BLOCKS_5P, BLOCKS_3P = 1, 2, 4, 8                                          # gtx_blocks_op.select
+BLOCKS_STRAND_OPS = {"+": 0, "-": 1, "r": 2}                                                          # gtx_blocks_op.strand_op
+
+
+class BlocksOp(ctypes.Structure):
+    """gtx_blocks_op (include/gtx.h): one of genomic_blocks' six operations, select's flags, strand's -op"""
+    _fields_ = [("kind", ctypes.c_int32), ("select", ctypes.c_int32), ("strand_op", ctypes.c_int32)]
+
+    @classmethod
+    def make(cls, kind, select=0, strand_op="+"):
+        """kind: a word of BLOCKS_KINDS; strand_op: "+", "-" or "r" (either may be the number as it goes to the library)"""
+        o = cls()
+        o.kind = BLOCKS_KINDS.get(kind, kind)
+        o.select = int(select)
+        o.strand_op = BLOCKS_STRAND_OPS.get(strand_op, strand_op)
+        return o
+
+
+CONVERT_BED, CONVERT_REG = 0, 1                                                                      # gtx_convert_op.to
 
 
 class ConvertOp(ctypes.Structure):
@@ -296,6 +315,10 @@ ABI = {
     "gtx_windows_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_windows_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, LINES_SINK, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_windows_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_blocks_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_blocks_result": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, LINES_SINK, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gtx_blocks_max_bytes": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p]),
+    "gtx_blocks_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_ref_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "gtx_set_join_buffer": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "gtx_join": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
@@ -404,6 +427,14 @@ def convert_limits():
     stage holds; the longest colour"""
     t, b, m = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     load().gtx_convert_limits(ctypes.byref(t), ctypes.byref(b), ctypes.byref(m))
+    return int(t.value), int(b.value), int(m.value)
+
+
+def blocks_limits():
+    """(tile, stage, max_blocks) of gtx_blocks_limits: lines per tile of the block operations' plan and one-line emit; bytes of such
+    a tile's output that the stage holds; the blocks of a plain 12-column line"""
+    t, b, m = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    load().gtx_blocks_limits(ctypes.byref(t), ctypes.byref(b), ctypes.byref(m))
     return int(t.value), int(b.value), int(m.value)
 
 
@@ -615,6 +646,35 @@ class Engine:
             tickets.append((text, t.value))
         for x in tickets:
             collect(*x)
+        return results
+
+    def blocks_text(self, blocks, op, chunk=None):
+        """gtx_blocks_text / gtx_blocks_result per block of text (bytes of complete lines), two blocks in flight: per block
+        (needs_host, the printed text, the number of printed lines, the number of sink calls).  chunk: gtx_set_lines_chunk first."""
+        if chunk is not None:
+            self.set_lines_chunk(chunk)
+        tickets, results = [], []
+
+        def collect(t):
+            parts = []
+
+            def take(user, p, n):
+                parts.append(ctypes.string_at(p, n))
+                return 0
+            redo, np_, nb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+            self._chk(self.lib.gtx_blocks_result(self.ctx, t, ctypes.byref(redo), LINES_SINK(take), None, ctypes.byref(np_), ctypes.byref(nb)))
+            out = b"".join(parts)
+            if nb.value != len(out):
+                raise GtxError("gtx_blocks_result: n_bytes %d, the sink was given %d" % (nb.value, len(out)))
+            results.append((redo.value, out, np_.value, len(parts)))
+        for text in blocks:
+            if len(tickets) == 2:
+                collect(tickets.pop(0))
+            t = ctypes.c_int(-1)
+            self._chk(self.lib.gtx_blocks_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
+            tickets.append(t.value)
+        while tickets:
+            collect(tickets.pop(0))
         return results
 
     def windows_text(self, blocks, op, chunk=None, refuse_at=None):

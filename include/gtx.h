@@ -942,6 +942,77 @@ int gtx_windows_result(gtx_ctx *ctx, int ticket, int *needs_host, gtx_lines_sink
                        int64_t *n_bytes /* may be NULL */);
 int gtx_windows_limits(int32_t *line_tile, int32_t *out_tile, int32_t *max_fixed);
 
+/* genomic_regions split | connect | select | diff | n | strand on text (gtools/genomic_regions.cpp:715-716, :721, :728, :732-733): the
+ * per-region operations that look inside a region's intervals, which for BED text means inside a 12-column line (a transcript with
+ * its exons, a spliced read).  A block of complete BED lines without header lines goes to the device as for gtx_rewrite_text (same
+ * buffers contract, two blocks in flight, tickets in order).  With START-1 = column 2, STOP = column 3 and, on a 12-column line,
+ * block k at (START-1 + starts[k], START-1 + starts[k] + sizes[k]] (genomic_intervals.cpp:2157-2182):
+ *   GTX_BLOCKS_SPLIT    one line per block through the BED PrintModified (:2502-2505, :2310-2314): CHROM TAB the block's START-1 TAB
+ *                       its STOP TAB LABEL TAB SCORE TAB STRAND NL.  Always six columns
+ *   GTX_BLOCKS_CONNECT  Connect (:1319-1339: one interval from the least start to the greatest stop), UpdateThick (:2326-2333), Print
+ *                       (:2188-2218): a 12-column line ends in 1 TAB STOP - (START-1) TAB 0
+ *   GTX_BLOCKS_SELECT   Select (:1493-1521) by `select`, bits GTX_BLOCKS_FIRST | LAST | 5P | 3P (5P is the first block on '+' and the
+ *                       last on '-', 3P the reverse); UpdateThick; Print.  No bit: nothing is printed.  Both ends: 1 and 2 blocks stay,
+ *                       3 or more keep the first and the last.  A line of 3 to 6 columns is its one interval
+ *   GTX_BLOCKS_DIFF     Diff (:1345-1361): the gaps between successive blocks as the region's blocks; UpdateThick; Print.  A single
+ *                       block, and blocks that all touch, print nothing
+ *   GTX_BLOCKS_SIZE     `n` (:1451-1454): LABEL TAB the sum of the blocks' sizes NL, 0 for an interval with start > stop
+ *   GTX_BLOCKS_STRAND   ModifyStrand (:1607-1620) by strand_op, GTX_BLOCKS_STRAND_PLUS | MINUS | REVERSE; Print.  A line of fewer than 6
+ *                       columns has no column to print the strand into and is printed as it stands
+ * Two conventions of this build (the reference prints an unset member there): a 3-column line has the label "_", a line of fewer than
+ * 5 columns the score 0 -- where split and n print them.
+ * The plain line, which is all the device takes, is one of two kinds.
+ * (a) 3 to 6 columns: plain exactly when gtx_rewrite_text calls it plain (above).
+ * (b) exactly 12 tab-separated tokens, none empty or holding a byte <= ' '; columns 2, 3, 7, 8 and 10 canonical decimals ("0", or no
+ *     leading zero; at most 10 digits); column 5 a canonical long of at most 18 digits; column 6 exactly "+" or "-"; column 10 in
+ *     1 .. max_blocks (gtx_blocks_limits: 1024); columns 11 and 12 lists of exactly that many canonical decimals separated by single
+ *     commas, with or without one trailing comma; every size >= 1; the first block starts at 0 and the last one ends at column 3 (a
+ *     line that does not say so is well defined by Print, but is left to the caller's loop: what Print makes of it is not what the
+ *     line holds); every block starts at or behind the end of the block before it (touching blocks are plain, overlapping and
+ *     out-of-order ones are not); every coordinate, columns 7 and 8 and the blocks' stops included, below 2^31 - 2.
+ * A block with ANY other line -- 7 to 11 columns, blanks as separators, a '.' / '1' / '-1' strand, a count that disagrees with its
+ * lists, an input error --, with a line that prints more than 2^25 bytes, or, for the five operations that print one line per line,
+ * with a tile of consecutive lines (gtx_blocks_limits) whose output is longer than the stage, comes back: gtx_blocks_result says
+ * needs_host, calls no sink and reports zero totals, and the caller renders that block by its own means.  split has no such stage.
+ * GTX_E_ARG: a kind that is none of the six, select bits outside the four, a strand_op outside the three.
+ * gtx_blocks_text copies the block in and enqueues the newline index (the tokenizer is not run: it calls a 12-column line not plain)
+ * and the plan of the lines with its prefixes.  gtx_blocks_result waits for the plan, renders the block and hands the printed lines,
+ * in order, to `sink` in calls of at most gtx_set_lines_chunk bytes that end at a line's end; a block that prints nothing (an empty
+ * block; select without a bit) makes no call (sink may then be NULL).  A sink that returns non-zero ends the call with GTX_E_SINK;
+ * the block is dropped and the context stays usable.  *n_printed and *n_bytes (either may be NULL) are the block's totals.  The result
+ * of a ticket must be fetched before the block after next is added.
+ * gtx_blocks_max_bytes: a bound on a block's printed bytes for the five operations that print one line per line -- a line's copied
+ * columns are its own bytes, and beside them stand at most six rendered coordinates, a count and two fresh list elements of at most
+ * 11 bytes for every block of the line, each of which took at least 4 bytes of its input: 7 * bytes + 96 * n_lines.  split prints a
+ * line's chromosome and label once per block and has no bound in the block's size: 0, and the plan's own total is what there is.
+ * gtx_blocks_limits: the lines per tile of the plan and of the one-line emit, the bytes of such a tile's output that the stage holds,
+ * the blocks of a plain line.
+ * Under gtx_profile_enable a gtx_blocks_text call is bracketed as gtx_convert_text is (ms_stream_kernel: the plan and its prefixes alone
+ * on text that is already in HBM behind its newline index), and the emit launch of gtx_blocks_result is a profiled call of its own. */
+#define GTX_BLOCKS_SPLIT   0
+#define GTX_BLOCKS_CONNECT 1
+#define GTX_BLOCKS_SELECT  2
+#define GTX_BLOCKS_DIFF    3
+#define GTX_BLOCKS_SIZE    4
+#define GTX_BLOCKS_STRAND  5
+#define GTX_BLOCKS_FIRST 1
+#define GTX_BLOCKS_LAST  2
+#define GTX_BLOCKS_5P    4
+#define GTX_BLOCKS_3P    8
+#define GTX_BLOCKS_STRAND_PLUS    0
+#define GTX_BLOCKS_STRAND_MINUS   1
+#define GTX_BLOCKS_STRAND_REVERSE 2
+typedef struct gtx_blocks_op {
+  int32_t kind;                                /* GTX_BLOCKS_SPLIT .. GTX_BLOCKS_STRAND */
+  int32_t select;                              /* GTX_BLOCKS_SELECT: bits GTX_BLOCKS_FIRST | LAST | 5P | 3P */
+  int32_t strand_op;                           /* GTX_BLOCKS_STRAND: GTX_BLOCKS_STRAND_PLUS | MINUS | REVERSE */
+} gtx_blocks_op;
+int gtx_blocks_text(gtx_ctx *ctx, const char *text, size_t bytes, int64_t n_lines, const gtx_blocks_op *op, int *ticket);
+int gtx_blocks_result(gtx_ctx *ctx, int ticket, int *needs_host, gtx_lines_sink sink, void *user, int64_t *n_printed /* may be NULL */,
+                      int64_t *n_bytes /* may be NULL */);
+size_t gtx_blocks_max_bytes(size_t bytes, int64_t n_lines, const gtx_blocks_op *op);
+int gtx_blocks_limits(int32_t *tile, int32_t *stage, int32_t *max_blocks);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 /* on = 1: every *_device call brackets its dominant kernel and the whole call with HIP events on the
