@@ -1,6 +1,6 @@
 // gtx_api_blocks.hip -- the C ABI's block operations on region text (gtx_blocks_*): split, connect, select, diff, n and strand of
 // BED lines, the 12-column ones included.  Host code only (the kernels: gtx_blocks.hip, and gtx_text.hip for the newline index); the
-// text reaches the device through text_stage of gtx_api_text.hip, the context is in gtx_ctx.h.
+// text reaches the device through text_stage of gtx_api_text.hip behind the handshake of gtx_api_textblock.h, the context is in gtx_ctx.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -8,6 +8,7 @@
 #include "gtx.h"
 #include "gtx_blocks.h"
 #include "gtx_ctx.h"
+#include "gtx_api_textblock.h"
 
 // the passes' view of a slot whose block gtx_blocks_text has planned (gtx_blocks.h)
 static gtx::BlocksDevice blocks_device(const TextSlot &t)
@@ -25,18 +26,13 @@ extern "C" {
 int gtx_blocks_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_blocks_op *op, int *ticket)
 {
   if (!c) return GTX_E_ARG;
-  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || op->kind < GTX_BLOCKS_SPLIT || op->kind > GTX_BLOCKS_STRAND ||
-      (op->select & ~(GTX_BLOCKS_FIRST | GTX_BLOCKS_LAST | GTX_BLOCKS_5P | GTX_BLOCKS_3P)) || op->strand_op < GTX_BLOCKS_STRAND_PLUS || op->strand_op > GTX_BLOCKS_STRAND_REVERSE)
+  if (!op || op->kind < GTX_BLOCKS_SPLIT || op->kind > GTX_BLOCKS_STRAND || (op->select & ~(GTX_BLOCKS_FIRST | GTX_BLOCKS_LAST | GTX_BLOCKS_5P | GTX_BLOCKS_3P)) ||
+      op->strand_op < GTX_BLOCKS_STRAND_PLUS || op->strand_op > GTX_BLOCKS_STRAND_REVERSE)
     return fail(c, GTX_E_ARG, "gtx_blocks_text: bad argument");
-  if (c->text.slot[c->text.seq & 1].blocksPending) return fail(c, GTX_E_STATE, "gtx_blocks_text: the result of the block before last has not been fetched (gtx_blocks_result)");
-  gtx_text_rules r; memset(&r, 0, sizeof r);
-  r.max_label_value = 1;
   TextSlot *tp = nullptr; bool empty = false;
-  { int rc = text_stage(c, text, bytes, nLines, &r, false, 0, nullptr, -1, &tp, ticket, &empty); if (rc) return rc; }
+  // (format -1: the newline index alone, the passes read the text themselves)
+  { int rc = textblock_front(c, "blocks", TEXT_BLOCKS, text, bytes, nLines, ticket, nullptr, 0, -1, &tp, &empty); if (rc) return rc; }
   TextSlot &t = *tp;
-  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
-  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
-  t.blocksPending = true;
   t.blKind = op->kind; t.blSelect = op->select; t.blStrand = op->strand_op; t.blBytes = bytes; t.blLines = (unsigned)nLines;
   if (empty) { t.blLines = 0; return GTX_OK; }
   const size_t nTiles = gtx::blocks_tiles((unsigned)nLines);
@@ -48,29 +44,18 @@ int gtx_blocks_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, 
   prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and base launches alone, on the text where it is)
   HIPCHK(c, prof_mark(c, 1, c->stream));
   HIPCHK(c, gtx::launch_blocks_plan(d, k, c->stream));
-  HIPCHK(c, prof_mark(c, 2, c->stream));
-  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], d.baseCount + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, prof_end(c, c->stream));
-  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
-  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
-  t.busy = true;
-  return GTX_OK;
+  return textblock_tail(c, t, d.baseBytes + nTiles, d.baseCount + nTiles);
 }
 
 // The block's printed text: rendered into one device buffer, copied into one page-locked buffer, handed to the sink in pieces that
 // end at a line's end.  The emit launch follows whatever the stream already holds of the block behind this one.
 int gtx_blocks_result(gtx_ctx *c, int ticket, int *needs_host, gtx_lines_sink sink, void *user, int64_t *n_printed, int64_t *n_bytes)
 {
-  if (!c || !needs_host || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_blocks_result: bad argument") : GTX_E_ARG;
-  TextSlot &t = c->text.slot[ticket];
+  if (!c) return GTX_E_ARG;
+  TextSlot *tp = nullptr;
+  { int rc = textblock_result(c, "blocks", TEXT_BLOCKS, ticket, needs_host, true, &tp); if (rc) return rc; }
+  TextSlot &t = *tp;
   TextState &s = c->text;
-  if (!t.evParsed || !t.blocksPending) return fail(c, GTX_E_STATE, "gtx_blocks_result: no such block");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(t.evParsed));
-  t.blocksPending = false;
-  *needs_host = *t.hostFlag.get();
   if (n_printed) *n_printed = 0;
   if (n_bytes) *n_bytes = 0;
   if (*needs_host || t.blLines == 0) return GTX_OK;

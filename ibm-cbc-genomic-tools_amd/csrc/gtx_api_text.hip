@@ -2,7 +2,7 @@
 // where the triples are (gtx_*_add_text), the subset of a block's lines by their hits (gtx_subset_*), their columns rewritten
 // (gtx_rewrite_*), their sliding windows (gtx_windows_*) and their conversion to BED or REG lines (gtx_convert_*).  Host code only
 // (the kernels: gtx_text.hip, gtx_rewrite.hip, gtx_windows.hip, gtx_convert.hip); the context and the helpers shared with the other
-// families are in gtx_ctx.h.
+// families are in gtx_ctx.h, the handshake of the entry points that hand text back under a ticket in gtx_api_textblock.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -19,6 +19,7 @@
 #include "gtx_windows.h"
 #include "gtx_convert.h"
 #include "gtx_ctx.h"
+#include "gtx_api_textblock.h"
 
 // ---------------------------------------------------------------------------------------------
 // region text tokenised on the device (gtx_text.hip)
@@ -166,6 +167,29 @@ static gtx::WindowsDevice windows_device(const TextSlot &t)
   return d;
 }
 
+// gtx_subset_result, gtx_rewrite_result, gtx_convert_result: the block's verdict and, of a block that stayed on the device, the
+// hostTotal[0] bytes of its printed text copied to out, which holds `capacity` (SIZE_MAX: the entry point has no such argument), and
+// its hostTotal[1] lines.  On the copy stream: the context's own may already hold the kernels of the block after this one
+static int text_out_result(gtx_ctx *c, const char *name, TextPending family, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_lines)
+{
+  TextSlot *tp = nullptr;
+  { int rc = textblock_result(c, name, family, ticket, needs_host, out_bytes != nullptr, &tp); if (rc) return rc; }
+  TextSlot &t = *tp;
+  *out_bytes = 0;
+  if (n_lines) *n_lines = 0;
+  if (*needs_host) return GTX_OK;
+  const size_t n = (size_t)t.hostTotal.get()[0];
+  if (n > 0 && (!out || n > capacity)) {
+    const std::string who = std::string("gtx_") + name;
+    c->err = capacity == SIZE_MAX ? who + "_result: bad argument" : who + "_result: out is missing or smaller than the block's text (" + who + "_max_bytes)";
+    return GTX_E_ARG;
+  }
+  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
+  *out_bytes = n;
+  if (n_lines) *n_lines = (int64_t)t.hostTotal.get()[1];
+  return GTX_OK;
+}
+
 extern "C" {
 int gtx_count_add_text(gtx_ctx *c, const char *text, size_t bytes, int64_t n_lines, const gtx_text_rules *rules, uint32_t flags, int *ticket)
 { return c ? add_text(c, TEXT_COUNT, text, bytes, n_lines, rules, flags, ticket) : GTX_E_ARG; }
@@ -190,19 +214,13 @@ int gtx_subset_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, 
 {
   if (!c) return GTX_E_ARG;
   if (c->nRefs < 0) return fail(c, GTX_E_STATE, "gtx_subset_text: gtx_set_refs has not been called");
-  if (!text || !r || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names) ||
-      (flags & (GTX_TEXT_SAM | GTX_TEXT_GFF)) || r->max_label_value > 1)
+  if (!r || r->n_chrom < 0 || (r->n_chrom > 0 && !r->chrom_names) || (flags & (GTX_TEXT_SAM | GTX_TEXT_GFF)) || r->max_label_value > 1)
     return fail(c, GTX_E_ARG, "gtx_subset_text: bad argument");
-  if (c->text.slot[c->text.seq & 1].subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_text: the result of the block before last has not been fetched (gtx_subset_result)");
   const int mode = join_mode(c, flags);
   { int rc = join_prepare(c); if (rc) return rc; }
   TextSlot *tp = nullptr; bool empty = false;
-  { int rc = text_stage(c, text, bytes, nLines, r, false, 0, nullptr, 0, &tp, ticket, &empty); if (rc) return rc; }
+  { int rc = textblock_front(c, "subset", TEXT_SUBSET, text, bytes, nLines, ticket, r, 0, 0, &tp, &empty); if (rc || empty) return rc; }
   TextSlot &t = *tp;
-  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
-  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
-  t.subsetPending = true;
-  if (empty) return GTX_OK;
   const size_t nTiles = gtxtext::subset_tiles((unsigned)nLines);
   if ((size_t)nLines > t.hits.cap) HIPCHK(c, t.hits.alloc(t.w.cap));
   if (2 * (nTiles + 1) > t.tile.cap) HIPCHK(c, t.tile.alloc(2 * (nTiles + 1) + (nTiles >> 2)));
@@ -226,23 +244,8 @@ int gtx_subset_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, 
 
 int gtx_subset_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t *out_bytes, int64_t *n_selected)
 {
-  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_subset_result: bad argument") : GTX_E_ARG;
-  TextSlot &t = c->text.slot[ticket];
-  if (!t.evParsed || !t.subsetPending) return fail(c, GTX_E_STATE, "gtx_subset_result: no such block");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(t.evParsed));
-  t.subsetPending = false;
-  *needs_host = *t.hostFlag.get();
-  *out_bytes = 0;
-  if (n_selected) *n_selected = 0;
-  if (*needs_host) return GTX_OK;
-  const size_t n = (size_t)t.hostTotal.get()[0];
-  if (n > 0 && !out) return fail(c, GTX_E_ARG, "gtx_subset_result: bad argument");
-  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
-  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
-  *out_bytes = n;
-  if (n_selected) *n_selected = (int64_t)t.hostTotal.get()[1];
-  return GTX_OK;
+  if (!c) return GTX_E_ARG;
+  return text_out_result(c, "subset", TEXT_SUBSET, ticket, needs_host, out, SIZE_MAX, out_bytes, n_selected);
 }
 
 // text -> triples in line order (the tokenizer's plain case, the class of every line) -> plan, two prefixes, emit (gtx_rewrite.h);
@@ -251,23 +254,17 @@ int gtx_rewrite_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines,
 {
   if (!c) return GTX_E_ARG;
   const int64_t kMaxAmount = 1ll << 62;                                    // columns of 10 digits stay far inside 64 bits with it
-  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || op->kind < GTX_REWRITE_SHIFT || op->kind > GTX_REWRITE_BOUNDS ||
-      op->a > kMaxAmount || op->a < -kMaxAmount || op->b > kMaxAmount || op->b < -kMaxAmount ||
+  if (!op || op->kind < GTX_REWRITE_SHIFT || op->kind > GTX_REWRITE_BOUNDS || op->a > kMaxAmount || op->a < -kMaxAmount || op->b > kMaxAmount || op->b < -kMaxAmount ||
       (op->kind == GTX_REWRITE_POS && (op->pos_op < GTX_REWRITE_POS_1 || op->pos_op > GTX_REWRITE_POS_C)) ||
       (op->kind == GTX_REWRITE_BOUNDS && (op->n_chrom < 0 || (op->n_chrom > 0 && (!op->chrom_names || !op->chrom_len)))))
     return fail(c, GTX_E_ARG, "gtx_rewrite_text: bad argument");
-  if (c->text.slot[c->text.seq & 1].rewritePending) return fail(c, GTX_E_STATE, "gtx_rewrite_text: the result of the block before last has not been fetched (gtx_rewrite_result)");
   const bool bounds = op->kind == GTX_REWRITE_BOUNDS;
-  gtx_text_rules r; memset(&r, 0, sizeof r);
+  gtx_text_rules r; memset(&r, 0, sizeof r);                               // (bounds: the tokenizer's classes are the names' places)
   r.chrom_names = bounds ? op->chrom_names : nullptr; r.n_chrom = bounds ? op->n_chrom : 0; r.max_label_value = 1;
   TextSlot *tp = nullptr; bool empty = false;
   // (the sorted scanner's rules: nothing about the interval is checked, and without sorted_rules nothing about the order)
-  { int rc = text_stage(c, text, bytes, nLines, &r, false, 2, nullptr, 0, &tp, ticket, &empty); if (rc) return rc; }
+  { int rc = textblock_front(c, "rewrite", TEXT_REWRITE, text, bytes, nLines, ticket, &r, 2, 0, &tp, &empty); if (rc || empty) return rc; }
   TextSlot &t = *tp;
-  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
-  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
-  t.rewritePending = true;
-  if (empty) return GTX_OK;
   if (bounds) {                                                            // the lengths per class: uploaded when they change
     std::vector<long long> len(op->chrom_len, op->chrom_len + op->n_chrom);
     if (len != c->text.h_chromLen || !c->text.chromLen) {
@@ -288,36 +285,13 @@ int gtx_rewrite_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines,
   prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and emit launches alone, on the text where it is)
   HIPCHK(c, prof_mark(c, 1, c->stream));
   HIPCHK(c, gtx::launch_rewrite(d, k, c->stream));
-  HIPCHK(c, prof_mark(c, 2, c->stream));
-  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], d.baseLines + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, prof_end(c, c->stream));
-  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
-  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
-  t.busy = true;
-  return GTX_OK;
+  return textblock_tail(c, t, d.baseBytes + nTiles, d.baseLines + nTiles);
 }
 
 int gtx_rewrite_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed)
 {
-  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_rewrite_result: bad argument") : GTX_E_ARG;
-  TextSlot &t = c->text.slot[ticket];
-  if (!t.evParsed || !t.rewritePending) return fail(c, GTX_E_STATE, "gtx_rewrite_result: no such block");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(t.evParsed));
-  t.rewritePending = false;
-  *needs_host = *t.hostFlag.get();
-  *out_bytes = 0;
-  if (n_printed) *n_printed = 0;
-  if (*needs_host) return GTX_OK;
-  const size_t n = (size_t)t.hostTotal.get()[0];
-  if (n > 0 && (!out || n > capacity)) return fail(c, GTX_E_ARG, "gtx_rewrite_result: out is missing or smaller than the block's text (gtx_rewrite_max_bytes)");
-  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
-  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
-  *out_bytes = n;
-  if (n_printed) *n_printed = (int64_t)t.hostTotal.get()[1];
-  return GTX_OK;
+  if (!c) return GTX_E_ARG;
+  return text_out_result(c, "rewrite", TEXT_REWRITE, ticket, needs_host, out, capacity, out_bytes, n_printed);
 }
 
 size_t gtx_rewrite_max_bytes(size_t bytes, int64_t n_lines) { return bytes + (size_t)gtx::kRewriteGrow * (size_t)(n_lines > 0 ? n_lines : 0); }
@@ -336,21 +310,14 @@ int gtx_convert_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines,
   if (!c) return GTX_E_ARG;
   const bool sam = (flags & GTX_TEXT_SAM) != 0, gff = (flags & GTX_TEXT_GFF) != 0;
   const size_t colorLen = op && op->color ? strlen(op->color) : 0;
-  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || (flags & ~(GTX_TEXT_SAM | GTX_TEXT_GFF)) || (sam && gff) ||
-      (op->to != GTX_CONVERT_BED && op->to != GTX_CONVERT_REG) || (op->to == GTX_CONVERT_BED && !sam && !gff) || colorLen > (size_t)gtx::kConvertMaxColor)
+  if (!op || (flags & ~(GTX_TEXT_SAM | GTX_TEXT_GFF)) || (sam && gff) || (op->to != GTX_CONVERT_BED && op->to != GTX_CONVERT_REG) ||
+      (op->to == GTX_CONVERT_BED && !sam && !gff) || colorLen > (size_t)gtx::kConvertMaxColor)
     return fail(c, GTX_E_ARG, "gtx_convert_text: bad argument");
-  if (c->text.slot[c->text.seq & 1].convertPending) return fail(c, GTX_E_STATE, "gtx_convert_text: the result of the block before last has not been fetched (gtx_convert_result)");
   const int format = sam ? 1 : gff ? 2 : 0;                                // (launch_tokenize's numbers)
-  gtx_text_rules r; memset(&r, 0, sizeof r);
-  r.max_label_value = 1;
   TextSlot *tp = nullptr; bool empty = false;
   // (the sorted scanner's rules, as for the rewrite: nothing about the interval is checked, and nothing about the order)
-  { int rc = text_stage(c, text, bytes, nLines, &r, false, 2, nullptr, format, &tp, ticket, &empty); if (rc) return rc; }
+  { int rc = textblock_front(c, "convert", TEXT_CONVERT, text, bytes, nLines, ticket, nullptr, 2, format, &tp, &empty); if (rc || empty) return rc; }
   TextSlot &t = *tp;
-  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
-  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
-  t.convertPending = true;
-  if (empty) return GTX_OK;
   const size_t nTiles = gtx::convert_tiles((unsigned)nLines), need = gtx_convert_max_bytes(bytes, nLines, op) + 32;
   if ((size_t)nLines > t.cvRec.cap) HIPCHK(c, t.cvRec.alloc(t.w.cap));
   if (nTiles > t.cvTile.cap) { HIPCHK(c, t.cvTile.alloc(nTiles + (nTiles >> 2))); HIPCHK(c, t.cvBase.alloc(nTiles + 1 + (nTiles >> 2))); }
@@ -365,35 +332,13 @@ int gtx_convert_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines,
   prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and emit launches alone, on the text where it is)
   HIPCHK(c, prof_mark(c, 1, c->stream));
   HIPCHK(c, gtx::launch_convert(d, k, c->stream));
-  HIPCHK(c, prof_mark(c, 2, c->stream));
-  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, prof_end(c, c->stream));
-  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
-  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
-  t.busy = true;
-  return GTX_OK;
+  return textblock_tail(c, t, d.baseBytes + nTiles, nullptr);
 }
 
 int gtx_convert_result(gtx_ctx *c, int ticket, int *needs_host, char *out, size_t capacity, size_t *out_bytes, int64_t *n_printed)
 {
-  if (!c || !needs_host || !out_bytes || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_convert_result: bad argument") : GTX_E_ARG;
-  TextSlot &t = c->text.slot[ticket];
-  if (!t.evParsed || !t.convertPending) return fail(c, GTX_E_STATE, "gtx_convert_result: no such block");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(t.evParsed));
-  t.convertPending = false;
-  *needs_host = *t.hostFlag.get();
-  *out_bytes = 0;
-  if (n_printed) *n_printed = 0;
-  if (*needs_host) return GTX_OK;
-  const size_t n = (size_t)t.hostTotal.get()[0];
-  if (n > 0 && (!out || n > capacity)) return fail(c, GTX_E_ARG, "gtx_convert_result: out is missing or smaller than the block's text (gtx_convert_max_bytes)");
-  // (on the copy stream: the context's own may already hold the kernels of the block after this one)
-  if (n > 0) { HIPCHK(c, hipMemcpyAsync(out, t.out.get(), n, hipMemcpyDeviceToHost, c->stage.copyStream)); HIPCHK(c, hipStreamSynchronize(c->stage.copyStream)); }
-  *out_bytes = n;
-  if (n_printed) *n_printed = (int64_t)t.hostTotal.get()[1];
-  return GTX_OK;
+  if (!c) return GTX_E_ARG;
+  return text_out_result(c, "convert", TEXT_CONVERT, ticket, needs_host, out, capacity, out_bytes, n_printed);
 }
 
 size_t gtx_convert_max_bytes(size_t bytes, int64_t n_lines, const gtx_convert_op *op)
@@ -416,19 +361,12 @@ int gtx_convert_limits(int32_t *tile, int32_t *stage, int32_t *max_color)
 int gtx_windows_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_windows_op *op, int *ticket)
 {
   if (!c) return GTX_E_ARG;
-  if (!text || !op || !ticket || nLines < 0 || bytes >= (1ull << 32) - 4096 || nLines >= (1ll << 31) || op->win_size < 1 || op->win_size > (1ll << 31) ||
-      op->win_step < 1 || op->win_step > (1ll << 31))
+  if (!op || op->win_size < 1 || op->win_size > (1ll << 31) || op->win_step < 1 || op->win_step > (1ll << 31))
     return fail(c, GTX_E_ARG, "gtx_windows_text: bad argument");
-  if (c->text.slot[c->text.seq & 1].windowsPending) return fail(c, GTX_E_STATE, "gtx_windows_text: the result of the block before last has not been fetched (gtx_windows_result)");
-  gtx_text_rules r; memset(&r, 0, sizeof r);
-  r.max_label_value = 1;
   TextSlot *tp = nullptr; bool empty = false;
   // (the sorted scanner's rules, as for the rewrite: nothing about the interval is checked, and nothing about the order)
-  { int rc = text_stage(c, text, bytes, nLines, &r, false, 2, nullptr, 0, &tp, ticket, &empty); if (rc) return rc; }
+  { int rc = textblock_front(c, "windows", TEXT_WINDOWS, text, bytes, nLines, ticket, nullptr, 2, 0, &tp, &empty); if (rc) return rc; }
   TextSlot &t = *tp;
-  if (!t.hostTotal) HIPCHK(c, t.hostTotal.alloc(2));
-  t.hostTotal.get()[0] = t.hostTotal.get()[1] = 0;
-  t.windowsPending = true;
   t.wnSize = op->win_size; t.wnStep = op->win_step; t.wnSmall = op->small ? 1 : 0; t.wnBytes = bytes; t.wnLines = (unsigned)nLines;
   if (empty) { t.wnLines = 0; return GTX_OK; }
   const size_t nTiles = gtx::windows_tiles((unsigned)nLines);
@@ -439,15 +377,7 @@ int gtx_windows_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines,
   prof_begin(c);                                                           // (gtx_profile_*: the plan, prefix and base launches alone, on the text where it is)
   HIPCHK(c, prof_mark(c, 1, c->stream));
   HIPCHK(c, gtx::launch_windows_plan(d, k, c->stream));
-  HIPCHK(c, prof_mark(c, 2, c->stream));
-  HIPCHK(c, hipMemcpyAsync(t.hostFlag.get(), t.flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[0], d.baseWindows + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&t.hostTotal.get()[1], d.baseBytes + nTiles, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, prof_end(c, c->stream));
-  HIPCHK(c, hipEventRecord(t.evParsed, c->stream));
-  HIPCHK(c, hipEventRecord(t.evConsumed, c->stream));
-  t.busy = true;
-  return GTX_OK;
+  return textblock_tail(c, t, d.baseWindows + nTiles, d.baseBytes + nTiles);
 }
 
 // The block's windows in ranges of whole output tiles through two device and two page-locked buffers, as gtx_window_lines streams
@@ -455,14 +385,11 @@ int gtx_windows_text(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines,
 // writes.  A range's place in the output is the sum of the ranges in front, known when it is enqueued.
 int gtx_windows_result(gtx_ctx *c, int ticket, int *needs_host, gtx_lines_sink sink, void *user, int64_t *n_windows, int64_t *n_bytes)
 {
-  if (!c || !needs_host || (ticket & ~1)) return c ? fail(c, GTX_E_ARG, "gtx_windows_result: bad argument") : GTX_E_ARG;
-  TextSlot &t = c->text.slot[ticket];
+  if (!c) return GTX_E_ARG;
+  TextSlot *tp = nullptr;
+  { int rc = textblock_result(c, "windows", TEXT_WINDOWS, ticket, needs_host, true, &tp); if (rc) return rc; }
+  TextSlot &t = *tp;
   TextState &s = c->text;
-  if (!t.evParsed || !t.windowsPending) return fail(c, GTX_E_STATE, "gtx_windows_result: no such block");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(t.evParsed));
-  t.windowsPending = false;
-  *needs_host = *t.hostFlag.get();
   if (n_windows) *n_windows = 0;
   if (n_bytes) *n_bytes = 0;
   if (*needs_host) return GTX_OK;

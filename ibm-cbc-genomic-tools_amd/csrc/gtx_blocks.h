@@ -14,9 +14,9 @@
 //                         (BlocksRec).  A line that prints nothing (select without a flag, diff of a single block or of touching
 //                         blocks) has outLen 0 and is counted out.  The tile's bytes and printed lines go to tileBytes / tileCount
 //   launch_tile_prefix    (gtx_compact.h) exclusive sums of both; the totals are the block's bytes and n_printed
-//   blocks_emit_kernel    connect, select, diff, n, strand: a tile's printed lines are one run of the output, built in LDS at the
-//                         run's offset inside its first 16-byte unit and stored in aligned 16-byte units; the bytes that share a unit
-//                         with the tile in front or behind go out one by one (gtx_convert.h's scheme).  A record cannot hold a block
+//   blocks_emit_kernel    connect, select, diff, n, strand: a tile's printed lines are one run of the output, placed by
+//                         tile_exclusive over the tile's one wave, built in LDS and stored through store_run (gtx_lineout.h, which
+//                         has the scheme of the store).  A record cannot hold a block
 //                         list: diff walks the two lists again, strand copies them.  A tile whose run is longer than kBlocksStage
 //                         makes the block not plain (flag 32, raised by the plan)
 //   blocks_base_kernel,   split prints blocks x (chromosome + label + about 45) bytes per line, far beyond any stage for a tile of

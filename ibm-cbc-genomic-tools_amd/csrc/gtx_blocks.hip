@@ -2,17 +2,20 @@
 #include "gtx_blocks.h"
 #include "gtx_compact.h"
 #include "gtx_textline.h"
+#include "gtx_lineout.h"
 
 namespace gtx {
 namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-typedef unsigned uint32x4 __attribute__((ext_vector_type(4)));
 
 using gtxtext::digits;
 using gtxtext::signed_len;
 using gtxtext::put_signed;
+using gtxline::line_begin;
+using gtxline::tile_exclusive;
+using gtxline::store_run;
 
 // ---- the plain line's grammar (include/gtx.h) -------------------------------------------------------------------------------------
 struct Tok { unsigned a, z; bool last; };
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(kBlocksTile) void blocks_plan_kernel(BlocksDevice d
   }
   unsigned len = 0, count = 0;
   if (j < d.nLines) {
-    const unsigned b = j ? d.nl[j - 1] + 1 : 0, e = d.nl[j];
+    const unsigned b = line_begin(d.nl, j), e = d.nl[j];
     const unsigned char *s = (const unsigned char *)d.text;
     BlocksRec r = {};
     bool ok = b <= e && (size_t)e < d.bytes && (j + 1 < d.nLines || (size_t)e + 1 == d.bytes) && parse_line(s, b, e, op.kind, r);
@@ -283,30 +286,13 @@ __global__ __launch_bounds__(kBlocksTile) void blocks_base_kernel(BlocksDevice d
   const unsigned tile = blockIdx.x, j = tile * kBlocksTile + threadIdx.x;
   unsigned c = 0; u64 n = 0;
   if (j < d.nLines) { c = d.rec[j].outCount; n = d.rec[j].outLen; }
-  unsigned ci = c; u64 ni = n;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned uc = __shfl_up(ci, o); const u64 un = __shfl_up(ni, o);
-    if ((int)threadIdx.x >= o) { ci += uc; ni += un; }
-  }
-  if (j < d.nLines) { d.lineOut[j] = (unsigned)d.baseCount[tile] + ci - c; d.lineByte[j] = d.baseBytes[tile] + (i64)(ni - n); }
-  if (j + 1 == d.nLines) { d.lineOut[d.nLines] = (unsigned)d.baseCount[tile] + ci; d.lineByte[d.nLines] = d.baseBytes[tile] + (i64)ni; }
+  const unsigned atC = (unsigned)d.baseCount[tile] + tile_exclusive<kBlocksTile, unsigned>(c, nullptr);   // (one wave: no LDS)
+  const i64 atN = d.baseBytes[tile] + (i64)tile_exclusive<kBlocksTile, u64>(n, nullptr);
+  if (j < d.nLines) { d.lineOut[j] = atC; d.lineByte[j] = atN; }
+  if (j + 1 == d.nLines) { d.lineOut[d.nLines] = atC + c; d.lineByte[d.nLines] = atN + (i64)n; }
 }
 
-// ---- emit ---------------------------------------------------------------------------------------------------------------------------
-// run[pad .. pad + total) is bytes [lo, lo + total) of the output, pad = lo & 15: whole 16-byte units as such, the bytes that share a
-// unit with the run in front or behind one by one
-template <int THREADS>
-__device__ __forceinline__ void store_run(char *__restrict__ outAll, const unsigned char *run, i64 lo, unsigned total)
-{
-  const unsigned pad = (unsigned)(lo & 15), end = pad + total;
-  char *__restrict__ out = outAll + (lo - pad);
-  for (unsigned k = threadIdx.x * 16; k < end; k += THREADS * 16) {
-    if (k >= pad && k + 16 <= end) *(uint32x4 *)(out + k) = *(const uint32x4 *)(run + k);
-    else for (unsigned q = max(k, pad); q < min(k + 16, end); q++) out[q] = (char)run[q];
-  }
-}
-
+// ---- emit (the runs go out through store_run, gtx_lineout.h) ------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlocksTile) void blocks_emit_kernel(BlocksDevice d, BlocksOp op, char *__restrict__ out)
 {
   __shared__ __attribute__((aligned(16))) unsigned char run[kBlocksStage + 32];
@@ -316,13 +302,10 @@ __global__ __launch_bounds__(kBlocksTile) void blocks_emit_kernel(BlocksDevice d
   if (hi == lo) return;
   BlocksRec r; r.outLen = 0;
   if (j < d.nLines) r = d.rec[j];
-  unsigned incl = r.outLen;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(incl, o); if ((int)threadIdx.x >= o) incl += up; }
-  const unsigned at = incl - r.outLen, pad = (unsigned)(lo & 15);   // pad + (hi - lo) <= 15 + kBlocksStage
+  const unsigned at = tile_exclusive<kBlocksTile, unsigned>(r.outLen, nullptr), pad = (unsigned)(lo & 15);   // pad + (hi - lo) <= 15 + kBlocksStage
   if (r.outLen) {
     ByteSink o; o.p = run + pad + at;
-    render_one<ByteSink, false>(o, op, (const unsigned char *)d.text + (j ? d.nl[j - 1] + 1 : 0), r);
+    render_one<ByteSink, false>(o, op, (const unsigned char *)d.text + line_begin(d.nl, j), r);
   }
   __syncthreads();
   store_run<kBlocksTile>(out, run, lo, (unsigned)(hi - lo));
@@ -344,7 +327,7 @@ __global__ __launch_bounds__(kBlocksOutTile) void blocks_split_kernel(BlocksDevi
     while (z - a > 1) { const unsigned m = a + (z - a) / 2; if ((i64)d.lineOut[m] <= o) a = m; else z = m; }
     const unsigned j = a, k = (unsigned)(o - d.lineOut[j]);
     r = d.rec[j];
-    L = (const unsigned char *)d.text + (j ? d.nl[j - 1] + 1 : 0);
+    L = (const unsigned char *)d.text + line_begin(d.nl, j);
     at = d.lineByte[j];
     A = r.s0; Z = r.e;
     if (r.nTok == 12) {                                           // to block k, past the bytes of the blocks in front

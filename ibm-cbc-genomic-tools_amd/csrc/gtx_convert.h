@@ -15,10 +15,9 @@
 //                         class -1 with start and stop 0.)
 //   launch_tile_prefix    (gtx_compact.h) exclusive sums of the tiles' bytes.  Every line of a plain block is printed, so the lines
 //                         need no prefix of their own
-//   convert_emit_kernel   a tile's lines are one run of the output, built in LDS at the run's offset inside its first 16-byte unit of
-//                         the output: label and chromosome copied from the text, the decimals rendered, the constant pieces
-//                         ("\t1000\t", the colour, "chr") put between them.  The run goes out with aligned 16-byte stores; the bytes
-//                         that share a unit with the tile in front or behind go out one by one
+//   convert_emit_kernel   a tile's lines are one run of the output, placed by tile_exclusive and built in LDS: label and chromosome
+//                         copied from the text, the decimals rendered, the constant pieces ("\t1000\t", the colour, "chr") put
+//                         between them.  The run goes out through store_run (gtx_lineout.h, which has the scheme of the store)
 //
 // Why the heads are walked in global memory and not staged: the text of 256 SAM lines is 60-150 KB, of which the plan needs some 50
 // bytes a line and the emit pass the 10-30 of QNAME and RNAME.  A lane's bytes lie in one or two 128-byte lines, which the vector

@@ -2,18 +2,22 @@
 #include "gtx_convert.h"
 #include "gtx_compact.h"
 #include "gtx_textline.h"
+#include "gtx_lineout.h"
 
 namespace gtx {
 namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-typedef unsigned uint32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kStageBytes = kConvertStage + 32;   // a run begins inside its first 16-byte unit and is read out in whole units
 
 using gtxtext::signed_len;
 using gtxtext::put_signed;
+using gtxline::line_begin;
+using gtxline::tile_total;
+using gtxline::tile_exclusive;
+using gtxline::store_run;
 
 // The walks below run on lines launch_tokenize has judged plain (gtx.h has the grammar), so they test nothing again; every loop still
 // ends at the line's end e, whatever the bytes are.
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(kConvertTile) void convert_plan_kernel(ConvertDevic
   const unsigned j = j0 + threadIdx.x;
   unsigned len = 0;
   if (j < j1) {
-    const unsigned b = j ? d.nl[j - 1] + 1 : 0, e = d.nl[j];
+    const unsigned b = line_begin(d.nl, j), e = d.nl[j];
     const unsigned char *s = (const unsigned char *)d.text;
     ConvertRec r; r.labelOff = 0; r.labelLen = 0; r.chromOff = 0; r.chromLen = 0; r.s0 = 0; r.e = 0; r.outLen = 0; r.strand = '+';
     bool ok = true;
@@ -138,10 +142,7 @@ __global__ __launch_bounds__(kConvertTile) void convert_plan_kernel(ConvertDevic
     d.rec[j] = r;
     len = r.outLen;
   }
-  unsigned sum = len;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&sBytes, sum);
+  tile_total(len, &sBytes);
   __syncthreads();
   if (threadIdx.x == 0) {
     if (sBytes > (unsigned)kConvertStage) atomicOr(d.flag, 32);
@@ -159,17 +160,10 @@ __global__ __launch_bounds__(kConvertTile) void convert_emit_kernel(ConvertDevic
   const unsigned j = j0 + threadIdx.x;
   ConvertRec r; r.outLen = 0;
   if (j < j1) r = d.rec[j];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned incl = r.outLen;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-  if (lane == 63) waveSum[w] = incl;
-  __syncthreads();
-  unsigned at = incl - r.outLen;                                  // where the line begins inside the run
-  for (int k = 0; k < w; k++) at += waveSum[k];
-  const unsigned pad = (unsigned)(lo & 15), total = (unsigned)(hi - lo);   // run[k] is byte lo - pad + k of the output; pad + total <= 15 + kConvertStage
+  const unsigned at = tile_exclusive<kConvertTile>(r.outLen, waveSum);   // where the line begins inside the run
+  const unsigned pad = (unsigned)(lo & 15);                       // run[k] is byte lo - pad + k of the output; pad + (hi - lo) <= 15 + kConvertStage
   if (r.outLen) {
-    const unsigned char *line = (const unsigned char *)d.text + (j ? d.nl[j - 1] + 1 : 0);
+    const unsigned char *line = (const unsigned char *)d.text + line_begin(d.nl, j);
     const unsigned char *label = line + r.labelOff, *chrom = line + r.chromOff;
     unsigned char *p = run + pad + at;
     auto put_label = [&]() { if (r.labelLen == 0) *p++ = '_'; else for (unsigned k = 0; k < r.labelLen; k++) *p++ = label[k]; };
@@ -204,12 +198,7 @@ __global__ __launch_bounds__(kConvertTile) void convert_emit_kernel(ConvertDevic
     *p++ = '\n';
   }
   __syncthreads();
-  char *__restrict__ out = d.out + (lo - pad);
-  const unsigned end = pad + total;
-  for (unsigned k = threadIdx.x * 16; k < end; k += kConvertTile * 16) {
-    if (k >= pad && k + 16 <= end) *(uint32x4 *)(out + k) = *(const uint32x4 *)(run + k);
-    else for (unsigned q = max(k, pad); q < min(k + 16, end); q++) out[q] = (char)run[q];   // the units shared with the tiles in front and behind
-  }
+  store_run<kConvertTile>(d.out, run, lo, (unsigned)(hi - lo));
 }
 
 }  // namespace

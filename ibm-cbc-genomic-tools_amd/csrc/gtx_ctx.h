@@ -146,6 +146,9 @@ struct RefExtras {
 // a group member's share of the finalize step (gtxi_set_share): tiles of its classes, its regions in the group's compact order
 struct Share { bool on = false; DevBuf<int> tiles; int nTiles = 0; DevBuf<int> regions; int64_t nRegions = 0, offset = 0; DevBuf<unsigned char> owned; };
 
+// whose block of text a slot holds between the family's _text call and its _result call (gtx_api_textblock.h)
+enum TextPending { TEXT_NONE, TEXT_SUBSET, TEXT_REWRITE, TEXT_WINDOWS, TEXT_CONVERT, TEXT_BLOCKS };
+
 // a block of region text tokenised on the device (gtx_count_add_text)
 struct TextSlot {
   DevBuf<char> text; DevBuf<unsigned> seg;
@@ -153,24 +156,21 @@ struct TextSlot {
   DevBuf<int> tri2; DevBuf<unsigned> blk; DevBuf<int> w2;      // ... w2 those of the strand-aware outputs
   DevBuf<int> flag; PinBuf<int> hostFlag; PinBuf<char> pin, seam; DevBuf<unsigned long long> sum;
   hipEvent_t evParsed = nullptr, evConsumed = nullptr, evCopied = nullptr; bool busy = false;
-  // gtx_subset_text: the lines' hits, the tiles' kept bytes / lines, the kept text and its
-  // totals on the host; whether the slot holds a subset block whose result has not been fetched
-  DevBuf<unsigned> hits; DevBuf<unsigned long long> tile; DevBuf<char> out; PinBuf<unsigned long long> hostTotal; bool subsetPending = false;
-  // gtx_rewrite_text: the lines' records, the tiles' bytes | lines and their prefixes (`out` and `hostTotal` as for the subset);
-  // whether the slot holds a rewritten block whose result has not been fetched
-  DevBuf<gtx::RewriteRec> rwRec; DevBuf<unsigned> rwTile; DevBuf<long long> rwBase; bool rewritePending = false;
+  // the family whose block the slot holds, its result not fetched yet: a slot holds one block, so the next family's block ends it
+  TextPending pending = TEXT_NONE;
+  // gtx_subset_text: the lines' hits, the tiles' kept bytes / lines, the kept text and its totals on the host
+  DevBuf<unsigned> hits; DevBuf<unsigned long long> tile; DevBuf<char> out; PinBuf<unsigned long long> hostTotal;
+  // gtx_rewrite_text: the lines' records, the tiles' bytes | lines and their prefixes (`out` and `hostTotal` as for the subset)
+  DevBuf<gtx::RewriteRec> rwRec; DevBuf<unsigned> rwTile; DevBuf<long long> rwBase;
   // gtx_windows_text: the lines' records, the tiles' windows | bytes and their prefixes, the lines' bases (windows | bytes); what
-  // gtx_windows_result needs of the call to render the block (`hostTotal`: the block's windows and bytes); whether the slot holds
-  // a planned block whose result has not been fetched
-  DevBuf<gtx::WindowsRec> wnRec; DevBuf<unsigned long long> wnTile; DevBuf<long long> wnBase, wnLine; bool windowsPending = false;
+  // gtx_windows_result needs of the call to render the block (`hostTotal`: the block's windows and bytes)
+  DevBuf<gtx::WindowsRec> wnRec; DevBuf<unsigned long long> wnTile; DevBuf<long long> wnBase, wnLine;
   long long wnSize = 0, wnStep = 0; int wnSmall = 0; size_t wnBytes = 0; unsigned wnLines = 0;
-  // gtx_convert_text: the lines' records, the tiles' bytes and their prefix (`out` and `hostTotal` as for the subset); whether the
-  // slot holds a converted block whose result has not been fetched
-  DevBuf<gtx::ConvertRec> cvRec; DevBuf<unsigned> cvTile; DevBuf<long long> cvBase; bool convertPending = false;
+  // gtx_convert_text: the lines' records, the tiles' bytes and their prefix (`out` and `hostTotal` as for the subset)
+  DevBuf<gtx::ConvertRec> cvRec; DevBuf<unsigned> cvTile; DevBuf<long long> cvBase;
   // gtx_blocks_text: the lines' records, the tiles' bytes | printed lines and their prefixes, split's bases of the lines (printed
-  // lines; bytes); what gtx_blocks_result needs of the call to render the block (`hostTotal`: the block's bytes and printed lines);
-  // whether the slot holds a planned block whose result has not been fetched
-  DevBuf<gtx::BlocksRec> blRec; DevBuf<unsigned> blTile, blLineOut; DevBuf<long long> blBase, blLineByte; bool blocksPending = false;
+  // lines; bytes); what gtx_blocks_result needs of the call to render the block (`hostTotal`: the block's bytes and printed lines)
+  DevBuf<gtx::BlocksRec> blRec; DevBuf<unsigned> blTile, blLineOut; DevBuf<long long> blBase, blLineByte;
   int blKind = 0, blSelect = 0, blStrand = 0; size_t blBytes = 0; unsigned blLines = 0;
 };
 
@@ -447,7 +447,7 @@ int join_prepare(gtx_ctx *c);
 int join_mode(gtx_ctx *c, uint32_t flags);
 // gtx_api_scan.hip
 int scan_hist_any(gtx_ctx *c, const void *dR, const int *dW, int64_t n, const gtx::ScanArgs &a, const int32_t *classLen, bool unsorted);
-// gtx_api_text.hip
+// gtx_api_text.hip (the handshake around it of the families that hand text back: gtx_api_textblock.h)
 int text_stage(gtx_ctx *c, const char *text, size_t bytes, int64_t nLines, const gtx_text_rules *r, bool grouped, int scanRules,
                unsigned long long *labelSum, int format, TextSlot **tp, int *ticket, bool *empty);
 

@@ -136,6 +136,39 @@ struct TextPump {
   int ticket_[2] = {-1, -1};
 };
 
+// ---- gtx_host_regionops.cpp: the device text loop of the tools that print lines from lines (with gtx_host_blocks.cpp) ----------
+// One GPU, and the page-locked pool is there: what every such tool asks before its own conditions.  (The first thing it does is
+// Devices(), before anything is printed: without a GPU the run ends there.)
+bool OneGpuWithPool();
+
+// a page-locked buffer for a block's printed text: grown on demand, to need + need / 8, and freed with the loop that owns it
+struct PinnedOut {
+  char *Reserve(gtx_ctx *ctx, size_t need);                       // at least `need` bytes; dies with the library's error
+  ~PinnedOut();
+ private:
+  gtx_ctx *ctx_ = NULL; char *p_ = NULL; size_t cap_ = 0;
+};
+
+// what DeviceTextLoop shows of itself to an `add` that renders a block on its own (the rewrite's short stream): such an add
+// settles the pump, counts the block as one that came back and returns a negative ticket
+struct LineLoopView { TextPump *pump; BedPacker *packer; const std::string *first; long int *came_back; };
+
+// A tool's side of the loop.  trace: the GTX_TEXT_TRACE line up to the colon; sam / gff: the format of the set's text, for the packer
+// and for the blocks that come back; chrom_names: the frozen table's names (bounds; else none).  add: one call of the C ABI, returns
+// the ticket.  result: fetches the ticket's block and writes what the device printed to stdout; true: the block came back.
+struct LineFamily {
+  const char *trace;
+  bool sam, gff;
+  std::vector<const char *> chrom_names;
+  std::function<int(gtx_ctx *, const TextPump::Block &)> add;
+  std::function<bool(gtx_ctx *, int ticket, const TextPump::Block &)> result;
+  LineLoopView *view;                                             // filled before the first add when not NULL
+};
+// The set's text block by block through f.add, two blocks in flight, the printed text to stdout in block order through f.result; a
+// block that comes back is rendered here (HostBlock with `render`), alone, and the next one goes to the device again.  The line the
+// set's constructor has read goes first, as a block of one line.
+void DeviceTextLoop(GenomicRegionSet *set, const LineFamily &f, const Renderer &render);
+
 // quick order hint for the kernel choice (a wrong hint only costs speed; the device verifies it and falls back by itself): adjacent
 // pairs of packed triples sampled at ~4096 places, with so many descents let through (a batch is a few sorted runs at most, e.g.
 // the '+' then the '-' reads).  Each caller keeps its own tolerance: the hint picks a kernel route.

@@ -74,50 +74,21 @@ void RenderBlocks(std::string &out, const BlocksSpec &op, GenomicRegion *r, cons
   WriteOut(out, 1u << 22);
 }
 
-// May the set's text go to the device?  Whatever its size, on one GPU
-bool BlocksUsable()
-{
-  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
-  if (gtx_group_size(devices) != 1) return false;
-  if (g_pool_future.valid()) g_pool_future.get();
-  return g_pool.buf[0] && g_pool.buf[1];
-}
-
-// the set's text block by block through gtx_blocks_text; gtx_blocks_result streams a block's printed lines to stdout, in block
-// order.  A block that comes back is rendered here, alone, and the next one goes to the device again
+// the set's text through gtx_blocks_text; gtx_blocks_result streams a block's printed lines to stdout (DeviceTextLoop)
 void BlocksTextLoop(GenomicRegionSet *set, const gtx_blocks_op &dev, const Renderer &render)
 {
-  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
-  std::string first; long int first_no = 0;
-  LineSource *src = set->DetachStream(&first, &first_no);
-  if (first_no <= 0) return;
-  ChromTable chroms;
-  chroms.Freeze();
-  PackOptions opt;
-  opt.chroms = &chroms;
-  BedPacker packer(src, opt);
-  TextPump pump(packer, opt);
-  long int on_device = 0, came_back = 0;
-  pump.settle = [&](const TextPump::Block &b, int ticket) {
-    int redo = 0;
-    DieGtx(ctx, gtx_blocks_result(ctx, ticket, &redo, WriteSink, stdout, NULL, NULL));
-    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render); }
-    else on_device++;
-    return true;
-  };
-  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
+  LineFamily f{"[gtx blocks] blocks rendered on the device", false, false, {}, nullptr, nullptr, NULL};
+  f.add = [&](gtx_ctx *ctx, const TextPump::Block &b) {
     int ticket = -1;
     DieGtx(ctx, gtx_blocks_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
     return ticket;
   };
-  // the line the set's constructor has read for its format check: a block of one line
-  first += '\n';
-  TextPump::Block &one = pump.blk[0];
-  one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
-  pump.Add(0);
-  pump.Run(1);
-  fflush(stdout);
-  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx blocks] blocks rendered on the device: %ld, came back: %ld\n", on_device, came_back);
+  f.result = [](gtx_ctx *ctx, int ticket, const TextPump::Block &) {
+    int redo = 0;
+    DieGtx(ctx, gtx_blocks_result(ctx, ticket, &redo, WriteSink, stdout, NULL, NULL));
+    return redo != 0;
+  };
+  DeviceTextLoop(set, f, render);
 }
 
 void RunBlocks(GenomicRegionSet *set, const BlocksSpec &op)
@@ -127,7 +98,7 @@ void RunBlocks(GenomicRegionSet *set, const BlocksSpec &op)
   if (set->load_in_memory) set->PrintError("the block operations stream their input on the MI355X path: open the set with load_in_memory = false!");
   // GTX_TEXT_ON_DEVICE=0: the host loop and nothing else.  Otherwise the device is looked for whatever the input's size: without
   // one the run ends with the library's error, as every other operation's does
-  bool device = !TextPolicy().never && BlocksUsable();
+  bool device = !TextPolicy().never && OneGpuWithPool();   // whatever the input's size
   gtx_blocks_op dev; memset(&dev, 0, sizeof dev);
   dev.kind = op.kind;
   dev.select = (op.first ? GTX_BLOCKS_FIRST : 0) | (op.last ? GTX_BLOCKS_LAST : 0) | (op.from5p ? GTX_BLOCKS_5P : 0) | (op.from3p ? GTX_BLOCKS_3P : 0);

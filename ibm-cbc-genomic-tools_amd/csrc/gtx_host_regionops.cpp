@@ -166,80 +166,105 @@ void gtx_host::HostBlock(const char *text, size_t bytes, long int first_line, co
   if (err.set) ExitOnLoadError(err);
 }
 
-namespace {
-
-// May the set's text go to the device as it is?  A streamed BED file, stdin or .gz (a regular file: of 32 MB or more, or
-// GTX_TEXT_ON_DEVICE=1; never with GTX_TEXT_ON_DEVICE=0), on one GPU, amounts the device's arithmetic takes
-bool TextUsable(GenomicRegionSet *set, const RegionOp &op)
+bool gtx_host::OneGpuWithPool()
 {
-  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
-  const long left = set->StreamBytesLeft();
-  if (left >= 0 && left < (long)TextPolicy().threshold_bytes) return false;
-  if (gtx_group_size(devices) != 1) return false;
+  if (gtx_group_size(Devices()) != 1) return false;
   if (g_pool_future.valid()) g_pool_future.get();
-  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
-  const long int lim = 1L << 62;
-  return op.a <= lim && op.a >= -lim && op.b <= lim && op.b >= -lim;
+  return g_pool.buf[0] && g_pool.buf[1];
 }
 
-// the set's text block by block through gtx_rewrite_text, the rewritten text to stdout in block order; a block that comes back is
-// rendered here, alone, and the next one goes to the device again
-void TextLoop(GenomicRegionSet *set, const RegionOp &op, const Renderer &render)
+char *gtx_host::PinnedOut::Reserve(gtx_ctx *ctx, size_t need)
+{
+  if (need > cap_) {
+    if (p_) gtx_host_free(ctx_, p_);
+    ctx_ = ctx; cap_ = need + (need >> 3);
+    p_ = (char *)gtx_host_alloc(ctx, cap_);
+    if (!p_) DieGtx(ctx, GTX_E_HIP);
+  }
+  return p_;
+}
+
+gtx_host::PinnedOut::~PinnedOut() { if (p_) gtx_host_free(ctx_, p_); }
+
+void gtx_host::DeviceTextLoop(GenomicRegionSet *set, const LineFamily &f, const Renderer &render)
 {
   gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
   std::string first; long int first_no = 0;
   LineSource *src = set->DetachStream(&first, &first_no);
   if (first_no <= 0) return;
-  // the names and lengths of bounds, in the map's (strcmp) order
   ChromTable chroms;
-  std::vector<const char *> names; std::vector<int64_t> lens;
-  if (op.kind == GTX_REWRITE_BOUNDS && op.bounds)
-    for (StringLIntMap::iterator it = op.bounds->begin(); it != op.bounds->end(); it++) { chroms.Add(it->first.c_str()); names.push_back(it->first.c_str()); lens.push_back(it->second); }
+  for (size_t k = 0; k < f.chrom_names.size(); k++) chroms.Add(f.chrom_names[k]);
   chroms.Freeze();
-  gtx_rewrite_op dev; memset(&dev, 0, sizeof dev);
-  dev.kind = op.kind; dev.a = op.a; dev.b = op.b;
-  dev.pos_op = op.pos_word == "2" ? GTX_REWRITE_POS_2 : op.pos_word == "5p" ? GTX_REWRITE_POS_5P : op.pos_word == "3p" ? GTX_REWRITE_POS_3P : op.pos_word == "c" ? GTX_REWRITE_POS_C : GTX_REWRITE_POS_1;
-  dev.chrom_names = names.empty() ? NULL : names.data(); dev.chrom_len = lens.empty() ? NULL : lens.data(); dev.n_chrom = (int32_t)names.size();
   PackOptions opt;
-  opt.chroms = &chroms;
+  opt.chroms = &chroms; opt.sam = f.sam; opt.gff = f.gff;
   BedPacker packer(src, opt);
   TextPump pump(packer, opt);
   long int on_device = 0, came_back = 0;
-  bool first_block = true;
-  char *out = NULL; size_t out_cap = 0;
+  if (f.view) *f.view = LineLoopView{&pump, &packer, &first, &came_back};
+  const std::string format = f.sam ? "SAM" : f.gff ? "GFF" : "BED";
   pump.settle = [&](const TextPump::Block &b, int ticket) {
-    const size_t need = gtx_rewrite_max_bytes(b.bytes, b.n_lines);
-    if (need > out_cap) {
-      if (out) gtx_host_free(ctx, out);
-      out_cap = need + (need >> 3);
-      out = (char *)gtx_host_alloc(ctx, out_cap);
-      if (!out) DieGtx(ctx, GTX_E_HIP);
-    }
-    int redo = 0; size_t got = 0;
-    DieGtx(ctx, gtx_rewrite_result(ctx, ticket, &redo, out, out_cap, &got, NULL));
-    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render); }
-    else { on_device++; if (got) fwrite(out, 1, got, stdout); }
+    if (f.result(ctx, ticket, b)) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render, format); }
+    else on_device++;
     return true;
   };
-  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
-    int ticket = -1;
-    // a short stream: the host loop is done before the device has the text
-    const bool here = first_block && b.text != first.data() && b.bytes < TextPolicy().threshold_bytes && packer.SourceAtEnd();
-    if (b.text != first.data()) first_block = false;
-    // (counted with the blocks that came back: the trace says how many blocks the loop rendered, whichever way they got to it)
-    if (here) { pump.SettleAll(); came_back++; HostBlock(b.text, b.bytes, b.first_line, render); return ticket; }
-    DieGtx(ctx, gtx_rewrite_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
-    return ticket;
-  };
+  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) { return f.add(ctx, b); };
   // the line the set's constructor has read for its format check: a block of one line
   first += '\n';
   TextPump::Block &one = pump.blk[0];
   one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
   pump.Add(0);
   pump.Run(1);
-  if (out) gtx_host_free(ctx, out);
   fflush(stdout);
-  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx regions] blocks rewritten on the device: %ld, came back: %ld\n", on_device, came_back);
+  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "%s: %ld, came back: %ld\n", f.trace, on_device, came_back);
+}
+
+namespace {
+
+// May the set's text go to the device as it is?  A streamed BED file, stdin or .gz (a regular file: of 32 MB or more, or
+// GTX_TEXT_ON_DEVICE=1; never with GTX_TEXT_ON_DEVICE=0), on one GPU, amounts the device's arithmetic takes
+bool TextUsable(GenomicRegionSet *set, const RegionOp &op)
+{
+  Devices();                                                      // (before anything is printed: without a GPU the run ends here)
+  const long left = set->StreamBytesLeft();
+  if (left >= 0 && left < (long)TextPolicy().threshold_bytes) return false;
+  const long int lim = 1L << 62;
+  return OneGpuWithPool() && op.a <= lim && op.a >= -lim && op.b <= lim && op.b >= -lim;
+}
+
+// the set's text through gtx_rewrite_text, the rewritten text to stdout (DeviceTextLoop)
+void TextLoop(GenomicRegionSet *set, const RegionOp &op, const Renderer &render)
+{
+  // the names and lengths of bounds, in the map's (strcmp) order
+  std::vector<const char *> names; std::vector<int64_t> lens;
+  if (op.kind == GTX_REWRITE_BOUNDS && op.bounds)
+    for (StringLIntMap::iterator it = op.bounds->begin(); it != op.bounds->end(); it++) { names.push_back(it->first.c_str()); lens.push_back(it->second); }
+  gtx_rewrite_op dev; memset(&dev, 0, sizeof dev);
+  dev.kind = op.kind; dev.a = op.a; dev.b = op.b;
+  dev.pos_op = op.pos_word == "2" ? GTX_REWRITE_POS_2 : op.pos_word == "5p" ? GTX_REWRITE_POS_5P : op.pos_word == "3p" ? GTX_REWRITE_POS_3P : op.pos_word == "c" ? GTX_REWRITE_POS_C : GTX_REWRITE_POS_1;
+  dev.chrom_names = names.empty() ? NULL : names.data(); dev.chrom_len = lens.empty() ? NULL : lens.data(); dev.n_chrom = (int32_t)names.size();
+  PinnedOut out;
+  LineLoopView loop;
+  bool first_block = true;
+  LineFamily f{"[gtx regions] blocks rewritten on the device", false, false, names, nullptr, nullptr, &loop};
+  f.add = [&](gtx_ctx *ctx, const TextPump::Block &b) {
+    int ticket = -1;
+    // a short stream: the host loop is done before the device has the text
+    const bool here = first_block && b.text != loop.first->data() && b.bytes < TextPolicy().threshold_bytes && loop.packer->SourceAtEnd();
+    if (b.text != loop.first->data()) first_block = false;
+    // (counted with the blocks that came back: the trace says how many blocks the loop rendered, whichever way they got to it)
+    if (here) { loop.pump->SettleAll(); ++*loop.came_back; HostBlock(b.text, b.bytes, b.first_line, render); return ticket; }
+    DieGtx(ctx, gtx_rewrite_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
+    return ticket;
+  };
+  f.result = [&](gtx_ctx *ctx, int ticket, const TextPump::Block &b) {
+    const size_t cap = gtx_rewrite_max_bytes(b.bytes, b.n_lines);
+    char *p = out.Reserve(ctx, cap);
+    int redo = 0; size_t got = 0;
+    DieGtx(ctx, gtx_rewrite_result(ctx, ticket, &redo, p, cap, &got, NULL));
+    if (!redo && got) fwrite(p, 1, got, stdout);
+    return redo != 0;
+  };
+  DeviceTextLoop(set, f, render);
 }
 
 void Run(GenomicRegionSet *set, const RegionOp &op)
@@ -291,55 +316,31 @@ int gtx_host::WriteSink(void *user, const char *text, size_t bytes) { return fwr
 
 namespace {
 
-// the set's text block by block through gtx_windows_text; gtx_windows_result streams a block's windows to stdout, in block order.  A
-// block that comes back is rendered here, alone, and the next one goes to the device again
+// the set's text through gtx_windows_text; gtx_windows_result streams a block's windows to stdout (DeviceTextLoop)
 void WindowsTextLoop(GenomicRegionSet *set, const WindowsOp &op, const Renderer &render)
 {
-  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
-  std::string first; long int first_no = 0;
-  LineSource *src = set->DetachStream(&first, &first_no);
-  if (first_no <= 0) return;
-  ChromTable chroms;
-  chroms.Freeze();
   gtx_windows_op dev; memset(&dev, 0, sizeof dev);
   dev.win_size = op.size; dev.win_step = op.step; dev.small = op.small ? 1 : 0;
-  PackOptions opt;
-  opt.chroms = &chroms;
-  BedPacker packer(src, opt);
-  TextPump pump(packer, opt);
-  long int on_device = 0, came_back = 0;
-  pump.settle = [&](const TextPump::Block &b, int ticket) {
-    int redo = 0;
-    DieGtx(ctx, gtx_windows_result(ctx, ticket, &redo, WriteSink, stdout, NULL, NULL));
-    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render); }
-    else on_device++;
-    return true;
-  };
-  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
+  LineFamily f{"[gtx windows] blocks expanded on the device", false, false, {}, nullptr, nullptr, NULL};
+  f.add = [&](gtx_ctx *ctx, const TextPump::Block &b) {
     int ticket = -1;
     DieGtx(ctx, gtx_windows_text(ctx, b.text, b.bytes, b.n_lines, &dev, &ticket));
     return ticket;
   };
-  // the line the set's constructor has read for its format check: a block of one line
-  first += '\n';
-  TextPump::Block &one = pump.blk[0];
-  one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
-  pump.Add(0);
-  pump.Run(1);
-  fflush(stdout);
-  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx windows] blocks expanded on the device: %ld, came back: %ld\n", on_device, came_back);
+  f.result = [](gtx_ctx *ctx, int ticket, const TextPump::Block &) {
+    int redo = 0;
+    DieGtx(ctx, gtx_windows_result(ctx, ticket, &redo, WriteSink, stdout, NULL, NULL));
+    return redo != 0;
+  };
+  DeviceTextLoop(set, f, render);
 }
 
 // May the set's text go to the device?  Whatever its size -- the output, not the input, decides what a run costs -- on one GPU, with
 // a size and a step the device's arithmetic takes
 bool WindowsUsable(const WindowsOp &op)
 {
-  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
-  if (gtx_group_size(devices) != 1) return false;
-  if (g_pool_future.valid()) g_pool_future.get();
-  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
   const long int lim = 1L << 31;
-  return op.size >= 1 && op.size <= lim && op.step <= lim;
+  return OneGpuWithPool() && op.size >= 1 && op.size <= lim && op.step <= lim;
 }
 
 // ---- bed, reg ------------------------------------------------------------------------------------------------------------------
@@ -398,63 +399,35 @@ void RenderReg(std::string &out, GenomicRegion *r, bool compact)
 // May the set's text go to the device?  Whatever its size, on one GPU, with a colour the device's constant piece holds
 bool ConvertUsable(const ConvertSpec &spec)
 {
-  gtx_group *devices = Devices();                                 // (before anything is printed: without a GPU the run ends here)
-  if (gtx_group_size(devices) != 1) return false;
-  if (g_pool_future.valid()) g_pool_future.get();
-  if (!g_pool.buf[0] || !g_pool.buf[1]) return false;
+  if (!OneGpuWithPool()) return false;
   int32_t max_color = 0;
   gtx_convert_limits(NULL, NULL, &max_color);
   return spec.color.size() <= (size_t)max_color;
 }
 
-// the set's text block by block through gtx_convert_text, the printed text to stdout in block order; a block that comes back is
-// rendered here, alone, and the next one goes to the device again
+// the set's text through gtx_convert_text, the printed text to stdout (DeviceTextLoop)
 void ConvertTextLoop(GenomicRegionSet *set, const ConvertSpec &spec, const Renderer &render)
 {
-  gtx_ctx *ctx = gtx_group_ctx(Devices(), 0);
-  const std::string format = set->format;
-  const uint32_t fmt = format == "SAM" ? GTX_TEXT_SAM : format == "GFF" ? GTX_TEXT_GFF : 0u;
-  std::string first; long int first_no = 0;
-  LineSource *src = set->DetachStream(&first, &first_no);
-  if (first_no <= 0) return;
-  ChromTable chroms;
-  chroms.Freeze();
+  const bool sam = set->format == "SAM", gff = set->format == "GFF";
+  const uint32_t fmt = sam ? GTX_TEXT_SAM : gff ? GTX_TEXT_GFF : 0u;
   gtx_convert_op dev; memset(&dev, 0, sizeof dev);
   dev.to = spec.to_reg ? GTX_CONVERT_REG : GTX_CONVERT_BED; dev.ucsc_names = spec.ucsc ? 1 : 0; dev.color = spec.to_reg ? NULL : spec.color.c_str();
-  PackOptions opt;
-  opt.chroms = &chroms; opt.sam = format == "SAM"; opt.gff = format == "GFF";
-  BedPacker packer(src, opt);
-  TextPump pump(packer, opt);
-  long int on_device = 0, came_back = 0;
-  char *out = NULL; size_t out_cap = 0;
-  pump.settle = [&](const TextPump::Block &b, int ticket) {
-    const size_t need = gtx_convert_max_bytes(b.bytes, b.n_lines, &dev);
-    if (need > out_cap) {
-      if (out) gtx_host_free(ctx, out);
-      out_cap = need + (need >> 3);
-      out = (char *)gtx_host_alloc(ctx, out_cap);
-      if (!out) DieGtx(ctx, GTX_E_HIP);
-    }
-    int redo = 0; size_t got = 0;
-    DieGtx(ctx, gtx_convert_result(ctx, ticket, &redo, out, out_cap, &got, NULL));
-    if (redo) { came_back++; HostBlock(b.text, b.bytes, b.first_line, render, format); }
-    else { on_device++; if (got) fwrite(out, 1, got, stdout); }
-    return true;
-  };
-  pump.add = [&](const TextPump::Block &b, const gtx_text_rules &) {
+  PinnedOut out;
+  LineFamily f{"[gtx convert] blocks converted on the device", sam, gff, {}, nullptr, nullptr, NULL};
+  f.add = [&](gtx_ctx *ctx, const TextPump::Block &b) {
     int ticket = -1;
     DieGtx(ctx, gtx_convert_text(ctx, b.text, b.bytes, b.n_lines, &dev, fmt, &ticket));
     return ticket;
   };
-  // the line the set's constructor has read for its format check: a block of one line
-  first += '\n';
-  TextPump::Block &one = pump.blk[0];
-  one.text = &first[0]; one.bytes = first.size(); one.first_line = first_no; one.n_lines = 1; one.have_prev = false;
-  pump.Add(0);
-  pump.Run(1);
-  if (out) gtx_host_free(ctx, out);
-  fflush(stdout);
-  if (getenv("GTX_TEXT_TRACE")) fprintf(stderr, "[gtx convert] blocks converted on the device: %ld, came back: %ld\n", on_device, came_back);
+  f.result = [&](gtx_ctx *ctx, int ticket, const TextPump::Block &b) {
+    const size_t cap = gtx_convert_max_bytes(b.bytes, b.n_lines, &dev);
+    char *p = out.Reserve(ctx, cap);
+    int redo = 0; size_t got = 0;
+    DieGtx(ctx, gtx_convert_result(ctx, ticket, &redo, p, cap, &got, NULL));
+    if (!redo && got) fwrite(p, 1, got, stdout);
+    return redo != 0;
+  };
+  DeviceTextLoop(set, f, render);
 }
 
 void RunConvert(GenomicRegionSet *set, const ConvertSpec &spec, const std::string &front)

@@ -4,18 +4,17 @@
 // Count, prefix, emit over tiles of kRewriteTile lines, one line per lane, a tile per block; the block's text is on the device with
 // its newline index and the tokenizer's triples (launch_tokenize, gtx_text.h):
 //
-//   rewrite_plan_kernel   the tile's text staged in LDS (coalesced 16-byte loads).  A lane walks its line with the predicate the
+//   rewrite_plan_kernel   the tile's text staged in LDS (stage_text, gtx_lineout.h).  A lane walks its line with the predicate the
 //                         subset's gather uses (verbatim_line, gtx_textline.h: the line is plain), which hands it columns 2, 3 and 6,
 //                         applies the operation in signed 64-bit arithmetic and records kept / dropped, s' - 1, e', the length of
 //                         column 1, where the tail begins and the output length (RewriteRec).  The tile's bytes and lines go to
 //                         tileBytes / tileLines.  `bounds` takes the chromosome from the tokenizer's class of the line (its hash
 //                         table of the names); the other operations never look at the name
 //   launch_tile_prefix    (gtx_compact.h) twice: exclusive sums of the tiles' bytes and lines
-//   rewrite_emit_kernel   a tile's kept lines are one run of the output.  The tile's text is staged again, the run is built in LDS --
-//                         column 1 copied, two signed decimals rendered, the tail copied with its newline -- at the run's offset
-//                         inside its first 16-byte unit of the output, and goes out with aligned 16-byte stores; the bytes that
-//                         share a unit with the tile in front or behind go out one by one.  A tile without a kept line returns
-//                         before it loads anything
+//   rewrite_emit_kernel   a tile's kept lines are one run of the output.  The tile's text is staged again, the lines are placed
+//                         (tile_exclusive), the run is built in LDS -- column 1 copied, two signed decimals rendered, the tail
+//                         copied with its newline -- and goes out through store_run (gtx_lineout.h, which has the scheme of the
+//                         store).  A tile without a kept line returns before it loads anything
 //
 // A tile whose text, or whose run, is longer than kRewriteStage bytes makes the block not plain (flag 32), as a line outside the
 // predicate does (flag 16): the emit pass writes nothing of such a block.  (The prefixes still sum the tiles that were planned;

@@ -2,27 +2,23 @@
 #include "gtx_rewrite.h"
 #include "gtx_compact.h"
 #include "gtx_textline.h"
+#include "gtx_lineout.h"
 
 namespace gtx {
 namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-typedef unsigned uint32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kStageBytes = kRewriteStage + 32;   // a stage begins at the 16-byte line below its first byte and is filled in whole units
 
 using gtxtext::signed_len;
 using gtxtext::put_signed;
-
-// the text of lines [j0, j1) into lds, from the 16-byte line below its first byte: lds[k] = text[a0 + k]
-__device__ __forceinline__ void stage_text(unsigned char *lds, const char *__restrict__ text, size_t bytes, size_t a0, size_t t1)
-{
-  for (size_t k = (size_t)threadIdx.x * 16; a0 + k < t1; k += (size_t)kRewriteTile * 16) {
-    if (a0 + k + 16 <= bytes) *(uint32x4 *)(lds + k) = *(const uint32x4 *)(text + a0 + k);
-    else for (size_t q = 0; a0 + k + q < bytes; q++) lds[k + q] = (unsigned char)text[a0 + k + q];
-  }
-}
+using gtxline::line_begin;
+using gtxline::stage_text;
+using gtxline::tile_total;
+using gtxline::tile_exclusive;
+using gtxline::store_run;
 
 // the operation on (s, e) of a line on `strand` whose tokenizer class is cls; false: the line is dropped
 __device__ __forceinline__ bool apply(const RewriteOp &op, int strand, int cls, i64 &s, i64 &e)
@@ -59,19 +55,19 @@ __global__ __launch_bounds__(kRewriteTile) void rewrite_plan_kernel(RewriteDevic
   const unsigned tile = blockIdx.x, j0 = tile * kRewriteTile, j1 = min(j0 + kRewriteTile, d.nLines);
   // the tokenizer's verdict: nl[] may hold nothing to go by
   if (*d.flag & 7) { if (threadIdx.x == 0) { d.tileBytes[tile] = 0; d.tileLines[tile] = 0; } return; }
-  const size_t t0 = j0 ? (size_t)d.nl[j0 - 1] + 1 : 0, t1 = (size_t)d.nl[j1 - 1] + 1;
+  const size_t t0 = line_begin(d.nl, j0), t1 = (size_t)d.nl[j1 - 1] + 1;
   if (t1 - t0 > (size_t)kRewriteStage) {                          // (the same in every thread of the block)
     if (threadIdx.x == 0) { atomicOr(d.flag, 32); d.tileBytes[tile] = 0; d.tileLines[tile] = 0; }
     return;
   }
   if (threadIdx.x == 0) { sBytes = 0; sLines = 0; }
   const size_t a0 = t0 & ~(size_t)15;
-  stage_text(in, d.text, d.bytes, a0, t1);
+  stage_text<kRewriteTile>(in, d.text, d.bytes, a0, t1);
   __syncthreads();
   const unsigned j = j0 + threadIdx.x;
   unsigned len = 0;
   if (j < j1) {
-    const unsigned b = (unsigned)((j ? (size_t)d.nl[j - 1] + 1 : 0) - a0), e = (unsigned)((size_t)d.nl[j] - a0);
+    const unsigned b = (unsigned)(line_begin(d.nl, j) - a0), e = (unsigned)((size_t)d.nl[j] - a0);
     gtxtext::LineCols c;
     RewriteRec r; r.s0 = 0; r.e1 = 0; r.nameLen = 0; r.tailOff = 0; r.outLen = 0; r.pad = 0;
     if (!gtxtext::verbatim_line((const unsigned char *)in, b, e, c)) atomicOr(d.flag, 16);
@@ -86,11 +82,9 @@ __global__ __launch_bounds__(kRewriteTile) void rewrite_plan_kernel(RewriteDevic
     len = r.outLen;
   }
   // the tile's totals: per wave in registers, then one add per wave
-  unsigned sum = len;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  tile_total(len, &sBytes);
   const u64 kept = __ballot(len != 0);
-  if ((threadIdx.x & 63) == 0) { atomicAdd(&sBytes, sum); atomicAdd(&sLines, (unsigned)__popcll(kept)); }
+  if ((threadIdx.x & 63) == 0) atomicAdd(&sLines, (unsigned)__popcll(kept));
   __syncthreads();
   if (threadIdx.x == 0) {
     if (sBytes > (unsigned)kRewriteStage) atomicOr(d.flag, 32);
@@ -107,22 +101,15 @@ __global__ __launch_bounds__(kRewriteTile) void rewrite_emit_kernel(RewriteDevic
   const unsigned tile = blockIdx.x, j0 = tile * kRewriteTile, j1 = min(j0 + kRewriteTile, d.nLines);
   const i64 lo = d.baseBytes[tile], hi = d.baseBytes[tile + 1];
   if (hi == lo) return;                                           // nothing kept here
-  const size_t t0 = j0 ? (size_t)d.nl[j0 - 1] + 1 : 0, t1 = (size_t)d.nl[j1 - 1] + 1, a0 = t0 & ~(size_t)15;
-  stage_text(in, d.text, d.bytes, a0, t1);
+  const size_t t0 = line_begin(d.nl, j0), t1 = (size_t)d.nl[j1 - 1] + 1, a0 = t0 & ~(size_t)15;
+  stage_text<kRewriteTile>(in, d.text, d.bytes, a0, t1);
   const unsigned j = j0 + threadIdx.x;
   RewriteRec r; r.outLen = 0;
   if (j < j1) r = d.rec[j];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned incl = r.outLen;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(incl, o); if (lane >= o) incl += up; }
-  if (lane == 63) waveSum[w] = incl;
-  __syncthreads();
-  unsigned at = incl - r.outLen;                                  // where the line begins inside the run
-  for (int k = 0; k < w; k++) at += waveSum[k];
-  const unsigned pad = (unsigned)(lo & 15), total = (unsigned)(hi - lo);   // run[k] is byte lo - pad + k of the output; pad + total <= 15 + kRewriteStage
+  const unsigned at = tile_exclusive<kRewriteTile>(r.outLen, waveSum);   // where the line begins inside the run (its barrier: `in` is staged)
+  const unsigned pad = (unsigned)(lo & 15);                       // run[k] is byte lo - pad + k of the output; pad + (hi - lo) <= 15 + kRewriteStage
   if (r.outLen) {
-    const unsigned b = (unsigned)((j ? (size_t)d.nl[j - 1] + 1 : 0) - a0), e = (unsigned)((size_t)d.nl[j] - a0);
+    const unsigned b = (unsigned)(line_begin(d.nl, j) - a0), e = (unsigned)((size_t)d.nl[j] - a0);
     unsigned char *p = run + pad + at;
     for (unsigned k = 0; k < r.nameLen; k++) p[k] = in[b + k];
     p += r.nameLen;
@@ -133,12 +120,7 @@ __global__ __launch_bounds__(kRewriteTile) void rewrite_emit_kernel(RewriteDevic
     for (unsigned k = b + r.tailOff; k <= e; k++) *p++ = in[k];   // the tail, the newline included
   }
   __syncthreads();
-  char *__restrict__ out = d.out + (lo - pad);
-  const unsigned end = pad + total;
-  for (unsigned k = threadIdx.x * 16; k < end; k += kRewriteTile * 16) {
-    if (k >= pad && k + 16 <= end) *(uint32x4 *)(out + k) = *(const uint32x4 *)(run + k);
-    else for (unsigned q = max(k, pad); q < min(k + 16, end); q++) out[q] = (char)run[q];   // the units shared with the tiles in front and behind
-  }
+  store_run<kRewriteTile>(d.out, run, lo, (unsigned)(hi - lo));
 }
 
 }  // namespace

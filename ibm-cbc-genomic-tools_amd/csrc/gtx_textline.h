@@ -1,6 +1,8 @@
 // gtx_textline.h -- the one predicate "GenomicRegionBED::Print would render this line as it stands" (see gtx_text.h), for the
 // kernels that write text out from text in: the subset's gather (gtx_text.hip), the column rewrite (gtx_rewrite.hip), the sliding
-// windows (gtx_windows.hip) and the format conversion of BED lines (gtx_convert.hip); and the decimals the last three render.  Device code.
+// windows (gtx_windows.hip) and the format conversion of BED lines (gtx_convert.hip); and the decimals (digits, signed_len,
+// put_signed) that the last three and the block operations (gtx_blocks.hip, which has a grammar of its own) render.  What these
+// kernels share of a tile's staging, scan and store is in gtx_lineout.h.  Device code.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -14,13 +14,14 @@
 // do with the input's -- one chromosome line is a hundred million windows, a read two or three -- so the passes are input-driven as
 // far as the plan goes and output-driven from there:
 //
-//   windows_plan_kernel    tiles of kWindowsLineTile lines, one per lane, the tile's text staged in LDS (the column rewrite's shape,
-//                          gtx_rewrite.h).  verbatim_line (gtx_textline.h) decides whether a line is plain; a plain line's record
+//   windows_plan_kernel    tiles of kWindowsLineTile lines, one per lane, the tile's text staged in LDS (stage_text, gtx_lineout.h:
+//                          the column rewrite's shape).  verbatim_line (gtx_textline.h) decides whether a line is plain; a plain line's record
 //                          (WindowsRec) holds n, c, v2, STOP, where its name and tail lie in the block's text and how long they are.
 //                          The tile's windows and bytes go to tileWindows / tileBytes, 64-bit both: one line can exceed 2^32 in either
 //   launch_tile_prefix64   (gtx_compact.h) twice: exclusive sums of the tiles' windows and bytes
 //   windows_base_kernel    a tile's lines once more: lineWin[j], lineByte[j] = the windows and bytes in front of line j in the block
-//                          (the tile's base plus a scan over its 256 lines); entry nLines holds the totals
+//                          (the tile's base plus tile_exclusive over its 256 lines, both sums in one scan); entry nLines holds
+//                          the totals
 //   windows_emit_kernel    one block of threads per output tile of kWindowsOutTile consecutive window ordinals of the block of text,
 //                          over a range of such tiles (the caller streams ranges, gtx_windows_result).  The block finds the line of
 //                          its first ordinal by a search over lineWin, 64 probes a step, and holds the bases of the kWindowsSpan
@@ -28,7 +29,7 @@
 //                          and the k of its windows there (else in global memory, between the first line and the last), their
 //                          byte offsets from lineByte and the closed form, and renders them
 //                          into the tile's run in LDS: name and tail from the block's text, the numbers with put_signed.  The run
-//                          goes out with aligned 16-byte stores; bytes that share a unit with a neighbouring tile go out one by one.
+//                          goes out through store_run (gtx_lineout.h), at its place in the range's buffer.
 //                          A tile may lie inside one line, hold part of a line and hundreds of short ones, or cross any number of
 //                          line tiles (lines without a window take no room in it): all the same to the search
 //

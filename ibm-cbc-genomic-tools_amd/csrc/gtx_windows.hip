@@ -2,15 +2,21 @@
 #include "gtx_windows.h"
 #include "gtx_compact.h"
 #include "gtx_textline.h"
+#include "gtx_lineout.h"
 
 namespace gtx {
 namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-typedef unsigned uint32x4 __attribute__((ext_vector_type(4)));
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
 using gtxtext::digits;
 using gtxtext::put_signed;
+using gtxline::line_begin;
+using gtxline::stage_text;
+using gtxline::tile_total;
+using gtxline::tile_exclusive;
+using gtxline::store_run;
 
 constexpr int kStageBytes = kWindowsStage + 32;   // a stage begins at the 16-byte line below its first byte and is filled in whole units
 constexpr int kRunBytes = kWindowsRunBytes + 32;  // ... and so does a run
@@ -84,22 +90,19 @@ __global__ __launch_bounds__(kWindowsLineTile) void windows_plan_kernel(WindowsD
   const unsigned tile = blockIdx.x, j0 = tile * kWindowsLineTile, j1 = min(j0 + kWindowsLineTile, d.nLines);
   // the tokenizer's verdict: nl[] may hold nothing to go by
   if (*d.flag & 7) { if (threadIdx.x == 0) { d.tileBytes[tile] = 0; d.tileWindows[tile] = 0; } return; }
-  const size_t t0 = j0 ? (size_t)d.nl[j0 - 1] + 1 : 0, t1 = (size_t)d.nl[j1 - 1] + 1;
+  const size_t t0 = line_begin(d.nl, j0), t1 = (size_t)d.nl[j1 - 1] + 1;
   if (t1 - t0 > (size_t)kWindowsStage) {                          // (the same in every thread of the block)
     if (threadIdx.x == 0) { atomicOr(d.flag, 32); d.tileBytes[tile] = 0; d.tileWindows[tile] = 0; }
     return;
   }
   if (threadIdx.x == 0) { sBytes = 0; sWindows = 0; }
   const size_t a0 = t0 & ~(size_t)15;
-  for (size_t k = (size_t)threadIdx.x * 16; a0 + k < t1; k += (size_t)kWindowsLineTile * 16) {
-    if (a0 + k + 16 <= d.bytes) *(uint32x4 *)(in + k) = *(const uint32x4 *)(d.text + a0 + k);
-    else for (size_t q = 0; a0 + k + q < d.bytes; q++) in[k + q] = (unsigned char)d.text[a0 + k + q];
-  }
+  stage_text<kWindowsLineTile>(in, d.text, d.bytes, a0, t1);
   __syncthreads();
   const unsigned j = j0 + threadIdx.x;
   i64 nWin = 0, nBytes = 0;
   if (j < j1) {
-    const unsigned b = (unsigned)((j ? (size_t)d.nl[j - 1] + 1 : 0) - a0), e = (unsigned)((size_t)d.nl[j] - a0);
+    const unsigned b = (unsigned)(line_begin(d.nl, j) - a0), e = (unsigned)((size_t)d.nl[j] - a0);
     gtxtext::LineCols c;
     WindowsRec r; r.n = 0; r.c = 0; r.bytes = 0; r.v2 = 0; r.stop = 0; r.nameOff = 0; r.tailOff = 0; r.nameLen = 0; r.tailLen = 0;
     if (!gtxtext::verbatim_line((const unsigned char *)in, b, e, c) || c.v2 >= 2147483645ll || c.v3 >= 2147483646ll) atomicOr(d.flag, 16);
@@ -120,9 +123,8 @@ __global__ __launch_bounds__(kWindowsLineTile) void windows_plan_kernel(WindowsD
     nWin = r.n; nBytes = r.bytes;
   }
   // the tile's totals: per wave in registers, then one add per wave
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { nWin += __shfl_xor(nWin, o); nBytes += __shfl_xor(nBytes, o); }
-  if ((threadIdx.x & 63) == 0) { atomicAdd(&sBytes, (u64)nBytes); atomicAdd(&sWindows, (u64)nWin); }
+  tile_total((u64)nBytes, &sBytes);
+  tile_total((u64)nWin, &sWindows);
   __syncthreads();
   if (threadIdx.x == 0) { d.tileBytes[tile] = sBytes; d.tileWindows[tile] = sWindows; }
 }
@@ -130,22 +132,13 @@ __global__ __launch_bounds__(kWindowsLineTile) void windows_plan_kernel(WindowsD
 // lineWin / lineByte of a tile's lines: the tile's bases plus the exclusive scan over its lines
 __global__ __launch_bounds__(kWindowsLineTile) void windows_base_kernel(WindowsDevice d)
 {
-  __shared__ i64 waveWin[kWindowsLineTile / 64], waveByte[kWindowsLineTile / 64];
+  __shared__ i64x2 waveSum[kWindowsLineTile / 64];                // (windows, bytes) of a wave
   if (*d.flag) return;
   const unsigned tile = blockIdx.x, j = tile * kWindowsLineTile + threadIdx.x;
   i64 n = 0, by = 0;
   if (j < d.nLines) { n = d.rec[j].n; by = d.rec[j].bytes; }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  i64 inclN = n, inclB = by;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const i64 upN = __shfl_up(inclN, o), upB = __shfl_up(inclB, o);
-    if (lane >= o) { inclN += upN; inclB += upB; }
-  }
-  if (lane == 63) { waveWin[w] = inclN; waveByte[w] = inclB; }
-  __syncthreads();
-  i64 atN = d.baseWindows[tile] + inclN - n, atB = d.baseBytes[tile] + inclB - by;
-  for (int k = 0; k < w; k++) { atN += waveWin[k]; atB += waveByte[k]; }
+  const i64x2 at = tile_exclusive<kWindowsLineTile>(i64x2{n, by}, waveSum);   // both sums in one scan, behind one barrier
+  const i64 atN = d.baseWindows[tile] + at.x, atB = d.baseBytes[tile] + at.y;
   if (j < d.nLines) { d.lineWin[j] = atN; d.lineByte[j] = atB; }
   if (j + 1 == d.nLines) { d.lineWin[d.nLines] = atN + n; d.lineByte[d.nLines] = atB + by; }
 }
@@ -193,7 +186,7 @@ __global__ __launch_bounds__(kWindowsThreads) void windows_emit_kernel(WindowsDe
   __syncthreads();
   const i64 lo = sLo, hi = sHi;
   const i64 at = lo - rg.base;                                    // where the run begins in the range's buffer
-  const unsigned pad = (unsigned)(at & 15), end = pad + (unsigned)(hi - lo);   // run[q] is byte at - pad + q of the buffer; end <= 15 + kWindowsRunBytes
+  const unsigned pad = (unsigned)(at & 15);                       // run[q] is byte at - pad + q of the buffer; pad + (hi - lo) <= 15 + kWindowsRunBytes
 #pragma unroll
   for (int i = 0; i < kWindowsPerLane; i++) {
     if (len[i] == 0) continue;
@@ -211,11 +204,7 @@ __global__ __launch_bounds__(kWindowsThreads) void windows_emit_kernel(WindowsDe
     p[r.tailLen] = '\n';
   }
   __syncthreads();
-  char *__restrict__ out = rg.out + (at - pad);
-  for (unsigned q = threadIdx.x * 16; q < end; q += kWindowsThreads * 16) {
-    if (q >= pad && q + 16 <= end) *(uint32x4 *)(out + q) = *(const uint32x4 *)(run + q);
-    else for (unsigned b = max(q, pad); b < min(q + 16, end); b++) out[b] = (char)run[b];   // the units shared with the tiles in front and behind
-  }
+  store_run<kWindowsThreads>(rg.out, run, at, (unsigned)(hi - lo));
   if (threadIdx.x == 0 && (blockIdx.x + 1 == gridDim.x)) *rg.rangeBytes = (u64)(hi - rg.base);
 }
 

@@ -465,6 +465,37 @@ def _text_format(sam, fmt=None):
     return TEXT_SAM if sam else 0
 
 
+def _two_in_flight(blocks, send, collect):
+    """The loop of the calls that hand a block of text over under a ticket and fetch its result later: send(text) -> ticket for every
+    block, collect(text, ticket) -> the block's result, two tickets in flight, the results in block order.  When either raises a
+    GtxError the blocks still in flight are fetched to be forgotten (collect(text, ticket, drop=True); the block whose call failed
+    is dropped by that call itself), so that the engine holds no block of the call, and the error is raised again."""
+    tickets, results = [], []
+    try:
+        for text in blocks:
+            if len(tickets) == 2:
+                results.append(collect(*tickets.pop(0)))
+            tickets.append((text, send(text)))
+        while tickets:
+            results.append(collect(*tickets.pop(0)))
+    except GtxError:
+        for x in tickets:
+            collect(*x, drop=True)
+        raise
+    return results
+
+
+def _guarded_out(cap, guard):
+    """a caller's buffer of cap bytes with `guard` bytes of 0xA5 behind it, and intact(n): whether the bytes behind the 16-byte unit
+    that a text of n bytes ends in are still what they were"""
+    out = ctypes.create_string_buffer(b"\xa5" * (cap + guard), cap + guard)
+
+    def intact(n):
+        behind = (n + 15) // 16 * 16
+        return out.raw[behind:] == b"\xa5" * (cap + guard - behind)
+    return out, intact
+
+
 class Engine:
     """One context on one GPU (one per process in multi-GPU runs)."""
 
@@ -578,104 +609,100 @@ class Engine:
         """the same through gtx_coverage_begin / gtx_coverage_add_text / gtx_coverage_end: (coverage, info, verdicts)"""
         return self._reduce_text("coverage", blocks, rules, flags, sam, fmt)
 
+    def _result_into(self, result, t, cap, guard, drop):
+        """gtx_*_result(ctx, t, &needs_host, out, cap, &bytes, &lines) into a guarded buffer: (needs_host, the text, the lines,
+        whether the guard is whole); drop: the block is fetched to be forgotten, whatever the call says"""
+        redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
+        out, intact = _guarded_out(cap, guard)
+        rc = result(self.ctx, t, ctypes.byref(redo), out, cap, ctypes.byref(nb), ctypes.byref(ns))
+        if drop:
+            return None
+        self._chk(rc)
+        return redo.value, out.raw[:nb.value], ns.value, intact(nb.value)
+
+    def _result_sink(self, name, result, t, drop, refuse=lambda: False):
+        """gtx_*_result(ctx, t, &needs_host, sink, user, &lines, &bytes) into a sink that collects the text: (needs_host, the text,
+        the lines, the number of sink calls).  The sink refuses a call when refuse() says so, and every call of a dropped block."""
+        parts, calls = [], [0]
+
+        def take(user, p, n):
+            calls[0] += 1
+            if drop or refuse():
+                return 1
+            parts.append(ctypes.string_at(p, n))
+            return 0
+        redo, nl, nb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = result(self.ctx, t, ctypes.byref(redo), LINES_SINK(take), None, ctypes.byref(nl), ctypes.byref(nb))
+        if drop:
+            return None
+        self._chk(rc)
+        out = b"".join(parts)
+        if nb.value != len(out):
+            raise GtxError("%s: n_bytes %d, the sink was given %d" % (name, nb.value, len(out)))
+        return redo.value, out, nl.value, calls[0]
+
     def subset_text(self, blocks, rules, flags=0):
         """gtx_subset_text / gtx_subset_result per block of text (bytes of complete lines), two blocks in flight: per block
         (needs_host, the selected text, the number of selected lines); a block that comes back selected nothing."""
-        tickets, results = [], []
-
-        def collect(text, t):
-            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
-            out = ctypes.create_string_buffer(max(len(text), 1))
-            self._chk(self.lib.gtx_subset_result(self.ctx, t, ctypes.byref(redo), out, ctypes.byref(nb), ctypes.byref(ns)))
-            results.append((redo.value, out.raw[:nb.value], ns.value))
-        for text in blocks:
-            if len(tickets) == 2:
-                collect(*tickets.pop(0))
+        def send(text):
             t = ctypes.c_int(-1)
             self._chk(self.lib.gtx_subset_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(rules), int(flags), ctypes.byref(t)))
-            tickets.append((text, t.value))
-        for x in tickets:
-            collect(*x)
-        return results
+            return t.value
+
+        def collect(text, t, drop=False):
+            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
+            out = ctypes.create_string_buffer(max(len(text), 1))
+            rc = self.lib.gtx_subset_result(self.ctx, t, ctypes.byref(redo), out, ctypes.byref(nb), ctypes.byref(ns))
+            if drop:
+                return None
+            self._chk(rc)
+            return redo.value, out.raw[:nb.value], ns.value
+        return _two_in_flight(blocks, send, collect)
 
     def rewrite_text(self, blocks, op, guard=64):
         """gtx_rewrite_text / gtx_rewrite_result per block of text (bytes of complete lines), two blocks in flight: per block
         (needs_host, the printed text, the number of printed lines, whether the bytes behind the text's 16-byte unit were left
         alone).  out is gtx_rewrite_max_bytes long, rounded up to 16, with `guard` bytes of 0xA5 behind it: the caller's buffer, not the
         device buffer the kernels store into."""
-        tickets, results = [], []
-
-        def collect(text, t):
-            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
-            cap = (int(self.lib.gtx_rewrite_max_bytes(len(text), text.count(b"\n"))) + 15) // 16 * 16
-            out = ctypes.create_string_buffer(b"\xa5" * (cap + guard), cap + guard)
-            self._chk(self.lib.gtx_rewrite_result(self.ctx, t, ctypes.byref(redo), out, cap, ctypes.byref(nb), ctypes.byref(ns)))
-            raw = out.raw
-            behind = (nb.value + 15) // 16 * 16
-            results.append((redo.value, raw[:nb.value], ns.value, raw[behind:] == b"\xa5" * (cap + guard - behind)))
-        for text in blocks:
-            if len(tickets) == 2:
-                collect(*tickets.pop(0))
+        def send(text):
             t = ctypes.c_int(-1)
             self._chk(self.lib.gtx_rewrite_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
-            tickets.append((text, t.value))
-        for x in tickets:
-            collect(*x)
-        return results
+            return t.value
+
+        def collect(text, t, drop=False):
+            cap = (int(self.lib.gtx_rewrite_max_bytes(len(text), text.count(b"\n"))) + 15) // 16 * 16
+            return self._result_into(self.lib.gtx_rewrite_result, t, cap, guard, drop)
+        return _two_in_flight(blocks, send, collect)
 
     def convert_text(self, blocks, op, fmt=0, guard=64):
         """gtx_convert_text / gtx_convert_result per block of text (bytes of complete lines; fmt: 0 for BED, TEXT_SAM or TEXT_GFF), two
         blocks in flight: per block (needs_host, the printed text, the number of printed lines, whether the bytes behind the text's
         16-byte unit were left alone).  out is gtx_convert_max_bytes long, rounded up to 16, with `guard` bytes of 0xA5 behind it:
         the caller's buffer, not the device buffer the kernels store into."""
-        tickets, results = [], []
-
-        def collect(text, t):
-            redo, nb, ns = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int64(0)
-            cap = (int(self.lib.gtx_convert_max_bytes(len(text), text.count(b"\n"), ctypes.byref(op))) + 15) // 16 * 16
-            out = ctypes.create_string_buffer(b"\xa5" * (cap + guard), cap + guard)
-            self._chk(self.lib.gtx_convert_result(self.ctx, t, ctypes.byref(redo), out, cap, ctypes.byref(nb), ctypes.byref(ns)))
-            raw = out.raw
-            behind = (nb.value + 15) // 16 * 16
-            results.append((redo.value, raw[:nb.value], ns.value, raw[behind:] == b"\xa5" * (cap + guard - behind)))
-        for text in blocks:
-            if len(tickets) == 2:
-                collect(*tickets.pop(0))
+        def send(text):
             t = ctypes.c_int(-1)
             self._chk(self.lib.gtx_convert_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), int(fmt), ctypes.byref(t)))
-            tickets.append((text, t.value))
-        for x in tickets:
-            collect(*x)
-        return results
+            return t.value
+
+        def collect(text, t, drop=False):
+            cap = (int(self.lib.gtx_convert_max_bytes(len(text), text.count(b"\n"), ctypes.byref(op))) + 15) // 16 * 16
+            return self._result_into(self.lib.gtx_convert_result, t, cap, guard, drop)
+        return _two_in_flight(blocks, send, collect)
 
     def blocks_text(self, blocks, op, chunk=None):
         """gtx_blocks_text / gtx_blocks_result per block of text (bytes of complete lines), two blocks in flight: per block
         (needs_host, the printed text, the number of printed lines, the number of sink calls).  chunk: gtx_set_lines_chunk first."""
         if chunk is not None:
             self.set_lines_chunk(chunk)
-        tickets, results = [], []
 
-        def collect(t):
-            parts = []
-
-            def take(user, p, n):
-                parts.append(ctypes.string_at(p, n))
-                return 0
-            redo, np_, nb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
-            self._chk(self.lib.gtx_blocks_result(self.ctx, t, ctypes.byref(redo), LINES_SINK(take), None, ctypes.byref(np_), ctypes.byref(nb)))
-            out = b"".join(parts)
-            if nb.value != len(out):
-                raise GtxError("gtx_blocks_result: n_bytes %d, the sink was given %d" % (nb.value, len(out)))
-            results.append((redo.value, out, np_.value, len(parts)))
-        for text in blocks:
-            if len(tickets) == 2:
-                collect(tickets.pop(0))
+        def send(text):
             t = ctypes.c_int(-1)
             self._chk(self.lib.gtx_blocks_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
-            tickets.append(t.value)
-        while tickets:
-            collect(tickets.pop(0))
-        return results
+            return t.value
+
+        def collect(text, t, drop=False):
+            return self._result_sink("gtx_blocks_result", self.lib.gtx_blocks_result, t, drop)
+        return _two_in_flight(blocks, send, collect)
 
     def windows_text(self, blocks, op, chunk=None, refuse_at=None):
         """gtx_windows_text / gtx_windows_result per block of text (bytes of complete lines), two blocks in flight: per block
@@ -684,40 +711,20 @@ class Engine:
         and the GtxError of GTX_E_SINK is raised."""
         if chunk is not None:
             self.set_lines_chunk(chunk)
-        tickets, results, calls = [], [], [0]
+        calls = [0]
 
-        def collect(text, t, refuse=False):
-            parts, mine = [], [0]
+        def refuse():
+            calls[0] += 1
+            return calls[0] == refuse_at
 
-            def take(user, p, n):
-                calls[0] += 1; mine[0] += 1
-                if refuse or calls[0] == refuse_at:
-                    return 1
-                parts.append(ctypes.string_at(p, n))
-                return 0
-            redo, nw, nb = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
-            rc = self.lib.gtx_windows_result(self.ctx, t, ctypes.byref(redo), LINES_SINK(take), None, ctypes.byref(nw), ctypes.byref(nb))
-            if refuse:
-                return
-            self._chk(rc)
-            out = b"".join(parts)
-            if nb.value != len(out):
-                raise GtxError("gtx_windows_result: n_bytes %d, the sink was given %d" % (nb.value, len(out)))
-            results.append((redo.value, out, nw.value, mine[0]))
-        try:
-            for text in blocks:
-                if len(tickets) == 2:
-                    collect(*tickets.pop(0))
-                t = ctypes.c_int(-1)
-                self._chk(self.lib.gtx_windows_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
-                tickets.append((text, t.value))
-            while tickets:
-                collect(*tickets.pop(0))
-        except GtxError:
-            for x in tickets:                                         # (a refused block is dropped by the call itself)
-                collect(*x, refuse=True)
-            raise
-        return results
+        def send(text):
+            t = ctypes.c_int(-1)
+            self._chk(self.lib.gtx_windows_text(self.ctx, text, len(text), text.count(b"\n"), ctypes.byref(op), ctypes.byref(t)))
+            return t.value
+
+        def collect(text, t, drop=False):
+            return self._result_sink("gtx_windows_result", self.lib.gtx_windows_result, t, drop, refuse)
+        return _two_in_flight(blocks, send, collect)
 
     def count(self, reads, weights=None, flags=READS_SORTED):
         reads = _triples(reads)
