@@ -43,6 +43,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "gtx_kernels.h"
+#include "gtx_scan.h"
 
 namespace gtx {
 
@@ -88,19 +89,6 @@ __device__ __forceinline__ void bucket_lookup(const int4 *__restrict__ clsCell, 
   for (int k = 0; k < N; k++) ph[k] = posHi[id[k]];
 #pragma unroll
   for (int k = 0; k < N; k++) while (s[k] > ph[k]) ph[k] = posHi[++id[k]];              // (two cuts inside one cell: rare.  The class's last bucket has posHi = INT_MAX)
-}
-
-// inclusive prefix sum over the 64 lanes by DPP (row shifts, then row broadcasts); call with all lanes active
-__device__ __forceinline__ unsigned wave_prefix(unsigned x)
-{
-  int v = (int)x;
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-  return (unsigned)v;
 }
 
 // LDS: the lookup tables (clsCell, posHi, cellTab); per bucket {reads of this tile, next free place of its chunk, chunks so far}
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(1024, ((WEIGHTED && PER == 4) || LINE) ? 4 : 8) voi
       // the chunk fills up: as many new ones as the rest needs, side by side.  Both running sums (places in the staged tile, pairs
       // of the arena) by wave prefix and one LDS atomic per wave
       const unsigned need = F > room ? F - room : 0u, fresh = (need + kChunk - 1) & ~(unsigned)(kChunk - 1);
-      const unsigned incL = wave_prefix(c), incF = wave_prefix(fresh);
+      const unsigned incL = gtxscan::wave_inclusive_dpp(c), incF = gtxscan::wave_inclusive_dpp(fresh);
       const unsigned totL = (unsigned)__builtin_amdgcn_readlane((int)incL, 63), totF = (unsigned)__builtin_amdgcn_readlane((int)incF, 63);
       unsigned baseL = 0, baseF = 0;
       if (totL) {                                                     // (wave-uniform; the sums are scalars: one lane adds them)
@@ -302,37 +290,15 @@ __global__ __launch_bounds__(256) void chunk_rows_kernel(BucketWork w, unsigned 
 {
   __shared__ unsigned wsum[4];
   unsigned *row = w.chunkCount + (size_t)blockIdx.x * nArenas;
-  const unsigned per = (nArenas + 255) / 256, i0 = threadIdx.x * per;
-  unsigned s = 0;
-  for (unsigned k = 0; k < per; k++) if (i0 + k < nArenas) s += row[i0 + k];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(inc, o); if (lane >= o) inc += up; }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  unsigned run = inc - s;
-  for (int k = 0; k < wv; k++) run += wsum[k];
-  for (unsigned k = 0; k < per; k++) if (i0 + k < nArenas) { const unsigned v = row[i0 + k]; row[i0 + k] = run; run += v; }
-  if (threadIdx.x == 255) w.rowOff[blockIdx.x] = run;             // the bucket's total, turned into its offset by the next kernel
+  const unsigned all = gtxscan::run_exclusive_sum<256>(row, nArenas, row, wsum);
+  if (threadIdx.x == 0) w.rowOff[blockIdx.x] = all;               // the bucket's total, turned into its offset by the next kernel
 }
 
 __global__ __launch_bounds__(1024) void chunk_offsets_kernel(BucketWork w, int nB)
 {
   __shared__ unsigned wsum[16];
-  const int per = (nB + 1023) / 1024, i0 = threadIdx.x * per;
-  unsigned s = 0;
-  for (int k = 0; k < per; k++) if (i0 + k < nB) s += w.rowOff[i0 + k];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(inc, o); if (lane >= o) inc += up; }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  unsigned run = inc - s;
-  for (int k = 0; k < wv; k++) run += wsum[k];
-  for (int k = 0; k < per; k++) if (i0 + k < nB) { const unsigned v = w.rowOff[i0 + k]; w.rowOff[i0 + k] = run; run += v; }
-  if (threadIdx.x == 1023) w.rowOff[nB] = run;
+  const unsigned all = gtxscan::run_exclusive_sum<1024>(w.rowOff, nB, w.rowOff, wsum);
+  if (threadIdx.x == 0) w.rowOff[nB] = all;
 }
 
 // block k: the chunks of its arena into the bucket-major list: entry = chunk << 6 | (fill - 1)
@@ -559,8 +525,9 @@ __global__ __launch_bounds__(1024) void bucket_cover_kernel(CoverArgs cv, Bucket
 // micro-windows in LDS -- no bucket is wider than a few parts.  (pos - 1) / step as in scan_slot (gtx_kernels.hip).
 static constexpr int kScanBins32 = 30720, kScanBins64 = 15360;   // 120 KB of LDS counters
 
+constexpr int kScanHistThreads = 1024;                              // the block of bucket_scanhist_kernel: its launches and its scan agree on it
 template <bool WEIGHTED>
-__global__ __launch_bounds__(1024) void bucket_scanhist_kernel(ScanArgs sc, BucketTable t, BucketWork w, const ScanPart *__restrict__ parts, u64 *__restrict__ out)
+__global__ __launch_bounds__(kScanHistThreads) void bucket_scanhist_kernel(ScanArgs sc, BucketTable t, BucketWork w, const ScanPart *__restrict__ parts, u64 *__restrict__ out)
 {
   typedef typename std::conditional<WEIGHTED, u64, unsigned>::type ct;
   extern __shared__ unsigned char ldsRaw[];
@@ -616,18 +583,12 @@ __global__ __launch_bounds__(1024) void bucket_scanhist_kernel(ScanArgs sc, Buck
     const int comb = sc.comb;
     // the histogram becomes its own inclusive prefix sum (a thread takes `per` consecutive bins -- an odd number, so that the lanes of
     // a wave stay on different banks --, wave scan of the threads' totals, offsets added in a second turn): a window is then two reads
-    __shared__ u64 wtot[16];
+    __shared__ u64 wtot[kScanHistThreads / 64];
     int per = (pt.count + (int)blockDim.x - 1) / (int)blockDim.x; per |= 1;
     const int lo = min((int)threadIdx.x * per, pt.count), hi = min(lo + per, pt.count);
     ct run = 0;
     for (int x = lo; x < hi; x++) { run += h[x]; h[x] = run; }
-    u64 inc = (u64)run;
-#pragma unroll
-    for (int d2 = 1; d2 < 64; d2 <<= 1) { const u64 up = __shfl_up(inc, d2); if ((int)lane >= d2) inc += up; }
-    if (lane == 63) wtot[wv] = inc;
-    __syncthreads();
-    u64 off = inc - (u64)run;
-    for (unsigned k2 = 0; k2 < wv; k2++) off += wtot[k2];
+    const u64 off = gtxscan::tile_exclusive<kScanHistThreads>((u64)run, wtot);
     if (off) for (int x = lo; x < hi; x++) h[x] += (ct)off;
     __syncthreads();
     for (int i = threadIdx.x; i < pt.count; i += blockDim.x) {
@@ -790,8 +751,8 @@ hipError_t launch_scan_bucketed(const void *reads, const void *weights, i64 n, c
   });
   if (e != hipSuccess) return e;
   const size_t lds = (size_t)scan_part_bins(weights != nullptr) * (weights ? 8 : 4);
-  if (weights) bucket_scanhist_kernel<true><<<(unsigned)nParts, 1024, lds, st>>>(sc, t, w, parts, out);
-  else bucket_scanhist_kernel<false><<<(unsigned)nParts, 1024, lds, st>>>(sc, t, w, parts, out);
+  if (weights) bucket_scanhist_kernel<true><<<(unsigned)nParts, kScanHistThreads, lds, st>>>(sc, t, w, parts, out);
+  else bucket_scanhist_kernel<false><<<(unsigned)nParts, kScanHistThreads, lds, st>>>(sc, t, w, parts, out);
   return hipGetLastError();
 }
 

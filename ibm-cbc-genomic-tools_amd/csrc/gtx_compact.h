@@ -34,6 +34,7 @@
 // Integer code only: whatever rounds stays with its rule.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gtx_scan.h"
 
 namespace gtx {
 
@@ -41,9 +42,10 @@ constexpr int kCompactThreads = 256, kCompactRows = 8;
 constexpr int kCompactTile = 64 * 2 * kCompactRows;                   // windows per wave: kCompactRows rows of two windows per lane
 inline long long compact_tiles(long long n) { return (n + kCompactTile - 1) / kCompactTile; }
 
-// The scans over per-tile values run in one block of kPartThreads lanes, each over a run of consecutive tiles: the loads of a run go
-// out kPartBatch at a time (they do not depend on one another; one at a time the kernel is a chain of memory latencies).
-constexpr int kPartThreads = 1024, kPartBatch = 8;
+// The scans over per-tile values run in one block of kPartThreads lanes, each over a run of consecutive tiles with its loads out
+// kPartBatch at a time (gtx_scan.h): block_exclusive_sum below, or a first and last pass of the kernel's own around a tile_exclusive.
+constexpr int kPartThreads = 1024;
+using gtxscan::kPartBatch;
 
 // base [tiles + 1] = the exclusive sums of count [tiles], base[tiles] their total (defined in gtx_select.hip)
 hipError_t launch_tile_prefix(const unsigned *tileCount, long long tiles, long long *tileBase, hipStream_t st);
@@ -52,6 +54,8 @@ hipError_t launch_tile_prefix64(const unsigned long long *tileCount, long long t
 
 // The body of that scan, for a block of kPartThreads threads with sh [kPartThreads] in LDS: base[k] = count[0] + .. + count[k - 1] for
 // k = 0 .. n.  It ends in a barrier: behind it every thread may read base[0 .. n] and sh is free.  COUNT: unsigned, or unsigned long long.
+// It keeps its own two turns and LDS ladder and is not gtxscan::run_exclusive_sum: built on that, launch_tile_prefix came out about 0.005 ms
+// slower than this in two sessions against the parent's library (profiles/scan_ab.txt), for a reason the ISA does not show.
 template <class COUNT>
 __device__ __forceinline__ void block_exclusive_sum(const COUNT *__restrict__ count, long long n, long long *__restrict__ base, long long *sh)
 {

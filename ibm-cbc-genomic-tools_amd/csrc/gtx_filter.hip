@@ -33,13 +33,15 @@ __global__ __launch_bounds__(256) void filter_first_kernel(const int *__restrict
 }
 
 // start[i], and runmax[i] = the largest stop among the sorted regions of i's class up to i: a segmented scan in one block, each thread
-// over a run of consecutive regions (the shape of the tile prefix, gtx_compact.h).  A run's summary is {a class begins inside it,
-// the largest stop since the last such beginning}; summaries combine left to right.
+// over a run of consecutive regions, the runs' summaries joined by tile_exclusive (gtx_scan.h).  A run's summary is {a class begins
+// inside it, the largest stop since the last such beginning}; summaries combine left to right.
 constexpr int kRunThreads = 1024;
+struct CutMax { int cut, m; };
+struct CutMaxComb { __device__ __forceinline__ CutMax operator()(CutMax a, CutMax b) const { return CutMax{a.cut | b.cut, b.cut ? b.m : max(a.m, b.m)}; } };
+
 __global__ __launch_bounds__(kRunThreads) void filter_runmax_kernel(const int *__restrict__ sorted, i64 n, int *__restrict__ start, int *__restrict__ runmax)
 {
-  __shared__ int shMax[kRunThreads];
-  __shared__ int shCut[kRunThreads];
+  __shared__ CutMax waveSum[kRunThreads / 64];
   const int tid = threadIdx.x;
   const i64 per = (n + kRunThreads - 1) / kRunThreads, b = min((i64)tid * per, n), e = min(b + per, n);
   int cut = 0, m = INT_MIN;
@@ -50,16 +52,7 @@ __global__ __launch_bounds__(kRunThreads) void filter_runmax_kernel(const int *_
     if (c != prev) { cut = 1; m = stop; } else m = max(m, stop);
     prev = c;
   }
-  shMax[tid] = m; shCut[tid] = cut;
-  __syncthreads();
-  for (int dd = 1; dd < kRunThreads; dd <<= 1) {
-    const bool has = tid >= dd;
-    const int lm = has ? shMax[tid - dd] : INT_MIN, lc = has ? shCut[tid - dd] : 0;
-    __syncthreads();
-    if (has) { if (!shCut[tid]) shMax[tid] = max(lm, shMax[tid]); shCut[tid] |= lc; }
-    __syncthreads();
-  }
-  int run = tid > 0 ? shMax[tid - 1] : INT_MIN;
+  int run = gtxscan::tile_exclusive<kRunThreads>(CutMax{cut, m}, waveSum, (CutMax *)nullptr, CutMax{0, INT_MIN}, CutMaxComb()).m;
   prev = b > 0 && b < n ? sorted[3 * (b - 1)] : -1;
 #pragma unroll 4
   for (i64 i = b; i < e; i++) {

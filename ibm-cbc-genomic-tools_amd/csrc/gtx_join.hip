@@ -3,6 +3,7 @@
 #include <climits>
 #include "gtx_join.h"
 #include "gtx_join_walk.h"
+#include "gtx_scan.h"
 
 namespace gtx {
 namespace {
@@ -42,54 +43,30 @@ __global__ __launch_bounds__(256) void join_emit_kernel(JoinQueries q, long long
 // ---- exclusive scan of int64 (tiles of 256 lanes x 8) ----
 constexpr int kScanThreads = 256, kScanItems = 8, kScanTile = kScanThreads * kScanItems;
 
-// exclusive scan of one value per lane over the block; returns the block total in *total
-__device__ __forceinline__ long long block_exclusive(long long v, long long *sh, long long *total)
-{
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < kScanThreads; d <<= 1) {
-    const long long add = tid >= d ? sh[tid - d] : 0;
-    __syncthreads();
-    sh[tid] += add;
-    __syncthreads();
-  }
-  const long long incl = sh[tid];
-  *total = sh[kScanThreads - 1];
-  __syncthreads();
-  return incl - v;
-}
-
 __global__ __launch_bounds__(kScanThreads) void scan_reduce_kernel(const long long *__restrict__ v, long long n, long long *__restrict__ partial)
 {
-  __shared__ long long sh[kScanThreads];
+  __shared__ long long waveSum[kScanThreads / 64];
   const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
   long long s = 0;
   for (int k = 0; k < kScanItems; k++) if (base + k < n) s += v[base + k];
   long long tot;
-  block_exclusive(s, sh, &tot);
+  gtxscan::tile_exclusive<kScanThreads>(s, waveSum, &tot);     // (only the block's sum is wanted)
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(kScanThreads) void scan_partials_kernel(long long *__restrict__ partial, long long nt)
 {
-  __shared__ long long sh[kScanThreads];
-  const long long per = (nt + kScanThreads - 1) / kScanThreads, b = (long long)threadIdx.x * per;
-  long long s = 0;
-  for (long long k = b; k < b + per && k < nt; k++) s += partial[k];
-  long long tot;
-  long long run = block_exclusive(s, sh, &tot);
-  for (long long k = b; k < b + per && k < nt; k++) { const long long x = partial[k]; partial[k] = run; run += x; }
+  __shared__ long long waveSum[kScanThreads / 64];
+  gtxscan::run_exclusive_sum<kScanThreads>(partial, nt, partial, waveSum);
 }
 
 __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(long long *__restrict__ v, long long n, const long long *__restrict__ partial)
 {
-  __shared__ long long sh[kScanThreads];
+  __shared__ long long waveSum[kScanThreads / 64];
   const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
   long long x[kScanItems], s = 0;
   for (int k = 0; k < kScanItems; k++) { x[k] = base + k < n ? v[base + k] : 0; s += x[k]; }
-  long long tot;
-  long long run = partial[blockIdx.x] + block_exclusive(s, sh, &tot);
+  long long run = partial[blockIdx.x] + gtxscan::tile_exclusive<kScanThreads>(s, waveSum);
   for (int k = 0; k < kScanItems; k++) if (base + k < n) { v[base + k] = run; run += x[k]; }
 }
 

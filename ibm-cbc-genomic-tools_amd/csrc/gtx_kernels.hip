@@ -42,6 +42,7 @@
 #include <vector>
 #include <algorithm>
 #include "gtx_kernels.h"
+#include "gtx_scan.h"
 
 namespace gtx {
 
@@ -59,31 +60,9 @@ __device__ __forceinline__ int rdlane(int v, int l) { return __builtin_amdgcn_re
 // value of the lane below (lane 0 keeps its own); DPP wave_shr:1 -- call with all lanes active
 __device__ __forceinline__ int lane_prev(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
 
-// inclusive prefix sum over the 64 lanes, DPP only (no LDS): Hillis-Steele inside each row of 16 lanes
-// (row_shr 1, 2, 4, 8 with zero fill), then row_bcast15 hands a row's total to the next odd row and
-// row_bcast31 the total of lanes 0..31 to the upper half.  Call with all lanes active.
-__device__ __forceinline__ int wave_scan_add(int v)
-{
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-  return v;
-}
-
-// the same for 64-bit values: both halves travel by DPP, the add carries
-__device__ __forceinline__ u64 wave_scan_add64(u64 v)
-{
-#define GTX_DPP64(ctrl, rmask, bc)                                                                                  \
-  v += ((u64)(unsigned)__builtin_amdgcn_update_dpp(0, (int)(v >> 32), ctrl, rmask, 0xf, bc) << 32) |                \
-       (u64)(unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, ctrl, rmask, 0xf, bc)
-  GTX_DPP64(0x111, 0xf, true); GTX_DPP64(0x112, 0xf, true); GTX_DPP64(0x114, 0xf, true); GTX_DPP64(0x118, 0xf, true);
-  GTX_DPP64(0x142, 0xa, false); GTX_DPP64(0x143, 0xc, false);
-#undef GTX_DPP64
-  return v;
-}
+// inclusive prefix sum over the 64 lanes by DPP (gtx_scan.h), under the names the kernels here call it by.  Call with all lanes active.
+__device__ __forceinline__ int wave_scan_add(int v) { return gtxscan::wave_inclusive_dpp(v); }
+__device__ __forceinline__ u64 wave_scan_add64(u64 v) { return gtxscan::wave_inclusive_dpp(v); }
 
 __device__ __forceinline__ int wave_min(int v)
 {

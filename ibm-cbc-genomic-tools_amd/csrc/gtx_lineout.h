@@ -4,6 +4,7 @@
 // LDS.  Device code; the grammars and the renderers stay with their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "gtx_scan.h"
 
 namespace gtxline {
 
@@ -34,39 +35,8 @@ __device__ __forceinline__ void tile_total(T v, T *ldsSum)
   if ((threadIdx.x & 63) == 0) atomicAdd(ldsSum, v);
 }
 
-// v of the lane o places below in the wave (undefined for the lowest o lanes); T of whole 32-bit words, a vector of them included
-template <class T>
-__device__ __forceinline__ T lane_up(T v, int o)
-{
-  static_assert(sizeof(T) % sizeof(int) == 0, "whole words");
-  int w[sizeof(T) / sizeof(int)];
-  __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (unsigned k = 0; k < sizeof(T) / sizeof(int); k++) w[k] = __shfl_up(w[k], o);
-  __builtin_memcpy(&v, w, sizeof(T));
-  return v;
-}
-
-// The sum of v over the threads in front of this one in a block of THREADS threads (64, or a multiple of it); every thread calls it.
-// T: an integer, or a vector of them for several sums at once.  One wave: registers only, no barrier, and waveSum is not touched.  More
-// waves: waveSum[THREADS / 64] in LDS and exactly one barrier, which the caller may rely on for what it wrote to LDS in front of it.
-template <int THREADS, class T>
-__device__ __forceinline__ T tile_exclusive(T v, T *waveSum)
-{
-  static_assert(THREADS >= 64 && THREADS % 64 == 0, "whole waves");
-  const int lane = threadIdx.x & 63;
-  T incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const T up = lane_up(incl, o); if (lane >= o) incl += up; }
-  T at = incl - v;
-  if constexpr (THREADS > 64) {
-    const int w = threadIdx.x >> 6;
-    if (lane == 63) waveSum[w] = incl;
-    __syncthreads();
-    for (int k = 0; k < w; k++) at += waveSum[k];
-  }
-  return at;
-}
+// where a line begins inside its tile's run: the block scan of gtx_scan.h, whose one-barrier contract the line kernels rely on
+using gtxscan::tile_exclusive;
 
 // Bytes [lo, lo + total) of out from LDS, by the THREADS threads of the block: run[pad + k] is byte lo + k, pad = lo & 15, so run is
 // 16-byte aligned and holds 15 + total bytes rounded up to 16; out is 16-byte aligned.  Whole 16-byte units of out go out as such;

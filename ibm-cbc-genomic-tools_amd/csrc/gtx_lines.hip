@@ -134,10 +134,7 @@ __global__ __launch_bounds__(kLinesThreads) void lines_kernel(LinesArgs a)
     // (ordinals that do not ascend are the caller's mistake; a lane then searches from the front, so that k >= 0 and a line stays within maxLine)
     if (keep0) { if (PAIRS && L.blockOff[b] > at0) b = 0; b = block_of(L.blockOff, L.nBlocks, b, at0); measure(L, b, at0, v.x, x0); }
     if (keep1) { if (PAIRS && L.blockOff[b] > at1) b = 0; b = block_of(L.blockOff, L.nBlocks, b, at1); measure(L, b, at1, v.y, x1); }
-    const int mine = x0.len + x1.len;
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+    const int mine = x0.len + x1.len, incl = gtxscan::wave_inclusive(mine);
     const int rowBytes = __shfl(incl, 63);
     nLines += (unsigned)(__popcll(b0) + __popcll(b1)); nBytes += (unsigned)rowBytes;
     if (EMIT) {

@@ -122,12 +122,13 @@ __global__ __launch_bounds__(kLinkThreads) void link_scan_kernel(const int *__re
 }
 
 // The two scans over per-tile values run in one block of kPartThreads lanes, each over a run of consecutive tiles with its loads out
-// kPartBatch at a time (gtx_compact.h).
+// kPartBatch at a time, the runs' summaries joined by tile_exclusive (gtx_scan.h).
+struct SegComb { __device__ __forceinline__ SegMax operator()(SegMax a, SegMax b) const { return seg_comb(a, b); } };
 
 // exclusive scan of the tiles' aggregates
 __global__ __launch_bounds__(kPartThreads) void link_prefix_kernel(const int2 *__restrict__ agg, i64 nt, int2 *__restrict__ prefix)
 {
-  __shared__ int2 sh[kPartThreads];
+  __shared__ SegMax waveAgg[kPartThreads / 64];
   const int tid = threadIdx.x;
   const i64 per = (nt + kPartThreads - 1) / kPartThreads, b = min((i64)tid * per, nt), e = min(b + per, nt);
   SegMax a = seg_identity();
@@ -138,17 +139,7 @@ __global__ __launch_bounds__(kPartThreads) void link_prefix_kernel(const int2 *_
 #pragma unroll
     for (int j = 0; j < kPartBatch; j++) { SegMax o; o.f = v[j].x; o.m = v[j].y; a = seg_comb(a, o); }
   }
-  sh[tid] = make_int2(a.f, a.m);
-  __syncthreads();
-  for (int dd = 1; dd < kPartThreads; dd <<= 1) {
-    SegMax o = seg_identity();
-    if (tid >= dd) { o.f = sh[tid - dd].x; o.m = sh[tid - dd].y; }
-    __syncthreads();
-    if (tid >= dd) { SegMax me; me.f = sh[tid].x; me.m = sh[tid].y; me = seg_comb(o, me); sh[tid] = make_int2(me.f, me.m); }
-    __syncthreads();
-  }
-  SegMax run = seg_identity();
-  if (tid > 0) { run.f = sh[tid - 1].x; run.m = sh[tid - 1].y; }
+  SegMax run = gtxscan::tile_exclusive<kPartThreads>(a, waveAgg, (SegMax *)nullptr, seg_identity(), SegComb());
   for (i64 k = b; k < e; k += kPartBatch) {
     int2 v[kPartBatch];
 #pragma unroll
@@ -236,11 +227,7 @@ __global__ __launch_bounds__(kLinkThreads) void link_groups_kernel(const int *__
   const i64 nGroups = info->nGroups, tb = base[t];
   // heads in front of every row of the tile
   const u64 myWord = lane < kLinkTile / 64 ? bits[t * (kLinkTile / 64) + lane] : 0;
-  int incl = __popcll(myWord);
-  const int own = incl;
-#pragma unroll
-  for (int dd = 1; dd < 64; dd <<= 1) { const int o = __shfl_up(incl, dd); if (lane >= dd) incl += o; }
-  const int excl = incl - own;
+  const int own = __popcll(myWord), incl = gtxscan::wave_inclusive(own), excl = incl - own;
   Part carry = part_identity<MODE>();
   bool leftOpen = true, dead = false;
 #pragma unroll

@@ -37,6 +37,7 @@
 #include <vector>
 #include "gtx.h"
 #include "gtx_internal.h"
+#include "gtx_scan.h"
 #include "gtx_text.h"
 #include "gtx_textline.h"
 
@@ -62,14 +63,19 @@ __device__ __forceinline__ unsigned nl_mask16(const uint4 v)
   return m;
 }
 
-// segment s = bytes [s * kSeg, ...): one wave, lane l owns 16 bytes
-__global__ __launch_bounds__(64) void nl_count_kernel(const char *__restrict__ text, size_t bytes, unsigned *__restrict__ segCount)
+// bytes [at, at + 16) of the text, one load where all 16 exist; what lies at or behind text[bytes] is not read and reads as 0
+__device__ __forceinline__ uint4 load16(const char *__restrict__ text, size_t bytes, size_t at)
 {
-  const size_t at = (size_t)blockIdx.x * kSeg + threadIdx.x * 16;
   uint4 v = make_uint4(0, 0, 0, 0);
   if (at + 16 <= bytes) v = *(const uint4 *)(text + at);
   else if (at < bytes) { unsigned char t[16] = {0}; for (size_t k = 0; at + k < bytes; k++) t[k] = (unsigned char)text[at + k]; v = *(const uint4 *)t; }
-  int c = __popc(nl_mask16(v));
+  return v;
+}
+
+// segment s = bytes [s * kSeg, ...): one wave, lane l owns 16 bytes
+__global__ __launch_bounds__(64) void nl_count_kernel(const char *__restrict__ text, size_t bytes, unsigned *__restrict__ segCount)
+{
+  int c = __popc(nl_mask16(load16(text, bytes, (size_t)blockIdx.x * kSeg + threadIdx.x * 16)));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
   if (threadIdx.x == 0) segCount[blockIdx.x] = (unsigned)c;
@@ -79,33 +85,16 @@ __global__ __launch_bounds__(64) void nl_count_kernel(const char *__restrict__ t
 __global__ __launch_bounds__(1024) void nl_scan_kernel(unsigned *__restrict__ segCount, unsigned nSeg)
 {
   __shared__ unsigned wsum[16];
-  const unsigned per = (nSeg + 1023) / 1024, i0 = threadIdx.x * per;
-  unsigned s = 0;
-  for (unsigned k = 0; k < per; k++) if (i0 + k < nSeg) s += segCount[i0 + k];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  unsigned inc = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned up = __shfl_up(inc, o); if (lane >= o) inc += up; }
-  if (lane == 63) wsum[wv] = inc;
-  __syncthreads();
-  unsigned run = inc - s;
-  for (int k = 0; k < wv; k++) run += wsum[k];
-  for (unsigned k = 0; k < per; k++) if (i0 + k < nSeg) { const unsigned v = segCount[i0 + k]; segCount[i0 + k] = run; run += v; }
-  if (threadIdx.x == 1023) segCount[nSeg] = run;
+  const unsigned all = gtxscan::run_exclusive_sum<1024>(segCount, nSeg, segCount, wsum);
+  if (threadIdx.x == 0) segCount[nSeg] = all;
 }
 
 __global__ __launch_bounds__(64) void nl_write_kernel(const char *__restrict__ text, size_t bytes, const unsigned *__restrict__ segOff, unsigned *__restrict__ nl, unsigned nLines)
 {
   const size_t at = (size_t)blockIdx.x * kSeg + threadIdx.x * 16;
-  uint4 v = make_uint4(0, 0, 0, 0);
-  if (at + 16 <= bytes) v = *(const uint4 *)(text + at);
-  else if (at < bytes) { unsigned char t[16] = {0}; for (size_t k = 0; at + k < bytes; k++) t[k] = (unsigned char)text[at + k]; v = *(const uint4 *)t; }
-  unsigned m = nl_mask16(v);
+  unsigned m = nl_mask16(load16(text, bytes, at));
   const int c = __popc(m);
-  int inc = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(inc, o); if ((int)threadIdx.x >= o) inc += up; }
-  unsigned k = segOff[blockIdx.x] + (unsigned)(inc - c);
+  unsigned k = segOff[blockIdx.x] + (unsigned)(gtxscan::wave_inclusive(c) - c);
   while (m) { const int b = __ffs(m) - 1; m &= m - 1; if (k < nLines) nl[k] = (unsigned)(at + b); k++; }
 }
 
@@ -590,26 +579,11 @@ __global__ __launch_bounds__(kTile) void subset_mark_kernel(SubsetDevice d, unsi
 // both halves of tile[] into exclusive prefixes, the totals at [nTiles] and [2 nTiles + 1]
 __global__ __launch_bounds__(1024) void subset_scan_kernel(unsigned long long *__restrict__ tile, unsigned nTiles)
 {
-  __shared__ unsigned long long sh[1024];
+  __shared__ unsigned long long wsum[16];
   for (int half = 0; half < 2; half++) {
     unsigned long long *v = tile + (size_t)half * ((size_t)nTiles + 1);
-    unsigned long long carry = 0;
-    for (unsigned base = 0; base < nTiles; base += 1024) {
-      const unsigned i = base + threadIdx.x;
-      const unsigned long long x = i < nTiles ? v[i] : 0;
-      sh[threadIdx.x] = x;
-      __syncthreads();
-      for (int o = 1; o < 1024; o <<= 1) {
-        const unsigned long long y = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += y;
-        __syncthreads();
-      }
-      if (i < nTiles) v[i] = carry + sh[threadIdx.x] - x;
-      carry += sh[1023];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) v[nTiles] = carry;
+    const unsigned long long all = gtxscan::run_exclusive_sum<1024>(v, nTiles, v, wsum);
+    if (threadIdx.x == 0) v[nTiles] = all;
   }
 }
 
@@ -620,20 +594,11 @@ __global__ __launch_bounds__(kTile) void subset_gather_kernel(SubsetDevice d)
   __shared__ unsigned off[kTile], src[kTile];
   if (*d.flag) return;
   const int t = threadIdx.x;
-  unsigned from;
+  unsigned from, total;
   const unsigned n = subset_line(d, blockIdx.x * kTile + t, from);
-  off[t] = n; src[t] = from;
+  const unsigned mine = gtxscan::tile_exclusive<kTile>(n, off, &total);   // where the line begins inside the run (the wave sums pass through off)
   __syncthreads();
-  for (int o = 1; o < kTile; o <<= 1) {                           // inclusive prefix of the kept bytes
-    const unsigned y = t >= o ? off[t - o] : 0;
-    __syncthreads();
-    off[t] += y;
-    __syncthreads();
-  }
-  const unsigned total = off[kTile - 1];
-  const unsigned mine = off[t] - n;
-  __syncthreads();
-  off[t] = mine;                                                  // exclusive: where the line begins inside the run
+  off[t] = mine; src[t] = from;
   __syncthreads();
   char *__restrict__ out = d.out + d.tile[blockIdx.x];
   for (unsigned i = t; i < total; i += kTile) {
